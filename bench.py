@@ -21,6 +21,10 @@ Prints ONE JSON line on rank 0.
 the parent does not import torch and does not touch the GPU; it starts `python -m torch.distributed.run ... bench.py <same args>` as a
 CHILD process, relays rank 0's JSON line and exits with the child's code (non-zero on failure, time-out or a missing line).
 --dry-launch: rendezvous + broadcast of the communicator id only (no solver, no ncclCommInitRank); runs without a GPU.
+--dump-outputs DIR (one GPU): after the timed steps of each leg, what its last timed step computed -- the field P (a fixed, seeded sample of
+2^21 interior cells beyond that size), the residual history of the last timed call and the final residual -- goes to DIR/<solver>_<prec>_*.npy.
+The settle sweeps run on a second instance of the problem, so the timed steps always start from the set-up state: with the same arguments,
+two runs (or two builds) compute from identical inputs and can be compared array for array.
 """
 import argparse
 import hashlib
@@ -55,7 +59,11 @@ ap.add_argument("--no-configs", action="store_true", help="skip the configs[2] /
 ap.add_argument("--cpu-seconds", type=float, default=12.0)
 ap.add_argument("--dry-launch", action="store_true", help="rendezvous and id broadcast only; works without a GPU")
 ap.add_argument("--launch-timeout", type=float, default=1500.0, help="seconds the self-launched job may take")
+ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                help="after the timed steps of every leg, write what its last timed step computed to DIR/<solver>_<prec>_<array>.npy (capture_outputs)")
 args = ap.parse_args()
+if args.dump_outputs and args.gpus > 1:
+    ap.error("--dump-outputs: single GPU only (a multi-GPU line times a number of regions that depends on the clock)")
 if args.prec is None:
     args.prec = "f64" if args.solver == "pbicgstab" else "f32"
 
@@ -109,6 +117,8 @@ if world != args.gpus:
     raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
 
 import ctypes as C  # noqa: E402
+
+import numpy as np  # noqa: E402
 
 import torch  # noqa: E402  (plumbing only: rendezvous, barrier, max-reduce of the timings)
 import torch.distributed as dist  # noqa: E402
@@ -248,6 +258,31 @@ def kernel_source_sha():
     return h.hexdigest()[:16]
 
 
+DUMP_POINTS = 1 << 21  # field values per leg: 8 MB in FP32, 16 MB in FP64; three legs stay below 64 MB
+
+
+def capture_outputs(cz):
+    """what a caller of the timed path holds after its last step: the field P (interior cells; a fixed seeded sample of DUMP_POINTS of them
+    when there are more), the residual history of the last call (one entry per step) and the final residual"""
+    P = cz.field()
+    g = cubez_amd.GUIDE
+    shape = (P.shape[0] - 2 * g, P.shape[1] - 2 * g, P.shape[2] - 2 * g)
+    total = shape[0] * shape[1] * shape[2]
+    if total <= DUMP_POINTS:
+        field = ("P", np.ascontiguousarray(P[g:-g, g:-g, g:-g]))
+    else:
+        flat = np.sort(np.random.default_rng(20240611).integers(0, total, DUMP_POINTS))
+        j, i, k = np.unravel_index(flat, shape)
+        field = ("P_sample", P[j + g, i + g, k + g])
+    return dict([field, ("residual_history", np.asarray(cz.history(), dtype=np.float64)), ("residual", np.array([cz.res], dtype=np.float64))])
+
+
+def dump_outputs(leg, arrays):
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(args.dump_outputs, f"{leg}_{name}.npy"), a)
+
+
 def measure(solver, prec, precond, steps, warmup, repeats, settle):
     """one leg: set up `cz <gsz> solver ...`, settle, W warm-up steps, `repeats` timed regions of `steps` steps; everything the line needs"""
     bicg = solver == "pbicgstab"
@@ -275,10 +310,17 @@ def measure(solver, prec, precond, steps, warmup, repeats, settle):
                 cz.timing(True)
             dts.append(timed(lib, cz.solve))
             assert len(cz.history()) == steps, "BiCGSTAB converged before the requested number of iterations"
+        outputs = capture_outputs(cz) if args.dump_outputs else None
     else:
+        # one GPU: the clock ramp sweeps a second instance of the same problem, so that the steps below start from the set-up state whatever
+        # number of sweeps the ramp took (--dump-outputs compares runs output for output); the ranks of a multi-GPU line ramp on their own
+        warm = cz
+        if world == 1 and settle > 0:
+            warm = CZ(prec, quiet=True, device=local_rank)
+            assert warm.setup(argv) == 1, "cz_setup failed"
         t0 = time.perf_counter()
         while settle > 0:  # every rank issues the same number of sweeps: rank 0's clock decides
-            cz.sweeps(40)
+            warm.sweeps(40)
             lib.czhip_sync()
             go = time.perf_counter() - t0 < settle
             if world > 1:
@@ -294,6 +336,9 @@ def measure(solver, prec, precond, steps, warmup, repeats, settle):
         # 128^3 pass, nothing at 512^3); one more region of K steps behind them, with the events on, gives the kernel durations
         for rep in range(repeats):
             dts.append(timed(lib, lambda: cz.sweeps(steps)))
+        outputs = capture_outputs(cz) if args.dump_outputs else None
+        if warm is not cz:
+            warm.close()
         # N > 1: a region of K = 20 steps is a few milliseconds, the same order as the jitter of N processes starting it together.  The
         # region stays EXACTLY K steps (the contract); what grows is the number of regions the median is taken over -- until they add up
         # to 0.25 s, at most 25.  Every rank sees the same all-reduced times, so every rank takes the same decision.
@@ -316,7 +361,7 @@ def measure(solver, prec, precond, steps, warmup, repeats, settle):
     cz.close()
     return dict(solver=solver, prec=prec, precond=precond, bicg=bicg, coef=coef, steps=steps, warmup=warmup, repeats=repeats, dts=dts, dt=statistics.median(dts),
                 my_points=my_points, jac_like=jl, line=line, single=single, fused=fused, fused4=fused4, labels=labels, info=info, settle_s=settled,
-                timed_steps=steps, event_span_ms=ev_ms)
+                timed_steps=steps, event_span_ms=ev_ms, outputs=outputs)
 
 
 def traffic_record(tkey):
@@ -447,6 +492,8 @@ def config_record(m):
 
 
 m = measure(args.solver, args.prec, args.precond, args.steps, args.warmup, args.repeats, args.settle)
+if args.dump_outputs:
+    dump_outputs(f"{args.solver}_{args.prec}", m["outputs"])
 bicg, dt, info = m["bicg"], m["dt"], m["info"]
 
 tot_points = float(m["my_points"])
@@ -518,8 +565,12 @@ if rank == 0:
 if world == 1 and args.solver == "jacobi" and args.prec == "f32" and not args.no_configs:
     cfgs = {}
     try:
-        cfgs["configs[2] 512^3 FP32 red-black SOR"] = config_record(measure("sor2sma", "f32", "jacobi", args.steps, args.warmup, min(args.repeats, 3), min(args.settle, 0.05)))
-        cfgs["configs[3] 512^3 FP64 BiCGSTAB + Jacobi(8)"] = config_record(measure("pbicgstab", "f64", "jacobi", min(args.steps, 10), 2, 2, 0.0))
+        for key, leg in (("configs[2] 512^3 FP32 red-black SOR", ("sor2sma", "f32", "jacobi", args.steps, args.warmup, min(args.repeats, 3), min(args.settle, 0.05))),
+                         ("configs[3] 512^3 FP64 BiCGSTAB + Jacobi(8)", ("pbicgstab", "f64", "jacobi", min(args.steps, 10), 2, 2, 0.0))):
+            mc = measure(*leg)
+            cfgs[key] = config_record(mc)
+            if args.dump_outputs:
+                dump_outputs(f"{leg[0]}_{leg[1]}", mc["outputs"])
     except Exception as e:  # never lose the headline over a side leg
         cfgs["error"] = repr(e)
     out["configs"] = cfgs

@@ -16,6 +16,8 @@ tests can run where /root/reference does not exist.
                              recorded in BASELINE.md section 2b (checked in tests/test_oracle.py)
     field_*.npy              final P of the <=32^3 cases
     solver_cases.json        index of the solver-level cases + expected Iter/Res/sha256(P)
+    ref_random_boxes.json    the reference's record of tests/test_oracle.py::random_box_record (scalars and
+                             sha256 of the arrays of its kernels on seeded random boxes), per precision
 """
 import hashlib
 import json
@@ -253,8 +255,15 @@ def solver_cases():
         json.dump(index, f, indent=1)
 
 
+def random_boxes():
+    from tests.test_oracle import random_box_record
+    with open(os.path.join(HERE, "ref_random_boxes.json"), "w") as f:
+        json.dump({prec: random_box_record(O.Kernels("ref", prec)) for prec in ("f32", "f64")}, f, indent=1)
+
+
 if __name__ == "__main__":
     assert O.have("ref", "f32") and O.have("ref", "f64"), "build oracle/_ref first: make -C oracle ref"
     kernel_vectors("f32")
     kernel_vectors("f64")
     solver_cases()
+    random_boxes()

@@ -32,3 +32,9 @@ def test_a_failing_rank_gives_a_nonzero_exit_code_and_no_line():
     r = _run("--gpus", "2", "--dry-launch", "--div", "1,3,1")  # 3 bricks for 2 ranks: every rank exits with an error
     assert r.returncode != 0
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_dump_outputs_is_refused_for_a_multi_gpu_line(tmp_path):
+    r = _run("--gpus", "2", "--dump-outputs", str(tmp_path / "out"))
+    assert r.returncode == 2 and "--dump-outputs: single GPU only" in r.stderr
+    assert not r.stdout.strip() and not (tmp_path / "out").exists()
