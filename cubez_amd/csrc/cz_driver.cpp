@@ -735,6 +735,7 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
     int first_itr, nsweep, src;
   };
   std::vector<Launch> launches;
+  exact_reruns = 0;
   int idx1[6];  // index range of the first sweep of a pair: one layer into the ghost cells across rank-internal faces
   for (int f = 0; f < 6; f++) idx1[f] = innerFidx[f] + ((nID[f] >= 0) ? ((f & 1) ? 1 : -1) : 0);
   if (plan.depth == 2 && numProc > 1) {
@@ -886,6 +887,7 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
                            0, nullptr, nullptr, nullptr);
         else
           czhip_jacobi_async(buf[last->src], buf[(last->src + 1) % nbuf], B, size, innerFidx, gc, cf, ac1, d_res + 4, 0, nullptr);
+        exact_reruns++;
       }
     }
     final_buf = (last->src + 1) % nbuf;
@@ -961,6 +963,7 @@ int CZ::RBSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double
   const bool rb4 = plan.kind == PassPlan::WHOLE && numProc == 1 && !maf &&
                    czhip_rbsor4_async(X, WRK, B, size, innerFidx, gc, cf, ip, ac1, d_res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 1) != 0;
   rb4_passes = 0;
+  exact_reruns = 0;
   hipEvent_t ev[POLL_SLOTS];
   int npoll = 0;
   bool stop = false;
@@ -1081,6 +1084,7 @@ int CZ::RBSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double
                                 nullptr, nullptr, nullptr)) {
           cz_fatal(1, "error : fused red-black iteration refused after a successful probe\n");
         }
+        exact_reruns++;
       }
     }
     const int fb = (last->src + 1) % nbuf;
@@ -1793,6 +1797,7 @@ int cz_info(const cz_handle* h, int what) {
     case 4: return c.last_lag;
     case 10: return c.bicg_fused;
     case 11: return c.rb4_passes;
+    case 12: return c.exact_reruns;
     case 5: return comm_transport_ranks(c.comm);
     case 6: return c.comm_cus;
     case 7: return c.last_plan.kind;

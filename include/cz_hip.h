@@ -337,7 +337,8 @@ double cz_last_solve_seconds(const cz_handle*);
  * solve: 7 kind of pass (0 single sweeps, 1 fused pass over the whole box, 2 fused pass as shell slabs + interior with the exchange
  * overlapped), 8 ghost layers exchanged per pass, 9 rotating field buffers; 10 vector updates of the last BiCGSTAB solve that were made inside
  * the first pair of the preconditioner solve they feed (czhip_jacobi2_from_zero_made_async); 11 passes of the last red-black SOR solve that made
- * two iterations each (czhip_rbsor4_async). */
+ * two iterations each (czhip_rbsor4_async); 12 converged iterations of the last Jacobi or red-black SOR solve that were the first of a fused pass
+ * (a pair of sweeps, or an rb4 pass of two iterations) and were therefore re-run alone from the pass's untouched input to give the converged iterate. */
 int cz_info(const cz_handle*, int what);
 double cz_kernel_ms(const cz_handle*, const char* label); /* HIP-event time of a labelled section, ms (avg per launch) */
 

@@ -438,6 +438,7 @@ class Result:
     P: np.ndarray | None = None
     errmax: float | None = None
     errloc: tuple | None = None
+    dot_log: list = field(default_factory=list)  # dots="exact": (itr, which, S, B, n) per dot product
 
     def history_text(self) -> str:
         """the reference's history file (cz_Evaluate.cpp:218, cz_Poisson.cpp:71)."""
@@ -447,11 +448,21 @@ class Result:
 class CZ:
     """Single-domain restatement of class CZ's solve path (cz.h:84-181)."""
 
-    def __init__(self, kernels: Kernels, wide: bool = False):
+    def __init__(self, kernels: Kernels, wide: bool = False, dots: str | None = None, perturb: int = 0):
         """wide=True: residuals and dot products come from the double accumulation of the same REAL-rounded
-        terms (oracle back-end only) -- the mode the GPU path is compared with (SURVEY.md 8c tolerance chain)."""
+        terms (oracle back-end only) -- the mode the GPU path is compared with (SURVEY.md 8c tolerance chain).
+
+        dots="exact": BiCGSTAB's two dot products (Fdot1 / Fdot2) take the same per-point products in REAL, sum them correctly
+        rounded (math.fsum) to S and return R(S + perturb * B), B = gamma_(n-1) * sum |t_i| with gamma_m = m u / (1 - m u),
+        u = 2^-53: the bound on how far ANY order of double accumulation of those n terms lies from S.  perturb in {-1, 0, +1}
+        pushes every dot to an edge of that bound.  Every call is logged in dot_log as (itr, which, S, B, n); `which` is
+        "rho", "q.r0", "t.s", "t.t" or "r.r".  Every other kernel stays the chosen back-end's."""
+        assert dots in (None, "exact") and perturb in (-1, 0, 1)
+        assert dots is None or not wide, "dots='exact' replaces the wide dots"
         self.k = kernels
         self.wide = wide
+        self.dots, self.perturb = dots, perturb
+        self.dot_log = []
         R = kernels.real
         self.R = R
         self.cf = np.array([1, 1, 1, 1, 1, 1, 6], dtype=R)  # cz.h:169-172
@@ -651,21 +662,42 @@ class CZ:
             else:
                 k.blas_calc_ax(ap, p, sz, idx, self.cf)
 
-        if self.wide:
-            def dot1(x):
+        itr = 1
+        if self.dots == "exact":
+            g, (ist, ied, jst, jed, kst, ked) = GUIDE - 1, idx
+            inner = (slice(jst + g, jed + g + 1), slice(ist + g, ied + g + 1), slice(kst + g, ked + g + 1))
+            n = (ied - ist + 1) * (jed - jst + 1) * (ked - kst + 1)
+            mu = (n - 1) * 2.0 ** -53
+            gamma = mu / (1.0 - mu)
+
+            def exact(t, which):
+                t = t.astype(np.float64).ravel()  # exact: a REAL product is representable in double
+                S = math.fsum(t)
+                B = gamma * math.fsum(np.abs(t))
+                self.dot_log.append((itr, which, S, B, n))
+                return R(S + self.perturb * B)
+
+            def dot1(x, which):
+                v = x[inner]
+                return exact(np.multiply(v, v, dtype=R), which)  # REAL products, one rounding each, no FMA
+
+            def dot2(x, y, which):
+                return exact(np.multiply(x[inner], y[inner], dtype=R), which)
+        elif self.wide:
+            def dot1(x, which=None):
                 w = np.zeros(1)
                 k.blas_dot1(x, sz, idx, wide=w)
                 return R(w[0])
 
-            def dot2(x, y):
+            def dot2(x, y, which=None):
                 w = np.zeros(1)
                 k.blas_dot2(x, y, sz, idx, wide=w)
                 return R(w[0])
         else:
-            def dot1(x):
+            def dot1(x, which=None):
                 return k.blas_dot1(x, sz, idx)
 
-            def dot2(x, y):
+            def dot2(x, y, which=None):
                 return k.blas_dot2(x, y, sz, idx)
         a = {n: k.alloc(sz) for n in ("p", "p_", "r", "r0", "q", "s", "s_", "t_")}
         res = 0.0
@@ -676,9 +708,8 @@ class CZ:
             k.blas_calc_rk(a["r"], X, B, sz, idx, self.cf)
         k.blas_copy(a["r0"], a["r"], sz)
         rho_old, alpha, omega = R(1.0), R(0.0), R(1.0)
-        itr = 1
         while itr < ItrMax:  # strict '<' (:373)
-            rho = dot2(a["r"], a["r0"])
+            rho = dot2(a["r"], a["r0"], "rho")
             if abs(float(rho)) < FLT_MIN:
                 itr = 0
                 break
@@ -690,15 +721,15 @@ class CZ:
             k.blas_clear(a["p_"], sz)
             self.Preconditioner(a["p_"], a["p"], pc)
             calc_ax(a["q"], a["p_"])
-            alpha = R(rho / dot2(a["q"], a["r0"]))  # :427
+            alpha = R(rho / dot2(a["q"], a["r0"], "q.r0"))  # :427
             k.blas_triad(a["s"], a["q"], a["r"], R(-alpha), sz, idx)
             k.blas_clear(a["s_"], sz)
             self.Preconditioner(a["s_"], a["s"], pc)
             calc_ax(a["t_"], a["s_"])
-            omega = R(dot2(a["t_"], a["s"]) / dot1(a["t_"]))  # :464
+            omega = R(dot2(a["t_"], a["s"], "t.s") / dot1(a["t_"], "t.t"))  # :464
             k.blas_bicg_2(X, a["p_"], a["s_"], alpha, omega, sz, idx)
             k.blas_triad(a["r"], a["t_"], a["s"], R(-omega), sz, idx)
-            res = float(dot1(a["r"]))
+            res = float(dot1(a["r"], "r.r"))
             res = math.sqrt(res * self.res_normal)
             self.history.append((itr, res))
             k.bc_k(sz, X, self.pitch, self.origin, self.nID)
@@ -718,9 +749,10 @@ class CZ:
         return k.err_t(self.size, self.idx, self.P, e)
 
 
-def run(gsz, solver, itr_max, coef, precond=None, kind="oracle", prec="f32", with_error=False, wide=False) -> Result:
-    """``cz gsz_x gsz_y gsz_z solver ItrMax coef [precond]`` on the chosen back-end, one thread semantics."""
-    cz = CZ(Kernels(kind, prec), wide=wide)
+def run(gsz, solver, itr_max, coef, precond=None, kind="oracle", prec="f32", with_error=False, wide=False, dots=None, perturb=0) -> Result:
+    """``cz gsz_x gsz_y gsz_z solver ItrMax coef [precond]`` on the chosen back-end, one thread semantics.
+    dots="exact" / perturb: BiCGSTAB's dot products correctly rounded (see CZ); Result.dot_log holds their log."""
+    cz = CZ(Kernels(kind, prec), wide=wide, dots=dots, perturb=perturb)
     cz.setup(gsz, coef)
     if solver in ("jacobi", "jacobi_maf"):
         itr, res = cz.JACOBI(cz.P, cz.RHS, itr_max, maf=solver.endswith("_maf"))
@@ -738,7 +770,7 @@ def run(gsz, solver, itr_max, coef, precond=None, kind="oracle", prec="f32", wit
         itr, res = cz.PBiCGSTAB(cz.P, cz.RHS, itr_max, precond or "none", maf=solver.endswith("_maf"))
     else:
         raise ValueError(solver)
-    out = Result(itr=itr, res=res, history=cz.history, P=cz.P)
+    out = Result(itr=itr, res=res, history=cz.history, P=cz.P, dot_log=cz.dot_log)
     if with_error:
         out.errmax, out.errloc = cz.error_max()
     return out

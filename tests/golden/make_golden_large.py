@@ -14,7 +14,7 @@ Runs only in the build container (needs oracle/_ref/libczref_f64.so = the refere
                                                  reference moves by its own summation-order rounding; the GPU tests bound |GPU - reference|
                                                  by a small multiple of it instead of by a number chosen by hand.
 
-usage: make_golden_large.py [perm] [256] [512] [perm256]     (default: the first three)
+usage: make_golden_large.py [perm [TAG...]] [256] [512] [perm256]     (default: the first three; TAG: only those permuted cases)
 """
 import hashlib
 import json
@@ -52,8 +52,10 @@ def large(n, itr_max, suffix):
     print(tag, r.itr, "%e" % r.res, "%.0f s" % (time.time() - t0), flush=True)
 
 
-def permuted():
-    cases = [c for c in json.load(open(os.path.join(HERE, "solver_cases.json"))) if c["solver"] in ("pbicgstab", "pbicgstab_maf")]
+def permuted(only=None):
+    """only: tags of the cases to (re)run; the other entries of perm_cases.json are kept"""
+    cases = [c for c in json.load(open(os.path.join(HERE, "solver_cases.json"))) if c["solver"] in ("pbicgstab", "pbicgstab_maf")
+             and (not only or c["tag"] in only)]
     out = _load("perm_cases.json")
     for c in cases:
         k = O.Kernels("oracle", c["prec"])
@@ -102,7 +104,7 @@ def permuted_large(n):
 if __name__ == "__main__":
     what = sys.argv[1:] or ["perm", "256", "512"]
     if "perm" in what:
-        permuted()
+        permuted({w for w in what if w not in ("perm", "256", "512", "perm256")})  # make_golden_large.py perm [TAG...]
     assert O.have("ref", "f64"), "build oracle/_ref first: make -C oracle ref"
     if "256" in what:
         large(256, 1000, "")

@@ -17,14 +17,15 @@ pytestmark = pytest.mark.gpu
 N = 512
 
 
-def _driver(prec, solver, nit, coef, t2):
+def _driver(prec, solver, nit, coef, t2, with_info=False):
+    """(Iter, history, field) of one solve; with_info: and CZ.info() of it"""
     from cubez_amd import CZ
     cz = CZ(prec, quiet=True)
     cz.lib.czhip_set_tuning2(0, 0, -1, 1 if t2 else 0)
     try:
         assert cz.setup([N, N, N, solver, nit, coef]) == 1
         itr = cz.solve()
-        out = (itr, cz.history(), cz.field())
+        out = (itr, cz.history(), cz.field()) + ((cz.info(),) if with_info else ())
     finally:
         cz.lib.czhip_set_tuning2(0, 0, -1, 1)
         cz.close()
@@ -33,8 +34,9 @@ def _driver(prec, solver, nit, coef, t2):
 
 def test_jacobi_512_against_oracle_and_between_paths():
     """4 sweeps of `cz 512 512 512 jacobi`: fused-pair path == single-sweep path == oracle, bit for bit."""
-    itr_a, hist_a, P_a = _driver("f32", "jacobi", 4, 0.8, t2=True)
+    itr_a, hist_a, P_a, info_a = _driver("f32", "jacobi", 4, 0.8, t2=True, with_info=True)
     itr_b, hist_b, P_b = _driver("f32", "jacobi", 4, 0.8, t2=False)
+    assert info_a["pass_kind"] == 1, info_a  # PassPlan::WHOLE: the fused pair is what ran
     assert itr_a == itr_b == 5
     assert P_a.tobytes() == P_b.tobytes()
     assert np.allclose(hist_a, hist_b, rtol=1e-12, atol=0)
@@ -46,8 +48,9 @@ def test_jacobi_512_against_oracle_and_between_paths():
 def test_rbsor_512_against_oracle_and_between_paths():
     """configs[2]: 5 iterations of `cz 512 512 512 sor2sma ... 1.5`: fused red-black pass == two colour launches == oracle, bit for bit
     (field) and to the double-accumulation tolerance (history)."""
-    itr_a, hist_a, P_a = _driver("f32", "sor2sma", 5, 1.5, t2=True)
+    itr_a, hist_a, P_a, info_a = _driver("f32", "sor2sma", 5, 1.5, t2=True, with_info=True)
     itr_b, hist_b, P_b = _driver("f32", "sor2sma", 5, 1.5, t2=False)
+    assert info_a["rb4_passes"] > 0, info_a  # the two-iteration pass (rb4_k) is what ran
     assert itr_a == itr_b == 6
     assert P_a.tobytes() == P_b.tobytes()
     assert np.allclose(hist_a, hist_b, rtol=1e-12, atol=0)

@@ -279,11 +279,13 @@ def _fused_equals_unfused(prec, gsz, pc, monkeypatch):
 
 @pytest.mark.parametrize("prec", ["f32", "f64"])
 @pytest.mark.parametrize("gsz,itmax,coef", [((32, 32, 32), 100000, 1.5), ((40, 28, 36), 100000, 1.3), ((48, 40, 200), 7, 1.5), ((48, 40, 200), 12, 1.5),
-                                            ((64, 64, 64), 100000, 1.5), ((24, 20, 1100), 9, 1.5)], ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+                                            ((64, 64, 64), 100000, 1.5), ((24, 20, 1100), 9, 1.5), ((24, 20, 28), 100000, 1.4)],
+                         ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
 def test_red_black_sor_two_iterations_per_pass_equals_one_per_pass(prec, gsz, itmax, coef):
     """Round 4: single-domain red-black SOR runs two iterations per pass over memory (rb4_k).  Same iteration count, same history, same field,
     bit for bit, as with one iteration per pass (czhip_set_rb4(0)) -- to convergence (whichever iteration of a pass converges: a converged
-    first one is re-run alone from the pass's input) and for fixed odd / even counts; and against the oracle."""
+    first one is re-run alone from the pass's input) and for fixed odd / even counts; and against the oracle.  Passes start at odd iterations,
+    so a solve that converges at an odd iteration must have re-run it (exact_reruns 1), one that converges at an even iteration must not."""
     from cubez_amd import CZ
     out = {}
     for on in (1, 0):
@@ -292,16 +294,45 @@ def test_red_black_sor_two_iterations_per_pass_equals_one_per_pass(prec, gsz, it
         try:
             assert cz.setup(list(gsz) + ["sor2sma", itmax, coef]) == 1
             itr = cz.solve()
-            out[on] = (itr, cz.res, list(cz.history()), cz.field().tobytes(), cz.info()["rb4_passes"])
+            info = cz.info()
+            out[on] = (itr, cz.res, list(cz.history()), cz.field().tobytes(), info["rb4_passes"], info["exact_reruns"])
         finally:
             cz.lib.czhip_set_rb4(1, -1, -1)
             cz.close()
     assert out[0][4] == 0 and out[1][4] > 0, (out[0][4], out[1][4])
+    # Iter of every case (the oracle's; asserted below): converged at an odd iteration = the first of an rb4 pass; Iter = ItrMax + 1: not converged
+    expected = {(32, 32, 32): 199, (40, 28, 36): 311, (64, 64, 64): 635, (24, 20, 28): 134, (48, 40, 200): itmax + 1, (24, 20, 1100): 3}
+    assert out[1][0] == expected[gsz]
+    converged = out[1][0] <= itmax
+    assert out[1][5] == (out[1][0] % 2 if converged else 0), (gsz, out[1][5])  # re-run exactly when the first iteration of a pass converged
+    assert out[0][5] == 0  # (one iteration per pass: nothing to re-run)
     assert out[1][0] == out[0][0] and out[1][3] == out[0][3]  # iteration count and field: bit for bit
     assert np.allclose(out[1][2], out[0][2], rtol=1e-12, atol=0) and abs(out[1][1] - out[0][1]) <= 1e-12 * out[0][1]  # (the partial sums are grouped by another tiling)
     o = O.run(gsz, "sor2sma", itmax, coef, None, kind="oracle", prec=prec, wide=True)
     assert out[1][0] == o.itr and out[1][3] == o.P.tobytes()
     assert np.allclose(out[1][2], [r for _, r in o.history], rtol=1e-11, atol=0)
+
+
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+@pytest.mark.parametrize("gsz,coef,converged", [((16, 16, 16), 0.8, 323), ((18, 16, 20), 1.0, 312)], ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_jacobi_two_sweeps_per_pass_to_convergence_vs_oracle(prec, gsz, coef, converged):
+    """The Jacobi counterpart: the whole-box pass makes two sweeps, passes start at odd iterations.  Converged at an odd iteration (323), the
+    pass went one sweep too far and its first sweep is re-run alone from the pass's input (exact_reruns 1); at an even one (312) nothing is
+    re-run.  Either way: iteration count, field bit for bit and history against the oracle."""
+    from cubez_amd import CZ
+    cz = CZ(prec, quiet=True)
+    try:
+        assert cz.setup(list(gsz) + ["jacobi", 100000, coef]) == 1
+        itr = cz.solve()
+        hist, P, info = cz.history(), cz.field(), cz.info()
+    finally:
+        cz.close()
+    o = O.run(gsz, "jacobi", 100000, coef, None, kind="oracle", prec=prec, wide=True)
+    assert o.itr == converged and itr == converged
+    assert info["pass_kind"] == 1, info  # PassPlan::WHOLE
+    assert info["exact_reruns"] == converged % 2, info
+    assert P.tobytes() == o.P.tobytes()
+    assert np.allclose(hist, [r for _, r in o.history], rtol=1e-11, atol=0)
 
 
 def test_convergence_stops_at_the_reference_iteration():

@@ -214,3 +214,40 @@ def test_sph_writer_restatement_matches_the_reference_file(prec):
     want = open(os.path.join(GOLDEN, f"sph_small_{prec}.sph"), "rb").read()
     got = O.sph_bytes([5, 4, 6], g["sph_in"], R(0.25), np.array([0.5, 0.25, 0.125], dtype=R))
     assert got == want
+
+
+def _bicg_parity():
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import bicg_parity
+    return bicg_parity
+
+
+@pytest.mark.parametrize("case", [c for c in _bicg_parity().CASES + _bicg_parity().DECOMP_CASES], ids=lambda c: c["id"])
+def test_bicgstab_parity_premise(case):
+    """The premise of tests/test_gpu_bicgstab_parity.py on the oracle alone: FP32 -- no dot product of the K iterations lies within its
+    summation bound of a float rounding boundary, and the runs with every dot at either edge of the bound are bit-identical to the unperturbed
+    one; FP64 -- the envelope of those runs stays below 1e-8 relative at every compared iteration count.  A failure here means: choose
+    another case, not: the GPU is wrong."""
+    BP = _bicg_parity()
+    if case["prec"] == "f32":
+        r = BP.premise_f32(case)
+    else:
+        for k in BP.ks(case):
+            r, _, _ = BP.envelope_f64(case, k + 1)
+    assert len(r.history) >= 3, "too short to say much about the recurrence"
+
+
+def test_exact_dot_mode_logs_every_dot_and_leaves_the_wide_path_alone():
+    """dots="exact": five dots per iteration, each the correctly rounded sum of the REAL products, within its bound of the wide (double,
+    loop-order) sum; the wide mode's result does not depend on the new mode existing."""
+    args = ((20, 18, 22), "pbicgstab", 4, 0.8, "jacobi")
+    for prec in ("f32", "f64"):
+        e = O.run(*args, prec=prec, dots="exact")
+        w = O.run(*args, prec=prec, wide=True)
+        assert [x[1] for x in e.dot_log] == ["rho", "q.r0", "t.s", "t.t", "r.r"] * len(e.history)
+        assert all(B > 0 and n == 18 * 16 * 20 for (_, _, _, B, n) in e.dot_log)
+        assert e.itr == w.itr
+        assert np.allclose([r for _, r in e.history], [r for _, r in w.history], rtol=1e-6 if prec == "f32" else 1e-12, atol=0)
+        w2 = O.run(*args, prec=prec, wide=True)
+        assert w2.P.tobytes() == w.P.tobytes() and w2.history == w.history and w.dot_log == []
