@@ -59,6 +59,7 @@ const char* printMethod(int t) {
     case LS_JACOBI_MAF: return "JACOBI_MAF";
     case LS_SOR2SMA_MAF: return "SOR2SMA_MAF";
     case LS_BICGSTAB_MAF: return "PBiCGSTAB_MAF";
+    case LS_PCG: return "PCG";
     default: return "NONE";
   }
 }
@@ -86,7 +87,7 @@ CZ::CZ() {
 CZ::~CZ() {
   czhip_sync();
   if (comm_cus > 0) reserve_comm_cus(0);  // the library context outlives this object
-  REAL_TYPE* arrs[] = {WRK, WRK2, P, RHS, pcg_p, pcg_p_, pcg_r, pcg_r0, pcg_q, pcg_s, pcg_s_, pcg_t_, pvt, MSK};
+  REAL_TYPE* arrs[] = {WRK, WRK2, P, RHS, pcg_p, pcg_p_, pcg_r, pcg_r0, pcg_q, pcg_s, pcg_s_, pcg_t_, cg_r, cg_z, cg_p[0], cg_p[1], cg_q, pvt, MSK};
   if (d_xc) (void)hipFree(d_xc);
   if (d_yc) (void)hipFree(d_yc);
   if (d_zc) (void)hipFree(d_zc);
@@ -209,6 +210,20 @@ void CZ::setLS(const char* q) {
     hist_name = "pbicgstab_maf.txt";
     setStrPre();
     SW_maf = 1;
+  } else if (!strcasecmp(q, "pcg")) {  // beyond the reference (DESIGN.md "PCG"): symmetric preconditioners only
+    ls_type = LS_PCG;
+    hist_name = "pcg.txt";
+    if (!strcasecmp(precon.c_str(), "none")) pc_type = LS_NONE;
+    else if (!strcasecmp(precon.c_str(), "jacobi")) pc_type = LS_JACOBI;
+    else {
+      Hostonly_ printf("Invalid preconditioner for pcg '%s' (none | jacobi)\n", precon.c_str());
+      exit(0);
+    }
+    // k relaxed Jacobi sweeps from zero are a polynomial in A: symmetric, and definite with A's sign for 0 < omega <= 1
+    if (pc_type == LS_JACOBI && !(ac1 > (REAL_TYPE)0 && ac1 <= (REAL_TYPE)1)) {
+      Hostonly_ printf("Invalid coefficient for pcg with jacobi '%g' (0 < coef <= 1: a symmetric definite preconditioner)\n", (double)ac1);
+      exit(0);
+    }
   } else {
     printf("Invalid solver\n");  // :799-802
     exit(0);
@@ -270,6 +285,7 @@ int CZ::Setup(int argc, char** argv) {
     }
     precon = argv[7];
   }
+  if (!strcasecmp(q, "pcg")) precon = (argc == 8 || argc == 11) ? argv[7] : "none";  // [none | jacobi]
   if (argc == 10) {  // :73-78
     div_type = 1;
     G_div[0] = atoi(argv[7]), G_div[1] = atoi(argv[8]), G_div[2] = atoi(argv[9]);
@@ -296,7 +312,7 @@ int CZ::Setup(int argc, char** argv) {
   setLS(q);
   if (!quiet) Hostonly_ {
     printf("Iterative Mehtod = %s\n", printMethod(ls_type));  // :194 (sic)
-    if (ls_type == LS_BICGSTAB || ls_type == LS_BICGSTAB_MAF) printf("Preconditioner = %s\n", printMethod(pc_type));
+    if (ls_type == LS_BICGSTAB || ls_type == LS_BICGSTAB_MAF || ls_type == LS_PCG) printf("Preconditioner = %s\n", printMethod(pc_type));
   }
 
   if (!quiet) Hostonly_ {  // :210-218
@@ -345,10 +361,15 @@ int CZ::Setup(int argc, char** argv) {
     pcg_r0 = czhip_alloc_s3d(size), pcg_q = czhip_alloc_s3d(size), pcg_s = czhip_alloc_s3d(size);
     pcg_s_ = czhip_alloc_s3d(size), pcg_t_ = czhip_alloc_s3d(size);
   }
+  const int narr = bicg ? 11 : ls_type == LS_PCG ? (pc_type == LS_JACOBI ? 8 : 7) : 3;
+  if (ls_type == LS_PCG) {  // zero-filled; only their inner boxes are ever written (the fused passes read the shells as zeros)
+    cg_r = czhip_alloc_s3d(size), cg_q = czhip_alloc_s3d(size), cg_p[0] = czhip_alloc_s3d(size), cg_p[1] = czhip_alloc_s3d(size);
+    if (pc_type == LS_JACOBI) cg_z = czhip_alloc_s3d(size);
+  }
   if (!quiet) Hostonly_ {
     const double arr = (double)(size[0] + 2 * gc) * (size[1] + 2 * gc) * (size[2] + 2 * gc) * sizeof(REAL_TYPE);
     printf("\n----------\n\n\tDevice memory per rank : %.1f MiB in %d arrays of (%d+4)x(%d+4)x(%d+4) %s\n", arr *
-           (bicg ? 11 : 3) / 1048576.0, bicg ? 11 : 3, size[0], size[1], size[2],
+           narr / 1048576.0, narr, size[0], size[1], size[2],
            sizeof(REAL_TYPE) == 4 ? "float" : "double");
   }
 
@@ -417,6 +438,9 @@ int CZ::Solve() {
     case LS_BICGSTAB_MAF:
       if (0 == (itr = PBiCGSTAB(res, P, RHS, flop, ls_type))) return 0;
       break;
+    case LS_PCG:
+      if (0 == (itr = PCG(res, P, RHS, flop))) return 0;
+      break;
     case LS_PCR_RB:
       if (0 == (itr = LSOR_PCR_RB(res, P, RHS, ItrMax, flop, ls_type))) return 0;
       break;
@@ -463,7 +487,7 @@ int CZ::Evaluate(int argc, char** argv) {
   if (!Solve()) return 0;
   if (!quiet) Hostonly_ {
     const double lups = 1.0 / res_normal * (double)(result_itr > ItrMax ? ItrMax : result_itr);
-    if (ls_type != LS_BICGSTAB && ls_type != LS_BICGSTAB_MAF)
+    if (ls_type != LS_BICGSTAB && ls_type != LS_BICGSTAB_MAF && ls_type != LS_PCG)
       printf("\n\tGPU time = %.6f s   %.1f MLUPS\n", solve_seconds, lups / solve_seconds * 1e-6);
     else
       printf("\n\tGPU time = %.6f s\n", solve_seconds);
@@ -1330,7 +1354,7 @@ REAL_TYPE CZ::Fdot2(REAL_TYPE* x, REAL_TYPE* y, double& flop) {
 
 // The work vectors the preconditioner solves into are allocated zero-filled and afterwards only written on the inner box,
 // so their guide cells and faces are zero for the whole run.
-bool CZ::xx_shell_is_zero(const REAL_TYPE* xx) const { return xx == pcg_p_ || xx == pcg_s_; }
+bool CZ::xx_shell_is_zero(const REAL_TYPE* xx) const { return xx == pcg_p_ || xx == pcg_s_ || (xx != nullptr && xx == cg_z); }
 
 // cz_Poisson.cpp:273-322
 // May PBiCGSTAB withhold `p = r + beta (p - omega q)` and `s = r - alpha q` and let the first pair of the preconditioner solve that follows
@@ -1556,6 +1580,106 @@ int CZ::PBiCGSTAB(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop, int s_t
     if (res < eps) break;  // :498
     rho_old = rho;
   }
+  return itr;
+}
+
+// Preconditioned conjugate gradient (beyond the reference; DESIGN.md "PCG").  The operator is symmetric and definite, and M^-1 is either the
+// identity (z IS r: no copy) or the 8 relaxed Jacobi sweeps from zero of PBiCGSTAB's preconditioner -- a polynomial in A, hence symmetric.
+//   r = b - A x;  for itr = 1 .. ItrMax:  z = M^-1 r;  rho = r.z;  p = z (itr 1) | z + beta p, beta = rho / rho_old;  q = A p;
+//   alpha = rho / p.q;  x = alpha p + x;  r = (-alpha) q + r;  res = sqrt(r.r * res_normal)
+// Every scalar is made on the device (cg_scal_k) from REAL-rounded double sums, so the host waits once per iteration, for r.r and rho.
+// CZ_CG_FUSE (default on): x, r and r.r in one pass (czhip_cg_update_async); in a single-domain run also the direction update inside the
+// SpMV pass (czhip_cg_dir_ax_async, ping-pong between cg_p[0] and cg_p[1]).  Off, and for the direction in decomposed runs: the update,
+// Comm_S(p), then the SpMV with its dot folded in.
+int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
+  const int gc = GUIDE;
+  hipStream_t st = stream();
+  const size_t nbytes = (size_t)(size[0] + 2 * gc) * (size[1] + 2 * gc) * (size[2] + 2 * gc) * sizeof(REAL_TYPE);
+  const double n = npts();
+  const bool pc = pc_type == LS_JACOBI;
+  const bool fuse = cfg.on(CZV_CG_FUSE, true);
+  const bool fuse_dir = fuse && numProc == 1;  // the direction pass reads z's and p's shells as zeros: single domain only
+  REAL_TYPE* const sc = reinterpret_cast<REAL_TYPE*>(d_res + 12);  // alpha, -alpha, beta, rho (cg_scal_k)
+  double* const d_rr = d_res + 5;
+  double* const d_pq = d_res + 3;                 // (the unfused SpMV writes q.q to d_res[4])
+  double* const d_rho = pc ? d_res + 2 : d_rr;    // none: rho is the r.r of the previous update
+  REAL_TYPE* const z = pc ? cg_z : cg_r;
+  res = 0.0;
+  cg_fused = 0;
+
+  calc_rk_async(cg_r, X, B, size, innerFidx, gc, cf);
+  flop += 14.0 * n;
+  if (!Comm_S(cg_r)) return 0;
+  REAL_TYPE rho = (REAL_TYPE)0;
+  if (!pc) {  // the one r.r that no update made
+    dot1_async(cg_r, size, innerFidx, gc, d_rr);
+    flop += 2.0 * n;
+    if (!Comm_SUM_dev(d_rr, 1)) return 0;
+    HIP_CHECK(hipMemcpyAsync(h_scal + 5, d_rr, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    rho = (REAL_TYPE)h_scal[5];
+  }
+  int cur = 0;  // cg_p[cur] is p
+  int itr;
+  for (itr = 1; itr <= ItrMax; itr++) {
+    if (!pc && fabs(rho) < FLT_MIN) {  // breakdown (as PBiCGSTAB)
+      itr = 0;
+      break;
+    }
+    if (pc) {
+      if (!Comm_S(cg_r)) return 0;  // (a decomposed pass reads the right-hand side in its ghost layer)
+      double fc = 0.0;
+      Preconditioner(cg_z, cg_r, fc, LS_JACOBI);
+      flop += fc;
+      dot2_async(cg_r, cg_z, size, innerFidx, gc, d_rho);
+      flop += 2.0 * n;
+      if (!Comm_SUM_dev(d_rho, 1)) return 0;
+    }
+    cg_scalar_async(0, d_rho, itr == 1, sc);  // rho; beta = rho / rho_old
+    if (fuse_dir) {
+      czhip_cg_dir_ax_async(cg_p[cur ^ 1], cg_q, z, cg_p[cur], itr == 1 ? nullptr : sc + 2, size, innerFidx, gc, cf, d_pq);
+      cur ^= 1;
+      cg_fused++;
+    } else {
+      if (itr == 1) HIP_CHECK(hipMemcpyAsync(cg_p[cur], z, nbytes, hipMemcpyDeviceToDevice, st));
+      else triad_async(cg_p[cur], cg_p[cur], z, (REAL_TYPE)0, size, innerFidx, gc, sc + 2);  // p = beta p + z
+      if (!Comm_S(cg_p[cur])) return 0;
+      calc_ax_dots_async(cg_q, cg_p[cur], cg_p[cur], size, innerFidx, gc, cf, nullptr, d_pq);
+    }
+    if (itr > 1) flop += 2.0 * n;
+    flop += 13.0 * n + 2.0 * n;
+    if (!Comm_SUM_dev(d_pq, 1)) return 0;
+    cg_scalar_async(1, d_pq, 0, sc);  // alpha = rho / p.q
+    REAL_TYPE* const p = cg_p[cur];
+    if (fuse) {
+      czhip_cg_update_async(X, cg_r, p, cg_q, sc, size, innerFidx, gc, d_rr);
+    } else {
+      triad_async(X, p, X, (REAL_TYPE)0, size, innerFidx, gc, sc);
+      triad_async(cg_r, cg_q, cg_r, (REAL_TYPE)0, size, innerFidx, gc, sc + 1);
+      dot1_async(cg_r, size, innerFidx, gc, d_rr);
+    }
+    flop += 6.0 * n;
+    if (!Comm_SUM_dev(d_rr, 1)) return 0;
+    // the one wait of the iteration: r.r (and this iteration's rho)
+    HIP_CHECK(hipMemcpyAsync(h_scal + 2, d_res + 2, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    const REAL_TYPE rr = (REAL_TYPE)h_scal[5];
+    if (pc) {
+      rho = (REAL_TYPE)h_scal[2];
+      if (fabs(rho) < FLT_MIN) {  // (found after the iteration's launches: the iterate is void, like any failed solve)
+        itr = 0;
+        break;
+      }
+    }
+    res = rr;
+    res *= res_normal;
+    res = sqrt(res);
+    history.push_back(res);
+    if (res < eps) break;
+    if (!pc) rho = rr;
+  }
+  if (itr > ItrMax) itr = ItrMax;
+  if (!Comm_S(X)) return 0;  // (the ghost layers of the result, as PBiCGSTAB leaves them)
   return itr;
 }
 
@@ -1798,6 +1922,7 @@ int cz_info(const cz_handle* h, int what) {
     case 10: return c.bicg_fused;
     case 11: return c.rb4_passes;
     case 12: return c.exact_reruns;
+    case 13: return c.cg_fused;
     case 5: return comm_transport_ranks(c.comm);
     case 6: return c.comm_cus;
     case 7: return c.last_plan.kind;

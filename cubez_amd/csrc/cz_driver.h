@@ -14,7 +14,7 @@ typedef CZ_REAL REAL_TYPE;  // cz_Define.h:28-37
 #define GUIDE 2             // cz_Define.h:40
 
 // cz_Define.h:68-89 (only the solvers of the hot path are accepted; the others are rejected by setLS)
-enum LinearSolver { LS_NONE = 0, LS_PSOR = 1, LS_SOR2SMA, LS_BICGSTAB, LS_JACOBI, LS_PCR = 5, LS_PCR_EDA, LS_PCR_ESA, LS_PCR_RB, LS_PCR_RB_ESA, LS_PCR_J_ESA, LS_PSOR_MAF = 11, LS_SOR2SMA_MAF, LS_BICGSTAB_MAF, LS_JACOBI_MAF, LS_PCR_MAF, LS_PCR_EDA_MAF, LS_PCR_ESA_MAF, LS_PCR_RB_MAF, LS_PCR_RB_ESA_MAF };
+enum LinearSolver { LS_NONE = 0, LS_PSOR = 1, LS_SOR2SMA, LS_BICGSTAB, LS_JACOBI, LS_PCR = 5, LS_PCR_EDA, LS_PCR_ESA, LS_PCR_RB, LS_PCR_RB_ESA, LS_PCR_J_ESA, LS_PSOR_MAF = 11, LS_SOR2SMA_MAF, LS_BICGSTAB_MAF, LS_JACOBI_MAF, LS_PCR_MAF, LS_PCR_EDA_MAF, LS_PCR_ESA_MAF, LS_PCR_RB_MAF, LS_PCR_RB_ESA_MAF, LS_PCG };  // (LS_PCG: beyond the reference)
 
 // CB_Define_stub.h:64-70 / cz_fparam.fi:10-16
 enum { I_minus = 0, I_plus, J_minus, J_plus, K_minus, K_plus };
@@ -54,6 +54,8 @@ class CZ {
   REAL_TYPE *d_xc = nullptr, *d_yc = nullptr, *d_zc = nullptr, *pvt = nullptr;
   REAL_TYPE *pcg_p = nullptr, *pcg_p_ = nullptr, *pcg_r = nullptr, *pcg_r0 = nullptr, *pcg_q = nullptr, *pcg_s = nullptr,
             *pcg_s_ = nullptr, *pcg_t_ = nullptr;
+  // PCG's work vectors (the pcg_* above are BiCGSTAB's, named as in the reference); allocated only when pcg is selected
+  REAL_TYPE *cg_r = nullptr, *cg_z = nullptr, *cg_p[2] = {nullptr, nullptr}, *cg_q = nullptr;
 
   // ---- build-specific state
   bool quiet = false;
@@ -71,6 +73,7 @@ class CZ {
   bool pairs_ok = true;          // decomposed runs: EVERY brick can run the fused pass (agreed at set-up; the exchange pattern depends on it)
   int rb4_passes = 0;            // two-iteration red-black passes (rb4_k) of the last RBSOR solve (cz_info 11)
   int exact_reruns = 0;          // converged first iterations of a fused pass re-run alone from the pass's input, last JACOBI / RBSOR solve (cz_info 12)
+  int cg_fused = 0;              // iterations of the last PCG solve whose direction update was made inside the SpMV pass (cz_info 13)
   int bicg_fused = 0;            // vector updates of the last BiCGSTAB solve that were made inside the first pair of a preconditioner solve (cz_info 10)
   bool in_precond = false;       // inside Preconditioner: an unchecked solve does not drain the queue (the caller's next launch follows in stream order)
   int last_lag = 0;              // the last stationary solve ran its all-reduce + test one pass behind (cz_info)
@@ -153,6 +156,7 @@ class CZ {
   REAL_TYPE Fdot2(REAL_TYPE* x, REAL_TYPE* y, double& flop);
   void Preconditioner(REAL_TYPE* xx, REAL_TYPE* bb, double& flop, int s_type, const BMade* made = nullptr);
   int PBiCGSTAB(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop, int s_type);
+  int PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop);  // beyond the reference (DESIGN.md "PCG")
 
   // cz_comm.cpp replacements (no-ops when numProc == 1, like cz_comm.cpp:25,76,104)
   bool Comm_S(REAL_TYPE* X, const int* skip_flag = nullptr);

@@ -73,6 +73,9 @@ void triad_dots_async(CZ_REAL* z, const CZ_REAL* x, const CZ_REAL* y, const CZ_R
 // BiCGSTAB's alpha (step 1) / omega (step 2) made on the device from the dot products of the launch before: sc_dev[0..3] = alpha, omega, -alpha,
 // -omega; the *_dev arguments of the updates above read them there, so the host does not wait for the dot products in mid-iteration
 void bicg_scalar_async(int step, const double* dots_dev, CZ_REAL rho, CZ_REAL* sc_dev);
+// PCG's rho / beta (step 0, from the dot in dot_dev[0]; first: no beta) and alpha (step 1, from p.Ap in dot_dev[0]) made on the device:
+// sc_dev[0..3] = alpha, -alpha, beta, rho (cg_scal_k)
+void cg_scalar_async(int step, const double* dot_dev, int first, CZ_REAL* sc_dev);
 // czhip_jacobi2_from_zero_made_async with the coefficient a of the made right-hand side read from the device (a_dev, may be null)
 int pass_from_zero_made(const CZ_REAL* u_shape, CZ_REAL* w, CZ_REAL* b_out, int op, const CZ_REAL* x, const CZ_REAL* y, const CZ_REAL* z, CZ_REAL a,
                         const CZ_REAL* a_dev, CZ_REAL bb, const int* sz, const int* idx, const int* idx1, int g, const CZ_REAL* cf, CZ_REAL omg,

@@ -286,6 +286,85 @@ triad_dots_k(REAL* Z, const REAL* X, const REAL* Y, const REAL* W, REAL a, EGeom
   }
 }
 
+// PCG's update (beyond the reference): x = alpha*p + x, r = (-alpha)*q + r (blas_triad twice) and dst[0] = sum r*r, one pass over the four
+// arrays.  alpha and -alpha come from the device (g.pa / g.pb, made by cg_scal_k); same structure and launch shape as triad_dots_k.
+template <int V>
+__global__ void __launch_bounds__(256)
+cg_update_k(REAL* X, REAL* Rr, const REAL* Pd, const REAL* Q, EGeom g, int nplanes, double* partials, double* dst, unsigned* counter) {
+  __shared__ double wsum[4];
+  __shared__ int last_flag;
+  const long long f = g.F0 + (long long)blockIdx.x * 256 + threadIdx.x;
+  const REAL a = *g.pa, na = *g.pb;
+  double acc = 0.0;
+  if (f < g.Fend) {
+    const int kv = (int)(f % g.R);
+    unsigned mk = 0;
+#pragma unroll
+    for (int cc = 0; cc < V; cc++) {
+      const int kk = kv * V + cc;
+      if (kk >= g.kk0 && kk <= g.kk1) mk |= 1u << cc;
+    }
+    if (mk != 0) {
+      const long long eo = egeom_eo<V>(g, f);
+      for (int pl = blockIdx.y; pl < nplanes; pl += gridDim.y) {
+        const long long pe = (long long)(g.jj0 + pl) * g.PSE + eo;
+        const Vec<V> p = ldve<V>(Pd, pe), q = ldve<V>(Q, pe), x = ldve<V>(X, pe), r = ldve<V>(Rr, pe);
+        Vec<V> xo, ro;
+#pragma unroll
+        for (int cc = 0; cc < V; cc++) {
+          xo.v[cc] = a * p.v[cc] + x.v[cc];
+          ro.v[cc] = na * q.v[cc] + r.v[cc];
+          const REAL rr = ro.v[cc] * ro.v[cc];
+          if (mk & (1u << cc)) acc += (double)rr;
+        }
+        if (mk == (1u << V) - 1) {
+          stve<V>(X, pe, xo);
+          stve<V>(Rr, pe, ro);
+        } else {
+#pragma unroll
+          for (int cc = 0; cc < V; cc++)
+            if (mk & (1u << cc)) X[pe + cc] = xo.v[cc], Rr[pe + cc] = ro.v[cc];
+        }
+      }
+    }
+  }
+  const double s = block_sum<256>(acc, wsum);
+  const int nblk = gridDim.x * gridDim.y;
+  const int me = blockIdx.y * gridDim.x + blockIdx.x;
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(&partials[me], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last_flag = arrive_and_test_last(counter, nblk);
+  }
+  __syncthreads();
+  if (last_flag) {
+    double x = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += 256) x += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    const double tot = block_sum<256>(x, wsum);
+    if (threadIdx.x == 0) {
+      dst[0] = tot;
+      *counter = 0u;
+    }
+  }
+}
+
+// PCG's scalars on the device, with the host's operations (REAL division of REAL-rounded double sums), like bicg_scal_k.
+// sc[0] = alpha, sc[1] = -alpha, sc[2] = beta, sc[3] = rho (the REAL of the current iteration; the previous one until STEP 0 replaces it).
+//   STEP 0: rho = (REAL)dot[0];  beta = rho / rho_old unless `first`;  rho_old <- rho
+//   STEP 1: alpha = rho / (REAL)dot[0]   (dot = p . A p)
+template <int STEP>
+__global__ void cg_scal_k(const double* __restrict__ dot, int first, REAL* __restrict__ sc) {
+  if (STEP == 0) {
+    const REAL rho = (REAL)dot[0];
+    if (!first) sc[2] = rho / sc[3];
+    sc[3] = rho;
+  } else {
+    const REAL pq = (REAL)dot[0];
+    const REAL alpha = sc[3] / pq;
+    sc[0] = alpha, sc[1] = -alpha;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // bc_k (cz_solver.f90:22-191): the sin*sin table is evaluated on the HOST with the host libm -- the same sinf/sin
 // the reference's Fortran calls -- so the Dirichlet data are bit-identical to the reference's; the kernels only

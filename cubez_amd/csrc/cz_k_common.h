@@ -37,7 +37,7 @@ struct Geom {
   long long last_eo = 0;  // ... this, so that its last vector is not read beyond the array (values clamped away are never used)
 };
 
-enum { MODE_JACOBI = 0, MODE_RB = 1, MODE_AX = 2, MODE_RK = 3 };
+enum { MODE_JACOBI = 0, MODE_RB = 1, MODE_AX = 2, MODE_RK = 3, MODE_DIRAX = 4 };
 
 // In-kernel finalisation of the residual: the workgroup that arrives last sums the per-workgroup partials in a fixed
 // order (deterministic) and, if asked, performs the convergence bookkeeping of cz_Poisson.cpp:67-77 -- no extra

@@ -6,6 +6,10 @@
 //   RB      cz_solver.f90:466-480   same, in place (OUT == P), only points of one colour
 //   AX      cz_blas.f90:626-632     out = ss - dd*p
 //   RK      cz_blas.f90:705-711     out = b - (ss - dd*p)
+//   DIRAX   PCG (beyond the reference): the operand is the new search direction u = z + beta*p_old, made at every stencil point as it is
+//           loaded (P = z, B = p_old); out = ss - dd*u as AX, u written to the inner box of a second array, fin.dst[0] = sum u*out.  MAF = 0
+//           only: its MafArgs slot carries the update instead of metric terms -- xc = beta on the device (nullptr: u = z, the first
+//           direction), pvt = the array u is written to.  Reads every operand's shell, so z and p_old must be zero outside the inner box.
 // with ss = c1*p(i+1) + c2*p(i-1) + c3*p(j+1) + c4*p(j-1) + c5*p(k+1) + c6*p(k-1), left to right.
 // Elements outside the inner box are never written.
 // ------------------------------------------------------------------------------------------------------------
@@ -40,7 +44,23 @@ stencil_k(const REAL* P, const REAL* B, REAL* OUT, Coef c, Geom g, int par, doub
 
   double acc = 0.0, acc2 = 0.0;
   const bool ax_dots = (MODE == MODE_AX) && fin.ax_dots;
-  const bool ldb = (MODE != MODE_AX) || ax_dots;           // does the step need the second input vector?
+  const bool ldb = (MODE != MODE_AX && MODE != MODE_DIRAX) || ax_dots;  // does the step need the second input vector?
+  // the operand at element offset e of a plane that starts at Pp (a row of P): P itself, or MODE_DIRAX's z + beta*p_old
+  const REAL* const dir_beta = (MODE == MODE_DIRAX) ? ma.xc : nullptr;
+  REAL beta = (REAL)0;
+  if (MODE == MODE_DIRAX && dir_beta) beta = *dir_beta;
+  auto ldop = [&](const REAL* Pp, long long e) -> Vec<V> {
+    Vec<V> u = ldve<V>(Pp, e);
+    if (MODE == MODE_DIRAX && dir_beta) {
+      const Vec<V> po = ldve<V>(B + (Pp - P), e);
+#pragma unroll
+      for (int cc = 0; cc < V; cc++) {
+        const REAL bp = beta * po.v[cc];
+        u.v[cc] = u.v[cc] + bp;
+      }
+    }
+    return u;
+  };
   const REAL* Bsrc = (MODE == MODE_AX) ? fin.doty : B;      // b of the sweep / y of the fused dot products
 
   if (ja <= jb && fb < g.Fend) {
@@ -102,8 +122,8 @@ stencil_k(const REAL* P, const REAL* B, REAL* OUT, Coef c, Geom g, int par, doub
 #pragma unroll
     for (int m = 0; m < M; m++) {
       const bool ok = f[m] < lim_ld;
-      pm[m] = ok ? ldve<V>(Pm, eo[m]) : zerov<V>();
-      pc[m] = ok ? ldve<V>(Pc, eo[m]) : zerov<V>();
+      pm[m] = ok ? ldop(Pm, eo[m]) : zerov<V>();
+      pc[m] = ok ? ldop(Pc, eo[m]) : zerov<V>();
     }
     // stage plane ja (own vectors + halo rows) into LDS buffer 0
     {
@@ -111,9 +131,9 @@ stencil_k(const REAL* P, const REAL* B, REAL* OUT, Coef c, Geom g, int par, doub
 #pragma unroll
       for (int m = 0; m < M; m++) buf[R + t + m * TB] = pc[m];
       for (int h = t; h < R; h += TB) {
-        buf[h] = ldve<V>(Pc, eoff(fb - R + h));
+        buf[h] = ldop(Pc, eoff(fb - R + h));
         const long long fh = fb + g.S + h;
-        buf[R + g.S + h] = (fh < lim_ld) ? ldve<V>(Pc, eoff(fh)) : zerov<V>();
+        buf[R + g.S + h] = (fh < lim_ld) ? ldop(Pc, eoff(fh)) : zerov<V>();
       }
     }
     if (PF) {
@@ -121,7 +141,7 @@ stencil_k(const REAL* P, const REAL* B, REAL* OUT, Coef c, Geom g, int par, doub
       const REAL* Bc = Bsrc + (long long)ja * g.PSE;
 #pragma unroll
       for (int m = 0; m < M; m++) {
-        pn[m] = (f[m] < lim_ld) ? ldve<V>(Pn, lim(eo[m], ja + 1)) : zerov<V>();
+        pn[m] = (f[m] < lim_ld) ? ldop(Pn, lim(eo[m], ja + 1)) : zerov<V>();
         if (ldb) bb[m] = (f[m] < g.Fend) ? ldve<V>(Bc, eo[m]) : zerov<V>();
       }
     }
@@ -140,7 +160,7 @@ stencil_k(const REAL* P, const REAL* B, REAL* OUT, Coef c, Geom g, int par, doub
           const REAL* Bn = Bsrc + (long long)(jj + 1) * g.PSE;
 #pragma unroll
           for (int m = 0; m < M; m++) {
-            pnn[m] = (f[m] < lim_ld) ? ldve<V>(Pnn, lim(eo[m], jj + 2)) : zerov<V>();
+            pnn[m] = (f[m] < lim_ld) ? ldop(Pnn, lim(eo[m], jj + 2)) : zerov<V>();
             if (ldb) bbn[m] = (f[m] < g.Fend) ? ldve<V>(Bn, eo[m]) : zerov<V>();
           }
         }
@@ -148,7 +168,7 @@ stencil_k(const REAL* P, const REAL* B, REAL* OUT, Coef c, Geom g, int par, doub
         const REAL* Bc = Bsrc + (long long)jj * g.PSE;
 #pragma unroll
         for (int m = 0; m < M; m++) {
-          pn[m] = (f[m] < lim_ld) ? ldve<V>(Pn, lim(eo[m], jj + 1)) : zerov<V>();
+          pn[m] = (f[m] < lim_ld) ? ldop(Pn, lim(eo[m], jj + 1)) : zerov<V>();
           if (ldb) bb[m] = (f[m] < g.Fend) ? ldve<V>(Bc, eo[m]) : zerov<V>();
         }
       }
@@ -156,9 +176,9 @@ stencil_k(const REAL* P, const REAL* B, REAL* OUT, Coef c, Geom g, int par, doub
       Vec<V> hlo = zerov<V>(), hhi = zerov<V>();
       const bool halo_in_regs = (R <= TB);
       if (more && halo_in_regs && t < R) {
-        hlo = ldve<V>(Pn, lim(eo_lo, jj + 1));
+        hlo = ldop(Pn, lim(eo_lo, jj + 1));
         const long long fh = fb + g.S + t;
-        if (fh < lim_ld) hhi = ldve<V>(Pn, lim(eo_hi, jj + 1));
+        if (fh < lim_ld) hhi = ldop(Pn, lim(eo_hi, jj + 1));
       }
 
       // ---- update plane jj
@@ -221,7 +241,7 @@ stencil_k(const REAL* P, const REAL* B, REAL* OUT, Coef c, Geom g, int par, doub
             o.v[cc] = pp + dp;
             const REAL d2 = dp * dp;
             if (wmask & (1u << cc)) acc += (double)d2;
-          } else if (MODE == MODE_AX) {
+          } else if (MODE == MODE_AX || MODE == MODE_DIRAX) {
             o.v[cc] = ss - c.dd * pp;
           } else {
             o.v[cc] = bb[m].v[cc] - (ss - c.dd * pp);
@@ -236,6 +256,22 @@ stencil_k(const REAL* P, const REAL* B, REAL* OUT, Coef c, Geom g, int par, doub
               acc += (double)oy;
               acc2 += (double)oo;
             }
+          }
+        }
+        if (MODE == MODE_DIRAX) {
+          // the direction itself (pc[m]) to its own array, and sum u*out for dot(p, A p)
+          REAL* Uc = const_cast<REAL*>(ma.pvt) + (long long)jj * g.PSE;
+#pragma unroll
+          for (int cc = 0; cc < V; cc++) {
+            const REAL uq = pc[m].v[cc] * o.v[cc];
+            if (wmask & (1u << cc)) acc += (double)uq;
+          }
+          if (wmask == (1u << V) - 1) {
+            stve<V>(Uc, eo[m], pc[m]);
+          } else {
+#pragma unroll
+            for (int cc = 0; cc < V; cc++)
+              if (wmask & (1u << cc)) Uc[eo[m] + cc] = pc[m].v[cc];
           }
         }
         if (MODE == MODE_RB) {
@@ -274,9 +310,9 @@ stencil_k(const REAL* P, const REAL* B, REAL* OUT, Coef c, Geom g, int par, doub
           }
         } else {
           for (int h = t; h < R; h += TB) {
-            nbuf[h] = ldve<V>(Pn, lim(eoff(fb - R + h), jj + 1));
+            nbuf[h] = ldop(Pn, lim(eoff(fb - R + h), jj + 1));
             const long long fh = fb + g.S + h;
-            nbuf[R + g.S + h] = (fh < lim_ld) ? ldve<V>(Pn, lim(eoff(fh), jj + 1)) : zerov<V>();
+            nbuf[R + g.S + h] = (fh < lim_ld) ? ldop(Pn, lim(eoff(fh), jj + 1)) : zerov<V>();
           }
         }
       }
@@ -294,7 +330,7 @@ stencil_k(const REAL* P, const REAL* B, REAL* OUT, Coef c, Geom g, int par, doub
     }
   }
 
-  if (MODE == MODE_JACOBI || MODE == MODE_RB || ax_dots) {
+  if (MODE == MODE_JACOBI || MODE == MODE_RB || MODE == MODE_DIRAX || ax_dots) {
     __syncthreads();
     const double s = block_sum<TB>(acc, wsum);
     double s2 = 0.0;

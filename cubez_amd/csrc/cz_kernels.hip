@@ -1356,3 +1356,66 @@ void bc_async(const int* sz, int g, REAL* p, REAL dh, const REAL* org, const int
   HIP_CHECK(hipGetLastError());
 }
 }  // namespace czhip_internal
+
+// ------------------------------------------------------------------------------------------------------------
+// PCG (beyond the reference; CZ::PCG, DESIGN.md "PCG"): the update pass, the direction + SpMV pass and the scalars
+// ------------------------------------------------------------------------------------------------------------
+namespace czhip_internal {
+// STEP 0: rho from dot_dev[0] (beta = rho / rho_old unless first); STEP 1: alpha = rho / dot_dev[0] (cg_scal_k; sc_dev[0..3] = alpha, -alpha,
+// beta, rho)
+void cg_scalar_async(int step, const double* dot_dev, int first, REAL* sc_dev) {
+  if (step == 0) hipLaunchKernelGGL(cg_scal_k<0>, dim3(1), dim3(1), 0, ctx.stream, dot_dev, first, sc_dev);
+  else hipLaunchKernelGGL(cg_scal_k<1>, dim3(1), dim3(1), 0, ctx.stream, dot_dev, first, sc_dev);
+  HIP_CHECK(hipGetLastError());
+}
+}  // namespace czhip_internal
+
+extern "C" {
+void czhip_cg_update_async(CZ_REAL* x, CZ_REAL* r, const CZ_REAL* p, const CZ_REAL* q, const CZ_REAL* alpha_dev, const int* sz, const int* idx, int g,
+                           double* dots_dev) {
+  ensure_init();
+  const Box b = make_box(sz, idx, g);
+  if (b.empty) {
+    HIP_CHECK(hipMemsetAsync(dots_dev, 0, sizeof(double), ctx.stream));
+    return;
+  }
+  const int nplanes = b.jj1 - b.jj0 + 1;
+  ScopedTimer tm(LBL_EWISE);
+  // the launch shape of triad_dots_async
+  if (rows_ok(b, {x, r, p, q})) {
+    EGeom e = make_egeom<VW>(b);
+    e.pa = alpha_dev, e.pb = alpha_dev + 1;
+    const unsigned gx = (unsigned)((e.Fend - e.F0 + 255) / 256);
+    const unsigned gy = (unsigned)std::max(1, std::min(nplanes, (int)(4096 / gx)));
+    ensure_partials((size_t)gx * gy);
+    hipLaunchKernelGGL((cg_update_k<VW>), dim3(gx, gy), dim3(256), 0, ctx.stream, x, r, p, q, e, nplanes, ctx.partials, dots_dev, ctx.counter);
+  } else {
+    EGeom e = make_egeom<1>(b);
+    e.pa = alpha_dev, e.pb = alpha_dev + 1;
+    const unsigned gx = (unsigned)((e.Fend - e.F0 + 255) / 256);
+    const unsigned gy = (unsigned)std::max(1, std::min(nplanes, (int)(4096 / gx)));
+    ensure_partials((size_t)gx * gy);
+    hipLaunchKernelGGL((cg_update_k<1>), dim3(gx, gy), dim3(256), 0, ctx.stream, x, r, p, q, e, nplanes, ctx.partials, dots_dev, ctx.counter);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+void czhip_cg_dir_ax_async(CZ_REAL* p_new, CZ_REAL* q, const CZ_REAL* z, const CZ_REAL* p_old, const CZ_REAL* beta_dev, const int* sz, const int* idx,
+                           int g, const CZ_REAL* cf, double* dots_dev) {
+  ensure_init();
+  const Box bx = make_box(sz, idx, g);
+  if (bx.empty) {
+    HIP_CHECK(hipMemsetAsync(dots_dev, 0, sizeof(double), ctx.stream));
+    return;
+  }
+  if (!beta_dev) p_old = z;  // (the first direction: p_old is not read)
+  Fin fin;
+  fin.dst = dots_dev, fin.counter = ctx.counter;
+  MafArgs da{beta_dev, nullptr, nullptr, p_new};  // MODE_DIRAX's reading of the slot (cz_k_stencil.h)
+  const Coef c = make_coef(cf, (REAL)0);
+  if (rows_ok(bx, {z, p_old, q, p_new}))
+    launch_stencil_inst<VW, 512, 2, 0, MODE_DIRAX>(z, p_old, q, c, bx, 0, ctx.tune.tj, nullptr, nullptr, fin, da);
+  else
+    launch_stencil_inst<1, 256, 2, 0, MODE_DIRAX>(z, p_old, q, c, bx, 0, ctx.tune.tj, nullptr, nullptr, fin, da);
+}
+}  // extern "C"

@@ -300,6 +300,17 @@ int czhip_set_comm_cus(int k);
 /* self-test: numerators (of 2^32) whose quotient by d in the two-stage pass differs from the IEEE division (expected 0); -1 = divisor not eligible */
 long long czhip_selftest_fastdiv(CZ_REAL d);
 
+/* PCG (beyond the reference; DESIGN.md "PCG"), the two passes of its iteration:
+ * czhip_cg_update_async: x = alpha*p + x, r = (-alpha)*q + r on the inner box (blas_triad_ twice) and dots_dev[0] = r.r (per-point products in
+ *   REAL, summed in double), one pass.  alpha_dev[0] = alpha, alpha_dev[1] = -alpha, read on the device.
+ * czhip_cg_dir_ax_async: u = z + beta*p_old at every point the 7-point stencil reads, u written to the inner box of p_new, q = A u
+ *   (blas_calc_ax_) and dots_dev[0] = u.q, one pass.  beta_dev: beta on the device; nullptr: u = z (p_old is not read).  Single-domain
+ *   arrays only: z and p_old must be zero outside the inner box (their faces and guide cells are read as operands); p_new is not p_old. */
+void czhip_cg_update_async(CZ_REAL* x, CZ_REAL* r, const CZ_REAL* p, const CZ_REAL* q, const CZ_REAL* alpha_dev, const int* sz, const int* idx, int g,
+                           double* dots_dev);
+void czhip_cg_dir_ax_async(CZ_REAL* p_new, CZ_REAL* q, const CZ_REAL* z, const CZ_REAL* p_old, const CZ_REAL* beta_dev, const int* sz, const int* idx,
+                           int g, const CZ_REAL* cf, double* dots_dev);
+
 /* Convergence bookkeeping on the device (cz_Poisson.cpp:67-77): res = sqrt(res_dev[0]*res_normal);
  * hist_dev[itr] = res; if (res < eps && !*flag) { *flag = 1; conv_itr_dev[0] = itr; }.  No-op when
  * already converged. */
@@ -338,7 +349,8 @@ double cz_last_solve_seconds(const cz_handle*);
  * overlapped), 8 ghost layers exchanged per pass, 9 rotating field buffers; 10 vector updates of the last BiCGSTAB solve that were made inside
  * the first pair of the preconditioner solve they feed (czhip_jacobi2_from_zero_made_async); 11 passes of the last red-black SOR solve that made
  * two iterations each (czhip_rbsor4_async); 12 converged iterations of the last Jacobi or red-black SOR solve that were the first of a fused pass
- * (a pair of sweeps, or an rb4 pass of two iterations) and were therefore re-run alone from the pass's untouched input to give the converged iterate. */
+ * (a pair of sweeps, or an rb4 pass of two iterations) and were therefore re-run alone from the pass's untouched input to give the converged iterate;
+ * 13 iterations of the last PCG solve whose search direction was made inside the SpMV pass (czhip_cg_dir_ax_async). */
 int cz_info(const cz_handle*, int what);
 double cz_kernel_ms(const cz_handle*, const char* label); /* HIP-event time of a labelled section, ms (avg per launch) */
 

@@ -1,6 +1,6 @@
 """Rates of arbitrary runs of the restated driver, one line each:
     python3 tools/rate.py prec:nx,ny,nz:solver[:precond][@ENV=VALUE,...] ...
-stationary solvers: MLUPS over unchecked sweeps (cz_sweeps) + mean kernel time by label; pbicgstab: ms per iteration of a 10-iteration solve."""
+stationary solvers: MLUPS over unchecked sweeps (cz_sweeps) + mean kernel time by label; pbicgstab, pcg: ms per iteration of a 10-iteration solve."""
 import os
 import sys
 import time
@@ -45,12 +45,13 @@ for spec in sys.argv[1:]:
         if "CZHIP_UNIT_COEF" in env:
             cz.lib.czhip_set_unit_coef(int(env["CZHIP_UNIT_COEF"]))
         pts = (gsz[0] - 2) * (gsz[1] - 2) * (gsz[2] - 2)
-        if solver.startswith("pbicgstab"):
+        if solver.startswith("pbicgstab") or solver == "pcg":
+            n10 = 11 if solver.startswith("pbicgstab") else 10  # (BiCGSTAB makes ItrMax - 1 iterations, PCG ItrMax)
             assert cz.setup(gsz + [solver, 3, COEF.get(pc, 0.8), pc or "jacobi"]) == 1
             cz.solve()
             cz.close()
             cz = CZ(prec, quiet=True)
-            assert cz.setup(gsz + [solver, 11, COEF.get(pc, 0.8), pc or "jacobi"]) == 1
+            assert cz.setup(gsz + [solver, n10, COEF.get(pc, 0.8), pc or "jacobi"]) == 1
             cz.lib.czhip_sync()
             t0 = time.perf_counter()
             cz.solve()
