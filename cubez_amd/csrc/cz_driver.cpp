@@ -760,6 +760,11 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
   };
   std::vector<Launch> launches;
   exact_reruns = 0;
+  // THREE sweeps per pass (jac3_k) where the whole inner box is one launch of one rank with constant coefficients, outside a preconditioner
+  // solve; triples while three sweeps remain, then the pair or the single sweep
+  const bool jac3 = plan.kind == PassPlan::WHOLE && numProc == 1 && !maf && !in_precond && itr_max >= 3 &&
+                    czhip_jacobi3_async(X, WRK, B, size, innerFidx, gc, cf, ac1, d_res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 1) != 0;
+  jac3_passes = 0;
   int idx1[6];  // index range of the first sweep of a pair: one layer into the ghost cells across rank-internal faces
   for (int f = 0; f < 6; f++) idx1[f] = innerFidx[f] + ((nID[f] >= 0) ? ((f & 1) ? 1 : -1) : 0);
   if (plan.depth == 2 && numProc > 1) {
@@ -812,6 +817,13 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
         czhip_check2_async(d_res, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);
       }
       done = 2;
+    } else if (pass && jac3 && itr + 2 <= itr_max && !(plan.zero_start && itr == 1)) {
+      if (!czhip_jacobi3_async(src, dst, B, size, innerFidx, gc, cf, ac1, d_res, res_normal, eps, itr, converge_check ? d_hist : nullptr, d_flag,
+                               d_flag + 1, skip, 0)) {  // :58 + :67-77, three times
+        cz_fatal(1, "error : the three-sweep pass refused after a successful probe\n");
+      }
+      done = 3;
+      jac3_passes++;
     } else if (pass) {  // the whole inner box in one launch
       const bool in_kernel_check = converge_check && numProc == 1;
       int launched;
@@ -903,8 +915,15 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
           last = &l;
           break;
         }
-      if (last->nsweep == 2 && ret == last->first_itr) {
-        // the first sweep of a fused pair converged: the pair wrote time n+2 into its destination; its source is
+      if (last->nsweep == 3 && ret == last->first_itr + 1) {
+        // the second sweep of a three-sweep pass converged: its source is untouched, one pair from it reproduces the converged iterate
+        if (!czhip_jacobi2_async(buf[last->src], buf[(last->src + 1) % nbuf], B, size, innerFidx, idx1, gc, cf, ac1, d_res + 4, 0.0, 0.0, 0, nullptr,
+                                 nullptr, nullptr, nullptr)) {
+          cz_fatal(1, "error : fused pass refused after a successful probe\n");
+        }
+        exact_reruns++;
+      } else if (last->nsweep >= 2 && ret == last->first_itr) {
+        // the first sweep of a fused pass converged: the pass wrote time n+2 (n+3) into its destination; its source is
         // untouched, so one plain sweep reproduces the converged iterate (exactly what the sequential loop holds)
         if (maf)
           jacobi_maf_async(buf[last->src], buf[(last->src + 1) % nbuf], B, size, innerFidx, gc, d_xc, d_yc, d_zc, ac1, d_res + 4, nullptr, 0, 0.0, 0.0,
@@ -1923,6 +1942,7 @@ int cz_info(const cz_handle* h, int what) {
     case 11: return c.rb4_passes;
     case 12: return c.exact_reruns;
     case 13: return c.cg_fused;
+    case 14: return c.jac3_passes;
     case 5: return comm_transport_ranks(c.comm);
     case 6: return c.comm_cus;
     case 7: return c.last_plan.kind;

@@ -21,6 +21,8 @@ struct Tuning {
                                               // the balance model (pair_tj_model, cz_h_launch.h); CZHIP_T2=enable,threads,2,tj fixes them
   int t2_kwin = -1;                               // two-stage pass: vectors per k window; -1 = chosen per launch, 0 = whole rows where they fit (CZHIP_T2_KWIN)
   int rb4 = 1, rb4_kwin = 0, rb4_tj = 0;          // two red-black iterations per pass (rb4_k) in single-domain runs; vectors per k window / planes per chunk (0: the launcher's rule); CZHIP_RB4
+  int jac3 = 1, jac3_kwin = 0, jac3_tj = 0;       // three Jacobi sweeps per pass (jac3_k) in single-domain runs: 0 off, 1 above the size gate, 2 also
+                                                  // below it; vectors per k window / planes per chunk (0: the launcher's rule); CZHIP_JAC3
   int unit_coef = 1;                              // the kernels' form for coefficients that are all exactly 1 (offdiag_sum<UNIT>; CZHIP_UNIT_COEF)
   int t2_pre = 1;                                 // two-stage pass on small grids: every operand of a chunk requested before its first step (jacobi2p_k<PRE>; CZHIP_T2_PRE)
   int t2_map = 1;                                 // two-stage pass: equal shares of (segment, chunk) items per XCD (CZHIP_T2_MAP=0: whole-segment bands)
@@ -75,9 +77,9 @@ struct Ctx {
 };
 thread_local Ctx ctx;  // one context per host thread (= per rank; LOCAL transport runs ranks as threads)
 
-enum { LBL_JACOBI = 0, LBL_RBSOR, LBL_AX, LBL_RK, LBL_REDUCE, LBL_EWISE, LBL_DOT, LBL_JACOBI2, LBL_RBSOR2, LBL_PCR, LBL_SHELL, LBL_PSOR, LBL_RBSOR4, LBL_COUNT };
+enum { LBL_JACOBI = 0, LBL_RBSOR, LBL_AX, LBL_RK, LBL_REDUCE, LBL_EWISE, LBL_DOT, LBL_JACOBI2, LBL_RBSOR2, LBL_PCR, LBL_SHELL, LBL_PSOR, LBL_RBSOR4, LBL_JACOBI3, LBL_COUNT };
 static_assert(LBL_COUNT <= 16, "Ctx::t_acc / t_cnt hold 16 labels");
-const char* const kLabelNames[LBL_COUNT] = {"jacobi", "rbsor", "calc_ax", "calc_rk", "reduce", "ewise", "dot", "jacobi2", "rbsor2", "pcr_rb", "pair_shell", "psor", "rbsor4"};
+const char* const kLabelNames[LBL_COUNT] = {"jacobi", "rbsor", "calc_ax", "calc_rk", "reduce", "ewise", "dot", "jacobi2", "rbsor2", "pcr_rb", "pair_shell", "psor", "rbsor4", "jacobi3"};
 
 struct ScopedTimer {
   bool on;

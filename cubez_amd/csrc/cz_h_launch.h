@@ -417,6 +417,83 @@ bool launch_rb4(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box&
   return true;
 }
 
+// THREE Jacobi sweeps per pass (jac3_k, cz_k_jac3.h): single-domain boxes, constant coefficients.  Returns false when the geometry does not suit
+// the kernel or the box lies below the size gate (the caller then runs the two-sweep pass).  The k axis is cut into windows of about
+// jac3_window() vectors: the four halo rows of a segment must stay a small share of the 1 024 vectors a workgroup holds.
+// By measurement (profiles/r06/jac3_three_sweeps_per_pass.txt), per sweep against the pair: FP32 windows of 26 vectors 1.09 x at 512^3 (43: 1.01 x,
+// 20: 0.98 x), 1.11 x at 384^3, 1.07 x at 1024^3, 1.01 x at 256^3; FP64 512^3 windows of 36 1.22 x (28: 1.19 x, 20: 1.11 x).
+inline int jac3_window(int) { return VW == 4 ? 26 : 36; }
+// size gate of ctx.tune.jac3 = 1: inner points of the box (256^3: no gain worth the switch; 384^3: 1.11 x)
+constexpr long long kJac3MinPoints = 300LL * 300 * 300;
+bool launch_jac3(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box& b, const int* skip, const Fin2& fin_in, bool probe) {
+  constexpr int V = VW, TB = 1024;
+  if (!ctx.tune.jac3 || !ctx.tune.fuse_fin || !ctx.tune.use_t2) return false;
+  if (!rows_ok(b, {U, B, W}) || !fastdiv_ok(c.dd)) return false;
+  if (b.ii0 < 2 || b.jj0 < 2 || b.ii1 > b.nip - 3 || b.jj1 > b.njp - 3) return false;
+  const long long npts = (long long)(b.ii1 - b.ii0 + 1) * (b.jj1 - b.jj0 + 1) * (b.kk1 - b.kk0 + 1);
+  if (ctx.tune.jac3 == 1 && (npts < kJac3MinPoints || pair_small_form_fits(b))) return false;  // (jac3 = 2: also there -- tests)
+  Geom2 g;
+  const int Rfull = (b.nkp + V - 1) / V;
+  const int hv = V == 4 ? 1 : 2;  // three stages reach three elements beyond a window
+  const int want = ctx.tune.jac3_kwin > 0 ? ctx.tune.jac3_kwin : jac3_window(Rfull);
+  g.R = Rfull;
+  if (Rfull > want + 2 * hv) {
+    g.nwin = (Rfull + want - 1) / want;
+    g.KT = (Rfull + g.nwin - 1) / g.nwin;
+    g.hv = hv, g.KW = g.KT * V, g.R = g.KT + 2 * hv;
+  }
+  if (2 * g.R > TB || 8 * g.R > TB) return false;  // at least half of the workgroup's vectors must be its own
+  g.PSV = (long long)g.R * b.nip;
+  g.nkp = b.nkp;
+  g.PSB = (long long)b.nkp * b.nip * (long long)sizeof(REAL);
+  if (g.PSB >= (1LL << 32)) return false;
+  g.jlast = b.njp - 1;
+  g.last_off = (unsigned)(g.PSB - (long long)sizeof(Vec<V>));
+  g.kk0 = b.kk0, g.kk1 = b.kk1, g.jj0 = b.jj0, g.jj1 = b.jj1;
+  g.F0 = (long long)b.ii0 * g.R;
+  g.Fend = (long long)(b.ii1 + 1) * g.R;
+  g.kk0a = b.kk0, g.kk1a = b.kk1, g.jj0a = b.jj0, g.jj1a = b.jj1, g.F0a = g.F0, g.Fenda = g.Fend;
+  g.S = TB - 4 * g.R;
+  g.par = 0;
+  g.zero_u = 0;
+  const long long nf = g.Fend - g.F0;
+  g.nsegw = (int)((nf + g.S - 1) / g.S);
+  g.nseg = g.nwin * g.nsegw;
+  const int nplanes = b.jj1 - b.jj0 + 1;
+  const size_t lds = ((size_t)2 * g.R + (size_t)2 * (TB + 2 * g.R) + (size_t)4 * TB) * sizeof(Vec<V>) + 18 * sizeof(double);
+  if (lds > 160 * 1024) return false;
+  int tj = 0;
+  pair_tj_model(g.nseg, nplanes, 1, pair_use_map(g.nseg), &tj, 5.5);  // (four redundant planes and a longer prologue per chunk)
+  if (ctx.tune.jac3_tj > 0) tj = ctx.tune.jac3_tj;
+  if (tj > nplanes) tj = nplanes;
+  g.TJ = tj;
+  const int nchunk = (nplanes + tj - 1) / tj;
+  g.band = 1;
+  g.map = nullptr;
+  long long nblk = 8LL * ((g.nseg + 7) / 8) * nchunk;
+  if (probe) return true;
+  if (pair_use_map(g.nseg)) g.map = pair_xcd_map(g.nseg, nchunk, &nblk);
+  ensure_partials((size_t)3 * nblk);
+  static bool attr_set = false;
+  if (!attr_set) {
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&jac3_k<V, TB, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&jac3_k<V, TB, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_set = true;
+  }
+  Fin2 fin = fin_in;
+  fin.counter = ctx.counter;
+  fin.single = 0;
+  {
+    ScopedTimer tm(LBL_JACOBI3);
+    if (ctx.tune.unit_coef && coef_is_unit(c))
+      hipLaunchKernelGGL((jac3_k<V, TB, 1>), dim3((unsigned)nblk), dim3(TB), lds, ctx.stream, U, B, W, c, g, ctx.partials, skip, fin);
+    else
+      hipLaunchKernelGGL((jac3_k<V, TB, 0>), dim3((unsigned)nblk), dim3(TB), lds, ctx.stream, U, B, W, c, g, ctx.partials, skip, fin);
+  }
+  HIP_CHECK(hipGetLastError());
+  return true;
+}
+
 // the shell boxes of a decomposed brick, all in one launch (pair_shell_k); boxes: n x (ist,ied,jst,jed,kst,ked), 1-based
 template <int RB, int MAF = 0>
 void launch_pair_shell(const REAL* U, const REAL* B, REAL* W, const Coef& c, const int* sz, int g, const Box& ba, const int* boxes, int n,

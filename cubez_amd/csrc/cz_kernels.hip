@@ -43,6 +43,7 @@ namespace {
 #include "cz_k_pair.h"
 #include "cz_k_pair2.h"
 #include "cz_k_rb4.h"
+#include "cz_k_jac3.h"
 #include "cz_k_linesor.h"
 #include "cz_k_psor.h"
 #include "cz_k_blas.h"
@@ -184,6 +185,11 @@ int czhip_init(int device) {
     int en = 1, kw = 0, tj = 0;
     sscanf(v, "%d,%d,%d", &en, &kw, &tj);
     ctx.tune.rb4 = en, ctx.tune.rb4_kwin = kw, ctx.tune.rb4_tj = tj;
+  }
+  if (const char* v = cfg.str(CZV_JAC3)) {  // "enable[,vectors per window[,planes per chunk]]"
+    int en = 1, kw = 0, tj = 0;
+    sscanf(v, "%d,%d,%d", &en, &kw, &tj);
+    ctx.tune.jac3 = en, ctx.tune.jac3_kwin = kw, ctx.tune.jac3_tj = tj;
   }
   if (const char* pp = cfg.str(CZV_PCR_PIPE)) {  // "form[,seconds[,groups[,rows per thread]]]": form as Tuning::pcr_pipe; bound of the waits inside the kernel
     int w = 1, rows = 0, q = 1;
@@ -490,6 +496,35 @@ int czhip_rbsor4_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int
     fin.hist = hist_dev, fin.flag = flag_dev, fin.conv_itr = conv_itr_dev;
   }
   return launch_rb4(u, b, w, make_coef(cf, omg), bx, hist_dev ? flag_dev : skip_flag_dev, fin, rb_parity(g, idx, ofst, 0), probe != 0) ? 1 : 0;
+}
+
+// THREE Jacobi sweeps in one pass over memory, u -> w (jac3_k; single-domain boxes).  res_dev[0..2] receive the sums dp^2 of sweeps itr, itr + 1,
+// itr + 2; with hist_dev the last workgroup does the bookkeeping of all three in order (a converged first or second sweep leaves the flag set
+// with conv_itr = itr or itr + 1: the caller recomputes that sweep or pair from u, which this kernel never modifies).  probe != 0: only answer
+// whether the launcher takes the geometry.  Returns 1 if launched (or launchable), 0 otherwise (the caller runs the two-sweep pass).
+int czhip_jacobi3_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, int g, const CZ_REAL* cf, CZ_REAL omg,
+                        double* res_dev, double res_normal, double eps, int itr, double* hist_dev, int* flag_dev, int* conv_itr_dev,
+                        const int* skip_flag_dev, int probe) {
+  ensure_init();
+  const Box bx = make_box(sz, idx, g);
+  if (bx.empty || g < 2) return 0;
+  Fin2 fin;
+  fin.dst = res_dev;
+  if (hist_dev) {
+    fin.do_check = 1, fin.itr = itr, fin.res_normal = res_normal, fin.eps = eps;
+    fin.hist = hist_dev, fin.flag = flag_dev, fin.conv_itr = conv_itr_dev;
+  }
+  return launch_jac3(u, b, w, make_coef(cf, omg), bx, hist_dev ? flag_dev : skip_flag_dev, fin, probe != 0) ? 1 : 0;
+}
+
+// jac3_k switches (measurements): enable 0 | 1 | 2 (2: also below the size gate -- tests), vectors per k window, planes per chunk (0: the
+// launcher's rule); negative: keep.
+int czhip_set_jac3(int enable, int window, int planes) {
+  ensure_init();
+  if (enable >= 0) ctx.tune.jac3 = enable;
+  if (window >= 0) ctx.tune.jac3_kwin = window;
+  if (planes >= 0) ctx.tune.jac3_tj = planes;
+  return 0;
 }
 
 // rb4_k switches (measurements): enable 0 | 1, vectors per k window, planes per chunk (0: the launcher's rule); negative: keep.

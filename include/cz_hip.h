@@ -224,6 +224,16 @@ int czhip_rbsor4_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int
 /* ... its switches (measurements; negative = keep): 0 off / 1 on / 2 on also for small grids (where the preloaded one-iteration pass is faster
  * and 1 leaves the box to it), vectors per k window, planes per chunk (0 = chosen per launch) */
 int czhip_set_rb4(int enable, int window, int planes);
+/* THREE relaxed-Jacobi sweeps in ONE pass over memory, u -> w out of place (single-domain boxes, constant coefficients): bit-identical to three
+ * czhip_jacobi_async sweeps.  res_dev[0..2] = the sums dp^2 of sweeps itr, itr + 1, itr + 2; check arguments as for czhip_jacobi2_async (three
+ * sweeps in order; a converged first or second sweep leaves conv_itr = itr or itr + 1 and the caller recomputes that sweep, or that pair, from
+ * u).  probe != 0: only says whether the launch would be taken.  Returns 0 when it is not (the caller then runs czhip_jacobi2_async). */
+int czhip_jacobi3_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, int g, const CZ_REAL* cf, CZ_REAL omg,
+                        double* res_dev, double res_normal, double eps, int itr, double* hist_dev, int* flag_dev, int* conv_itr_dev,
+                        const int* skip_flag_dev, int probe);
+/* ... its switches (measurements; negative = keep): 0 off / 1 on above the size gate / 2 on also for small grids (tests), vectors per k window,
+ * planes per chunk (0 = chosen per launch).  czhip_set_tuning2 with enable 0 (single sweeps) turns it off as well. */
+int czhip_set_jac3(int enable, int window, int planes);
 /* The fused pass split the way a decomposed brick runs it (replaces the reference's "sweep, then Comm_S",
  * cz_Poisson.cpp:58-63): first the slabs two cells thick behind every face with nID[f] >= 0 (the cells the neighbours
  * receive), then the interior, so that the exchange can start after the first launch.  Same result as the unsplit op.
