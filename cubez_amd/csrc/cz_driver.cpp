@@ -126,6 +126,7 @@ double CZ::range_inner_index() {
   innerFidx[I_minus] = ist, innerFidx[I_plus] = ied;
   innerFidx[J_minus] = jst, innerFidx[J_plus] = jed;
   innerFidx[K_minus] = kst, innerFidx[K_plus] = ked;
+  for (int f = 0; f < 6; f++) idx1[f] = innerFidx[f] + ((nID[f] >= 0) ? ((f & 1) ? 1 : -1) : 0);
   return (double)(ied - ist + 1) * (double)(jed - jst + 1) * (double)(ked - kst + 1);
 }
 
@@ -335,8 +336,6 @@ int CZ::Setup(int argc, char** argv) {
   if (numProc > 1) {
     // The fused pass needs the two-layer exchange, single sweeps the one-layer exchange: all bricks must take the same path.
     // Bricks of an uneven division can differ (k-extent multiple of the vector width or not): agree on the weakest.
-    int idx1[6];
-    for (int f = 0; f < 6; f++) idx1[f] = innerFidx[f] + ((nID[f] >= 0) ? ((f & 1) ? 1 : -1) : 0);
     // (the MAF flavour of the pass needs a little more LDS -- the table of the k metric terms -- and is probed as well where it will run)
     const double mine = (pair_probe(P, WRK, RHS, size, innerFidx, idx1, GUIDE, cf[6], 0) && (!SW_maf || pair_probe(P, WRK, RHS, size, innerFidx, idx1, GUIDE, cf[6], 1))) ? 0.0 : 1.0;
     pairs_ok = comm_allreduce_max_host(comm, mine) == 0.0;
@@ -563,7 +562,7 @@ bool CZ::Comm_S2(REAL_TYPE* X, const int* skip_flag) {
 bool CZ::Comm_SUM_dev(double* d_val, int count, const int* skip_flag) {
   if (numProc == 1) return true;
   // INVARIANT: collectives are issued unconditionally -- never gated by a device flag the host has not read, never by host timing.
-  // What a rank issues depends only on its argv, on the agreed launch count and on `stop` (see the poll in CZ::JACOBI).
+  // What a rank issues depends only on its argv, on the agreed launch count and on `stop` (see CZ::FlagPoll).
   (void)skip_flag;
   return comm_allreduce_sum(comm, d_val, count, stream());
 }
@@ -627,7 +626,7 @@ void CZ::plan_overlap() {
 //   comm_stream : wait ev_src -> shell slabs -> pack, send/recv, unpack -> [ev_comm]
 // The slabs and the interior write disjoint cells of dst and read only src; the unpack writes ghost cells of dst.
 // Returns false (nothing launched) when the split does not apply; the caller then takes the unsplit path.
-bool CZ::pair_overlapped(REAL_TYPE* src, REAL_TYPE* dst, REAL_TYPE* B, const int* idx1, int rb, const int* skip, double* res_slot, const MafPtrs* maf) {
+bool CZ::pair_overlapped(REAL_TYPE* src, REAL_TYPE* dst, REAL_TYPE* B, int rb, const int* skip, double* res_slot, const MafPtrs* maf) {
   if (n_shell == 0) return false;
   double* rs = res_slot ? res_slot : d_res;
   const int gc = GUIDE;
@@ -650,8 +649,7 @@ bool CZ::pair_overlapped(REAL_TYPE* src, REAL_TYPE* dst, REAL_TYPE* B, const int
 }
 
 // Drain the queue and turn the device-side bookkeeping into the loop's return values.
-int CZ::finish_stationary(int itr_max, int first_itr, bool converge_check, double& res) {
-  (void)first_itr;
+int CZ::finish_stationary(int itr_max, bool converge_check, double& res) {
   if (!converge_check) {
     // (a preconditioner solve inside BiCGSTAB returns without draining: 20-30 us of idle GPU per solve otherwise, see
     // profiles/r03/bicgstab_iteration_timeline_512_f64.txt)
@@ -662,13 +660,26 @@ int CZ::finish_stationary(int itr_max, int first_itr, bool converge_check, doubl
   HIP_CHECK(hipStreamSynchronize(stream()));
   const bool conv = h_flag[0] != 0;
   const int n_exec = conv ? h_flag[1] : itr_max;
+  read_history(n_exec, res);
+  return conv ? n_exec : itr_max + 1;
+}
+
+// the residuals of iterations 1..n_exec of the last checked solve, appended to `history`; res = the last of them
+void CZ::read_history(int n_exec, double& res) {
   const size_t base = history.size();
   history.resize(base + n_exec);
   if (n_exec > 0) {
     HIP_CHECK(hipMemcpy(history.data() + base, d_hist + 1, (size_t)n_exec * sizeof(double), hipMemcpyDeviceToHost));
     res = history.back();
   }
-  return conv ? n_exec : itr_max + 1;
+}
+
+// :67-77 after a sweep (nres = 1) or a pair of sweeps (nres = 2): all-reduce of the residual(s), then the test on the device
+bool CZ::reduce_test(int nres, int itr, const int* skip) {
+  if (!Comm_SUM_dev(d_res, nres, skip)) return false;
+  if (nres == 2) czhip_check2_async(d_res, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);
+  else czhip_check_async(d_res, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);
+  return true;
 }
 
 // d_res[0] of the sweep(s) just issued, read back behind them: NaN = the sweep gave up a wait between its workgroups (pcr_lex_wg_k)
@@ -701,8 +712,6 @@ CZ::PassPlan CZ::plan_pass(REAL_TYPE* X, REAL_TYPE* B, int s_type, int itr_max, 
   p.maf = (s_type == LS_JACOBI_MAF || s_type == LS_SOR2SMA_MAF) ? 1 : 0;
   p.rb = rb ? 1 : 0;
   p.comm_cus = comm_cus;
-  int idx1[6];
-  for (int f = 0; f < 6; f++) idx1[f] = innerFidx[f] + ((nID[f] >= 0) ? ((f & 1) ? 1 : -1) : 0);
   bool fused = czhip_use_t2() != 0 && (rb || itr_max >= 2);
   if (fused) {
     const bool mine = pair_probe(X, WRK, B, size, innerFidx, idx1, GUIDE, cf[6], p.maf) != 0;
@@ -730,93 +739,210 @@ CZ::PassPlan CZ::plan_pass(REAL_TYPE* X, REAL_TYPE* B, int s_type, int itr_max, 
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// cz_Poisson.cpp:30-82
-int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double& flop, int s_type, bool converge_check,
-               bool x_is_zero, const BMade* made) {
-  const int gc = GUIDE;
-  hipStream_t st = stream();
-  const PassPlan plan = plan_pass(X, B, s_type, itr_max, converge_check, x_is_zero, false);
+// The host's lagging, non-blocking view of the device convergence flag.  Each poll issues a stream-ordered copy of d_flag[0] and looks at
+// the copy issued two polls earlier; the caller decides when to poll (its cadence).  The events are released with the poller, early returns
+// included.
+// INVARIANT (rank lock step): the answer decides whether this rank issues further passes, i.e. further collectives.  It is a function of
+// the copy two polls back only: a copy of the device flag taken at a fixed position of the stream (lagged mode: behind the tests of all
+// passes issued up to that poll, which run on the exchange stream), and the flag is computed from all-reduced sums -- the same bits on every
+// rank.  When the host gets to look at the copy (skew_wait: a test delays one rank here) cannot change what it reads.
+class CZ::FlagPoll {
+ public:
+  FlagPoll(CZ& cz, bool lag) : cz_(cz), lag_(lag) {}
+  ~FlagPoll() {
+    for (int i = 0; i < std::min(npoll_, POLL_SLOTS); i++) HIP_CHECK(hipEventDestroy(ev_[i]));
+  }
+  FlagPoll(const FlagPoll&) = delete;
+  FlagPoll& operator=(const FlagPoll&) = delete;
+  // true: the flag was set (the solve has converged) as of two polls ago
+  bool stop() {
+    const int slot = npoll_ % POLL_SLOTS;
+    if (npoll_ >= POLL_SLOTS) HIP_CHECK(hipEventDestroy(ev_[slot]));
+    if (lag_) cz_.wait_lagged_tests();  // every rank must read the same flag: the copy follows the tests of all passes issued so far
+    HIP_CHECK(hipMemcpyAsync(cz_.h_flag + 2 * slot, cz_.d_flag, sizeof(int), hipMemcpyDeviceToHost, stream()));
+    HIP_CHECK(hipEventCreateWithFlags(&ev_[slot], hipEventDisableTiming));
+    HIP_CHECK(hipEventRecord(ev_[slot], stream()));
+    if (++npoll_ < 3) return false;
+    const int old = (npoll_ - 3) % POLL_SLOTS;
+    cz_.skew_wait();
+    HIP_CHECK(hipEventSynchronize(ev_[old]));
+    return cz_.h_flag[2 * old] != 0;
+  }
+
+ private:
+  CZ& cz_;
+  const bool lag_;
+  hipEvent_t ev_[POLL_SLOTS];
+  int npoll_ = 0;
+};
+
+// lagged mode: the compute stream waits for the convergence tests still in flight on the exchange stream
+void CZ::wait_lagged_tests() {
+  HIP_CHECK(hipStreamWaitEvent(stream(), ev_chk[0], 0));
+  HIP_CHECK(hipStreamWaitEvent(stream(), ev_chk[1], 0));
+}
+
+// What JACOBI and RBSOR share around their choice of kernels.  The field rotates through buf[0 .. nbuf) -- X, WRK and, lagged, WRK2 -- and
+// every launch of a fused plan is recorded (first iteration, iterations, source buffer) so that the state at the converged iteration can be
+// produced exactly (fused_end).
+class CZ::FusedLoop {
+ public:
+  FusedLoop(CZ& cz, const PassPlan& p, REAL_TYPE* b, bool check) : plan(p), B(b), converge_check(check), nbuf(p.buffers), poll(cz, p.lag != 0) {}
+  const PassPlan& plan;
+  REAL_TYPE* const B;
+  const bool converge_check;
+  const int* skip = nullptr;  // checked solves: d_flag (launches queued after convergence are no-ops)
+  REAL_TYPE* buf[3] = {nullptr, nullptr, nullptr};
+  const int nbuf;
+  int cur = 0;
+  std::vector<Launch> launches;
+  FlagPoll poll;
+  REAL_TYPE* src() const { return buf[cur]; }
+  REAL_TYPE* dst() const { return buf[(cur + 1) % nbuf]; }
+  void record(int itr, int n) {
+    launches.push_back({itr, n, cur});
+    cur = (cur + 1) % nbuf;
+  }
+};
+
+// The start of a JACOBI / RBSOR solve, after its plan.  Every ping-pong reads X's shell and ghost cells from WRK (and WRK2) as well.
+bool CZ::fused_begin(FusedLoop& L, REAL_TYPE* X, int itr_max, bool x_is_zero, const BMade* made) {
+  const PassPlan& plan = L.plan;
   if (made && !(plan.kind == PassPlan::WHOLE && plan.zero_start)) {  // (bicg_fusable asked the same questions before the update was withheld)
     cz_fatal(1, "error : the solve that was to make its right-hand side does not start with a whole fused pass from zero\n");
   }
+  exact_reruns = 0;
+  if (x_is_zero && !plan.zero_start) {
+    // the caller skipped its blas_clear_ (cz_Poisson.cpp:405, 441) and this solve does not take the zero as a literal: clear now
+    // (guide cells / faces are zero already)
+    const size_t nbytes = (size_t)(size[0] + 2 * GUIDE) * (size[1] + 2 * GUIDE) * (size[2] + 2 * GUIDE) * sizeof(REAL_TYPE);
+    HIP_CHECK(hipMemsetAsync(X, 0, nbytes, stream()));
+  }
+  reset_ticket();
+  if (L.converge_check) {
+    ensure_hist(itr_max + 3);
+    HIP_CHECK(hipMemsetAsync(d_flag, 0, 4 * sizeof(int), stream()));  // flag, iteration, the two snapshots of the lagged mode
+    L.skip = d_flag;
+  }
+  // the fused pass reads two ghost layers (and the edge cells) of X and one of B
+  if (plan.depth == 2 && numProc > 1 && (!Comm_S2(X) || !Comm_S2(L.B))) return false;
+  L.buf[0] = X, L.buf[1] = WRK;
+  if (!plan.rb || plan.kind != PassPlan::SINGLE) sync_wrk_shell(X);  // ping-pong partner (the red-black SINGLE plan sweeps in place)
+  // Lagged mode (decomposed, checked runs): the residual all-reduce and the convergence test of pass n run on the exchange stream while
+  // pass n+1 is being swept (pass n+2 waits for the test of pass n).  A pass may therefore run beyond convergence once; with THREE rotating
+  // buffers it cannot touch the source or the destination of the converged pass, so the exact-iteration fix-up (fused_end) still finds both.
+  if (plan.lag) {
+    if (!WRK2) WRK2 = czhip_alloc_s3d(size);
+    copy_shell_async(WRK2, X, size, innerFidx, GUIDE);
+    L.buf[2] = WRK2;
+  }
+  return true;
+}
+
+// One SPLIT pass src -> dst (pair_overlapped) with its all-reduce and test: rb < 0 two Jacobi sweeps (nres = 2 residuals), else one
+// red-black iteration of colour parity rb (nres = 1).  Pass p is the p-th launch of the solve.
+bool CZ::split_pass(FusedLoop& L, int rb, int nres, int itr, const MafPtrs* mpp) {
+  if (!L.plan.lag) {
+    if (!pair_overlapped(L.src(), L.dst(), L.B, rb, L.skip, nullptr, mpp)) return false;  // :58 (:205-209), :63 (:215) behind the interior
+    return !L.converge_check || reduce_test(nres, itr, L.skip);                          // :67-77
+  }
+  hipStream_t st = stream();
+  const int p = (int)L.launches.size();
+  if (p >= 2) HIP_CHECK(hipStreamWaitEvent(st, ev_chk[p & 1], 0));  // the test of pass p-2
+  double* rs = d_res + ((p & 1) ? 10 : 0);
+  // Pass p looks at the flag as the test of pass p-2 left it (d_flag[2 + (p & 1)], written by that test and by nothing else until
+  // pass p is over): every workgroup of the pass, its pack and its unpack take the same decision.  The live flag d_flag[0] may be
+  // set by the test of pass p-1 while pass p is running.
+  int* snap = d_flag + 2 + (p & 1);
+  if (!pair_overlapped(L.src(), L.dst(), L.B, rb, snap, rs, mpp)) return false;
+  HIP_CHECK(hipEventRecord(ev_int, st));
+  HIP_CHECK(hipStreamWaitEvent(comm_stream, ev_int, 0));
+  if (!comm_allreduce_sum(comm, rs, nres, comm_stream)) return false;  // :67, all the pass's residuals
+  if (nres == 2) check2_on_stream(comm_stream, rs, res_normal, eps, itr, d_hist, d_flag, d_flag + 1, snap);  // :69-77
+  else check_on_stream(comm_stream, rs, res_normal, eps, itr, d_hist, d_flag, d_flag + 1, snap);
+  HIP_CHECK(hipEventRecord(ev_chk[p & 1], comm_stream));
+  return true;
+}
+
+// After a WHOLE pass of a decomposed run: the two layers of its destination once per pass (:63, :215), one all-reduce of all the pass's
+// residuals and the test (:67-77)
+bool CZ::whole_exchange_test(FusedLoop& L, int nres, int itr) {
+  if (numProc == 1) return true;
+  if (!Comm_S2(L.dst(), L.skip)) return false;
+  return !L.converge_check || reduce_test(nres, itr, L.skip);
+}
+
+// The first pass of a preconditioner solve whose start vector is identically zero: neither cleared in memory nor read; with `made` the
+// right-hand side is made on the way (BiCGSTAB's vector update folded in).  rb < 0: two Jacobi sweeps, else one red-black iteration.
+int CZ::zero_start_pass(REAL_TYPE* src, REAL_TYPE* dst, REAL_TYPE* B, const BMade* made, int rb) {
+  static const BMade read_b{0, nullptr, nullptr, nullptr, (REAL_TYPE)0, (REAL_TYPE)0, nullptr};
+  const BMade& m = made ? *made : read_b;
+  return pass_from_zero_made(src, dst, B, m.op, m.x, m.y, m.z, m.a, m.a_dev, m.b, size, innerFidx, idx1, GUIDE, cf, ac1, rb, d_res, 0);
+}
+
+// The end of a JACOBI / RBSOR solve: drain, read the bookkeeping back, and hand the iterate of the converged (or last) iteration to the
+// caller.  Launches after convergence were no-ops or -- lagged mode -- wrote the third buffer.  A launch whose converged iteration is not
+// its last wrote later iterates into its destination; its source is untouched, so `rerun(launch, k, src, dst)` -- k = the converged
+// iteration's index within the launch -- reproduces the converged iterate from it (exactly what the sequential loop holds).
+int CZ::fused_end(FusedLoop& L, REAL_TYPE* X, int itr_max, double& res, const Rerun& rerun) {
+  if (L.plan.lag) HIP_CHECK(hipStreamSynchronize(comm_stream));  // the last tests
+  last_lag = L.plan.lag;
+  const int ret = finish_stationary(itr_max, L.converge_check, res);
+  if (L.launches.empty()) return ret;
+  const Launch* last = &L.launches.back();
+  if (L.converge_check && ret <= itr_max) {  // converged at iteration `ret`: the launch that contains it
+    for (const Launch& l : L.launches)
+      if (ret >= l.first_itr && ret < l.first_itr + l.n) {
+        last = &l;
+        break;
+      }
+    if (ret < last->first_itr + last->n - 1) {
+      rerun(*last, ret - last->first_itr, L.buf[last->src], L.buf[(last->src + 1) % L.nbuf]);
+      exact_reruns++;
+    }
+  }
+  const int fb = (last->src + 1) % L.nbuf;
+  if (fb != 0) {
+    // the result is in WRK (or WRK2).  The arrays are ours: swap the roles instead of copying back.
+    if (X == P) {
+      REAL_TYPE* t = P;
+      P = L.buf[fb];
+      if (fb == 1) WRK = t;
+      else WRK2 = t;
+    } else {
+      copy_inner_async(X, L.buf[fb], size, innerFidx, GUIDE);
+    }
+  }
+  return ret;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// cz_Poisson.cpp:30-82.  Ping-pong X <-> WRK; fused plans apply the sweeps two (or three) at a time per pass over memory (temporal blocking,
+// the intermediate field stays on chip).
+int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double& flop, int s_type, bool converge_check,
+               bool x_is_zero, const BMade* made) {
+  const int gc = GUIDE;
+  const PassPlan plan = plan_pass(X, B, s_type, itr_max, converge_check, x_is_zero, false);
   const bool maf = plan.maf != 0;  // cz_Poisson.cpp:45-53
   const MafPtrs mp{d_xc, d_yc, d_zc, nullptr};
   const MafPtrs* mpp = maf ? &mp : nullptr;
-  // ping-pong partner: same guide cells / Dirichlet faces as X
-  sync_wrk_shell(X);
-  REAL_TYPE* buf[3] = {X, WRK, nullptr};
-  const int nbuf = plan.buffers;
-  const int* skip = nullptr;
-  reset_ticket();
-  if (converge_check) {
-    ensure_hist(itr_max + 3);
-    HIP_CHECK(hipMemsetAsync(d_flag, 0, 4 * sizeof(int), st));  // flag, iteration, the two snapshots of the lagged mode
-    skip = d_flag;
-  }
-  // Fused passes apply the sweeps two at a time (temporal blocking, the intermediate field stays on chip).  Every launch is remembered so
-  // that the state at the converged iteration can be produced exactly.
-  struct Launch {
-    int first_itr, nsweep, src;
-  };
-  std::vector<Launch> launches;
-  exact_reruns = 0;
+  FusedLoop L(*this, plan, B, converge_check);
+  if (!fused_begin(L, X, itr_max, x_is_zero, made)) return 0;
+  const int* skip = L.skip;
   // THREE sweeps per pass (jac3_k) where the whole inner box is one launch of one rank with constant coefficients, outside a preconditioner
   // solve; triples while three sweeps remain, then the pair or the single sweep
   const bool jac3 = plan.kind == PassPlan::WHOLE && numProc == 1 && !maf && !in_precond && itr_max >= 3 &&
                     czhip_jacobi3_async(X, WRK, B, size, innerFidx, gc, cf, ac1, d_res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 1) != 0;
   jac3_passes = 0;
-  int idx1[6];  // index range of the first sweep of a pair: one layer into the ghost cells across rank-internal faces
-  for (int f = 0; f < 6; f++) idx1[f] = innerFidx[f] + ((nID[f] >= 0) ? ((f & 1) ? 1 : -1) : 0);
-  if (plan.depth == 2 && numProc > 1) {
-    // the pair reads two ghost layers (and the edge cells) of X and one of B
-    if (!Comm_S2(X) || !Comm_S2(B)) return 0;
-    sync_wrk_shell(X);
-  }
-  // Lagged mode (decomposed, checked runs): the residual all-reduce and the convergence test of pass n run on the exchange stream while
-  // pass n+1 is being swept (pass n+2 waits for the test of pass n).  A pass may therefore run beyond convergence once; with THREE rotating
-  // buffers it cannot touch the source or the destination of the converged pass, so the exact-iteration fix-up below still finds both.
-  if (plan.lag) {
-    if (!WRK2) WRK2 = czhip_alloc_s3d(size);
-    copy_shell_async(WRK2, X, size, innerFidx, gc);
-    buf[2] = WRK2;
-  }
-  if (x_is_zero && !plan.zero_start) {
-    // the caller skipped its blas_clear_ (cz_Poisson.cpp:405, 441) and this solve does not take the zero as a literal: clear now
-    // (guide cells / faces are zero already)
-    const size_t nbytes = (size_t)(size[0] + 2 * gc) * (size[1] + 2 * gc) * (size[2] + 2 * gc) * sizeof(REAL_TYPE);
-    HIP_CHECK(hipMemsetAsync(X, 0, nbytes, st));
-  }
-  hipEvent_t ev[POLL_SLOTS];
-  int npoll = 0, cur = 0;
   bool stop = false;
   int itr = 1;
   while (itr <= itr_max && !stop) {
-    REAL_TYPE* src = buf[cur];
-    REAL_TYPE* dst = buf[(cur + 1) % nbuf];
-    int done = 0;
+    REAL_TYPE* src = L.src();
+    REAL_TYPE* dst = L.dst();
+    int done = 2;
     const bool pass = plan.kind != PassPlan::SINGLE && itr + 1 <= itr_max;
-    if (pass && plan.kind == PassPlan::SPLIT && plan.lag) {
-      const int p = (int)launches.size();
-      if (p >= 2) HIP_CHECK(hipStreamWaitEvent(st, ev_chk[p & 1], 0));  // the test of pass p-2
-      double* rs = d_res + ((p & 1) ? 10 : 0);
-      // Pass p looks at the flag as the test of pass p-2 left it (d_flag[2 + (p & 1)], written by that test and by nothing else until
-      // pass p is over): every workgroup of the pass, its pack and its unpack take the same decision.  The live flag d_flag[0] may be
-      // set by the test of pass p-1 while pass p is running.
-      int* snap = d_flag + 2 + (p & 1);
-      if (!pair_overlapped(src, dst, B, idx1, -1, snap, rs, mpp)) return 0;  // :58 twice, :63 hidden behind the interior
-      HIP_CHECK(hipEventRecord(ev_int, st));
-      HIP_CHECK(hipStreamWaitEvent(comm_stream, ev_int, 0));
-      if (!comm_allreduce_sum(comm, rs, 2, comm_stream)) return 0;                                            // :67, both sweeps
-      check2_on_stream(comm_stream, rs, res_normal, eps, itr, d_hist, d_flag, d_flag + 1, snap);               // :69-77
-      HIP_CHECK(hipEventRecord(ev_chk[p & 1], comm_stream));
-      done = 2;
-    } else if (pass && plan.kind == PassPlan::SPLIT) {
-      if (!pair_overlapped(src, dst, B, idx1, -1, skip, nullptr, mpp)) return 0;
-      if (converge_check) {
-        if (!Comm_SUM_dev(d_res, 2, skip)) return 0;
-        czhip_check2_async(d_res, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);
-      }
-      done = 2;
+    if (pass && plan.kind == PassPlan::SPLIT) {
+      if (!split_pass(L, -1, 2, itr, mpp)) return 0;  // :58 twice, :63 hidden behind the interior, :67-77 for both sweeps
     } else if (pass && jac3 && itr + 2 <= itr_max && !(plan.zero_start && itr == 1)) {
       if (!czhip_jacobi3_async(src, dst, B, size, innerFidx, gc, cf, ac1, d_res, res_normal, eps, itr, converge_check ? d_hist : nullptr, d_flag,
                                d_flag + 1, skip, 0)) {  // :58 + :67-77, three times
@@ -827,11 +953,8 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
     } else if (pass) {  // the whole inner box in one launch
       const bool in_kernel_check = converge_check && numProc == 1;
       int launched;
-      if (plan.zero_start && itr == 1 && made)  // ... and the right-hand side made on the way (BiCGSTAB's vector update folded in)
-        launched = pass_from_zero_made(src, dst, B, made->op, made->x, made->y, made->z, made->a, made->a_dev, made->b, size, innerFidx, idx1, gc,
-                                       cf, ac1, -1, d_res, 0);
-      else if (plan.zero_start && itr == 1)  // start vector identically zero (preconditioner): neither cleared in memory nor read
-        launched = czhip_jacobi2_from_zero_async(src, dst, B, size, innerFidx, idx1, gc, cf, ac1, d_res);
+      if (plan.zero_start && itr == 1)
+        launched = zero_start_pass(src, dst, B, made, -1);
       else if (maf)
         launched = pair_maf_async(src, dst, B, size, innerFidx, idx1, gc, d_xc, d_yc, d_zc, ac1, -1, d_res, res_normal, eps, itr,
                                   in_kernel_check ? d_hist : nullptr, d_flag, d_flag + 1, skip);  // :45-53 twice
@@ -841,19 +964,9 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
       if (!launched) {
         cz_fatal(1, "error : fused pass refused after a successful probe\n");
       }
-      if (numProc > 1) {
-        if (!Comm_S2(dst, skip)) return 0;  // :63, two layers once per pair
-        if (converge_check) {
-          if (!Comm_SUM_dev(d_res, 2, skip)) return 0;  // :67 for both sweeps in one all-reduce
-          czhip_check2_async(d_res, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);
-        }
-      }
-      done = 2;
+      if (!whole_exchange_test(L, 2, itr)) return 0;
     } else {  // one sweep: the SINGLE plan, or the odd last sweep of a fused one
-      if (plan.lag) {  // the tests still in flight on the exchange stream come first
-        HIP_CHECK(hipStreamWaitEvent(st, ev_chk[0], 0));
-        HIP_CHECK(hipStreamWaitEvent(st, ev_chk[1], 0));
-      }
+      if (plan.lag) wait_lagged_tests();  // the tests still in flight on the exchange stream come first
       const bool fused_check = converge_check && numProc == 1;  // no all-reduce between sweep and test: one launch
       if (maf)
         jacobi_maf_async(src, dst, B, size, innerFidx, gc, d_xc, d_yc, d_zc, ac1, d_res, skip, fused_check ? 1 : 0, res_normal, eps,
@@ -863,115 +976,39 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
                                    d_flag + 1);  // :58 + :67-77
       else
         czhip_jacobi_async(src, dst, B, size, innerFidx, gc, cf, ac1, d_res, 0, skip);  // :58
-      if (!Comm_S(dst, skip)) return 0;  // :63
-      if (converge_check && !fused_check) {
-        if (!Comm_SUM_dev(d_res, 1, skip)) return 0;                                 // :67
-        czhip_check_async(d_res, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);  // :69-77
-      }
+      if (!Comm_S(dst, skip)) return 0;                                             // :63
+      if (converge_check && !fused_check && !reduce_test(1, itr, skip)) return 0;  // :67-77
       done = 1;
     }
     flop += (maf ? 66.0 : 18.0) * npts() * done;
-    launches.push_back({itr, done, cur});
+    L.record(itr, done);
     itr += done;
-    cur = (cur + 1) % nbuf;
-    if (converge_check && launches.size() % (POLL_EVERY / 2) == 0 && itr <= itr_max) {
-      // lagging, non-blocking view of the flag: look at the copy issued two polls ago
-      const int slot = npoll % POLL_SLOTS;
-      if (npoll >= POLL_SLOTS) HIP_CHECK(hipEventDestroy(ev[slot]));
-      if (plan.lag) {
-        // every rank must read the same flag here (they all stop issuing passes at the same one): the copy follows the tests of
-        // all passes issued so far, which run on the other stream
-        HIP_CHECK(hipStreamWaitEvent(st, ev_chk[0], 0));
-        HIP_CHECK(hipStreamWaitEvent(st, ev_chk[1], 0));
-      }
-      HIP_CHECK(hipMemcpyAsync(h_flag + 2 * slot + 0, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-      HIP_CHECK(hipEventCreateWithFlags(&ev[slot], hipEventDisableTiming));
-      HIP_CHECK(hipEventRecord(ev[slot], st));
-      npoll++;
-      if (npoll >= 3) {
-        // INVARIANT (rank lock step): `stop` decides whether this rank issues further passes, i.e. further collectives.  It is a
-        // function of h_flag[2 * old] only: a copy of the device flag taken at a fixed position of the stream (behind the tests of all
-        // passes issued up to poll npoll-3), and the flag is computed from all-reduced sums -- the same bits on every rank.  When the
-        // host gets to look at the copy (skew_wait: a test delays one rank here) cannot change what it reads.
-        const int old = (npoll - 3) % POLL_SLOTS;
-        skew_wait();
-        HIP_CHECK(hipEventSynchronize(ev[old]));
-        if (h_flag[2 * old] != 0) stop = true;
-      }
-    }
+    if (converge_check && L.launches.size() % (POLL_EVERY / 2) == 0 && itr <= itr_max) stop = L.poll.stop();
   }
-  for (int i = 0; i < (npoll < POLL_SLOTS ? npoll : POLL_SLOTS); i++) HIP_CHECK(hipEventDestroy(ev[i]));
-  if (plan.lag) HIP_CHECK(hipStreamSynchronize(comm_stream));  // the last tests
-  last_lag = plan.lag;
-  const int ret = finish_stationary(itr_max, 1, converge_check, res);
-
-  // which buffer holds the iterate of the last executed sweep?
-  int final_buf = 0;
-  if (!launches.empty()) {
-    const Launch* last = &launches.back();
-    if (converge_check && ret <= itr_max) {  // converged at iteration `ret`: find the launch that contains it
-      for (const Launch& l : launches)
-        if (ret >= l.first_itr && ret < l.first_itr + l.nsweep) {
-          last = &l;
-          break;
-        }
-      if (last->nsweep == 3 && ret == last->first_itr + 1) {
-        // the second sweep of a three-sweep pass converged: its source is untouched, one pair from it reproduces the converged iterate
-        if (!czhip_jacobi2_async(buf[last->src], buf[(last->src + 1) % nbuf], B, size, innerFidx, idx1, gc, cf, ac1, d_res + 4, 0.0, 0.0, 0, nullptr,
-                                 nullptr, nullptr, nullptr)) {
-          cz_fatal(1, "error : fused pass refused after a successful probe\n");
-        }
-        exact_reruns++;
-      } else if (last->nsweep >= 2 && ret == last->first_itr) {
-        // the first sweep of a fused pass converged: the pass wrote time n+2 (n+3) into its destination; its source is
-        // untouched, so one plain sweep reproduces the converged iterate (exactly what the sequential loop holds)
-        if (maf)
-          jacobi_maf_async(buf[last->src], buf[(last->src + 1) % nbuf], B, size, innerFidx, gc, d_xc, d_yc, d_zc, ac1, d_res + 4, nullptr, 0, 0.0, 0.0,
-                           0, nullptr, nullptr, nullptr);
-        else
-          czhip_jacobi_async(buf[last->src], buf[(last->src + 1) % nbuf], B, size, innerFidx, gc, cf, ac1, d_res + 4, 0, nullptr);
-        exact_reruns++;
+  return fused_end(L, X, itr_max, res, [&](const Launch& l, int k, REAL_TYPE* s, REAL_TYPE* d) {
+    if (k == 1) {  // the second sweep of a three-sweep pass: one pair
+      if (!czhip_jacobi2_async(s, d, B, size, innerFidx, idx1, gc, cf, ac1, d_res + 4, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr)) {
+        cz_fatal(1, "error : fused pass refused after a successful probe\n");
       }
-    }
-    final_buf = (last->src + 1) % nbuf;
-  }
-  if (final_buf != 0) {
-    // the result is in WRK (or WRK2).  The arrays are ours: swap the roles instead of copying back.
-    if (X == P) {
-      REAL_TYPE* t = P;
-      P = buf[final_buf];
-      if (final_buf == 1) WRK = t;
-      else WRK2 = t;
+    } else if (maf) {  // the first sweep of a fused pass: one plain sweep
+      jacobi_maf_async(s, d, B, size, innerFidx, gc, d_xc, d_yc, d_zc, ac1, d_res + 4, nullptr, 0, 0.0, 0.0, 0, nullptr, nullptr, nullptr);
     } else {
-      copy_inner_async(X, buf[final_buf], size, innerFidx, gc);
+      czhip_jacobi_async(s, d, B, size, innerFidx, gc, cf, ac1, d_res + 4, 0, nullptr);
     }
-  }
-  return ret;
+  });
 }
 
 // cz_Poisson.cpp:159-235
 int CZ::RBSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double& flop, int s_type, bool converge_check, bool x_is_zero,
               const BMade* made) {
   const int gc = GUIDE;
-  hipStream_t st = stream();
   const PassPlan plan = plan_pass(X, B, s_type, itr_max, converge_check, x_is_zero, true);
-  if (made && !(plan.kind == PassPlan::WHOLE && plan.zero_start)) {  // (see CZ::JACOBI)
-    cz_fatal(1, "error : the solve that was to make its right-hand side does not start with a whole fused pass from zero\n");
-  }
-  if (x_is_zero && !plan.zero_start) {  // the caller skipped its blas_clear_ and this solve does not take the zero as a literal: clear now
-    const size_t nb = (size_t)(size[0] + 2 * gc) * (size[1] + 2 * gc) * (size[2] + 2 * gc) * sizeof(REAL_TYPE);
-    HIP_CHECK(hipMemsetAsync(X, 0, nb, st));
-  }
   const bool maf = plan.maf != 0;  // cz_Poisson.cpp:190-200
   const MafPtrs mp{d_xc, d_yc, d_zc, nullptr};
   const MafPtrs* mpp = maf ? &mp : nullptr;
-  const int* skip = nullptr;
-  reset_ticket();
-  if (converge_check) {
-    ensure_hist(itr_max + 2);
-    HIP_CHECK(hipMemsetAsync(d_flag, 0, 4 * sizeof(int), st));
-    skip = d_flag;
-  }
+  FusedLoop L(*this, plan, B, converge_check);
+  if (!fused_begin(L, X, itr_max, x_is_zero, made)) return 0;
+  const int* skip = L.skip;
   // :178-186.  ip makes colour 0 the points of even GLOBAL i+j+k; the kernel's parity is relative to kst
   // (cz_solver.f90:466), which is 1 instead of 2 on a face that borders another rank.
   int ip = 0;
@@ -979,60 +1016,19 @@ int CZ::RBSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double
 
   // Fused plans: the whole iteration (colour 0, then colour 1) in ONE pass over memory, out of place X <-> WRK; decomposed runs then
   // exchange two ghost layers once per iteration.  SINGLE: the reference's two in-place colour launches with an exchange after each colour.
-  const bool fused = plan.kind != PassPlan::SINGLE;
-  int idx1[6];
-  for (int f = 0; f < 6; f++) idx1[f] = innerFidx[f] + ((nID[f] >= 0) ? ((f & 1) ? 1 : -1) : 0);
-  REAL_TYPE* buf[3] = {X, WRK, nullptr};
-  const int nbuf = plan.buffers;
-  int cur = 0, n_fused = 0;
-  if (fused) {
-    if (numProc > 1 && (!Comm_S2(X) || !Comm_S2(B))) return 0;
-    sync_wrk_shell(X);
-  }
-  // lagged mode: residual all-reduce + test one iteration behind on the exchange stream, three rotating buffers (see CZ::JACOBI); the
-  // iterate of iteration k is in buf[k % nbuf]
-  if (plan.lag) {
-    if (!WRK2) WRK2 = czhip_alloc_s3d(size);
-    copy_shell_async(WRK2, X, size, innerFidx, gc);
-    buf[2] = WRK2;
-  }
   // Round 4: TWO iterations per pass over memory (rb4_k) where the whole inner box is one launch of one rank with constant coefficients.
-  // Every fused launch is remembered (first iteration, iterations, source buffer) so that the state at the converged iteration can be
-  // produced exactly, as in CZ::JACOBI: a converged FIRST iteration of such a pass is re-run alone from the pass's untouched input.
-  struct Launch {
-    int first_itr, niter, src;
-  };
-  std::vector<Launch> launches;
   const bool rb4 = plan.kind == PassPlan::WHOLE && numProc == 1 && !maf &&
                    czhip_rbsor4_async(X, WRK, B, size, innerFidx, gc, cf, ip, ac1, d_res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 1) != 0;
   rb4_passes = 0;
-  exact_reruns = 0;
-  hipEvent_t ev[POLL_SLOTS];
-  int npoll = 0;
   bool stop = false;
   int itr = 1;
   while (itr <= itr_max && !stop) {
     int done = 1;
     const bool in_kernel_check = converge_check && numProc == 1;
-    REAL_TYPE* src = buf[cur];
-    REAL_TYPE* dst = buf[(cur + 1) % nbuf];
-    if (plan.kind == PassPlan::SPLIT && plan.lag) {
-      const int p = itr - 1;
-      if (p >= 2) HIP_CHECK(hipStreamWaitEvent(st, ev_chk[p & 1], 0));  // the test of iteration itr-2
-      double* rs = d_res + ((p & 1) ? 10 : 0);
-      int* snap = d_flag + 2 + (p & 1);  // the flag as the test of iteration itr-2 left it (see CZ::JACOBI)
-      if (!pair_overlapped(src, dst, B, idx1, rb_par(gc, innerFidx, ip), snap, rs, mpp)) return 0;
-      HIP_CHECK(hipEventRecord(ev_int, st));
-      HIP_CHECK(hipStreamWaitEvent(comm_stream, ev_int, 0));
-      if (!comm_allreduce_sum(comm, rs, 1, comm_stream)) return 0;
-      check_on_stream(comm_stream, rs, res_normal, eps, itr, d_hist, d_flag, d_flag + 1, snap);
-      HIP_CHECK(hipEventRecord(ev_chk[p & 1], comm_stream));
-    } else if (plan.kind == PassPlan::SPLIT) {
-      if (!pair_overlapped(src, dst, B, idx1, rb_par(gc, innerFidx, ip), skip, nullptr, mpp)) return 0;
-      if (converge_check) {
-        if (!Comm_SUM_dev(d_res, 1, skip)) return 0;
-        czhip_check_async(d_res, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);
-      }
+    REAL_TYPE* src = L.src();
+    REAL_TYPE* dst = L.dst();
+    if (plan.kind == PassPlan::SPLIT) {
+      if (!split_pass(L, rb_par(gc, innerFidx, ip), 1, itr, mpp)) return 0;
     } else if (plan.kind == PassPlan::WHOLE && rb4 && itr + 1 <= itr_max && !(plan.zero_start && itr == 1)) {
       if (!czhip_rbsor4_async(src, dst, B, size, innerFidx, gc, cf, ip, ac1, d_res, res_normal, eps, itr, in_kernel_check ? d_hist : nullptr, d_flag,
                               d_flag + 1, skip, 0)) {  // :205-209 twice (+ :218-230 for both iterations)
@@ -1041,10 +1037,7 @@ int CZ::RBSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double
       done = 2;
       rb4_passes++;
     } else if (plan.kind == PassPlan::WHOLE) {
-      const int launched = (plan.zero_start && itr == 1)  // start vector identically zero (preconditioner), the right-hand side made on the way or read
-                               ? pass_from_zero_made(src, dst, B, made ? made->op : 0, made ? made->x : nullptr, made ? made->y : nullptr,
-                                                     made ? made->z : nullptr, made ? made->a : (REAL_TYPE)0, made ? made->a_dev : nullptr,
-                                                     made ? made->b : (REAL_TYPE)0, size, innerFidx, idx1, gc, cf, ac1, ip, d_res, 0)
+      const int launched = (plan.zero_start && itr == 1) ? zero_start_pass(src, dst, B, made, ip)
                            : maf ? pair_maf_async(src, dst, B, size, innerFidx, idx1, gc, d_xc, d_yc, d_zc, ac1, ip, d_res, res_normal, eps, itr,
                                                 in_kernel_check ? d_hist : nullptr, d_flag, d_flag + 1, skip)  // :190-200
                                : czhip_rbsor2_async(src, dst, B, size, innerFidx, idx1, gc, cf, ip, ac1, d_res, res_normal, eps, itr,
@@ -1052,13 +1045,7 @@ int CZ::RBSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double
       if (!launched) {
         cz_fatal(1, "error : fused red-black iteration refused after a successful probe\n");
       }
-      if (numProc > 1) {
-        if (!Comm_S2(dst, skip)) return 0;  // :215
-        if (converge_check) {
-          if (!Comm_SUM_dev(d_res, 1, skip)) return 0;
-          czhip_check_async(d_res, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);
-        }
-      }
+      if (!whole_exchange_test(L, 1, itr)) return 0;
     } else {
       for (int color = 0; color < 2; color++) {  // :205-209
         if (maf)
@@ -1073,118 +1060,46 @@ int CZ::RBSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double
         // identical to the single-domain one
         if (!Comm_S(X, skip)) return 0;
       }
-      if (converge_check && !in_kernel_check) {
-        if (!Comm_SUM_dev(d_res, 1, skip)) return 0;
-        czhip_check_async(d_res, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);
-      }
+      if (converge_check && !in_kernel_check && !reduce_test(1, itr, skip)) return 0;
     }
     flop += (maf ? 66.0 : 18.0) * npts() * done;
-    if (fused) {
-      launches.push_back({itr, done, cur});
-      cur = (cur + 1) % nbuf;
-      n_fused++;
-    }
+    if (plan.kind != PassPlan::SINGLE) L.record(itr, done);
     const int last_done = itr + done - 1;
     const bool poll_now = last_done / POLL_EVERY > (itr - 1) / POLL_EVERY;  // a multiple of POLL_EVERY iterations was completed by this launch
     itr += done;
-    if (converge_check && poll_now && last_done < itr_max) {
-      const int slot = npoll % POLL_SLOTS;
-      if (npoll >= POLL_SLOTS) HIP_CHECK(hipEventDestroy(ev[slot]));
-      if (plan.lag) {  // the same flag on every rank: after the tests of all iterations issued so far (see CZ::JACOBI)
-        HIP_CHECK(hipStreamWaitEvent(st, ev_chk[0], 0));
-        HIP_CHECK(hipStreamWaitEvent(st, ev_chk[1], 0));
-      }
-      HIP_CHECK(hipMemcpyAsync(h_flag + 2 * slot + 0, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-      HIP_CHECK(hipEventCreateWithFlags(&ev[slot], hipEventDisableTiming));
-      HIP_CHECK(hipEventRecord(ev[slot], st));
-      npoll++;
-      if (npoll >= 3) {
-        const int old = (npoll - 3) % POLL_SLOTS;  // same invariant as in CZ::JACOBI: a stream-ordered copy of all-reduced state
-        skew_wait();
-        HIP_CHECK(hipEventSynchronize(ev[old]));
-        if (h_flag[2 * old] != 0) stop = true;
-      }
-    }
+    if (converge_check && poll_now && last_done < itr_max) stop = L.poll.stop();
   }
-  for (int i = 0; i < (npoll < POLL_SLOTS ? npoll : POLL_SLOTS); i++) HIP_CHECK(hipEventDestroy(ev[i]));
-  if (plan.lag) HIP_CHECK(hipStreamSynchronize(comm_stream));  // the last tests
-  last_lag = plan.lag;
-  const int ret = finish_stationary(itr_max, 1, converge_check, res);
-  if (n_fused > 0) {
-    // out-of-place iterations: which buffer holds the iterate of the last executed iteration?  (launches after convergence were no-ops,
-    // or -- lagged mode -- wrote the third buffer)
-    const Launch* last = &launches.back();
-    if (converge_check && ret <= itr_max) {  // converged at iteration `ret`: the launch that contains it
-      for (const Launch& l : launches)
-        if (ret >= l.first_itr && ret < l.first_itr + l.niter) {
-          last = &l;
-          break;
-        }
-      if (last->niter == 2 && ret == last->first_itr) {
-        // the first iteration of a two-iteration pass converged: the pass wrote iteration n+2 into its destination; its source is untouched,
-        // so one fused iteration from it reproduces the converged iterate (exactly what the sequential loop holds)
-        if (!czhip_rbsor2_async(buf[last->src], buf[(last->src + 1) % nbuf], B, size, innerFidx, idx1, gc, cf, ip, ac1, d_res + 4, 0.0, 0.0, 0, nullptr,
-                                nullptr, nullptr, nullptr)) {
-          cz_fatal(1, "error : fused red-black iteration refused after a successful probe\n");
-        }
-        exact_reruns++;
-      }
+  // the first iteration of a two-iteration pass converged: one fused iteration
+  return fused_end(L, X, itr_max, res, [&](const Launch&, int, REAL_TYPE* s, REAL_TYPE* d) {
+    if (!czhip_rbsor2_async(s, d, B, size, innerFidx, idx1, gc, cf, ip, ac1, d_res + 4, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr)) {
+      cz_fatal(1, "error : fused red-black iteration refused after a successful probe\n");
     }
-    const int fb = (last->src + 1) % nbuf;
-    if (fb != 0) {
-      if (X == P) {
-        REAL_TYPE* t = P;
-        P = buf[fb];
-        if (fb == 1) WRK = t;
-        else WRK2 = t;
-      } else {
-        copy_inner_async(X, buf[fb], size, innerFidx, gc);
-      }
-    }
-  }
-  return ret;
+  });
 }
 
 // cz_Poisson.cpp:95-146.  Lexicographic point SOR, in place; one sweep = the launches of psor_async (tile hyperplanes).
 int CZ::PSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double& flop, int s_type, bool converge_check) {
   const bool maf = (s_type == LS_PSOR_MAF);  // :108-114
   const int gc = GUIDE;
-  hipStream_t st = stream();
   reset_ticket();
   const int* skip = nullptr;
   if (converge_check) {
     ensure_hist(itr_max + 2);
-    HIP_CHECK(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), st));
+    HIP_CHECK(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), stream()));
     skip = d_flag;
   }
-  hipEvent_t ev[POLL_SLOTS];
-  int npoll = 0;
+  FlagPoll poll(*this, false);
   bool stop = false;
-  int itr;
-  for (itr = 1; itr <= itr_max && !stop; itr++) {
+  for (int itr = 1; itr <= itr_max && !stop; itr++) {
     psor_async(X, B, size, innerFidx, gc, cf, maf ? d_xc : nullptr, d_yc, d_zc, ac1, d_res, 0, skip);  // :108-122
     flop += (maf ? 66.0 : 18.0) * npts();
     if (!Comm_S(X, skip)) return 0;  // :124 (decomposed: block-local sweeps, ghosts of the last exchange)
     if (converge_check) {
-      if (!Comm_SUM_dev(d_res, 1, skip)) return 0;                                 // :127
-      czhip_check_async(d_res, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);  // :128-141 on the device
-      if (itr % POLL_EVERY == 0 && itr < itr_max) {  // lagging, non-blocking view of the flag (as in RBSOR)
-        const int slot = npoll % POLL_SLOTS;
-        if (npoll >= POLL_SLOTS) HIP_CHECK(hipEventDestroy(ev[slot]));
-        HIP_CHECK(hipMemcpyAsync(h_flag + 2 * slot + 0, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipEventCreateWithFlags(&ev[slot], hipEventDisableTiming));
-        HIP_CHECK(hipEventRecord(ev[slot], st));
-        npoll++;
-        if (npoll >= 3) {
-          const int old = (npoll - 3) % POLL_SLOTS;
-          HIP_CHECK(hipEventSynchronize(ev[old]));
-          if (h_flag[2 * old] != 0) stop = true;
-        }
-      }
+      if (!reduce_test(1, itr, skip)) return 0;                              // :127-141 on the device
+      if (itr % POLL_EVERY == 0 && itr < itr_max) stop = poll.stop();
     }
   }
-  for (int i = 0; i < (npoll < POLL_SLOTS ? npoll : POLL_SLOTS); i++) HIP_CHECK(hipEventDestroy(ev[i]));
-  const int ret = finish_stationary(itr_max, 1, converge_check, res);
+  const int ret = finish_stationary(itr_max, converge_check, res);
   if (psor_failed()) {  // a column of the one-launch sweep gave up waiting for the columns before it: the iterate is void
     fprintf(stderr, "cz rank %d: %s: a sweep gave up a hand-off between its workgroups (bound: czhip_set_pcr_lex_timeout); the iterate is void.  "
                     "CZHIP_PSOR=0 selects the launch-per-tile-hyperplane form.\n", myRank, printMethod(s_type));
@@ -1194,29 +1109,48 @@ int CZ::PSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double&
   return ret;
 }
 
-// cz_Poisson.cpp:621-742 (pcr_rb_esa), :745-826 (pcr), :910-1005 (pcr_esa), :1008-1095 (pcr_j_esa): the line-SOR variants that end
-// in 4x4 systems and / or visit the columns in another order; one loop, the variant picks order and final stage.
-int CZ::LSOR_PCR_VARIANT(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double& flop, int s_type, bool converge_check) {
-  const int gc = GUIDE;
-  hipStream_t st = stream();
-  reset_ticket();
-  const int n = innerFidx[K_plus] - innerFidx[K_minus] + 1;
-  const int pn = pcr_num_stage(n);
+// ------------------------------------------------------------------------------------------------------------
+// The line solvers' shared steps.  pcr_num_stage of the k lines (:535-538): no stage count, no solve.
+int CZ::line_stages() {
+  const int pn = pcr_num_stage(innerFidx[K_plus] - innerFidx[K_minus] + 1);
   if (pn < 0) {
     printf("error : number of stage\n");
     exit(0);
   }
+  return pn;
+}
+
+// The test after an iteration (:584-601).  The line solves are long launches: a host round trip per iteration is negligible, so the
+// reference's sequential test is kept as is.  1: converged, 0: go on, -1: failed (message printed).
+int CZ::line_test(int itr, int s_type) {
+  if (!reduce_test(1, itr)) return -1;
+  HIP_CHECK(hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, stream()));
+  if (sweep_failed(printMethod(s_type))) return -1;  // (synchronises)
+  return h_flag[0] ? 1 : 0;
+}
+
+// The end of a line solve: the history of the iterations executed, or (unchecked) the NaN test of the last sweep.
+int CZ::line_finish(int itr, int itr_max, bool converge_check, double& res, int s_type) {
+  if (!converge_check) return sweep_failed(printMethod(s_type)) ? 0 : itr;  // (synchronises)
+  read_history(itr > itr_max ? itr_max : itr, res);
+  return itr;
+}
+
+// cz_Poisson.cpp:621-742 (pcr_rb_esa), :745-826 (pcr), :910-1005 (pcr_esa), :1008-1095 (pcr_j_esa): the line-SOR variants that end
+// in 4x4 systems and / or visit the columns in another order; one loop, the variant picks order and final stage.
+int CZ::LSOR_PCR_VARIANT(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double& flop, int s_type, bool converge_check) {
+  const int gc = GUIDE;
+  reset_ticket();
+  const int n = innerFidx[K_plus] - innerFidx[K_minus] + 1;
+  const int pn = line_stages();
   const int final4 = (s_type == LS_PCR_J_ESA || s_type == LS_PCR_EDA) ? 0 : 1;
   const int order = (s_type == LS_PCR_RB_ESA) ? 0 : (s_type == LS_PCR_J_ESA) ? 2 : 1;
   const int stages = final4 ? pn - 2 : pn - 1;
   const double fin = final4 ? (double)(1 << (pn - 2)) * (s_type == LS_PCR ? 74.0 : 78.0) : (double)(1 << (pn - 1)) * 9.0;
-  const int* skip = nullptr;
   if (converge_check) {
     ensure_hist(itr_max + 2);
-    HIP_CHECK(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), st));
-    skip = d_flag;
+    HIP_CHECK(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), stream()));
   }
-  (void)skip;
   int itr;
   for (itr = 1; itr <= itr_max; itr++) {
     if (order == 0) {
@@ -1234,43 +1168,26 @@ int CZ::LSOR_PCR_VARIANT(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_
     }
     flop += (npts() / n) * (n * 6.0 + n * (double)stages * 14.0 + fin + n * 6.0 + 6.0);
     if (converge_check) {
-      // long launches: a host round trip per iteration is negligible, the reference's sequential test is kept as is
-      if (!Comm_SUM_dev(d_res, 1)) return 0;
-      czhip_check_async(d_res, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);
-      HIP_CHECK(hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-      if (sweep_failed(printMethod(s_type))) return 0;  // (synchronises)
-      if (h_flag[0]) break;
+      const int t = line_test(itr, s_type);
+      if (t < 0) return 0;
+      if (t > 0) break;
     }
   }
-  if (converge_check) {
-    const int n_exec = itr > itr_max ? itr_max : itr;
-    const size_t base = history.size();
-    history.resize(base + n_exec);
-    HIP_CHECK(hipMemcpy(history.data() + base, d_hist + 1, (size_t)n_exec * sizeof(double), hipMemcpyDeviceToHost));
-    res = history.back();
-  } else {
-    if (sweep_failed(printMethod(s_type))) return 0;  // (synchronises)
-  }
-  return itr;
+  return line_finish(itr, itr_max, converge_check, res, s_type);
 }
 
 // The line solvers of the MAF flavour (cz_Poisson.cpp:549-557, 665-683, 770-776, 853-859, 940-946 call pcr_rb_maf_, pcr_rb_esa_maf_,
 // pcr_maf_, pcr_eda_maf_, pcr_esa_maf_): coefficients from the metrics of the 1-D grids, pn-1 stages + 2x2 systems.
 int CZ::LSOR_PCR_MAF(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double& flop, int s_type, bool converge_check) {
   const int gc = GUIDE;
-  hipStream_t st = stream();
   reset_ticket();
   const int n = innerFidx[K_plus] - innerFidx[K_minus] + 1;
-  const int pn = pcr_num_stage(n);
-  if (pn < 0) {
-    printf("error : number of stage\n");
-    exit(0);
-  }
+  const int pn = line_stages();
   const bool rb = (s_type == LS_PCR_RB_MAF || s_type == LS_PCR_RB_ESA_MAF);
   const double fin = (s_type == LS_PCR_EDA_MAF || s_type == LS_PCR_ESA_MAF) ? 9.0 : 11.0;
   if (converge_check) {
     ensure_hist(itr_max + 2);
-    HIP_CHECK(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), st));
+    HIP_CHECK(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), stream()));
   }
   int itr;
   for (itr = 1; itr <= itr_max; itr++) {
@@ -1285,40 +1202,23 @@ int CZ::LSOR_PCR_MAF(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max,
     }
     flop += (npts() / n) * ((24.0 + 6.0 + 12.0) + n * 21.0 + (n - 2.0) * 6.0 + n * (double)(pn - 1) * 16.0 + (double)(1 << (pn - 1)) * fin + n * 6.0);
     if (converge_check) {
-      if (!Comm_SUM_dev(d_res, 1)) return 0;
-      czhip_check_async(d_res, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);
-      HIP_CHECK(hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-      if (sweep_failed(printMethod(s_type))) return 0;  // (synchronises)
-      if (h_flag[0]) break;
+      const int t = line_test(itr, s_type);
+      if (t < 0) return 0;
+      if (t > 0) break;
     }
   }
-  if (converge_check) {
-    const int n_exec = itr > itr_max ? itr_max : itr;
-    const size_t base = history.size();
-    history.resize(base + n_exec);
-    HIP_CHECK(hipMemcpy(history.data() + base, d_hist + 1, (size_t)n_exec * sizeof(double), hipMemcpyDeviceToHost));
-    res = history.back();
-  } else {
-    if (sweep_failed(printMethod(s_type))) return 0;  // (synchronises)
-  }
-  return itr;
+  return line_finish(itr, itr_max, converge_check, res, s_type);
 }
 
 // cz_Poisson.cpp:518-611.  Line SOR: every (i,j) column of one checkerboard colour is solved along k by parallel cyclic
 // reduction (pcr_rb_k), colour 0 then colour 1, in place.  Single-domain.
 int CZ::LSOR_PCR_RB(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double& flop, int s_type, bool converge_check) {
   const int gc = GUIDE;
-  hipStream_t st = stream();
   reset_ticket();
-  const int n = innerFidx[K_plus] - innerFidx[K_minus] + 1;
-  const int pn = pcr_num_stage(n);  // :535-538
-  if (pn < 0) {
-    printf("error : number of stage\n");
-    exit(0);
-  }
+  const int pn = line_stages();
   if (converge_check) {
     ensure_hist(itr_max + 2);
-    HIP_CHECK(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), st));
+    HIP_CHECK(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), stream()));
   }
   int itr;
   for (itr = 1; itr <= itr_max; itr++) {
@@ -1330,25 +1230,12 @@ int CZ::LSOR_PCR_RB(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, 
     }
     flop += npts() * (12.0 + (pn - 1) * 14.0);
     if (converge_check) {
-      // the line solves are long launches: a host round trip per iteration is negligible here, so the reference's
-      // sequential test (:584-601) is kept as is
-      if (!Comm_SUM_dev(d_res, 1)) return 0;
-      czhip_check_async(d_res, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);
-      HIP_CHECK(hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-      if (sweep_failed(printMethod(s_type))) return 0;  // (synchronises)
-      if (h_flag[0]) break;
+      const int t = line_test(itr, s_type);
+      if (t < 0) return 0;
+      if (t > 0) break;
     }
   }
-  if (converge_check) {
-    const int n_exec = itr > itr_max ? itr_max : itr;
-    const size_t base = history.size();
-    history.resize(base + n_exec);
-    HIP_CHECK(hipMemcpy(history.data() + base, d_hist + 1, (size_t)n_exec * sizeof(double), hipMemcpyDeviceToHost));
-    res = history.back();
-  } else {
-    if (sweep_failed(printMethod(s_type))) return 0;  // (synchronises)
-  }
-  return itr;
+  return line_finish(itr, itr_max, converge_check, res, s_type);
 }
 
 // cz_Poisson.cpp:239-270.  The reference reduces in REAL on every rank and all-reduces the REAL; here the double
@@ -1385,8 +1272,6 @@ bool CZ::bicg_fusable(int pc_type) {
   const bool rb = pc_type == LS_SOR2SMA;
   const PassPlan plan = plan_pass(pcg_p_, pcg_p, pc_type, 8, false, true, rb, true);
   if (!(plan.kind == PassPlan::WHOLE && plan.zero_start)) return false;
-  int idx1[6];
-  for (int f = 0; f < 6; f++) idx1[f] = innerFidx[f];
   return czhip_jacobi2_from_zero_made_async(pcg_p_, WRK, pcg_s, 2, pcg_r, pcg_q, pcg_p, (REAL_TYPE)0, (REAL_TYPE)0, size, innerFidx, idx1, GUIDE, cf, ac1,
                                             rb ? 0 : -1, d_res, 1) != 0;
 }

@@ -4,6 +4,7 @@
 #define CZ_DRIVER_H_
 
 #include <cstdio>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -34,6 +35,7 @@ class CZ {
   int G_size[3] = {0, 0, 0};
   REAL_TYPE G_origin[3] = {0, 0, 0};
   int innerFidx[6] = {0, 0, 0, 0, 0, 0};
+  int idx1[6] = {0, 0, 0, 0, 0, 0};  // first sweep of a fused pass: innerFidx plus one layer into the ghost cells across rank-internal faces
 
   // ---- CZ (cz.h:84-133, 154-181)
   int debug_mode = 0;
@@ -163,13 +165,33 @@ class CZ {
   bool Comm_S(REAL_TYPE* X, const int* skip_flag = nullptr);
   bool Comm_S2(REAL_TYPE* X, const int* skip_flag = nullptr);  // two layers + edges (fused Jacobi pairs)
   bool Comm_SUM_dev(double* d_val, int count, const int* skip_flag = nullptr);
+  bool reduce_test(int nres, int itr, const int* skip = nullptr);
   void plan_overlap();
-  bool pair_overlapped(REAL_TYPE* src, REAL_TYPE* dst, REAL_TYPE* B, const int* idx1, int rb, const int* skip, double* res_slot = nullptr,
+  bool pair_overlapped(REAL_TYPE* src, REAL_TYPE* dst, REAL_TYPE* B, int rb, const int* skip, double* res_slot = nullptr,
                        const czhip_internal::MafPtrs* maf = nullptr);
   PassPlan plan_pass(REAL_TYPE* X, REAL_TYPE* B, int s_type, int itr_max, bool converge_check, bool x_is_zero, bool rb, bool probe_only = false);
   bool Comm_SUM_1(double* host_val);
 
-  int finish_stationary(int itr_max, int first_itr, bool converge_check, double& res);
+  // the host's lagging look at the device convergence flag (JACOBI, RBSOR, PSOR) and the skeleton JACOBI and RBSOR share (cz_driver.cpp)
+  class FlagPoll;
+  void wait_lagged_tests();
+  struct Launch {
+    int first_itr, n, src;  // first iteration, iterations, index of the source buffer
+  };
+  class FusedLoop;
+  using Rerun = std::function<void(const Launch& l, int k, REAL_TYPE* src, REAL_TYPE* dst)>;
+  bool fused_begin(FusedLoop& L, REAL_TYPE* X, int itr_max, bool x_is_zero, const BMade* made);
+  bool split_pass(FusedLoop& L, int rb, int nres, int itr, const czhip_internal::MafPtrs* mpp);
+  bool whole_exchange_test(FusedLoop& L, int nres, int itr);
+  int zero_start_pass(REAL_TYPE* src, REAL_TYPE* dst, REAL_TYPE* B, const BMade* made, int rb);
+  int fused_end(FusedLoop& L, REAL_TYPE* X, int itr_max, double& res, const Rerun& rerun);
+
+  int finish_stationary(int itr_max, bool converge_check, double& res);
+  void read_history(int n_exec, double& res);
+  // line solvers: the stage count of the k lines (exits when there is none), the test after an iteration, the end of the solve
+  int line_stages();
+  int line_test(int itr, int s_type);
+  int line_finish(int itr, int itr_max, bool converge_check, double& res, int s_type);
   // line solvers: the one-launch lexicographic sweep reports a lost hand-off between its workgroups as a NaN residual (every wait inside
   // it is bounded); the iterate is then void and the solve ends with "Solver error" instead of sweeping on (true = failed; message printed)
   bool sweep_failed(const char* solver);

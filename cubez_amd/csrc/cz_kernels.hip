@@ -415,14 +415,9 @@ int czhip_jacobi2_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const in
 // the same with literal zeros.  `u_shape` is only used for its alignment/geometry checks.  No convergence bookkeeping.
 int czhip_jacobi2_from_zero_async(const CZ_REAL* u_shape, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, const int* idx1,
                                   int g, const CZ_REAL* cf, CZ_REAL omg, double* res_dev) {
-  ensure_init();
-  if (!ctx.tune.fuse_fin) return 0;
-  const Box bx = make_box(sz, idx, g);
-  if (bx.empty || g < 2) return 0;
-  const Box ba = idx1 ? make_box(sz, idx1, g) : bx;
-  Fin2 fin;
-  fin.dst = res_dev;
-  return launch_jacobi2<0>(u_shape, b, w, make_coef(cf, omg), bx, ba, nullptr, fin, 0, 1) ? 1 : 0;
+  // (op 0 only reads b)
+  return czhip_internal::pass_from_zero_made(u_shape, w, const_cast<CZ_REAL*>(b), 0, nullptr, nullptr, nullptr, (CZ_REAL)0, nullptr, (CZ_REAL)0, sz, idx,
+                                             idx1, g, cf, omg, -1, res_dev, 0);
 }
 
 // The same with the right-hand side of the solve MADE on the way: op 1: b = a*x + y (blas_triad_: s = r - alpha q), op 2: b = x + a*(z - bb*y)
