@@ -69,6 +69,33 @@ class DeviceArray:
             self.ptr = None
 
 
+class DeviceBuffer:
+    """A small device array of doubles or ints (residual sums, history, convergence flag) for the checked launches of part 3.
+    Allocated through czhip_alloc_s3d (zero-filled, on the library's device), so no other allocator or stream is involved."""
+
+    def __init__(self, hip: "CzHip", n: int, dtype):
+        self.hip, self.n, self.dtype = hip, int(n), np.dtype(dtype)
+        self.nbytes = self.n * self.dtype.itemsize
+        k = -(-self.nbytes // (25 * hip.real().itemsize))  # (1+4) x (1+4) x (k+4) REALs hold at least nbytes
+        self.ptr = hip.lib.czhip_alloc_s3d((C.c_int * 3)(1, 1, max(k, 1)))
+
+    def put(self, host):
+        host = np.ascontiguousarray(host, dtype=self.dtype)
+        assert host.size == self.n
+        self.hip.lib.czhip_h2d(self.ptr, host.ctypes.data_as(C.c_void_p), self.nbytes)
+        return self
+
+    def get(self) -> np.ndarray:
+        out = np.empty(self.n, dtype=self.dtype)
+        self.hip.lib.czhip_d2h(out.ctypes.data_as(C.c_void_p), self.ptr, self.nbytes)
+        return out
+
+    def free(self):
+        if self.ptr:
+            self.hip.lib.czhip_free(self.ptr)
+            self.ptr = None
+
+
 class CzHip:
     """The drop-in kernels with the reference's argument conventions (everything by pointer)."""
 
@@ -210,6 +237,66 @@ class CzHip:
         out = (C.c_double * 2)()
         self.lib.czhip_d2h(out, self._dres, 16)
         return bool(ok), out[0], out[1]
+
+    # -- part 3 with the convergence bookkeeping.  ck: dict of device state -- res (DeviceBuffer of doubles: the sums), hist (doubles or None),
+    # flag, conv (ints), skip (ints or None) -- and the scalars res_normal, eps, itr
+    def dbuf(self, n, dtype=np.float64, fill=None) -> DeviceBuffer:
+        d = DeviceBuffer(self, n, dtype)
+        if fill is not None:
+            d.put(np.full(n, fill, dtype=dtype))
+        return d
+
+    @staticmethod
+    def _ck(ck):
+        p = lambda d: d.ptr if d is not None else None  # noqa: E731
+        return (ck["res"].ptr, float(ck.get("res_normal", 0.0)), float(ck.get("eps", 0.0)), int(ck.get("itr", 0)), p(ck.get("hist")),
+                p(ck.get("flag")), p(ck.get("conv")))
+
+    def jacobi_checked(self, u, w, b, sz, idx, cf, omg, ck):
+        """czhip_jacobi_checked_async: one sweep u -> w, its sum in res[0], the bookkeeping of iteration itr; flag doubles as skip flag"""
+        (_, szp), (_, idxp), (_, cfp) = self._i(sz), self._i(idx), self._r(cf)
+        f = self.lib.czhip_jacobi_checked_async
+        f.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_void_p, self.creal, C.c_void_p, C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 3
+        f(u.ptr, w.ptr, b.ptr, szp, idxp, GUIDE, cfp, float(omg), *self._ck(ck))
+
+    def rbsor_async(self, p, b, sz, idx, cf, ofst, color, omg, res, accumulate=0, skip=None):
+        """czhip_rbsor_async: one colour in place, sum in res[0] (= or +=); skip: DeviceBuffer of ints or None"""
+        (_, szp), (_, idxp), (_, cfp) = self._i(sz), self._i(idx), self._r(cf)
+        f = self.lib.czhip_rbsor_async
+        f.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_int, self.creal, C.c_void_p, C.c_int, C.c_void_p]
+        f(p.ptr, b.ptr, szp, idxp, GUIDE, cfp, int(ofst), int(color), float(omg), res.ptr, int(accumulate), skip.ptr if skip is not None else None)
+
+    def rbsor_checked(self, p, b, sz, idx, cf, ofst, color, omg, accumulate, ck):
+        """czhip_rbsor_checked_async: one colour in place with the bookkeeping of iteration itr (the driver passes it with colour 1)"""
+        (_, szp), (_, idxp), (_, cfp) = self._i(sz), self._i(idx), self._r(cf)
+        f = self.lib.czhip_rbsor_checked_async
+        f.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_int, self.creal, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        res, rn, eps, itr, hist, flag, conv = self._ck(ck)
+        f(p.ptr, b.ptr, szp, idxp, GUIDE, cfp, int(ofst), int(color), float(omg), res, int(accumulate), rn, eps, itr, hist, flag, conv)
+
+    def pass_checked(self, kind, u, w, b, sz, idx, cf, omg, ck, ofst=0) -> bool:
+        """one fused pass u -> w with the bookkeeping of its iterations (hist given) or only a skip flag (hist None, skip given):
+        kind jacobi2 | rbsor2 | rbsor4 | jacobi3; returns launched"""
+        (_, szp), (_, idxp), (_, cfp) = self._i(sz), self._i(idx), self._r(cf)
+        res, rn, eps, itr, hist, flag, conv = self._ck(ck)
+        skip = ck["skip"].ptr if ck.get("skip") is not None else None
+        tail = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if kind in ("jacobi2", "rbsor2"):
+            f = getattr(self.lib, f"czhip_{kind}_async")
+            f.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_void_p] + ([C.c_int] if kind == "rbsor2" else []) + [self.creal] + tail
+            mid = [int(ofst)] if kind == "rbsor2" else []
+            return bool(f(u.ptr, w.ptr, b.ptr, szp, idxp, None, GUIDE, cfp, *mid, float(omg), res, rn, eps, itr, hist, flag, conv, skip))
+        f = self.lib.czhip_rbsor4_async if kind == "rbsor4" else self.lib.czhip_jacobi3_async
+        f.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_void_p] + ([C.c_int] if kind == "rbsor4" else []) + [self.creal] + tail + [C.c_int]
+        mid = [int(ofst)] if kind == "rbsor4" else []
+        return bool(f(u.ptr, w.ptr, b.ptr, szp, idxp, GUIDE, cfp, *mid, float(omg), res, rn, eps, itr, hist, flag, conv, skip, 0))
+
+    def check(self, ck, pair=False):
+        """czhip_check_async (pair: czhip_check2_async) on the sums in res"""
+        f = self.lib.czhip_check2_async if pair else self.lib.czhip_check_async
+        f.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        f(*self._ck(ck))
 
     def timing(self, enable: bool):
         """HIP-event timing of the library's launches, per label (czhip_timing)."""

@@ -254,7 +254,8 @@ int czhip_jacobi2_from_zero_async(const CZ_REAL* u_shape, CZ_REAL* w, const CZ_R
 int czhip_jacobi2_from_zero_made_async(const CZ_REAL* u_shape, CZ_REAL* w, CZ_REAL* b_out, int op, const CZ_REAL* x, const CZ_REAL* y,
                                        const CZ_REAL* z, CZ_REAL a, CZ_REAL bb, const int* sz, const int* idx, const int* idx1, int g,
                                        const CZ_REAL* cf, CZ_REAL omg, int rb_ofst, double* res_dev, int probe);
-/* The same bookkeeping for a pair whose two sums were all-reduced first (decomposed runs). */
+/* The same bookkeeping for a pair whose two sums were all-reduced first (decomposed runs).  Here and in every checked pass of several
+ * iterations the bookkeeping stops at the first converged iteration: hist entries of the later iterations of the pass are not written. */
 void czhip_check2_async(const double* res_dev, double res_normal, double eps, int itr, double* hist_dev, int* flag_dev,
                         int* conv_itr_dev);
 /* The MAF flavour of the two calls above (cz_maf.f90:131-438): weights recomputed at every point from the host coordinate arrays X, Y, Z

@@ -28,10 +28,24 @@ def _single(prec, gsz, solver, itmax, coef, pc=None):
 
 def _decomposed(prec, gsz, solver, itmax, coef, div, pc=None, overlap=1, solves=1, env=None):
     import os
+    # CZ_OVERLAP is read by the driver when a CZ is created, the kernel switches by each rank thread when its library context is created (the
+    # threads are new); whatever happens here, the environment of the tests that follow is restored
+    switches = dict(env or {}, CZ_OVERLAP=str(overlap))
+    saved = {k: os.environ.get(k) for k in switches}
+    os.environ.update(switches)
+    try:
+        return _decomposed_run(prec, gsz, solver, itmax, coef, div, pc, solves)
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def _decomposed_run(prec, gsz, solver, itmax, coef, div, pc, solves):
+    import os
     from cubez_amd import CZ, load
-    os.environ["CZ_OVERLAP"] = str(overlap)  # read by the driver when a CZ is created
-    for k, v in (env or {}).items():  # kernel switches: read by each rank thread when its library context is created (the threads are new)
-        os.environ[k] = v
     lib = load(prec)
     import ctypes as C
     lib.cz_comm_local_world.restype = C.c_void_p
@@ -75,9 +89,6 @@ def _decomposed(prec, gsz, solver, itmax, coef, div, pc=None, overlap=1, solves=
         os._exit(3)
     assert not errors, errors
     assert all(r is not None for r in results)
-    os.environ.pop("CZ_OVERLAP")
-    for k in (env or {}):
-        os.environ.pop(k)
     lib.cz_comm_local_world_free(world)
     # assemble the global field from the owned cells of every brick
     g = 2
