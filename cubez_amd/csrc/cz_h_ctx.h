@@ -66,6 +66,7 @@ struct Ctx {
   std::map<std::vector<double>, REAL*> bc_tabs;  // key: ix, jx, dh, org0, org1
   struct PairMap { int* dev = nullptr; long long nblk = 0; };
   std::map<long long, PairMap> pair_maps;        // workgroup id -> (segment, chunk) tables of the two-stage pass, key nseg << 32 | nchunk
+  std::set<const void*> lds_allowed;             // kernels whose dynamic LDS limit is raised on this context's device (allow_dynamic_lds)
   int num_cu = 256;
   int cu_reserved = 0;          // CUs per XCD the sweeps leave to the exchange stream (decomposed runs; reserve_comm_cus): the launch geometry counts them out
   // optional per-launch HIP-event timing of the labelled kernels (bench.py roofline leg)
@@ -131,6 +132,14 @@ void ensure_partials(size_t n) {
   size_t cap = n < 65536 ? 65536 : n;
   HIP_CHECK(hipMalloc(&ctx.partials, cap * sizeof(double)));
   ctx.partials_cap = cap;
+}
+
+// Dynamic LDS beyond the default is opted into per kernel (hipFuncSetAttribute); once per kernel and context, i.e. on the context's device
+template <typename K>
+void allow_dynamic_lds(K* kernel, int bytes) {
+  const void* k = reinterpret_cast<const void*>(kernel);
+  if (!ctx.lds_allowed.insert(k).second) return;
+  HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
 }
 
 struct Box {

@@ -40,12 +40,7 @@ void launch_stencil_inst(const REAL* P, const REAL* B, REAL* OUT, const Coef& c,
     cz_fatal(1, "czhip: k-row of %d elements needs %zu bytes of LDS (>160 KiB)\n", b.nkp, lds);
   }
   if (MODE == MODE_JACOBI || MODE == MODE_RB || MODE == MODE_AX || MODE == MODE_DIRAX) ensure_partials((size_t)2 * nblk);
-  static bool attr_set = false;
-  if (!attr_set) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&stencil_k<V, TB, M, PF, MODE, MAF>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  allow_dynamic_lds(&stencil_k<V, TB, M, PF, MODE, MAF>, 160 * 1024);
   {
     ScopedTimer tm(MODE == MODE_JACOBI ? LBL_JACOBI : MODE == MODE_RB ? LBL_RBSOR : (MODE == MODE_AX || MODE == MODE_DIRAX) ? LBL_AX : LBL_RK);
     hipLaunchKernelGGL((stencil_k<V, TB, M, PF, MODE, MAF>), dim3((unsigned)nblk), dim3(TB), lds, ctx.stream, P, B, OUT, c, g, par,
@@ -77,6 +72,14 @@ void launch_stencil(const REAL* P, const REAL* B, REAL* OUT, const Coef& c, cons
   launch_stencil_inst<VW, 512, 2, 0, MODE>(P, B, OUT, c, b, par, tu.tj, skip, nblk_out, fin);
 }
 
+// the coefficients of the MAF kernels, which compute their weights per point: only omg
+Coef make_coef_omg(REAL omg) {
+  Coef c;
+  c.c1 = c.c2 = c.c3 = c.c4 = c.c5 = c.c6 = c.dd = (REAL)0;
+  c.omg = omg;
+  return c;
+}
+
 // MAF flavour: one tuned shape (and the scalar fallback); coordinates / pvt are device pointers
 template <int MODE>
 void launch_stencil_maf(const REAL* P, const REAL* B, REAL* OUT, REAL omg, const Box& b, int par, const int* skip, int* nblk_out,
@@ -84,9 +87,7 @@ void launch_stencil_maf(const REAL* P, const REAL* B, REAL* OUT, REAL omg, const
   if (b.g != 2) {
     cz_fatal(1, "czhip: the MAF kernels assume GUIDE = 2 (X(-1:sz+2), cz_maf.f90:146-148)\n");
   }
-  Coef c;
-  c.c1 = c.c2 = c.c3 = c.c4 = c.c5 = c.c6 = c.dd = (REAL)0;
-  c.omg = omg;
+  const Coef c = make_coef_omg(omg);
   if (rows_ok(b, {P, B, OUT, ma.pvt}))
     launch_stencil_inst<VW, 512, 2, 0, MODE, 1>(P, B, OUT, c, b, par, ctx.tune.tj, skip, nblk_out, fin, ma);
   else
@@ -180,28 +181,38 @@ inline bool coef_is_unit(const Coef& c) {
   return c.c1 == (REAL)1 && c.c2 == (REAL)1 && c.c3 == (REAL)1 && c.c4 == (REAL)1 && c.c5 == (REAL)1 && c.c6 == (REAL)1;
 }
 
-// two fused sweeps (jacobi2p_k); returns false when the geometry does not suit the kernel (caller falls back to two stencil_k launches)
-template <int TB, int MV, int RB, int ZU, int MAF = 0, int BS = 0, int PRE = 0, int UNIT = 0>
-bool launch_jacobi2_inst(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box& b, const Box& ba, int tj_req,
-                         const int* skip, const Fin2& fin_in, int par, bool probe, double* model_cost, const MafArgs& ma = MafArgs(),
-                         const BSrc& bs = BSrc()) {
-  constexpr int V = VW;
+// A multi-stage pass (jacobi2p_k, rb4_k, jac3_k, all on Geom2): what its launcher chooses, and what plan_pass makes of it
+struct PassPlan {
+  int TB = 0;             // threads per workgroup
+  int own = 0;            // vectors a workgroup holds; S = own - halo_rows * R of them are its own
+  int halo_rows = 2;
+  int max_R = 0;          // longest row (window and halo vectors) a workgroup takes
+  int kwin = 0;           // vectors per k window; 0: whole rows
+  int hv = 1;             // halo vectors on either side of a window
+  int wg_per_cu = 0;      // resident workgroups per CU for the chunk model; 0: as many as LDS and threads allow
+  double extra = 3.5;     // plane steps a chunk costs beyond its own (pair_tj_model)
+  int tj = 0;             // planes per chunk; 0: the model's choice
+  int nres = 2;           // residual slots per workgroup in ctx.partials
+  int par = 0, zero_u = 0;
+  // filled in by plan_pass
   Geom2 g;
-  const int Rfull = (b.nkp + V - 1) / V;  // rows as vectors from a vector boundary each; the last one partial where nkp % V != 0 (Geom2)
-  // k windows (Geom2): whole rows where a segment of them is a decent share of the workgroup's vectors, else windows of about kPairWin vectors;
-  // CZHIP_T2_KWIN / ctx.tune.t2_kwin: > 0 = vectors per window, 0 = whole rows wherever they fit, -1 = this rule
-  const bool whole_fits = 2 * Rfull <= TB && 4 * Rfull < TB * MV;  // the outer rows are staged by 2R threads / halo rows would dominate
-  int want = ctx.tune.t2_kwin;
-  if (want < 0) want = (whole_fits && (pair_whole_rows_ok(Rfull, TB * MV) || BS)) ? 0 : kPairWin;  // (BS: the pass that makes its right-hand side reads
-                                                                                                     // three or four arrays; the halo vectors of two windows cost it 6-8 % at 512^3 FP64)
-  if (want == 0 && !whole_fits) want = kPairWin;
-  g.R = Rfull;
-  if (want > 0 && want < Rfull) {
-    g.nwin = (Rfull + want - 1) / want;
-    g.KT = (Rfull + g.nwin - 1) / g.nwin;
-    g.hv = 1, g.KW = g.KT * V, g.R = g.KT + 2;
+  size_t lds = 0;
+  int nchunk = 0;
+};
+
+// Geometry of a multi-stage pass over the output box b with the stage-1 box ba; lds_bytes(R, S) is the kernel's dynamic LDS.  Returns false
+// where the geometry does not suit the kernel.  model_cost: the launch's cost by pair_tj_model, in plane steps x work per CU and step.
+template <class LdsBytes>
+bool plan_pass(PassPlan& p, const Box& b, const Box& ba, LdsBytes lds_bytes, double* model_cost = nullptr) {
+  constexpr int V = VW;
+  Geom2& g = p.g;
+  g.R = (b.nkp + V - 1) / V;  // rows as vectors from a vector boundary each; the last one partial where nkp % V != 0 (Geom2)
+  if (p.kwin > 0) {
+    g.nwin = (g.R + p.kwin - 1) / p.kwin;
+    g.KT = (g.R + g.nwin - 1) / g.nwin;
+    g.hv = p.hv, g.KW = g.KT * V, g.R = g.KT + 2 * p.hv;
   }
-  if (2 * g.R > TB || 4 * g.R >= TB * MV) return false;
+  if (g.R > p.max_R) return false;
   g.PSV = (long long)g.R * b.nip;
   g.nkp = b.nkp;
   g.PSB = (long long)b.nkp * b.nip * (long long)sizeof(REAL);
@@ -214,50 +225,75 @@ bool launch_jacobi2_inst(const REAL* U, const REAL* B, REAL* W, const Coef& c, c
   g.kk0a = ba.kk0, g.kk1a = ba.kk1, g.jj0a = ba.jj0, g.jj1a = ba.jj1;
   g.F0a = (long long)ba.ii0 * g.R;
   g.Fenda = (long long)(ba.ii1 + 1) * g.R;
-  g.S = TB * MV - 2 * g.R;
-  g.par = par;
-  g.zero_u = ZU;
-  const long long nf = g.Fend - g.F0;
-  g.nsegw = (int)((nf + g.S - 1) / g.S);
+  g.S = p.own - p.halo_rows * g.R;
+  g.par = p.par, g.zero_u = p.zero_u;
+  g.nsegw = (int)((g.Fend - g.F0 + g.S - 1) / g.S);
   g.nseg = g.nwin * g.nsegw;
+  g.band = 1, g.map = nullptr;
+  p.lds = lds_bytes(g.R, g.S);
+  if (p.lds > 160 * 1024) return false;
   const int nplanes = b.jj1 - b.jj0 + 1;
-  const size_t lds = (size_t)2 * ((g.S + 4 * g.R) + (g.S + 2 * g.R)) * sizeof(Vec<V>) + 18 * sizeof(double) +
-                     (MAF ? (size_t)2 * g.R * V * sizeof(REAL) : 0);  // MAF: the table of the k metric terms
-  if (lds > 160 * 1024) return false;
-  const int wg_per_cu = (MAF && TB == 512) ? 1 : std::max(1, std::min((int)(160 * 1024 / lds), 2048 / TB));  // (MAF: a 512-thread workgroup of up to 256 registers per thread fills a CU's register file)
-  int tj = tj_req;
-  if (PRE) {
-    // the preloaded form (jacobi2p_k<PRE>): chunks of PRE planes, and only where every workgroup of the pass is resident at once -- one
-    // workgroup per CU (its operands live in ~190 registers per thread) less the CUs left to the exchange stream of a decomposed run
-    tj = std::min(PRE, nplanes);
-    const long long slots = (long long)std::max(1, ctx.num_cu / 8 - ctx.cu_reserved) * 8;  // (one per CU also for the 256 x 1 shape: measured, profiles/r04/small_grids_preloaded_shapes.txt)
-    if ((long long)g.nseg * ((nplanes + tj - 1) / tj) > slots) return false;
-  } else {
-    const double cost = pair_tj_model(g.nseg, nplanes, wg_per_cu, pair_use_map(g.nseg), tj > 0 ? &g.TJ : &tj);
-    if (model_cost) *model_cost = cost * wg_per_cu * (double)(TB * MV + g.S);  // plane steps x work per CU and step
+  const int wg_per_cu = p.wg_per_cu > 0 ? p.wg_per_cu : std::max(1, std::min((int)(160 * 1024 / p.lds), 2048 / p.TB));
+  int tj = p.tj;
+  if (tj <= 0 || model_cost) {
+    int best = 0;
+    const double cost = pair_tj_model(g.nseg, nplanes, wg_per_cu, pair_use_map(g.nseg), &best, p.extra);
+    if (model_cost) *model_cost = cost * wg_per_cu * (double)(p.own + g.S);
+    if (tj <= 0) tj = best;
   }
-  if (tj > nplanes) tj = nplanes;
-  g.TJ = tj;
-  const int nchunk = (nplanes + tj - 1) / tj;
-  g.band = 1;
-  g.map = nullptr;
-  long long nblk = 8LL * ((g.nseg + 7) / 8) * nchunk;
-  if (probe) return true;
-  if (pair_use_map(g.nseg)) g.map = pair_xcd_map(g.nseg, nchunk, &nblk);
-  ensure_partials((size_t)2 * nblk);
-  static bool attr_set = false;
-  if (!attr_set) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&jacobi2p_k<V, TB, MV, RB, ZU, MAF, BS, PRE, UNIT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024));
-    attr_set = true;
-  }
-  Fin2 fin = fin_in;
+  g.TJ = std::min(tj, nplanes);
+  p.nchunk = (nplanes + g.TJ - 1) / g.TJ;
+  return true;
+}
+
+// Launch of a planned pass: workgroup order, partials, arrival counter; the kernel takes (U, B, W, c, g, partials, skip, fin, extra...)
+template <typename... P, typename... A>
+void launch_pass(void (*kernel)(P...), int label, PassPlan& p, const REAL* U, const REAL* B, REAL* W, const Coef& c, const int* skip, Fin2 fin,
+                 const A&... extra) {
+  long long nblk = 8LL * ((p.g.nseg + 7) / 8) * p.nchunk;
+  if (pair_use_map(p.g.nseg)) p.g.map = pair_xcd_map(p.g.nseg, p.nchunk, &nblk);
+  ensure_partials((size_t)p.nres * nblk);
+  allow_dynamic_lds(kernel, 160 * 1024);
   fin.counter = ctx.counter;
   {
-    ScopedTimer tm(RB ? LBL_RBSOR2 : LBL_JACOBI2);
-    hipLaunchKernelGGL((jacobi2p_k<V, TB, MV, RB, ZU, MAF, BS, PRE, UNIT>), dim3((unsigned)nblk), dim3(TB), lds, ctx.stream, U, B, W, c, g, ctx.partials, skip, fin, ma, bs);
+    ScopedTimer tm(label);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(p.TB), p.lds, ctx.stream, U, B, W, c, p.g, ctx.partials, skip, fin, extra...);
   }
   HIP_CHECK(hipGetLastError());
+}
+
+// two fused sweeps (jacobi2p_k); returns false when the geometry does not suit the kernel (caller falls back to two stencil_k launches)
+template <int TB, int MV, int RB, int ZU, int MAF = 0, int BS = 0, int PRE = 0, int UNIT = 0>
+bool launch_jacobi2_inst(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box& b, const Box& ba, int tj_req,
+                         const int* skip, const Fin2& fin, int par, bool probe, double* model_cost, const MafArgs& ma = MafArgs(),
+                         const BSrc& bs = BSrc()) {
+  PassPlan p;
+  p.TB = TB, p.own = TB * MV, p.par = par, p.zero_u = ZU;
+  p.max_R = std::min(TB / 2, (TB * MV - 1) / 4);  // 2R <= TB: the outer rows are staged by 2R threads; 4R < TB MV: halo rows would dominate
+  p.wg_per_cu = (MAF && TB == 512) ? 1 : 0;  // (MAF: a 512-thread workgroup of up to 256 registers per thread fills a CU's register file)
+  p.tj = PRE ? PRE : tj_req;  // (the preloaded form, jacobi2p_k<PRE>: chunks of PRE planes)
+  // k windows (Geom2): whole rows where a segment of them is a decent share of the workgroup's vectors, else windows of about kPairWin vectors;
+  // CZHIP_T2_KWIN / ctx.tune.t2_kwin: > 0 = vectors per window, 0 = whole rows wherever they fit, -1 = this rule
+  const int Rfull = (b.nkp + VW - 1) / VW;
+  const bool whole_fits = Rfull <= p.max_R;
+  int want = ctx.tune.t2_kwin;
+  if (want < 0) want = (whole_fits && (pair_whole_rows_ok(Rfull, TB * MV) || BS)) ? 0 : kPairWin;  // (BS: the pass that makes its right-hand side reads
+                                                                                                     // three or four arrays; the halo vectors of two windows cost it 6-8 % at 512^3 FP64)
+  if (want == 0 && !whole_fits) want = kPairWin;
+  if (want > 0 && want < Rfull) p.kwin = want;
+  const auto lds_bytes = [](int R, int S) {
+    return (size_t)2 * ((S + 4 * R) + (S + 2 * R)) * sizeof(Vec<VW>) + 18 * sizeof(double) +
+           (MAF ? (size_t)2 * R * VW * sizeof(REAL) : 0);  // MAF: the table of the k metric terms
+  };
+  if (!plan_pass(p, b, ba, lds_bytes, model_cost)) return false;
+  if (PRE) {
+    // the preloaded form only where every workgroup of the pass is resident at once -- one workgroup per CU (its operands live in ~190
+    // registers per thread) less the CUs left to the exchange stream of a decomposed run
+    const long long slots = (long long)std::max(1, ctx.num_cu / 8 - ctx.cu_reserved) * 8;  // (one per CU also for the 256 x 1 shape: measured, profiles/r04/small_grids_preloaded_shapes.txt)
+    if ((long long)p.g.nseg * p.nchunk > slots) return false;
+  }
+  if (probe) return true;
+  launch_pass(&jacobi2p_k<VW, TB, MV, RB, ZU, MAF, BS, PRE, UNIT>, RB ? LBL_RBSOR2 : LBL_JACOBI2, p, U, B, W, c, skip, fin, ma, bs);
   return true;
 }
 
@@ -328,6 +364,11 @@ bool launch_jacobi2(const REAL* U, const REAL* B, REAL* W, const Coef& c, const 
   return launch_jacobi2_inst<1024, 2, RB, 0>(U, B, W, c, b, ba, tu.t2_tj, skip, fin, par, probe, nullptr);
 }
 
+// rb4_k, jac3_k: arrays of any REAL alignment, a dd that takes the hoisted division, and two layers between the box and the array's i, j edges
+inline bool deep_pass_ok(const REAL* U, const REAL* B, const REAL* W, const Coef& c, const Box& b) {
+  return rows_ok(b, {U, B, W}) && fastdiv_ok(c.dd) && b.ii0 >= 2 && b.jj0 >= 2 && b.ii1 <= b.nip - 3 && b.jj1 <= b.njp - 3;
+}
+
 // TWO red-black iterations per pass (rb4_k, cz_k_rb4.h): single-domain boxes, constant coefficients.  Returns false when the geometry does not suit
 // the kernel (the caller then runs two fused iterations, jacobi2p_k<RB = 1>).  The k axis is cut into windows of about kRb4Win vectors whatever
 // the row length: the six halo rows of a segment must stay a small share of the 1 024 vectors a workgroup holds.
@@ -347,73 +388,26 @@ inline bool pair_small_form_fits(const Box& b) {
   const long long slots = (long long)std::max(1, ctx.num_cu / 8 - ctx.cu_reserved) * 8;
   return nseg * ((nplanes + 1) / 2) <= slots || nseg * ((nplanes + 3) / 4) <= slots;
 }
-bool launch_rb4(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box& b, const int* skip, const Fin2& fin_in, int par, bool probe) {
-  constexpr int V = VW, TB = 1024;
-  if (!ctx.tune.rb4 || !ctx.tune.fuse_fin) return false;
-  if (!rows_ok(b, {U, B, W}) || !fastdiv_ok(c.dd)) return false;
-  if (b.ii0 < 2 || b.jj0 < 2 || b.ii1 > b.nip - 3 || b.jj1 > b.njp - 3) return false;
+bool launch_rb4(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box& b, const int* skip, Fin2 fin, int par, bool probe) {
+  constexpr int TB = 1024;
+  if (!ctx.tune.rb4 || !ctx.tune.fuse_fin || !deep_pass_ok(U, B, W, c, b)) return false;
   if (ctx.tune.rb4 == 1 && pair_small_form_fits(b)) return false;  // (rb4 = 2: also there -- measurements and tests)
-  Geom2 g;
-  const int Rfull = (b.nkp + V - 1) / V;
-  const int hv = V == 4 ? 1 : 2;  // four stages reach three elements beyond a window
-  int want = ctx.tune.rb4_kwin > 0 ? ctx.tune.rb4_kwin : rb4_window(Rfull);
-  g.R = Rfull;
-  if (Rfull > (ctx.tune.rb4_kwin > 0 ? want : kRb4Win) + 2 * hv) {
-    g.nwin = (Rfull + want - 1) / want;
-    g.KT = (Rfull + g.nwin - 1) / g.nwin;
-    g.hv = hv, g.KW = g.KT * V, g.R = g.KT + 2 * hv;
-  }
-  if (2 * g.R > TB || 8 * g.R > TB) return false;  // at least a quarter of the workgroup's vectors must be its own
-  g.PSV = (long long)g.R * b.nip;
-  g.nkp = b.nkp;
-  g.PSB = (long long)b.nkp * b.nip * (long long)sizeof(REAL);
-  if (g.PSB >= (1LL << 32)) return false;
-  g.jlast = b.njp - 1;
-  g.last_off = (unsigned)(g.PSB - (long long)sizeof(Vec<V>));
-  g.kk0 = b.kk0, g.kk1 = b.kk1, g.jj0 = b.jj0, g.jj1 = b.jj1;
-  g.F0 = (long long)b.ii0 * g.R;
-  g.Fend = (long long)(b.ii1 + 1) * g.R;
-  g.kk0a = b.kk0, g.kk1a = b.kk1, g.jj0a = b.jj0, g.jj1a = b.jj1, g.F0a = g.F0, g.Fenda = g.Fend;
-  g.S = TB - 6 * g.R;
-  g.par = par;
-  g.zero_u = 0;
-  const long long nf = g.Fend - g.F0;
-  g.nsegw = (int)((nf + g.S - 1) / g.S);
-  g.nseg = g.nwin * g.nsegw;
-  const int nplanes = b.jj1 - b.jj0 + 1;
-  const size_t lds = ((size_t)2 * g.R + (size_t)2 * (TB + 2 * g.R) + (size_t)6 * TB) * sizeof(Vec<V>) + 18 * sizeof(double);
-  if (lds > 160 * 1024) return false;
-  int tj = 0;
-  pair_tj_model(g.nseg, nplanes, 1, pair_use_map(g.nseg), &tj, 7.5);  // (six redundant planes and a longer prologue per chunk)
-  if (ctx.tune.rb4_tj > 0) tj = ctx.tune.rb4_tj;
-  if (tj > nplanes) tj = nplanes;
-  g.TJ = tj;
-  const int nchunk = (nplanes + tj - 1) / tj;
-  g.band = 1;
-  g.map = nullptr;
-  long long nblk = 8LL * ((g.nseg + 7) / 8) * nchunk;
+  PassPlan p;
+  p.TB = TB, p.own = TB, p.halo_rows = 6, p.max_R = TB / 8;  // at least a quarter of the workgroup's vectors must be its own
+  p.hv = VW == 4 ? 1 : 2;                                    // four stages reach three elements beyond a window
+  p.wg_per_cu = 1, p.extra = 7.5;                            // (six redundant planes and a longer prologue per chunk)
+  p.tj = ctx.tune.rb4_tj, p.par = par;
+  const int Rfull = (b.nkp + VW - 1) / VW;
+  const int want = ctx.tune.rb4_kwin > 0 ? ctx.tune.rb4_kwin : rb4_window(Rfull);
+  if (Rfull > (ctx.tune.rb4_kwin > 0 ? want : kRb4Win) + 2 * p.hv) p.kwin = want;
+  const auto lds_bytes = [](int R, int) { return ((size_t)2 * R + (size_t)2 * (TB + 2 * R) + (size_t)6 * TB) * sizeof(Vec<VW>) + 18 * sizeof(double); };
+  if (!plan_pass(p, b, b, lds_bytes)) return false;
   if (probe) return true;
-  if (pair_use_map(g.nseg)) g.map = pair_xcd_map(g.nseg, nchunk, &nblk);
-  ensure_partials((size_t)2 * nblk);
-  static bool attr_set = false;
-  if (!attr_set) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rb4_k<V, TB, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rb4_k<V, TB, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
-  Fin2 fin = fin_in;
-  fin.counter = ctx.counter;
   fin.single = 0;
-  {
-    // (unit coefficients: rb4_k is an arithmetic kernel -- vector ALU 93 % busy -- and the six multiplications are a fifth of a point's
-    // instructions: 6-7 % at 512^3 FP32, profiles/r04/unit_coefficients.txt)
-    ScopedTimer tm(LBL_RBSOR4);
-    if (ctx.tune.unit_coef && coef_is_unit(c))
-      hipLaunchKernelGGL((rb4_k<V, TB, 1>), dim3((unsigned)nblk), dim3(TB), lds, ctx.stream, U, B, W, c, g, ctx.partials, skip, fin);
-    else
-      hipLaunchKernelGGL((rb4_k<V, TB, 0>), dim3((unsigned)nblk), dim3(TB), lds, ctx.stream, U, B, W, c, g, ctx.partials, skip, fin);
-  }
-  HIP_CHECK(hipGetLastError());
+  // (unit coefficients: rb4_k is an arithmetic kernel -- vector ALU 93 % busy -- and the six multiplications are a fifth of a point's
+  // instructions: 6-7 % at 512^3 FP32, profiles/r04/unit_coefficients.txt)
+  const bool unit = ctx.tune.unit_coef && coef_is_unit(c);
+  launch_pass(!unit ? &rb4_k<VW, TB, 0> : &rb4_k<VW, TB, 1>, LBL_RBSOR4, p, U, B, W, c, skip, fin);  // (UNIT = 0 named first: it keeps its place in the code object)
   return true;
 }
 
@@ -425,72 +419,25 @@ bool launch_rb4(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box&
 inline int jac3_window(int) { return VW == 4 ? 26 : 36; }
 // size gate of ctx.tune.jac3 = 1: inner points of the box (256^3: no gain worth the switch; 384^3: 1.11 x)
 constexpr long long kJac3MinPoints = 300LL * 300 * 300;
-bool launch_jac3(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box& b, const int* skip, const Fin2& fin_in, bool probe) {
-  constexpr int V = VW, TB = 1024;
-  if (!ctx.tune.jac3 || !ctx.tune.fuse_fin || !ctx.tune.use_t2) return false;
-  if (!rows_ok(b, {U, B, W}) || !fastdiv_ok(c.dd)) return false;
-  if (b.ii0 < 2 || b.jj0 < 2 || b.ii1 > b.nip - 3 || b.jj1 > b.njp - 3) return false;
+bool launch_jac3(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box& b, const int* skip, Fin2 fin, bool probe) {
+  constexpr int TB = 1024;
+  if (!ctx.tune.jac3 || !ctx.tune.fuse_fin || !ctx.tune.use_t2 || !deep_pass_ok(U, B, W, c, b)) return false;
   const long long npts = (long long)(b.ii1 - b.ii0 + 1) * (b.jj1 - b.jj0 + 1) * (b.kk1 - b.kk0 + 1);
   if (ctx.tune.jac3 == 1 && (npts < kJac3MinPoints || pair_small_form_fits(b))) return false;  // (jac3 = 2: also there -- tests)
-  Geom2 g;
-  const int Rfull = (b.nkp + V - 1) / V;
-  const int hv = V == 4 ? 1 : 2;  // three stages reach three elements beyond a window
+  PassPlan p;
+  p.TB = TB, p.own = TB, p.halo_rows = 4, p.max_R = TB / 8;  // at least half of the workgroup's vectors must be its own
+  p.hv = VW == 4 ? 1 : 2;                                    // three stages reach three elements beyond a window
+  p.wg_per_cu = 1, p.extra = 5.5;                            // (four redundant planes and a longer prologue per chunk)
+  p.tj = ctx.tune.jac3_tj, p.nres = 3;
+  const int Rfull = (b.nkp + VW - 1) / VW;
   const int want = ctx.tune.jac3_kwin > 0 ? ctx.tune.jac3_kwin : jac3_window(Rfull);
-  g.R = Rfull;
-  if (Rfull > want + 2 * hv) {
-    g.nwin = (Rfull + want - 1) / want;
-    g.KT = (Rfull + g.nwin - 1) / g.nwin;
-    g.hv = hv, g.KW = g.KT * V, g.R = g.KT + 2 * hv;
-  }
-  if (2 * g.R > TB || 8 * g.R > TB) return false;  // at least half of the workgroup's vectors must be its own
-  g.PSV = (long long)g.R * b.nip;
-  g.nkp = b.nkp;
-  g.PSB = (long long)b.nkp * b.nip * (long long)sizeof(REAL);
-  if (g.PSB >= (1LL << 32)) return false;
-  g.jlast = b.njp - 1;
-  g.last_off = (unsigned)(g.PSB - (long long)sizeof(Vec<V>));
-  g.kk0 = b.kk0, g.kk1 = b.kk1, g.jj0 = b.jj0, g.jj1 = b.jj1;
-  g.F0 = (long long)b.ii0 * g.R;
-  g.Fend = (long long)(b.ii1 + 1) * g.R;
-  g.kk0a = b.kk0, g.kk1a = b.kk1, g.jj0a = b.jj0, g.jj1a = b.jj1, g.F0a = g.F0, g.Fenda = g.Fend;
-  g.S = TB - 4 * g.R;
-  g.par = 0;
-  g.zero_u = 0;
-  const long long nf = g.Fend - g.F0;
-  g.nsegw = (int)((nf + g.S - 1) / g.S);
-  g.nseg = g.nwin * g.nsegw;
-  const int nplanes = b.jj1 - b.jj0 + 1;
-  const size_t lds = ((size_t)2 * g.R + (size_t)2 * (TB + 2 * g.R) + (size_t)4 * TB) * sizeof(Vec<V>) + 18 * sizeof(double);
-  if (lds > 160 * 1024) return false;
-  int tj = 0;
-  pair_tj_model(g.nseg, nplanes, 1, pair_use_map(g.nseg), &tj, 5.5);  // (four redundant planes and a longer prologue per chunk)
-  if (ctx.tune.jac3_tj > 0) tj = ctx.tune.jac3_tj;
-  if (tj > nplanes) tj = nplanes;
-  g.TJ = tj;
-  const int nchunk = (nplanes + tj - 1) / tj;
-  g.band = 1;
-  g.map = nullptr;
-  long long nblk = 8LL * ((g.nseg + 7) / 8) * nchunk;
+  if (Rfull > want + 2 * p.hv) p.kwin = want;
+  const auto lds_bytes = [](int R, int) { return ((size_t)2 * R + (size_t)2 * (TB + 2 * R) + (size_t)4 * TB) * sizeof(Vec<VW>) + 18 * sizeof(double); };
+  if (!plan_pass(p, b, b, lds_bytes)) return false;
   if (probe) return true;
-  if (pair_use_map(g.nseg)) g.map = pair_xcd_map(g.nseg, nchunk, &nblk);
-  ensure_partials((size_t)3 * nblk);
-  static bool attr_set = false;
-  if (!attr_set) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&jac3_k<V, TB, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&jac3_k<V, TB, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
-  Fin2 fin = fin_in;
-  fin.counter = ctx.counter;
   fin.single = 0;
-  {
-    ScopedTimer tm(LBL_JACOBI3);
-    if (ctx.tune.unit_coef && coef_is_unit(c))
-      hipLaunchKernelGGL((jac3_k<V, TB, 1>), dim3((unsigned)nblk), dim3(TB), lds, ctx.stream, U, B, W, c, g, ctx.partials, skip, fin);
-    else
-      hipLaunchKernelGGL((jac3_k<V, TB, 0>), dim3((unsigned)nblk), dim3(TB), lds, ctx.stream, U, B, W, c, g, ctx.partials, skip, fin);
-  }
-  HIP_CHECK(hipGetLastError());
+  const bool unit = ctx.tune.unit_coef && coef_is_unit(c);
+  launch_pass(!unit ? &jac3_k<VW, TB, 0> : &jac3_k<VW, TB, 1>, LBL_JACOBI3, p, U, B, W, c, skip, fin);  // (UNIT = 0 named first: it keeps its place in the code object)
   return true;
 }
 
@@ -532,36 +479,37 @@ void launch_pair_shell(const REAL* U, const REAL* B, REAL* W, const Coef& c, con
   ctx.shell_pending = (int)(gx * n);
 }
 
-Coef make_coef_omg(REAL omg) {
-  Coef c;
-  c.c1 = c.c2 = c.c3 = c.c4 = c.c5 = c.c6 = c.dd = (REAL)0;
-  c.omg = omg;
-  return c;
-}
-
 Coef make_coef(const REAL* cf, REAL omg) {
   Coef c;
   c.c1 = cf[0], c.c2 = cf[1], c.c3 = cf[2], c.c4 = cf[3], c.c5 = cf[4], c.c6 = cf[5], c.dd = cf[6], c.omg = omg;
   return c;
 }
 
+template <int V, int OP>
+void launch_ewise_inst(REAL* Z, const REAL* X, const REAL* Y, REAL a, REAL bcoef, const Box& b, const REAL* a_dev, const REAL* b_dev) {
+  EGeom e = make_egeom<V>(b);
+  e.pa = a_dev, e.pb = b_dev;
+  dim3 grid((unsigned)((e.Fend - e.F0 + 255) / 256), (unsigned)(b.jj1 - b.jj0 + 1));
+  hipLaunchKernelGGL((ewise_k<V, OP>), grid, dim3(256), 0, ctx.stream, Z, X, Y, a, bcoef, e);
+}
+
 template <int OP>
 void launch_ewise(REAL* Z, const REAL* X, const REAL* Y, REAL a, REAL bcoef, const Box& b, const REAL* a_dev = nullptr, const REAL* b_dev = nullptr) {
   if (b.empty) return;
   ScopedTimer tm(LBL_EWISE);
-  const int nplanes = b.jj1 - b.jj0 + 1;
-  if (rows_ok(b, {Z, X, Y})) {
-    EGeom e = make_egeom<VW>(b);
-    e.pa = a_dev, e.pb = b_dev;
-    dim3 grid((unsigned)((e.Fend - e.F0 + 255) / 256), (unsigned)nplanes);
-    hipLaunchKernelGGL((ewise_k<VW, OP>), grid, dim3(256), 0, ctx.stream, Z, X, Y, a, bcoef, e);
-  } else {
-    EGeom e = make_egeom<1>(b);
-    e.pa = a_dev, e.pb = b_dev;
-    dim3 grid((unsigned)((e.Fend - e.F0 + 255) / 256), (unsigned)nplanes);
-    hipLaunchKernelGGL((ewise_k<1, OP>), grid, dim3(256), 0, ctx.stream, Z, X, Y, a, bcoef, e);
-  }
+  if (rows_ok(b, {Z, X, Y})) launch_ewise_inst<VW, OP>(Z, X, Y, a, bcoef, b, a_dev, b_dev);
+  else launch_ewise_inst<1, OP>(Z, X, Y, a, bcoef, b, a_dev, b_dev);
   HIP_CHECK(hipGetLastError());
+}
+
+template <int V, int TWO>
+void launch_dot_inst(const REAL* X, const REAL* Y, const Box& b, double* dst) {
+  const int nplanes = b.jj1 - b.jj0 + 1;
+  EGeom e = make_egeom<V>(b);
+  const unsigned gx = (unsigned)((e.Fend - e.F0 + 255) / 256);
+  const unsigned gy = (unsigned)std::max(1, std::min(nplanes, (int)(4096 / gx)));
+  ensure_partials((size_t)gx * gy);
+  hipLaunchKernelGGL((dot_k<V, TWO>), dim3(gx, gy), dim3(256), 0, ctx.stream, X, Y, e, nplanes, ctx.partials, dst, ctx.counter);
 }
 
 // dot -> device double dst[0]
@@ -571,21 +519,9 @@ void launch_dot(const REAL* X, const REAL* Y, const Box& b, double* dst) {
     HIP_CHECK(hipMemsetAsync(dst, 0, sizeof(double), ctx.stream));
     return;
   }
-  const int nplanes = b.jj1 - b.jj0 + 1;
   ScopedTimer tm(LBL_DOT);
-  if (rows_ok(b, {X, Y})) {
-    EGeom e = make_egeom<VW>(b);
-    const unsigned gx = (unsigned)((e.Fend - e.F0 + 255) / 256);
-    const unsigned gy = (unsigned)std::max(1, std::min(nplanes, (int)(4096 / gx)));
-    ensure_partials((size_t)gx * gy);
-    hipLaunchKernelGGL((dot_k<VW, TWO>), dim3(gx, gy), dim3(256), 0, ctx.stream, X, Y, e, nplanes, ctx.partials, dst, ctx.counter);
-  } else {
-    EGeom e = make_egeom<1>(b);
-    const unsigned gx = (unsigned)((e.Fend - e.F0 + 255) / 256);
-    const unsigned gy = (unsigned)std::max(1, std::min(nplanes, (int)(4096 / gx)));
-    ensure_partials((size_t)gx * gy);
-    hipLaunchKernelGGL((dot_k<1, TWO>), dim3(gx, gy), dim3(256), 0, ctx.stream, X, Y, e, nplanes, ctx.partials, dst, ctx.counter);
-  }
+  if (rows_ok(b, {X, Y})) launch_dot_inst<VW, TWO>(X, Y, b, dst);
+  else launch_dot_inst<1, TWO>(X, Y, b, dst);
   HIP_CHECK(hipGetLastError());
 }
 

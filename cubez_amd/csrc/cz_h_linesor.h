@@ -35,11 +35,7 @@ bool try_pcr_rb(REAL* x, const REAL* msk, const REAL* rhs, PcrGeom g, REAL omg, 
     return false;
   }
   ensure_partials(nblk);
-  static bool attr_set = false;
-  if (!attr_set) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pcr_rb_k<NW, ORDER, MAF, FINAL4, GS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  allow_dynamic_lds(&pcr_rb_k<NW, ORDER, MAF, FINAL4, GS>, 160 * 1024);
   ScopedTimer tm(LBL_PCR);
   hipLaunchKernelGGL((pcr_rb_k<NW, ORDER, MAF, FINAL4, GS>), dim3(nblk), dim3(64 * NW), lds, ctx.stream, x, wout, msk, rhs, g, omg, ctx.partials, res_dev,
                      accumulate, ctx.counter, ma, ctx.pcr_scratch, ncol);
@@ -56,12 +52,7 @@ bool try_pcr_rb2_inst(REAL* x, REAL* wout, const REAL* msk, const REAL* rhs, con
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)160 * 1024 / lds, (size_t)(32 / NW)));
   const unsigned nblk = (unsigned)std::max<long long>(1, std::min<long long>((ngroups + NW - 1) / NW, (long long)ctx.num_cu * per_cu));
   ensure_partials(nblk);
-  static bool attr_set = false;
-  if (!attr_set) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pcr_rb2_k<NW, L, FINAL4, ORDER, TG>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024));
-    attr_set = true;
-  }
+  allow_dynamic_lds(&pcr_rb2_k<NW, L, FINAL4, ORDER, TG>, 160 * 1024);
   ScopedTimer tm(LBL_PCR);
   hipLaunchKernelGGL((pcr_rb2_k<NW, L, FINAL4, ORDER, TG>), dim3(nblk), dim3(64 * NW), lds, ctx.stream, x, wout, msk, rhs, g, omg, ctx.pcr_tab,
                      tab_len, nfin, ctx.partials, res_dev, accumulate, ctx.counter);
@@ -75,11 +66,7 @@ bool ensure_pcr_table(int n, int pn, int final4, int nfin, int tab_len) {
   if (ctx.pcr_tab_n == n && ctx.pcr_tab_pn == pn && ctx.pcr_tab_final4 == final4) return true;
   const size_t coef_lds = (size_t)4 * (n + 2) * sizeof(REAL);
   if (coef_lds > 160 * 1024) return false;
-  static bool attr_set = false;
-  if (!attr_set) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pcr_coef_k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  allow_dynamic_lds(&pcr_coef_k, 160 * 1024);
   if ((size_t)tab_len > ctx.pcr_tab_cap) {
     if (ctx.pcr_tab) {
       HIP_CHECK(hipStreamSynchronize(ctx.stream));
@@ -104,12 +91,7 @@ bool try_pcr_reg_inst(REAL* x, REAL* wout, const REAL* msk, const REAL* rhs, con
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)160 * 1024 / lds, (size_t)(32 / NW)));
   const unsigned nblk = (unsigned)std::max<long long>(1, std::min<long long>((ngroups + NW - 1) / NW, (long long)ctx.num_cu * per_cu));
   ensure_partials(nblk);
-  static bool attr_set = false;
-  if (!attr_set) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pcr_line_reg_k<M, NW, L, FINAL4, ORDER>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  allow_dynamic_lds(&pcr_line_reg_k<M, NW, L, FINAL4, ORDER>, 160 * 1024);
   ScopedTimer tm(LBL_PCR);
   hipLaunchKernelGGL((pcr_line_reg_k<M, NW, L, FINAL4, ORDER>), dim3(nblk), dim3(64 * NW), lds, ctx.stream, x, wout, msk, rhs, g, omg,
                      ctx.pcr_tab_perm, tab_len, ctx.partials, res_dev, accumulate, ctx.counter);
@@ -194,11 +176,7 @@ bool try_pcr_lex_wg_inst(REAL* x, const REAL* msk, const REAL* rhs, const PcrGeo
   const int ntab = MAF ? 0 : 3 * nstage + (FINAL4 ? 7 : 3);
   const size_t lds = ((size_t)(MAF ? 9 : 3) * RS * (NT + 2) + (size_t)R * NT + (size_t)ntab * NT) * sizeof(REAL) + 8 * sizeof(int) + 16 + 20 * sizeof(double);
   if (lds > 160 * 1024) return false;  // (the coefficients of every entry sit in LDS)
-  static bool attr_set = false;
-  if (!attr_set) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pcr_lex_wg_k<FINAL4, NT, Q, MAF>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  allow_dynamic_lds(&pcr_lex_wg_k<FINAL4, NT, Q, MAF>, 160 * 1024);
   const size_t ctl_words = (size_t)kPipeCtlStride * (nstrips + 2);
   if (ctl_words > ctx.pipe_ctl_cap) {
     if (ctx.pipe_ctl) {
@@ -587,12 +565,8 @@ void launch_psor(REAL* p, const REAL* b, const Coef& c, const Box& bx, double* r
   const size_t ntiles = (size_t)g.ntk * g.nti * g.ntj;
   ensure_partials(ntiles);
   const size_t lds = ((size_t)(T + 2) * (T + 2) * (T + 2) + (size_t)T * T * T) * sizeof(REAL);
-  static bool attr_set = false;
-  if (!attr_set) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&psor_tile_k<T, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&psor_tile_k<T, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    attr_set = true;
-  }
+  allow_dynamic_lds(&psor_tile_k<T, 0>, 96 * 1024);
+  allow_dynamic_lds(&psor_tile_k<T, 1>, 96 * 1024);
   {
     ScopedTimer tm(LBL_PSOR);
     for (int H = 0; H <= g.ntk + g.nti + g.ntj - 3; H++) {

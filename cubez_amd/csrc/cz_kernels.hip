@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -53,29 +54,29 @@ namespace {
 }  // namespace
 
 namespace {
-struct CheckArgs {
-  int enabled = 0, itr = 0;
-  double res_normal = 0.0, eps = 0.0;
-  double* hist = nullptr;
-  int* flag = nullptr;
-  int* conv_itr = nullptr;
-};
+// a Fin or Fin2 with the convergence bookkeeping of cz_Poisson.cpp:67-77 for iteration itr (none where on is false)
+template <class F>
+F fin_check(bool on, double res_normal, double eps, int itr, double* hist, int* flag, int* conv_itr) {
+  F f;
+  if (on) f.do_check = 1, f.itr = itr, f.res_normal = res_normal, f.eps = eps, f.hist = hist, f.flag = flag, f.conv_itr = conv_itr;
+  return f;
+}
+
+// ck: the bookkeeping (fin_check<Fin>) or Fin()
 template <int MODE>
 void sweep_async(const REAL* p_in, REAL* p_out, const REAL* b, const Box& bx, const Coef& cf, int par, double* res_dev,
-                 int accumulate, const int* skip, const CheckArgs& ck, const MafArgs* ma = nullptr) {
+                 int accumulate, const int* skip, const Fin& ck, const MafArgs* ma = nullptr) {
   int nblk = 0;
   if (ctx.tune.fuse_fin) {
-    Fin fin;
+    Fin fin = ck;
     fin.dst = res_dev, fin.accumulate = accumulate, fin.counter = ctx.counter;
-    fin.do_check = ck.enabled, fin.itr = ck.itr, fin.res_normal = ck.res_normal, fin.eps = ck.eps;
-    fin.hist = ck.hist, fin.flag = ck.flag, fin.conv_itr = ck.conv_itr;
     if (ma) launch_stencil_maf<MODE>(p_in, b, p_out, cf.omg, bx, par, skip, &nblk, fin, *ma);
     else launch_stencil<MODE>(p_in, b, p_out, cf, bx, par, skip, &nblk, fin);
   } else {
     if (ma) launch_stencil_maf<MODE>(p_in, b, p_out, cf.omg, bx, par, skip, &nblk, Fin(), *ma);
     else launch_stencil<MODE>(p_in, b, p_out, cf, bx, par, skip, &nblk);
     reduce_partials(nblk, res_dev, accumulate, skip);
-    if (ck.enabled) czhip_check_async(res_dev, ck.res_normal, ck.eps, ck.itr, ck.hist, ck.flag, ck.conv_itr);
+    if (ck.do_check) czhip_check_async(res_dev, ck.res_normal, ck.eps, ck.itr, ck.hist, ck.flag, ck.conv_itr);
   }
 }
 }  // namespace
@@ -344,7 +345,7 @@ void czhip_jacobi_async(const CZ_REAL* p_in, CZ_REAL* p_out, const CZ_REAL* b, c
     if (!accumulate) HIP_CHECK(hipMemsetAsync(res_dev, 0, sizeof(double), ctx.stream));
     return;
   }
-  sweep_async<MODE_JACOBI>(p_in, p_out, b, bx, make_coef(cf, omg), 0, res_dev, accumulate, skip, CheckArgs());
+  sweep_async<MODE_JACOBI>(p_in, p_out, b, bx, make_coef(cf, omg), 0, res_dev, accumulate, skip, Fin());
 }
 
 void czhip_jacobi_checked_async(const CZ_REAL* p_in, CZ_REAL* p_out, const CZ_REAL* b, const int* sz, const int* idx, int g,
@@ -352,8 +353,7 @@ void czhip_jacobi_checked_async(const CZ_REAL* p_in, CZ_REAL* p_out, const CZ_RE
                                 double* hist_dev, int* flag_dev, int* conv_itr_dev) {
   ensure_init();
   const Box bx = make_box(sz, idx, g);
-  CheckArgs ck;
-  ck.enabled = 1, ck.itr = itr, ck.res_normal = res_normal, ck.eps = eps, ck.hist = hist_dev, ck.flag = flag_dev, ck.conv_itr = conv_itr_dev;
+  const Fin ck = fin_check<Fin>(true, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev);
   if (bx.empty) {
     HIP_CHECK(hipMemsetAsync(res_dev, 0, sizeof(double), ctx.stream));
     czhip_check_async(res_dev, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev);
@@ -370,7 +370,7 @@ void czhip_rbsor_async(CZ_REAL* p, const CZ_REAL* b, const int* sz, const int* i
     if (!accumulate) HIP_CHECK(hipMemsetAsync(res_dev, 0, sizeof(double), ctx.stream));
     return;
   }
-  sweep_async<MODE_RB>(p, p, b, bx, make_coef(cf, omg), rb_parity(g, idx, ofst, color), res_dev, accumulate, skip, CheckArgs());
+  sweep_async<MODE_RB>(p, p, b, bx, make_coef(cf, omg), rb_parity(g, idx, ofst, color), res_dev, accumulate, skip, Fin());
 }
 
 void czhip_rbsor_checked_async(CZ_REAL* p, const CZ_REAL* b, const int* sz, const int* idx, int g, const CZ_REAL* cf, int ofst,
@@ -378,8 +378,7 @@ void czhip_rbsor_checked_async(CZ_REAL* p, const CZ_REAL* b, const int* sz, cons
                                double* hist_dev, int* flag_dev, int* conv_itr_dev) {
   ensure_init();
   const Box bx = make_box(sz, idx, g);
-  CheckArgs ck;
-  ck.enabled = 1, ck.itr = itr, ck.res_normal = res_normal, ck.eps = eps, ck.hist = hist_dev, ck.flag = flag_dev, ck.conv_itr = conv_itr_dev;
+  const Fin ck = fin_check<Fin>(true, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev);
   if (bx.empty) {
     if (!accumulate) HIP_CHECK(hipMemsetAsync(res_dev, 0, sizeof(double), ctx.stream));
     czhip_check_async(res_dev, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev);
@@ -401,12 +400,8 @@ int czhip_jacobi2_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const in
   const Box bx = make_box(sz, idx, g);
   if (bx.empty || g < 2) return 0;
   const Box ba = idx1 ? make_box(sz, idx1, g) : bx;
-  Fin2 fin;
+  Fin2 fin = fin_check<Fin2>(hist_dev, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev);
   fin.dst = res_dev;
-  if (hist_dev) {
-    fin.do_check = 1, fin.itr = itr, fin.res_normal = res_normal, fin.eps = eps;
-    fin.hist = hist_dev, fin.flag = flag_dev, fin.conv_itr = conv_itr_dev;
-  }
   return launch_jacobi2<0>(u, b, w, make_coef(cf, omg), bx, ba, hist_dev ? flag_dev : skip_flag_dev, fin) ? 1 : 0;
 }
 
@@ -464,13 +459,9 @@ int czhip_rbsor2_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int
   const Box bx = make_box(sz, idx, g);
   if (bx.empty || g < 2) return 0;
   const Box ba = idx1 ? make_box(sz, idx1, g) : bx;
-  Fin2 fin;
+  Fin2 fin = fin_check<Fin2>(hist_dev, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev);
   fin.dst = res_dev;
   fin.single = 1;
-  if (hist_dev) {
-    fin.do_check = 1, fin.itr = itr, fin.res_normal = res_normal, fin.eps = eps;
-    fin.hist = hist_dev, fin.flag = flag_dev, fin.conv_itr = conv_itr_dev;
-  }
   return launch_jacobi2<1>(u, b, w, make_coef(cf, omg), bx, ba, hist_dev ? flag_dev : skip_flag_dev, fin, rb_parity(g, idx, ofst, 0)) ? 1 : 0;
 }
 
@@ -484,12 +475,8 @@ int czhip_rbsor4_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int
   ensure_init();
   const Box bx = make_box(sz, idx, g);
   if (bx.empty || g < 2) return 0;
-  Fin2 fin;
+  Fin2 fin = fin_check<Fin2>(hist_dev, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev);
   fin.dst = res_dev;
-  if (hist_dev) {
-    fin.do_check = 1, fin.itr = itr, fin.res_normal = res_normal, fin.eps = eps;
-    fin.hist = hist_dev, fin.flag = flag_dev, fin.conv_itr = conv_itr_dev;
-  }
   return launch_rb4(u, b, w, make_coef(cf, omg), bx, hist_dev ? flag_dev : skip_flag_dev, fin, rb_parity(g, idx, ofst, 0), probe != 0) ? 1 : 0;
 }
 
@@ -503,12 +490,8 @@ int czhip_jacobi3_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const in
   ensure_init();
   const Box bx = make_box(sz, idx, g);
   if (bx.empty || g < 2) return 0;
-  Fin2 fin;
+  Fin2 fin = fin_check<Fin2>(hist_dev, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev);
   fin.dst = res_dev;
-  if (hist_dev) {
-    fin.do_check = 1, fin.itr = itr, fin.res_normal = res_normal, fin.eps = eps;
-    fin.hist = hist_dev, fin.flag = flag_dev, fin.conv_itr = conv_itr_dev;
-  }
   return launch_jac3(u, b, w, make_coef(cf, omg), bx, hist_dev ? flag_dev : skip_flag_dev, fin, probe != 0) ? 1 : 0;
 }
 
@@ -818,7 +801,7 @@ void jacobi_maf_(CZ_REAL* p, int* sz, int* idx, int* g, CZ_REAL* X, CZ_REAL* Y, 
   const Box bx = make_box(sz, idx, *g);
   if (bx.empty) return;
   const MafArgs ma = upload_xyz(sz, *g, X, Y, Z, nullptr);
-  sweep_async<MODE_JACOBI>(p, wk2, b, bx, make_coef_omg(*omg), 0, ctx.scal_dev + 0, 0, nullptr, CheckArgs(), &ma);
+  sweep_async<MODE_JACOBI>(p, wk2, b, bx, make_coef_omg(*omg), 0, ctx.scal_dev + 0, 0, nullptr, Fin(), &ma);
   launch_ewise<OP_COPY>(p, wk2, nullptr, (REAL)0, (REAL)0, bx);
   *res += read_scalar(0);
 }
@@ -832,7 +815,7 @@ void psor2sma_core_maf_(CZ_REAL* p, int* sz, int* idx, int* g, CZ_REAL* X, CZ_RE
   if (bx.empty) return;
   const MafArgs ma = upload_xyz(sz, *g, X, Y, Z, nullptr);
   sweep_async<MODE_RB>(p, p, b, bx, make_coef_omg(*omg), rb_parity(*g, idx, *ip, *color), ctx.scal_dev + 0, 0, nullptr,
-                       CheckArgs(), &ma);
+                       Fin(), &ma);
   *res += read_scalar(0);
 }
 
@@ -1186,8 +1169,7 @@ void jacobi_maf_async(const REAL* p_in, REAL* p_out, const REAL* b, const int* s
   const Box bx = make_box(sz, idx, g);
   if (bx.empty) return;
   MafArgs ma{xc, yc, zc, nullptr};
-  CheckArgs ck;
-  if (check) ck.enabled = 1, ck.itr = itr, ck.res_normal = res_normal, ck.eps = eps, ck.hist = hist, ck.flag = flag, ck.conv_itr = conv_itr;
+  const Fin ck = fin_check<Fin>(check, res_normal, eps, itr, hist, flag, conv_itr);
   sweep_async<MODE_JACOBI>(p_in, p_out, b, bx, make_coef_omg(omg), 0, res_dev, 0, check ? flag : skip, ck, &ma);
 }
 void rbsor_maf_async(REAL* p, const REAL* b, const int* sz, const int* idx, int g, const REAL* xc, const REAL* yc, const REAL* zc,
@@ -1196,8 +1178,7 @@ void rbsor_maf_async(REAL* p, const REAL* b, const int* sz, const int* idx, int 
   const Box bx = make_box(sz, idx, g);
   if (bx.empty) return;
   MafArgs ma{xc, yc, zc, nullptr};
-  CheckArgs ck;
-  if (check) ck.enabled = 1, ck.itr = itr, ck.res_normal = res_normal, ck.eps = eps, ck.hist = hist, ck.flag = flag, ck.conv_itr = conv_itr;
+  const Fin ck = fin_check<Fin>(check, res_normal, eps, itr, hist, flag, conv_itr);
   sweep_async<MODE_RB>(p, p, b, bx, make_coef_omg(omg), rb_parity(g, idx, ofst, color), res_dev, accumulate, check ? flag : skip, ck,
                        &ma);
 }
@@ -1213,13 +1194,9 @@ int pair_maf_async(const REAL* u, REAL* w, const REAL* b, const int* sz, const i
   if (bx.empty || g < 2) return 0;
   const Box ba = idx1 ? make_box(sz, idx1, g) : bx;
   MafArgs ma{xc, yc, zc, nullptr};
-  Fin2 fin;
+  Fin2 fin = fin_check<Fin2>(hist_dev, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev);
   fin.dst = res_dev;
   fin.single = rb_ofst >= 0;
-  if (hist_dev) {
-    fin.do_check = 1, fin.itr = itr, fin.res_normal = res_normal, fin.eps = eps;
-    fin.hist = hist_dev, fin.flag = flag_dev, fin.conv_itr = conv_itr_dev;
-  }
   const int* skip = hist_dev ? flag_dev : skip_flag_dev;
   if (rb_ofst >= 0) return launch_jacobi2<1>(u, b, w, make_coef_omg(omg), bx, ba, skip, fin, rb_parity(g, idx, rb_ofst, 0), 0, false, &ma) ? 1 : 0;
   return launch_jacobi2<0>(u, b, w, make_coef_omg(omg), bx, ba, skip, fin, 0, 0, false, &ma) ? 1 : 0;
