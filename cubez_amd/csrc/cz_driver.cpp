@@ -60,6 +60,7 @@ const char* printMethod(int t) {
     case LS_SOR2SMA_MAF: return "SOR2SMA_MAF";
     case LS_BICGSTAB_MAF: return "PBiCGSTAB_MAF";
     case LS_PCG: return "PCG";
+    case LS_MG: return "MG";
     default: return "NONE";
   }
 }
@@ -88,6 +89,7 @@ CZ::~CZ() {
   czhip_sync();
   if (comm_cus > 0) reserve_comm_cus(0);  // the library context outlives this object
   REAL_TYPE* arrs[] = {WRK, WRK2, P, RHS, pcg_p, pcg_p_, pcg_r, pcg_r0, pcg_q, pcg_s, pcg_s_, pcg_t_, cg_r, cg_z, cg_p[0], cg_p[1], cg_q, pvt, MSK};
+  if (mg) czhip_mg_destroy(mg);
   if (d_xc) (void)hipFree(d_xc);
   if (d_yc) (void)hipFree(d_yc);
   if (d_zc) (void)hipFree(d_zc);
@@ -216,8 +218,19 @@ void CZ::setLS(const char* q) {
     hist_name = "pcg.txt";
     if (!strcasecmp(precon.c_str(), "none")) pc_type = LS_NONE;
     else if (!strcasecmp(precon.c_str(), "jacobi")) pc_type = LS_JACOBI;
+    else if (!strcasecmp(precon.c_str(), "mg")) pc_type = LS_MG;
     else {
       Hostonly_ printf("Invalid preconditioner for pcg '%s' (none | jacobi)\n", precon.c_str());
+      exit(0);
+    }
+    // the V-cycle's smoothers are relaxed Jacobi sweeps: the same range keeps it symmetric and definite
+    if (pc_type == LS_MG && !(ac1 > (REAL_TYPE)0 && ac1 <= (REAL_TYPE)1)) {
+      Hostonly_ printf("Invalid coefficient for pcg with mg '%g' (0 < coef <= 1: a symmetric definite preconditioner)\n", (double)ac1);
+      exit(0);
+    }
+    // the coarse levels of a brick would need the other bricks' points (agglomeration across ranks): single domain only
+    if (pc_type == LS_MG && numProc > 1) {
+      Hostonly_ printf("pcg with mg runs on a single domain only (%d processes): the coarse levels are not agglomerated across ranks\n", numProc);
       exit(0);
     }
     // k relaxed Jacobi sweeps from zero are a polynomial in A: symmetric, and definite with A's sign for 0 < omega <= 1
@@ -360,16 +373,21 @@ int CZ::Setup(int argc, char** argv) {
     pcg_r0 = czhip_alloc_s3d(size), pcg_q = czhip_alloc_s3d(size), pcg_s = czhip_alloc_s3d(size);
     pcg_s_ = czhip_alloc_s3d(size), pcg_t_ = czhip_alloc_s3d(size);
   }
-  const int narr = bicg ? 11 : ls_type == LS_PCG ? (pc_type == LS_JACOBI ? 8 : 7) : 3;
+  const int narr = bicg ? 11 : ls_type == LS_PCG ? (pc_type == LS_JACOBI ? 8 : pc_type == LS_MG ? 9 : 7) : 3;
   if (ls_type == LS_PCG) {  // zero-filled; only their inner boxes are ever written (the fused passes read the shells as zeros)
     cg_r = czhip_alloc_s3d(size), cg_q = czhip_alloc_s3d(size), cg_p[0] = czhip_alloc_s3d(size), cg_p[1] = czhip_alloc_s3d(size);
-    if (pc_type == LS_JACOBI) cg_z = czhip_alloc_s3d(size);
+    if (pc_type == LS_JACOBI || pc_type == LS_MG) cg_z = czhip_alloc_s3d(size);
+    if (pc_type == LS_MG && !(mg = czhip_mg_create(size, innerFidx, GUIDE, cf))) {
+      Hostonly_ printf("pcg with mg: unsupported coefficients (c1 .. c6 = 1, dd = 6 only)\n");
+      return 0;
+    }
   }
   if (!quiet) Hostonly_ {
     const double arr = (double)(size[0] + 2 * gc) * (size[1] + 2 * gc) * (size[2] + 2 * gc) * sizeof(REAL_TYPE);
     printf("\n----------\n\n\tDevice memory per rank : %.1f MiB in %d arrays of (%d+4)x(%d+4)x(%d+4) %s\n", arr *
            narr / 1048576.0, narr, size[0], size[1], size[2],
            sizeof(REAL_TYPE) == 4 ? "float" : "double");
+    if (mg) printf("\tMultigrid levels       : %d (coarse arrays about 3/7 of one array more)\n", czhip_mg_levels(mg));
   }
 
   ItrMax = atoi(argv[5]);  // :330
@@ -1500,7 +1518,7 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   hipStream_t st = stream();
   const size_t nbytes = (size_t)(size[0] + 2 * gc) * (size[1] + 2 * gc) * (size[2] + 2 * gc) * sizeof(REAL_TYPE);
   const double n = npts();
-  const bool pc = pc_type == LS_JACOBI;
+  const bool pc = pc_type == LS_JACOBI || pc_type == LS_MG;
   const bool fuse = cfg.on(CZV_CG_FUSE, true);
   const bool fuse_dir = fuse && numProc == 1;  // the direction pass reads z's and p's shells as zeros: single domain only
   REAL_TYPE* const sc = reinterpret_cast<REAL_TYPE*>(d_res + 12);  // alpha, -alpha, beta, rho (cg_scal_k)
@@ -1510,6 +1528,7 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   REAL_TYPE* const z = pc ? cg_z : cg_r;
   res = 0.0;
   cg_fused = 0;
+  mg_cycles = 0;
 
   calc_rk_async(cg_r, X, B, size, innerFidx, gc, cf);
   flop += 14.0 * n;
@@ -1532,9 +1551,14 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
     }
     if (pc) {
       if (!Comm_S(cg_r)) return 0;  // (a decomposed pass reads the right-hand side in its ghost layer)
-      double fc = 0.0;
-      Preconditioner(cg_z, cg_r, fc, LS_JACOBI);
-      flop += fc;
+      if (mg) {
+        if (!czhip_mg_apply_async(mg, cg_z, cg_r, ac1)) return 0;  // z = V_0(r)
+        mg_cycles++;
+      } else {
+        double fc = 0.0;
+        Preconditioner(cg_z, cg_r, fc, LS_JACOBI);
+        flop += fc;
+      }
       dot2_async(cg_r, cg_z, size, innerFidx, gc, d_rho);
       flop += 2.0 * n;
       if (!Comm_SUM_dev(d_rho, 1)) return 0;
@@ -1621,6 +1645,10 @@ void CZ::WriteProfile(FILE* fp) const {
       {"Dot1 / Dot2", "dot", 2.0 * n},
       {"Blas_TRIAD / BiCG_1 / BiCG_2", "ewise", 0.0},
       {"Residual reduction", "reduce", 0.0},
+      {"MG restriction (residual + sum)", "mg_restrict", 0.0},
+      {"MG Jacobi sweep (coarse level)", "mg_smooth", 0.0},
+      {"MG prolongation", "mg_prolong", 0.0},
+      {"MG tail (coarse levels in LDS)", "mg_tail", 0.0},
   };
   char host[256] = "unknown";
   gethostname(host, sizeof(host) - 1);
@@ -1828,6 +1856,8 @@ int cz_info(const cz_handle* h, int what) {
     case 12: return c.exact_reruns;
     case 13: return c.cg_fused;
     case 14: return c.jac3_passes;
+    case 15: return c.mg ? czhip_mg_levels(c.mg) : 0;
+    case 16: return c.mg_cycles;
     case 5: return comm_transport_ranks(c.comm);
     case 6: return c.comm_cus;
     case 7: return c.last_plan.kind;

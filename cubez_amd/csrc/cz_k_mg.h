@@ -1,0 +1,200 @@
+// cz_k_mg.h -- part of cz_kernels.hip (ONE translation unit per precision; this file is included inside its anonymous
+// namespace and is not a stand-alone header): the level kernels of the multigrid V-cycle preconditioner of PCG.
+//
+// Aggregation multigrid with the exact Galerkin operator: level l+1 has ceil(n/2) points per direction, coarse point I covers the
+// level-0 points [I 2^l, min((I+1) 2^l, n)), so its extent in fine points is E(I) = min(2^l, n - I 2^l).  The level-l operator (the
+// correction is zero outside the box) is
+//   A_l u = Wx u(i+1) + Wx u(i-1) + Wy u(j+1) + Wy u(j-1) + Wz u(k+1) + Wz u(k-1) - D u,  Wx = Ey Ez, Wy = Ex Ez, Wz = Ex Ey, D = 2 (Wx+Wy+Wz)
+// summed in that order (c1 .. c6 of the reference).  The weights are small integers computed from (I, J, K, l, n0): exact in either
+// precision, no coefficient arrays.  At level 0 they are 1 and 6: the fine operator itself, whose sweep w * 1 = w gives the bits of jacobi_.
+// Every kernel is pointwise-independent and contains no reduction: the cycle is deterministic, bit for bit.
+//
+// Geometry of one level's array (MgLev): padded extents and the padded 0-based index of the first inner point.  The global arrays use the
+// S3D layout with guide g; the tail kernel's LDS arrays the same description with one zero shell (nip = ni + 2, first point at 1).
+constexpr int MG_MAXLEV = 32;       // levels of a hierarchy at most (ceil(log2 n) + 1 for any int extent)
+constexpr int MG_TAIL_MAXLEV = 8;   // levels of the tail at most (its LDS holds far fewer)
+constexpr int MG_TAIL_THREADS = 1024;
+constexpr int MG_GUIDE = 2;         // the guide of the hierarchy's arrays (S3D arrays)
+
+struct MgLev {
+  int nip, nkp;        // padded rows per plane, elements per row
+  int i0, j0, k0;      // padded 0-based index of the first inner point
+  int ni, nj, nk;      // points of the level per direction
+  int l;               // level
+  int n0i, n0j, n0k;   // level-0 points per direction (the extents E)
+};
+
+__device__ __forceinline__ long long mg_at(const MgLev& L, int I, int J, int K) {
+  return (long long)(L.k0 + K) + (long long)(L.i0 + I) * L.nkp + (long long)(L.j0 + J) * L.nkp * L.nip;
+}
+__device__ __forceinline__ int mg_ext(int I, int l, int n0) {
+  const int s = 1 << l, e = n0 - (I << l);
+  return e < s ? e : s;
+}
+
+struct MgW {
+  REAL wx, wy, wz, d;
+};
+__device__ __forceinline__ MgW mg_weights(const MgLev& L, int I, int J, int K) {
+  const int ex = mg_ext(I, L.l, L.n0i), ey = mg_ext(J, L.l, L.n0j), ez = mg_ext(K, L.l, L.n0k);
+  const int wx = ey * ez, wy = ex * ez, wz = ex * ey;
+  return MgW{(REAL)wx, (REAL)wy, (REAL)wz, (REAL)(2 * (wx + wy + wz))};
+}
+
+// the six weighted neighbours, in the reference's c1 .. c6 order; ZERO: u is identically zero (literal zeros, the same arithmetic)
+template <bool ZERO>
+__device__ __forceinline__ REAL mg_ss(const REAL* u, const MgLev& L, const MgW& w, long long p) {
+  const long long si = L.nkp, sj = (long long)L.nkp * L.nip;
+  const REAL z = (REAL)0;
+  const REAL ip = ZERO ? z : u[p + si], im = ZERO ? z : u[p - si], jp = ZERO ? z : u[p + sj], jm = ZERO ? z : u[p - sj];
+  const REAL kp = ZERO ? z : u[p + 1], km = ZERO ? z : u[p - 1];
+  return w.wx * ip + w.wx * im + w.wy * jp + w.wy * jm + w.wz * kp + w.wz * km;
+}
+
+// one relaxed Jacobi sweep at a point (cz_solver.f90:334-351 with the level's weights): pn = pp + ((ss - bb)/D - pp) omg, IEEE division
+template <bool ZERO>
+__device__ __forceinline__ REAL mg_sweep_pt(const REAL* u, const REAL* b, const MgLev& L, int I, int J, int K, REAL omg) {
+  const MgW w = mg_weights(L, I, J, K);
+  const long long p = mg_at(L, I, J, K);
+  const REAL pp = ZERO ? (REAL)0 : u[p];
+  const REAL ss = mg_ss<ZERO>(u, L, w, p);
+  const REAL dp = ((ss - b[p]) / w.d - pp) * omg;
+  return pp + dp;
+}
+
+// residual at a point, written like blas_calc_rk_ (cz_blas.f90:705-711): b - (ss - D x)
+__device__ __forceinline__ REAL mg_res_pt(const REAL* x, const REAL* b, const MgLev& L, int I, int J, int K) {
+  const MgW w = mg_weights(L, I, J, K);
+  const long long p = mg_at(L, I, J, K);
+  const REAL ss = mg_ss<false>(x, L, w, p);
+  return b[p] - (ss - w.d * x[p]);
+}
+
+// b_{l+1}(I, J, K) = the residual summed over the <= 8 children (j, i, k; k innermost) as the tree
+// ((r000 + r001) + (r010 + r011)) + ((r100 + r101) + (r110 + r111)); absent children drop out of it
+__device__ __forceinline__ REAL mg_restrict_pt(const REAL* x, const REAL* b, const MgLev& F, int I, int J, int K) {
+  const int i0 = 2 * I, j0 = 2 * J, k0 = 2 * K;
+  const bool hi = i0 + 1 < F.ni, hj = j0 + 1 < F.nj, hk = k0 + 1 < F.nk;
+  REAL t[2];
+#pragma unroll
+  for (int jb = 0; jb < 2; jb++) {
+    if (jb && !hj) break;
+    REAL s[2];
+#pragma unroll
+    for (int ib = 0; ib < 2; ib++) {
+      if (ib && !hi) break;
+      s[ib] = mg_res_pt(x, b, F, i0 + ib, j0 + jb, k0);
+      if (hk) s[ib] = s[ib] + mg_res_pt(x, b, F, i0 + ib, j0 + jb, k0 + 1);
+    }
+    t[jb] = hi ? s[0] + s[1] : s[0];
+  }
+  return hj ? t[0] + t[1] : t[0];
+}
+
+// u = x + R(alpha xc(parent)), alpha = R(1.8): one rounding per operation (no contraction: the build has -ffp-contract=off)
+__device__ __forceinline__ REAL mg_prolong_pt(const REAL* x, const REAL* xc, const MgLev& F, const MgLev& Cl, int I, int J, int K) {
+  const REAL alpha = (REAL)1.8;
+  const REAL c = alpha * xc[mg_at(Cl, I >> 1, J >> 1, K >> 1)];
+  return x[mg_at(F, I, J, K)] + c;
+}
+
+// ---- the level kernels: one thread per point of the level written; block (64, 4), grid (k, i, j)
+template <bool ZERO>
+__global__ void __launch_bounds__(256) mg_smooth_k(const REAL* __restrict__ u, REAL* __restrict__ w, const REAL* __restrict__ b, MgLev L, REAL omg) {
+  const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
+  if (K >= L.nk || I >= L.ni) return;
+  w[mg_at(L, I, J, K)] = mg_sweep_pt<ZERO>(u, b, L, I, J, K, omg);
+}
+
+__global__ void __launch_bounds__(256) mg_restrict_k(REAL* __restrict__ bc, const REAL* __restrict__ x, const REAL* __restrict__ b, MgLev F, MgLev Cl) {
+  const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
+  if (K >= Cl.nk || I >= Cl.ni) return;
+  bc[mg_at(Cl, I, J, K)] = mg_restrict_pt(x, b, F, I, J, K);
+}
+
+// u may be x (in place: every point reads its own x and its parent only)
+__global__ void __launch_bounds__(256) mg_prolong_k(REAL* u, const REAL* x, const REAL* __restrict__ xc, MgLev F, MgLev Cl) {
+  const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
+  if (K >= F.nk || I >= F.ni) return;
+  u[mg_at(F, I, J, K)] = mg_prolong_pt(x, xc, F, Cl, I, J, K);
+}
+
+// ---- the tail: x = V_t(b) from level t down to the coarsest and back, in ONE workgroup with every level's b, x and t in LDS
+struct MgTail {
+  int nlev;                // levels t .. t + nlev - 1 (the last is the coarsest)
+  MgLev gl;                // the global arrays of level t (b read, x written)
+  MgLev s[MG_TAIL_MAXLEV];      // the LDS arrays of every tail level (one zero shell)
+  int off[MG_TAIL_MAXLEV];      // REAL offset of level m's b in LDS; x and t follow at + len[m], + 2 len[m]
+  int len[MG_TAIL_MAXLEV];      // REALs per LDS array of level m
+  int total;               // REALs of LDS in all
+  REAL omg;
+};
+
+// every point of level L, by the workgroup
+template <class F>
+__device__ __forceinline__ void mg_each(const MgLev& L, F f) {
+  const int n = L.ni * L.nj * L.nk;
+  for (int q = threadIdx.x; q < n; q += blockDim.x) {
+    const int K = q % L.nk, r = q / L.nk, I = r % L.ni, J = r / L.ni;
+    f(I, J, K);
+  }
+}
+
+__global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ xg, const REAL* __restrict__ bg, MgTail T) {
+  extern __shared__ __align__(16) unsigned char mg_lds_raw[];
+  REAL* const lds = reinterpret_cast<REAL*>(mg_lds_raw);
+  for (int q = threadIdx.x; q < T.total; q += blockDim.x) lds[q] = (REAL)0;  // the zero shells (and a defined start)
+  __syncthreads();
+  {
+    REAL* b0 = lds + T.off[0];
+    mg_each(T.s[0], [&](int I, int J, int K) { b0[mg_at(T.s[0], I, J, K)] = bg[mg_at(T.gl, I, J, K)]; });
+  }
+  __syncthreads();
+  const REAL omg = T.omg;
+  // down: pre-smoothing pair from zero (b -> t -> x), residual restricted into the next level's b
+  for (int m = 0; m + 1 < T.nlev; m++) {
+    const MgLev& L = T.s[m];
+    REAL *b = lds + T.off[m], *x = b + T.len[m], *t = x + T.len[m];
+    mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<true>(t, b, L, I, J, K, omg); });
+    __syncthreads();
+    mg_each(L, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_sweep_pt<false>(t, b, L, I, J, K, omg); });
+    __syncthreads();
+    const MgLev& Cl = T.s[m + 1];
+    REAL* bc = lds + T.off[m + 1];
+    mg_each(Cl, [&](int I, int J, int K) { bc[mg_at(Cl, I, J, K)] = mg_restrict_pt(x, b, L, I, J, K); });
+    __syncthreads();
+  }
+  {  // the coarsest level: 8 sweeps from zero, b -> t -> x -> t ... -> x
+    const int m = T.nlev - 1;
+    const MgLev& L = T.s[m];
+    REAL *b = lds + T.off[m], *x = b + T.len[m], *t = x + T.len[m];
+    mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<true>(t, b, L, I, J, K, omg); });
+    __syncthreads();
+    for (int s = 1; s < 8; s++) {
+      const REAL* src = (s & 1) ? t : x;
+      REAL* dst = (s & 1) ? x : t;
+      mg_each(L, [&](int I, int J, int K) { dst[mg_at(L, I, J, K)] = mg_sweep_pt<false>(src, b, L, I, J, K, omg); });
+      __syncthreads();
+    }
+  }
+  // up: x += R(alpha x_c(parent)) in place, post-smoothing pair x -> t -> x
+  for (int m = T.nlev - 2; m >= 0; m--) {
+    const MgLev& L = T.s[m];
+    const MgLev& Cl = T.s[m + 1];
+    REAL *b = lds + T.off[m], *x = b + T.len[m], *t = x + T.len[m];
+    const REAL* xc = lds + T.off[m + 1] + T.len[m + 1];
+    mg_each(L, [&](int I, int J, int K) {
+      const long long p = mg_at(L, I, J, K);
+      x[p] = mg_prolong_pt(x, xc, L, Cl, I, J, K);
+    });
+    __syncthreads();
+    mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<false>(x, b, L, I, J, K, omg); });
+    __syncthreads();
+    mg_each(L, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_sweep_pt<false>(t, b, L, I, J, K, omg); });
+    __syncthreads();
+  }
+  {
+    const REAL* x0 = lds + T.off[0] + T.len[0];
+    mg_each(T.s[0], [&](int I, int J, int K) { xg[mg_at(T.gl, I, J, K)] = x0[mg_at(T.s[0], I, J, K)]; });
+  }
+}

@@ -18,7 +18,7 @@ ABI_SYMBOLS = [
     "czhip_real_bytes", "czhip_arch", "czhip_init", "czhip_finalize", "czhip_alloc_s3d", "czhip_free", "czhip_h2d",
     "czhip_d2h", "czhip_sync", "czhip_stream", "czhip_set_tuning", "czhip_get_tuning",
     "czhip_jacobi_async", "czhip_rbsor_async", "czhip_check_async", "czhip_jacobi_checked_async",
-    "czhip_rbsor_checked_async", "czhip_jacobi2_async", "czhip_set_tuning2", "czhip_set_pcr_mode", "czhip_set_pcr_lex", "czhip_set_pcr_lex_timeout", "czhip_set_pcr_lex_limits", "czhip_set_psor", "czhip_set_psor_ahead", "czhip_use_t2", "czhip_set_pair_window", "czhip_set_pair_preload", "czhip_set_unit_coef", "czhip_config_describe", "czhip_set_comm_cus", "czhip_selftest_fastdiv", "czhip_pair_maf_async", "czhip_rbsor2_async", "czhip_rbsor4_async", "czhip_set_rb4", "czhip_jacobi3_async", "czhip_set_jac3", "czhip_jacobi2_from_zero_async", "czhip_jacobi2_from_zero_made_async", "czhip_check2_async", "czhip_pair_split_async", "czhip_cg_update_async", "czhip_cg_dir_ax_async", "psor_", "psor_maf_", "pcr_", "pcr_eda_", "pcr_esa_", "pcr_rb_esa_", "pcr_j_esa_", "pcr_rb_maf_", "pcr_rb_esa_maf_", "pcr_maf_", "pcr_eda_maf_", "pcr_esa_maf_",
+    "czhip_rbsor_checked_async", "czhip_jacobi2_async", "czhip_set_tuning2", "czhip_set_pcr_mode", "czhip_set_pcr_lex", "czhip_set_pcr_lex_timeout", "czhip_set_pcr_lex_limits", "czhip_set_psor", "czhip_set_psor_ahead", "czhip_use_t2", "czhip_set_pair_window", "czhip_set_pair_preload", "czhip_set_unit_coef", "czhip_config_describe", "czhip_set_comm_cus", "czhip_selftest_fastdiv", "czhip_pair_maf_async", "czhip_rbsor2_async", "czhip_rbsor4_async", "czhip_set_rb4", "czhip_jacobi3_async", "czhip_set_jac3", "czhip_jacobi2_from_zero_async", "czhip_jacobi2_from_zero_made_async", "czhip_check2_async", "czhip_pair_split_async", "czhip_cg_update_async", "czhip_cg_dir_ax_async", "czhip_mg_smooth_async", "czhip_mg_restrict_async", "czhip_mg_prolong_async", "czhip_mg_tail_async", "czhip_mg_create", "czhip_mg_levels", "czhip_mg_apply_async", "czhip_mg_destroy", "psor_", "psor_maf_", "pcr_", "pcr_eda_", "pcr_esa_", "pcr_rb_esa_", "pcr_j_esa_", "pcr_rb_maf_", "pcr_rb_esa_maf_", "pcr_maf_", "pcr_eda_maf_", "pcr_esa_maf_",
     "cz_create", "cz_destroy", "cz_evaluate", "cz_setup", "cz_solve", "cz_sweeps", "cz_result_iter", "cz_result_res",
     "cz_history", "cz_field", "cz_local_size", "cz_error_max", "cz_set_quiet", "cz_last_solve_seconds", "cz_kernel_ms",
     "cz_set_debug", "cz_set_profile", "cz_info", "czhip_timing", "czhip_timing_read",
@@ -489,3 +489,49 @@ class CzHip:
         (_, szp), (_, idxp), (_, cfp), g, fl = self._i(sz), self._i(idx), self._r(cf), C.c_int(GUIDE), C.c_double(0.0)
         self.lib.blas_calc_rk_(C.c_void_p(r.ptr), C.c_void_p(p.ptr), C.c_void_p(b.ptr), szp, idxp, C.byref(g), cfp,
                                C.byref(fl))
+
+    # -- the multigrid V-cycle of pcg ... mg: level kernels on arrays of guide 2, and the hierarchy handle
+    def mg_smooth(self, u, w, b, sz, idx, level, n0, omg) -> bool:
+        """w = one level-`level` relaxed Jacobi sweep from u (u None: from zero)"""
+        (_, szp), (_, idxp), (_, n0p) = self._i(sz), self._i(idx), self._i(n0)
+        f = self.lib.czhip_mg_smooth_async
+        f.argtypes = [C.c_void_p] * 3 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, self.creal]
+        return bool(f(u.ptr if u is not None else None, w.ptr, b.ptr, szp, idxp, GUIDE, int(level), n0p, float(omg)))
+
+    def mg_restrict(self, bc, szc, idxc, x, b, sz, idx, level, n0) -> bool:
+        (_, szcp), (_, idxcp), (_, szp), (_, idxp), (_, n0p) = self._i(szc), self._i(idxc), self._i(sz), self._i(idx), self._i(n0)
+        f = self.lib.czhip_mg_restrict_async
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        return bool(f(bc.ptr, szcp, idxcp, x.ptr, b.ptr, szp, idxp, GUIDE, int(level), n0p))
+
+    def mg_prolong(self, u, x, xc, szc, idxc, sz, idx, level, n0) -> bool:
+        (_, szcp), (_, idxcp), (_, szp), (_, idxp), (_, n0p) = self._i(szc), self._i(idxc), self._i(sz), self._i(idx), self._i(n0)
+        f = self.lib.czhip_mg_prolong_async
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        return bool(f(u.ptr, x.ptr, xc.ptr, szcp, idxcp, szp, idxp, GUIDE, int(level), n0p))
+
+    def mg_tail(self, x, b, sz, idx, level, n0, omg) -> bool:
+        (_, szp), (_, idxp), (_, n0p) = self._i(sz), self._i(idx), self._i(n0)
+        f = self.lib.czhip_mg_tail_async
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, self.creal]
+        return bool(f(x.ptr, b.ptr, szp, idxp, GUIDE, int(level), n0p, float(omg)))
+
+    def mg_create(self, sz, idx, cf=(1, 1, 1, 1, 1, 1, 6)):
+        """the hierarchy handle (None when refused)"""
+        (_, szp), (_, idxp), (_, cfp) = self._i(sz), self._i(idx), self._r(cf)
+        self.lib.czhip_mg_create.restype = C.c_void_p
+        self.lib.czhip_mg_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        return self.lib.czhip_mg_create(szp, idxp, GUIDE, cfp)
+
+    def mg_levels(self, h) -> int:
+        self.lib.czhip_mg_levels.argtypes = [C.c_void_p]
+        return self.lib.czhip_mg_levels(h)
+
+    def mg_apply(self, h, z, r, omg) -> bool:
+        f = self.lib.czhip_mg_apply_async
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, self.creal]
+        return bool(f(h, z.ptr, r.ptr, float(omg)))
+
+    def mg_destroy(self, h):
+        self.lib.czhip_mg_destroy.argtypes = [C.c_void_p]
+        self.lib.czhip_mg_destroy(h)

@@ -322,6 +322,33 @@ void czhip_cg_update_async(CZ_REAL* x, CZ_REAL* r, const CZ_REAL* p, const CZ_RE
 void czhip_cg_dir_ax_async(CZ_REAL* p_new, CZ_REAL* q, const CZ_REAL* z, const CZ_REAL* p_old, const CZ_REAL* beta_dev, const int* sz, const int* idx,
                            int g, const CZ_REAL* cf, double* dots_dev);
 
+/* Multigrid V-cycle preconditioner of PCG (beyond the reference): aggregation multigrid with the exact Galerkin operator.
+ * Level l+1 has ceil(n/2) points per direction of level l; level l's array has its points as the inner box idx of an array sz with guide g
+ * (the hierarchy's coarse arrays: sz = n + 2, idx = 2 .. n + 1, zero faces), n0 = the level-0 points per direction (the face weights
+ * Wx = Ey Ez, Wy = Ex Ez, Wz = Ex Ey, D = 2 (Wx + Wy + Wz), E = min(2^l, n0 - I 2^l)).  Every entry returns 1 when launched, 0 when the
+ * arrays do not describe that level (or alias where they must not).
+ * czhip_mg_smooth_async: w = one relaxed Jacobi sweep of level l from u (u = NULL: from zero, u not read), pn = pp + ((ss - bb)/D - pp) omg.
+ * czhip_mg_restrict_async: bc (level l+1) = the residual b - (ss - D x) of level l summed over the <= 8 children, the fine residual not
+ *   stored.
+ * czhip_mg_prolong_async: u = x + R(1.8 xc(parent)) on level l (u may be x), xc of level l+1.
+ * czhip_mg_tail_async: x = V_l(b) from level l down to the coarsest and back in one workgroup, every level in LDS; 0 if they do not fit. */
+int czhip_mg_smooth_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, int g, int level, const int* n0, CZ_REAL omg);
+int czhip_mg_restrict_async(CZ_REAL* bc, const int* szc, const int* idxc, const CZ_REAL* x, const CZ_REAL* b, const int* sz, const int* idx, int g, int level,
+                            const int* n0);
+int czhip_mg_prolong_async(CZ_REAL* u, const CZ_REAL* x, const CZ_REAL* xc, const int* szc, const int* idxc, const int* sz, const int* idx, int g, int level,
+                           const int* n0);
+int czhip_mg_tail_async(CZ_REAL* x, const CZ_REAL* b, const int* sz, const int* idx, int g, int level, const int* n0, CZ_REAL omg);
+/* The hierarchy of a single-domain array (sz, idx, g = 2) for the operator cf: levels down to the first whose largest extent is <= 4, the
+ * coarse arrays b, x, t of every level >= 1 (about 3/7 of a fine array) and one fine temporary.  NULL (0) for coefficients other than
+ * c1 .. c6 = 1, dd = 6.  czhip_mg_apply_async: z = M^-1 r = V_0(r) with relaxation coefficient omg (0 < omg <= 1), z and r arrays of sz
+ * whose faces and guide cells are zero (only inner boxes are written); a level-0 box that is already the coarsest gives the 8 relaxed
+ * sweeps from zero.  No reduction: the same bits on every run.  CZ_MG_TAIL=0 at create: no tail kernel (the same bits). */
+typedef struct cz_mg cz_mg;
+cz_mg* czhip_mg_create(const int* sz, const int* idx, int g, const CZ_REAL* cf);
+int czhip_mg_levels(const cz_mg* h);
+int czhip_mg_apply_async(cz_mg* h, CZ_REAL* z, const CZ_REAL* r, CZ_REAL omg);
+void czhip_mg_destroy(cz_mg* h);
+
 /* Convergence bookkeeping on the device (cz_Poisson.cpp:67-77): res = sqrt(res_dev[0]*res_normal);
  * hist_dev[itr] = res; if (res < eps && !*flag) { *flag = 1; conv_itr_dev[0] = itr; }.  No-op when
  * already converged. */
@@ -361,7 +388,9 @@ double cz_last_solve_seconds(const cz_handle*);
  * the first pair of the preconditioner solve they feed (czhip_jacobi2_from_zero_made_async); 11 passes of the last red-black SOR solve that made
  * two iterations each (czhip_rbsor4_async); 12 converged iterations of the last Jacobi or red-black SOR solve that were the first of a fused pass
  * (a pair of sweeps, or an rb4 pass of two iterations) and were therefore re-run alone from the pass's untouched input to give the converged iterate;
- * 13 iterations of the last PCG solve whose search direction was made inside the SpMV pass (czhip_cg_dir_ax_async). */
+ * 13 iterations of the last PCG solve whose search direction was made inside the SpMV pass (czhip_cg_dir_ax_async); 14 three-sweep
+ * Jacobi passes of the last Jacobi solve (czhip_jacobi3_async); 15 levels of the multigrid hierarchy (pcg ... mg; 0 otherwise); 16 V-cycles
+ * of the last PCG solve with mg. */
 int cz_info(const cz_handle*, int what);
 double cz_kernel_ms(const cz_handle*, const char* label); /* HIP-event time of a labelled section, ms (avg per launch) */
 
