@@ -411,11 +411,42 @@ bool launch_rb4(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box&
   return true;
 }
 
+// numerators (of 2^32; see fastdiv_check_k) whose quotient by d in division form FORM (0 hoisted, 1 short, 2 medium) differs from `n / d`
+template <int FORM>
+long long div_check_count(REAL d) {
+  unsigned long long* bad = nullptr;
+  HIP_CHECK(hipMalloc(&bad, sizeof(*bad)));
+  HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(*bad), ctx.stream));
+  hipLaunchKernelGGL(fastdiv_check_k<FORM>, dim3(4096), dim3(256), 0, ctx.stream, d, bad);
+  HIP_CHECK(hipGetLastError());
+  unsigned long long h = 0;
+  HIP_CHECK(hipMemcpyAsync(&h, bad, sizeof(h), hipMemcpyDeviceToHost, ctx.stream));
+  HIP_CHECK(hipStreamSynchronize(ctx.stream));
+  HIP_CHECK(hipFree(bad));
+  return (long long)h;
+}
+// Does jac3_k divide by d with mediumdiv (cz_k_fastdiv.h: 8 instructions against 10)?  FP32 only, ctx.tune.jac3_medium.  Only a divisor whose
+// quotients agree with `n / d` in every bit for all 2^32 numerators: the comparison runs once per context and divisor (a few ms, synchronous),
+// at the first launch that needs it -- never inside a timed loop that has warmed up.
+inline bool jac3_medium(REAL d) {
+  if (sizeof(REAL) != 4 || !ctx.tune.jac3_medium || !fastdiv_ok(d)) return false;
+  unsigned long long key = 0;
+  memcpy(&key, &d, sizeof(REAL));
+  auto it = ctx.medium_div.find(key);
+  if (it == ctx.medium_div.end()) {
+    long long bad = -1;
+    if constexpr (sizeof(REAL) == 4) bad = div_check_count<2>(d);
+    it = ctx.medium_div.emplace(key, bad == 0).first;
+  }
+  return it->second;
+}
+
 // THREE Jacobi sweeps per pass (jac3_k, cz_k_jac3.h): single-domain boxes, constant coefficients.  Returns false when the geometry does not suit
 // the kernel or the box lies below the size gate (the caller then runs the two-sweep pass).  The k axis is cut into windows of about
 // jac3_window() vectors: the four halo rows of a segment must stay a small share of the 1 024 vectors a workgroup holds.
 // By measurement (profiles/r06/jac3_three_sweeps_per_pass.txt), per sweep against the pair: FP32 windows of 26 vectors 1.09 x at 512^3 (43: 1.01 x,
 // 20: 0.98 x), 1.11 x at 384^3, 1.07 x at 1024^3, 1.01 x at 256^3; FP64 512^3 windows of 36 1.22 x (28: 1.19 x, 20: 1.11 x).
+// Re-swept with the shorter FP32 division (profiles/r08/jac3_fetch_split_and_medium_division.txt): no window or gate beats these beyond noise.
 inline int jac3_window(int) { return VW == 4 ? 26 : 36; }
 // size gate of ctx.tune.jac3 = 1: inner points of the box (256^3: no gain worth the switch; 384^3: 1.11 x)
 constexpr long long kJac3MinPoints = 300LL * 300 * 300;
@@ -437,7 +468,11 @@ bool launch_jac3(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box
   if (probe) return true;
   fin.single = 0;
   const bool unit = ctx.tune.unit_coef && coef_is_unit(c);
-  launch_pass(!unit ? &jac3_k<VW, TB, 0> : &jac3_k<VW, TB, 1>, LBL_JACOBI3, p, U, B, W, c, skip, fin);  // (UNIT = 0 named first: it keeps its place in the code object)
+  if (!jac3_medium(c.dd)) {
+    launch_pass(!unit ? &jac3_k<VW, TB, 0, 0> : &jac3_k<VW, TB, 1, 0>, LBL_JACOBI3, p, U, B, W, c, skip, fin);  // (UNIT = 0 named first: it keeps its place in the code object)
+  } else {
+    if constexpr (sizeof(REAL) == 4) launch_pass(!unit ? &jac3_k<VW, TB, 0, 1> : &jac3_k<VW, TB, 1, 1>, LBL_JACOBI3, p, U, B, W, c, skip, fin);
+  }
   return true;
 }
 

@@ -10,8 +10,8 @@
 //     LDS         u: 2 x (LV + 2R), f1, f2: 2 x LV each (by plane parity; the j-1 operand of a vector is read by the thread that wrote it)
 //     k windows   KT vectors + hv halo vectors per side; three stages reach 3 elements beyond a window: hv = 1 (FP32), 2 (FP64)
 //     planes      stage s at step q works on plane q - s + 1: f1(q) from u(q-1..q+1), f2(q-1) from f1, f3(q-2) -> W
-// Per point: relax_vec<V, UNIT> with the hoisted IEEE division, the operations of jacobi2p_k on the same values => the same bits as three
-// single sweeps.  The three residuals (sum dp^2 of sweeps n+1, n+2, n+3) are produced and finalised in the kernel; if the first or the second
+// Per point: relax_vec<V, UNIT> with the hoisted IEEE division (or its checked shorter form, MED), the operations of jacobi2p_k on the same
+// values => the same bits as three single sweeps.  The three residuals (sum dp^2 of sweeps n+1, n+2, n+3) are produced and finalised in the kernel; if the first or the second
 // converges, the driver re-runs one sweep or one pair from the untouched input (out of place, like the pair).
 // ------------------------------------------------------------------------------------------------------------
 
@@ -48,7 +48,9 @@ __device__ __forceinline__ void jac3_finalize(const double* partials, int nblk, 
   }
 }
 
-template <int V, int TB, int UNIT>
+// MED = 1 (FP32): the division with one correction step (mediumdiv, cz_k_fastdiv.h), taken only for a divisor that passed the exhaustive
+// comparison with `n / d` on this context (jac3_medium, cz_h_launch.h)
+template <int V, int TB, int UNIT, int MED>
 __global__ void __launch_bounds__(TB, 1)
 jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict__ W, Coef c, Geom2 g, double* partials,
        const int* __restrict__ skip, Fin2 fin) {
@@ -93,7 +95,7 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
   if (jb > g.jj1) jb = g.jj1;
 
   double acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-  const HoistedDiv dv{fastdiv_init(c.dd)};
+  const typename std::conditional<MED != 0, MediumDiv, HoistedDiv>::type dv{fastdiv_init(c.dd)};
 
   if (ja <= jb && fb < g.Fend) {
     const long long e2_0 = fb - 2 * (long long)R;  // first vector of E2

@@ -24,6 +24,7 @@
 #include <map>
 #include <set>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "cz_config.h"
@@ -193,6 +194,7 @@ int czhip_init(int device) {
     sscanf(v, "%d,%d,%d", &en, &kw, &tj);
     ctx.tune.jac3 = en, ctx.tune.jac3_kwin = kw, ctx.tune.jac3_tj = tj;
   }
+  ctx.tune.jac3_medium = cfg.num(CZV_JAC3_MEDIUM, ctx.tune.jac3_medium);
   if (const char* pp = cfg.str(CZV_PCR_PIPE)) {  // "form[,seconds[,groups[,rows per thread]]]": form as Tuning::pcr_pipe; bound of the waits inside the kernel
     int w = 1, rows = 0, q = 1;
     double sec = 2.0;
@@ -506,6 +508,22 @@ int czhip_set_jac3(int enable, int window, int planes) {
   return 0;
 }
 
+// jac3_k FP32: the checked shorter division on (1) or off (0); negative: keep.  Returns the setting that was in force.
+int czhip_set_jac3_medium(int enable) {
+  ensure_init();
+  const int before = ctx.tune.jac3_medium;
+  if (enable >= 0) ctx.tune.jac3_medium = enable;
+  return before;
+}
+
+// the division jac3_k takes for the divisor d on this context: 1 = mediumdiv, 0 = the hoisted form, -1 = the pass does not take d at all
+// (fastdiv_ok).  Runs the exhaustive check where it is due, as the first launch would.
+int czhip_jac3_division(CZ_REAL d) {
+  ensure_init();
+  if (!fastdiv_ok(d)) return -1;
+  return jac3_medium(d) ? 1 : 0;
+}
+
 // rb4_k switches (measurements): enable 0 | 1, vectors per k window, planes per chunk (0: the launcher's rule); negative: keep.
 int czhip_set_rb4(int enable, int window, int planes) {
   ensure_init();
@@ -586,16 +604,15 @@ int czhip_set_pair_window(int vectors) {
 long long czhip_selftest_fastdiv(CZ_REAL d) {
   ensure_init();
   if (!fastdiv_ok(d)) return -1;
-  unsigned long long* bad = nullptr;
-  HIP_CHECK(hipMalloc(&bad, sizeof(*bad)));
-  HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(*bad), ctx.stream));
-  hipLaunchKernelGGL(fastdiv_check_k<0>, dim3(4096), dim3(256), 0, ctx.stream, d, bad);
-  HIP_CHECK(hipGetLastError());
-  unsigned long long h = 0;
-  HIP_CHECK(hipMemcpyAsync(&h, bad, sizeof(h), hipMemcpyDeviceToHost, ctx.stream));
-  HIP_CHECK(hipStreamSynchronize(ctx.stream));
-  HIP_CHECK(hipFree(bad));
-  return (long long)h;
+  return div_check_count<0>(d);
+}
+
+// The same for the division with one correction step (mediumdiv; FP32, every float numerator): the count jac3_medium decides by.  -1 where the
+// divisor is not eligible, and in FP64 (no such form).
+long long czhip_selftest_mediumdiv(CZ_REAL d) {
+  ensure_init();
+  if (sizeof(CZ_REAL) != 4 || !fastdiv_ok(d)) return -1;
+  return div_check_count<2>(d);
 }
 
 // Measurement aid (tools/cu_reserve_cost.py): put the CU reservation of decomposed runs in force on this context by hand; returns what is in force.

@@ -234,6 +234,13 @@ int czhip_jacobi3_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const in
 /* ... its switches (measurements; negative = keep): 0 off / 1 on above the size gate / 2 on also for small grids (tests), vectors per k window,
  * planes per chunk (0 = chosen per launch).  czhip_set_tuning2 with enable 0 (single sweeps) turns it off as well. */
 int czhip_set_jac3(int enable, int window, int planes);
+/* ... FP32: its division by the diagonal with one correction step instead of two, for a divisor whose quotients were compared with the IEEE
+ * division for all 2^32 numerators on this context (once per divisor, at the first launch) and agreed in every bit; others keep the hoisted
+ * form.  1 = on (default), 0 = off, negative = keep.  Returns the previous setting.  Results do not depend on it. */
+int czhip_set_jac3_medium(int enable);
+/* ... the division that pass takes for divisor d on this context: 1 = the shorter form, 0 = the hoisted form, -1 = the pass does not take d
+ * (it runs the comparison where it is due, like the first launch). */
+int czhip_jac3_division(CZ_REAL d);
 /* The fused pass split the way a decomposed brick runs it (replaces the reference's "sweep, then Comm_S",
  * cz_Poisson.cpp:58-63): first the slabs two cells thick behind every face with nID[f] >= 0 (the cells the neighbours
  * receive), then the interior, so that the exchange can start after the first launch.  Same result as the unsplit op.
@@ -310,6 +317,8 @@ const char* czhip_config_describe(int only_set);
 int czhip_set_comm_cus(int k);
 /* self-test: numerators (of 2^32) whose quotient by d in the two-stage pass differs from the IEEE division (expected 0); -1 = divisor not eligible */
 long long czhip_selftest_fastdiv(CZ_REAL d);
+/* the same for the shorter form jac3_k takes where it agrees (FP32; -1 = divisor not eligible, and in FP64, which has no such form) */
+long long czhip_selftest_mediumdiv(CZ_REAL d);
 
 /* PCG (beyond the reference; DESIGN.md "PCG"), the two passes of its iteration:
  * czhip_cg_update_async: x = alpha*p + x, r = (-alpha)*q + r on the inner box (blas_triad_ twice) and dots_dev[0] = r.r (per-point products in
