@@ -15,6 +15,9 @@
 //                                needs ghost layer 2 behind it and the edge cells (ghost in two directions) beside it;
 //                                edges travel directly to the diagonal neighbours, so the exchange stays single-phase
 // Corners are never read by a 7-point stencil at this depth.
+//   depth 1, faces + 12 edges + 8 corners    the distributed levels of the V-cycle (cz_mg_dist.cpp): a coarse point's children on the
+//                                            + neighbours and a fine point's parent on the - neighbours can sit across an edge or corner
+// comm_allgather: equal-sized (padded) blocks of every rank, in rank order, an exact copy (ncclAllGather / device copies).
 #include "cz_comm.h"
 
 #include <rccl/rccl.h>
@@ -168,7 +171,7 @@ struct Boot {
 thread_local Boot boot;
 
 
-constexpr int MAX_BOX = 18;  // 6 faces + 12 edges
+constexpr int MAX_BOX = 26;  // 6 faces + 12 edges + 8 corners
 
 enum BoxKind { BOX_GENERIC = 0, BOX_ROWS = 1 /* I face: whole padded k-rows */, BOX_KPAIR = 2 /* K face */, BOX_DIRECT = 3 /* J face: not packed */ };
 
@@ -291,6 +294,8 @@ struct CommCtx {
   CzConfig cfg;  // the environment as read when this communicator context was created (cz_config.h)
   double* h_red = nullptr;
   Pattern shallow, deep;   // depth 1 faces / depth 2 faces + edges
+  Pattern full;            // depth 1 faces + edges + corners
+  const void* cur_send = nullptr;  // LOCAL: the block being all-gathered
   const Pattern* cur = nullptr;  // LOCAL: pattern being exchanged (published for the neighbours)
   const void* cur_X = nullptr;   // LOCAL: the array being exchanged (source of the neighbours' direct messages)
   Watch watch;
@@ -348,7 +353,7 @@ bool comm_decompose(const int G[3], const int D[3], int nproc, int rank, int siz
 
 
 namespace {
-void build_pattern(CommCtx* c, Pattern& p, int depth, bool edges) {
+void build_pattern(CommCtx* c, Pattern& p, int depth, bool edges, bool corners = false) {
   const int N[3] = {c->size[0], c->size[1], c->size[2]};
   const int g = c->g;
   p.nmsg = 0;
@@ -358,7 +363,7 @@ void build_pattern(CommCtx* c, Pattern& p, int depth, bool edges) {
       for (int di = -1; di <= 1; di++) {
         const int d[3] = {di, dj, dk};
         const int nz = (di != 0) + (dj != 0) + (dk != 0);
-        if (nz == 0 || nz == 3 || (nz == 2 && !edges)) continue;
+        if (nz == 0 || (nz == 3 && !corners) || (nz == 2 && !edges)) continue;
         int rc[3];
         bool exists = true;
         for (int a = 0; a < 3; a++) {
@@ -366,7 +371,7 @@ void build_pattern(CommCtx* c, Pattern& p, int depth, bool edges) {
           if (rc[a] < 0 || rc[a] >= c->div[a]) exists = false;
         }
         if (!exists) continue;
-        const int dep = (nz == 1) ? depth : 1;  // faces carry `depth` layers, edges one cell in each cut direction
+        const int dep = (nz == 1) ? depth : 1;  // faces carry `depth` layers, edges and corners one cell in each cut direction
         BoxDesc sb, rb;
         int s0[3], r0[3], ext[3];
         for (int a = 0; a < 3; a++) {
@@ -453,6 +458,7 @@ bool exchange(CommCtx* c, const Pattern& p, T* X, const int* skip, hipStream_t s
   } else {  // LOCAL: every rank has packed; copy what each neighbour packed for me (its message in direction -d)
     c->cur = &p;
     c->cur_X = X;
+    c->world->ranks[c->rank] = c;  // (a rank has one context per level of the V-cycle: the one exchanging now is the one to read)
     HIP_CHECK(hipStreamSynchronize(st));
     c->world->barrier(c->rank);
     for (int m = 0; m < p.nmsg; m++) {
@@ -475,7 +481,7 @@ bool exchange(CommCtx* c, const Pattern& p, T* X, const int* skip, hipStream_t s
     hipLaunchKernelGGL((box_copy_k<T, 1>), grid, dim3(256), 0, st, (T*)p.recvbuf, X, p.recv, nkp, nip, skip);
     HIP_CHECK(hipGetLastError());
   }
-  c->watch.note(&p == &c->deep ? "halo exchange, two layers + edges" : "halo exchange, one layer", st);
+  c->watch.note(&p == &c->deep ? "halo exchange, two layers + edges" : &p == &c->full ? "halo exchange, one layer + edges + corners" : "halo exchange, one layer", st);
   return true;
 }
 }  // namespace
@@ -494,6 +500,7 @@ CommCtx* comm_create(int rank, int nproc, const int size[3], const int nID[6], i
   c->coord[0] = rank % div[0], c->coord[1] = (rank / div[0]) % div[1], c->coord[2] = rank / (div[0] * div[1]);
   build_pattern(c, c->shallow, 1, false);
   build_pattern(c, c->deep, 2, true);
+  build_pattern(c, c->full, 1, true, true);
   HIP_CHECK(hipHostMalloc(&c->h_red, 16 * sizeof(double), hipHostMallocDefault));
   if (c->tr == T_LOCAL) {
     std::lock_guard<std::mutex> lk(c->world->mu);
@@ -506,7 +513,7 @@ CommCtx* comm_create(int rank, int nproc, const int size[3], const int nID[6], i
 void comm_destroy(CommCtx* c) {
   if (!c) return;
   c->watch.stop();
-  for (Pattern* p : {&c->shallow, &c->deep}) {
+  for (Pattern* p : {&c->shallow, &c->deep, &c->full}) {
     if (p->sendbuf) (void)hipFree(p->sendbuf);
     if (p->recvbuf) (void)hipFree(p->recvbuf);
   }
@@ -523,6 +530,44 @@ bool comm_halo2(CommCtx* c, void* X, const int* skip, hipStream_t st) {
   if (!c) return true;
   if (c->g != 2) return false;
   return c->eb == 4 ? exchange<float>(c, c->deep, (float*)X, skip, st) : exchange<double>(c, c->deep, (double*)X, skip, st);
+}
+
+bool comm_halo_full(CommCtx* c, void* X, hipStream_t st) {
+  if (!c) return true;
+  return c->eb == 4 ? exchange<float>(c, c->full, (float*)X, nullptr, st) : exchange<double>(c, c->full, (double*)X, nullptr, st);
+}
+
+bool comm_allgather(CommCtx* c, const void* send, void* recv, size_t count, hipStream_t st) {
+  if (!c) return true;
+  const size_t bytes = count * c->eb;
+  if (c->tr == T_RCCL) {
+    NCCL_CHECK(ncclAllGather(send, recv, count, c->eb == 4 ? ncclFloat : ncclDouble, c->nccl, st));
+    c->watch.note("all-gather", st);
+    return true;
+  }
+  LocalWorld* w = c->world;
+  c->cur_send = send;
+  w->ranks[c->rank] = c;
+  HIP_CHECK(hipStreamSynchronize(st));
+  w->barrier(c->rank);
+  for (int r = 0; r < w->n; r++)
+    if (bytes) HIP_CHECK(hipMemcpyAsync((char*)recv + (size_t)r * bytes, w->ranks[r]->cur_send, bytes, hipMemcpyDeviceToDevice, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  w->barrier(c->rank);  // nobody rewrites its block before everyone has copied
+  return true;
+}
+
+long long comm_halo_full_bytes(const CommCtx* c) {
+  if (!c) return 0;
+  long long n = 0;
+  for (int m = 0; m < c->full.nmsg; m++) n += (long long)c->full.count[m];
+  return n * c->eb;
+}
+
+void comm_mg_own(int h, int m, int level, int* first, int* count) {
+  const long long s = 1LL << level;
+  const long long a = (h + s - 1) / s, b = (h + m + s - 1) / s;
+  *first = (int)a, *count = (int)(b - a);
 }
 
 bool comm_allreduce_sum(CommCtx* c, double* d_val, int count, hipStream_t st) {

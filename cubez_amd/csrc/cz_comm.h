@@ -26,6 +26,14 @@ void comm_destroy(CommCtx*);
 bool comm_halo(CommCtx*, void* X, const int* skip_flag_dev, hipStream_t st);
 // two ghost layers on the faces + the 12 edges, single phase (diagonal neighbours get the edges directly); needs g == 2
 bool comm_halo2(CommCtx*, void* X, const int* skip_flag_dev, hipStream_t st);
+// one layer on the faces + the 12 edges + the 8 corners (the distributed levels of the V-cycle)
+bool comm_halo_full(CommCtx*, void* X, hipStream_t st);
+long long comm_halo_full_bytes(const CommCtx*);  // bytes this brick sends in one comm_halo_full
+// every rank's block of `count` elements (equal sizes: pad to the largest) into recv, in rank order -- an exact copy
+bool comm_allgather(CommCtx*, const void* send, void* recv, size_t count, hipStream_t st);
+// ownership of the coarse points of level `level`: a brick whose global 0-based level-0 points along one direction are
+// [h, h+m) owns that level's points [ceil(h / 2^level), ceil((h+m) / 2^level)): *first and *count (0: none)
+void comm_mg_own(int h, int m, int level, int* first, int* count);
 bool comm_allreduce_sum(CommCtx*, double* d_val, int count, hipStream_t st);
 double comm_allreduce_max_host(CommCtx*, double v);
 // ranks of the RCCL communicator behind the context (ncclCommCount); 0 for the LOCAL transport or no context

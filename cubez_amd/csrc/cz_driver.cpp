@@ -90,6 +90,7 @@ CZ::~CZ() {
   if (comm_cus > 0) reserve_comm_cus(0);  // the library context outlives this object
   REAL_TYPE* arrs[] = {WRK, WRK2, P, RHS, pcg_p, pcg_p_, pcg_r, pcg_r0, pcg_q, pcg_s, pcg_s_, pcg_t_, cg_r, cg_z, cg_p[0], cg_p[1], cg_q, pvt, MSK};
   if (mg) czhip_mg_destroy(mg);
+  if (mgd) mgd_destroy(mgd);
   if (d_xc) (void)hipFree(d_xc);
   if (d_yc) (void)hipFree(d_yc);
   if (d_zc) (void)hipFree(d_zc);
@@ -226,11 +227,6 @@ void CZ::setLS(const char* q) {
     // the V-cycle's smoothers are relaxed Jacobi sweeps: the same range keeps it symmetric and definite
     if (pc_type == LS_MG && !(ac1 > (REAL_TYPE)0 && ac1 <= (REAL_TYPE)1)) {
       Hostonly_ printf("Invalid coefficient for pcg with mg '%g' (0 < coef <= 1: a symmetric definite preconditioner)\n", (double)ac1);
-      exit(0);
-    }
-    // the coarse levels of a brick would need the other bricks' points (agglomeration across ranks): single domain only
-    if (pc_type == LS_MG && numProc > 1) {
-      Hostonly_ printf("pcg with mg runs on a single domain only (%d processes): the coarse levels are not agglomerated across ranks\n", numProc);
       exit(0);
     }
     // k relaxed Jacobi sweeps from zero are a polynomial in A: symmetric, and definite with A's sign for 0 < omega <= 1
@@ -377,7 +373,12 @@ int CZ::Setup(int argc, char** argv) {
   if (ls_type == LS_PCG) {  // zero-filled; only their inner boxes are ever written (the fused passes read the shells as zeros)
     cg_r = czhip_alloc_s3d(size), cg_q = czhip_alloc_s3d(size), cg_p[0] = czhip_alloc_s3d(size), cg_p[1] = czhip_alloc_s3d(size);
     if (pc_type == LS_JACOBI || pc_type == LS_MG) cg_z = czhip_alloc_s3d(size);
-    if (pc_type == LS_MG && !(mg = czhip_mg_create(size, innerFidx, GUIDE, cf))) {
+    // (a decomposed run: the distributed cycle, DESIGN.md §5.10 "Decomposed runs"; the coefficients are the unit ones of the command line)
+    if (pc_type == LS_MG && numProc > 1 && !(mgd = mgd_create(*this, comm, cfg.num(CZV_MG_GATHER, 32768), cfg.on(CZV_MG_TAIL, true)))) {
+      Hostonly_ printf("pcg with mg: the distributed V-cycle could not be set up\n");
+      return 0;
+    }
+    if (pc_type == LS_MG && numProc == 1 && !(mg = czhip_mg_create(size, innerFidx, GUIDE, cf))) {
       Hostonly_ printf("pcg with mg: unsupported coefficients (c1 .. c6 = 1, dd = 6 only)\n");
       return 0;
     }
@@ -388,6 +389,7 @@ int CZ::Setup(int argc, char** argv) {
            narr / 1048576.0, narr, size[0], size[1], size[2],
            sizeof(REAL_TYPE) == 4 ? "float" : "double");
     if (mg) printf("\tMultigrid levels       : %d (coarse arrays about 3/7 of one array more)\n", czhip_mg_levels(mg));
+    if (mgd) printf("\tMultigrid levels       : %d, gathered from level %d on\n", mgd_levels(mgd), mgd_gather_level(mgd));
   }
 
   ItrMax = atoi(argv[5]);  // :330
@@ -1551,8 +1553,8 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
     }
     if (pc) {
       if (!Comm_S(cg_r)) return 0;  // (a decomposed pass reads the right-hand side in its ghost layer)
-      if (mg) {
-        if (!czhip_mg_apply_async(mg, cg_z, cg_r, ac1)) return 0;  // z = V_0(r)
+      if (mg || mgd) {
+        if (mg ? !czhip_mg_apply_async(mg, cg_z, cg_r, ac1) : !mgd_apply(mgd, cg_z, cg_r, ac1)) return 0;  // z = V_0(r)
         mg_cycles++;
       } else {
         double fc = 0.0;
@@ -1856,8 +1858,10 @@ int cz_info(const cz_handle* h, int what) {
     case 12: return c.exact_reruns;
     case 13: return c.cg_fused;
     case 14: return c.jac3_passes;
-    case 15: return c.mg ? czhip_mg_levels(c.mg) : 0;
+    case 15: return c.mg ? czhip_mg_levels(c.mg) : c.mgd ? mgd_levels(c.mgd) : 0;
     case 16: return c.mg_cycles;
+    case 17: return mgd_gather_level(c.mgd);
+    case 18: return mgd_exchanges(c.mgd);
     case 5: return comm_transport_ranks(c.comm);
     case 6: return c.comm_cus;
     case 7: return c.last_plan.kind;
@@ -1865,6 +1869,18 @@ int cz_info(const cz_handle* h, int what) {
     case 9: return c.last_plan.buffers;
     default: return -1;
   }
+}
+int cz_precondition(cz_handle* h, const CZ_REAL* r_dense, CZ_REAL* z_dense) {
+  CZ& c = h->cz;
+  if (!c.set_up || !(c.mg || c.mgd)) return 0;
+  const size_t n = (size_t)(c.size[0] + 2 * GUIDE) * (c.size[1] + 2 * GUIDE) * (c.size[2] + 2 * GUIDE);
+  czhip_h2d(c.cg_r, r_dense, n * sizeof(CZ_REAL));
+  czhip_sync();
+  const int ok = c.mg ? czhip_mg_apply_async(c.mg, c.cg_z, c.cg_r, c.ac1) : mgd_apply(c.mgd, c.cg_z, c.cg_r, c.ac1);
+  czhip_sync();
+  if (!ok) return -1;
+  czhip_d2h(z_dense, c.cg_z, n * sizeof(CZ_REAL));
+  return 1;
 }
 double cz_kernel_ms(const cz_handle* h, const char* label) {
   (void)h;

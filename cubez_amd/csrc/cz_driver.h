@@ -59,6 +59,7 @@ class CZ {
   // PCG's work vectors (the pcg_* above are BiCGSTAB's, named as in the reference); allocated only when pcg is selected
   REAL_TYPE *cg_r = nullptr, *cg_z = nullptr, *cg_p[2] = {nullptr, nullptr}, *cg_q = nullptr;
   cz_mg* mg = nullptr;           // the multigrid hierarchy of pcg ... mg, allocated only then
+  struct MgDist* mgd = nullptr;  // decomposed runs: the distributed V-cycle of pcg ... mg instead (cz_mg_dist.cpp)
 
   // ---- build-specific state
   bool quiet = false;
@@ -200,5 +201,15 @@ class CZ {
   bool line_error = false;       // set by sweep_failed; PBiCGSTAB gives up when a line-solver preconditioner set it
   double npts() const;
 };
+
+// the distributed V-cycle of pcg ... mg (cz_mg_dist.cpp, DESIGN.md §5.10 "Decomposed runs")
+constexpr int MG_DIST_MAXLEV = 32;
+// nullptr on a single domain; gather_points: CZ_MG_GATHER, tail: CZ_MG_TAIL
+MgDist* mgd_create(const CZ& cz, CommCtx* comm0, int gather_points, bool tail);
+void mgd_destroy(MgDist*);
+int mgd_apply(MgDist*, REAL_TYPE* z, const REAL_TYPE* r, REAL_TYPE omg);  // z = V_0(r) on this rank's brick, collective
+int mgd_levels(const MgDist*);
+int mgd_gather_level(const MgDist*);
+int mgd_exchanges(const MgDist*);  // halo exchanges + all-gathers of the last cycle
 
 #endif

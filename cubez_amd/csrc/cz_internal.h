@@ -127,6 +127,23 @@ int pair_box_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz
 void copy_shell_async(CZ_REAL* dst, const CZ_REAL* src, const int* sz, const int* idx, int g);
 void copy_inner_async(CZ_REAL* dst, const CZ_REAL* src, const int* sz, const int* idx, int g);
 void bc_async(const int* sz, int g, CZ_REAL* p, CZ_REAL dh, const CZ_REAL* org, const int* nID, int ioff = 0, int joff = 0);
+
+// the distributed levels of the V-cycle of a decomposed run (cz_k_mg.h MgDLev): one brick's array of level `level`
+// (guide 2; sz / idx as a fine brick's: inner 1 .. size on rank-internal faces, 2 .. size-1 on physical ones), the global index o of its
+// first owned point, the level's global points gn, the level-0 points n0.  dense: a shell-less block of sz points (idx unused).
+struct MgdLevel {
+  int sz[3], idx[6];
+  int level;
+  int n0[3], o[3], gn[3];
+  int dense;
+};
+int mgd_smooth_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const MgdLevel& L, CZ_REAL omg);  // u = nullptr: from zero
+// rt = residual of the first owned layer on the - faces flagged in minus[3]
+int mgd_resface_async(CZ_REAL* rt, const CZ_REAL* x, const CZ_REAL* b, const MgdLevel& L, const int* minus);
+int mgd_restrict_async(CZ_REAL* bc, const MgdLevel& C, const CZ_REAL* x, const CZ_REAL* b, const CZ_REAL* rt, const MgdLevel& F);
+int mgd_prolong_async(CZ_REAL* u, const CZ_REAL* x, const CZ_REAL* xc, const MgdLevel& C, const MgdLevel& F);
+// a dense block of cnt points into the global level array G (o = the block's global offset)
+int mgd_unpack_async(CZ_REAL* X, const MgdLevel& G, const CZ_REAL* blk, const int* o, const int* cnt);
 }  // namespace czhip_internal
 
 #endif

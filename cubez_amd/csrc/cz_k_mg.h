@@ -24,6 +24,12 @@ struct MgLev {
   int n0i, n0j, n0k;   // level-0 points per direction (the extents E)
 };
 
+// global index of a level array's local point (0, 0, 0): zero on a single domain, the brick's first owned point of the level in the
+// distributed cycle (the weights depend on the global index, addresses on the local one)
+struct MgG {
+  int i, j, k;
+};
+
 __device__ __forceinline__ long long mg_at(const MgLev& L, int I, int J, int K) {
   return (long long)(L.k0 + K) + (long long)(L.i0 + I) * L.nkp + (long long)(L.j0 + J) * L.nkp * L.nip;
 }
@@ -53,8 +59,8 @@ __device__ __forceinline__ REAL mg_ss(const REAL* u, const MgLev& L, const MgW& 
 
 // one relaxed Jacobi sweep at a point (cz_solver.f90:334-351 with the level's weights): pn = pp + ((ss - bb)/D - pp) omg, IEEE division
 template <bool ZERO>
-__device__ __forceinline__ REAL mg_sweep_pt(const REAL* u, const REAL* b, const MgLev& L, int I, int J, int K, REAL omg) {
-  const MgW w = mg_weights(L, I, J, K);
+__device__ __forceinline__ REAL mg_sweep_pt(const REAL* u, const REAL* b, const MgLev& L, int I, int J, int K, REAL omg, MgG o = MgG{0, 0, 0}) {
+  const MgW w = mg_weights(L, I + o.i, J + o.j, K + o.k);
   const long long p = mg_at(L, I, J, K);
   const REAL pp = ZERO ? (REAL)0 : u[p];
   const REAL ss = mg_ss<ZERO>(u, L, w, p);
@@ -63,18 +69,18 @@ __device__ __forceinline__ REAL mg_sweep_pt(const REAL* u, const REAL* b, const 
 }
 
 // residual at a point, written like blas_calc_rk_ (cz_blas.f90:705-711): b - (ss - D x)
-__device__ __forceinline__ REAL mg_res_pt(const REAL* x, const REAL* b, const MgLev& L, int I, int J, int K) {
-  const MgW w = mg_weights(L, I, J, K);
+__device__ __forceinline__ REAL mg_res_pt(const REAL* x, const REAL* b, const MgLev& L, int I, int J, int K, MgG o = MgG{0, 0, 0}) {
+  const MgW w = mg_weights(L, I + o.i, J + o.j, K + o.k);
   const long long p = mg_at(L, I, J, K);
   const REAL ss = mg_ss<false>(x, L, w, p);
   return b[p] - (ss - w.d * x[p]);
 }
 
 // b_{l+1}(I, J, K) = the residual summed over the <= 8 children (j, i, k; k innermost) as the tree
-// ((r000 + r001) + (r010 + r011)) + ((r100 + r101) + (r110 + r111)); absent children drop out of it
-__device__ __forceinline__ REAL mg_restrict_pt(const REAL* x, const REAL* b, const MgLev& F, int I, int J, int K) {
-  const int i0 = 2 * I, j0 = 2 * J, k0 = 2 * K;
-  const bool hi = i0 + 1 < F.ni, hj = j0 + 1 < F.nj, hk = k0 + 1 < F.nk;
+// ((r000 + r001) + (r010 + r011)) + ((r100 + r101) + (r110 + r111)); absent children drop out of it.  res(ib, jb, kb) is child
+// (2I + ib, 2J + jb, 2K + kb)'s residual; hi, hj, hk: the second child exists in that direction
+template <class R>
+__device__ __forceinline__ REAL mg_tree(bool hi, bool hj, bool hk, R res) {
   REAL t[2];
 #pragma unroll
   for (int jb = 0; jb < 2; jb++) {
@@ -83,18 +89,26 @@ __device__ __forceinline__ REAL mg_restrict_pt(const REAL* x, const REAL* b, con
 #pragma unroll
     for (int ib = 0; ib < 2; ib++) {
       if (ib && !hi) break;
-      s[ib] = mg_res_pt(x, b, F, i0 + ib, j0 + jb, k0);
-      if (hk) s[ib] = s[ib] + mg_res_pt(x, b, F, i0 + ib, j0 + jb, k0 + 1);
+      s[ib] = res(ib, jb, 0);
+      if (hk) s[ib] = s[ib] + res(ib, jb, 1);
     }
     t[jb] = hi ? s[0] + s[1] : s[0];
   }
   return hj ? t[0] + t[1] : t[0];
 }
 
+__device__ __forceinline__ REAL mg_restrict_pt(const REAL* x, const REAL* b, const MgLev& F, int I, int J, int K) {
+  const int i0 = 2 * I, j0 = 2 * J, k0 = 2 * K;
+  const bool hi = i0 + 1 < F.ni, hj = j0 + 1 < F.nj, hk = k0 + 1 < F.nk;
+  return mg_tree(hi, hj, hk, [&](int ib, int jb, int kb) { return mg_res_pt(x, b, F, i0 + ib, j0 + jb, k0 + kb); });
+}
+
 // u = x + R(alpha xc(parent)), alpha = R(1.8): one rounding per operation (no contraction: the build has -ffp-contract=off)
-__device__ __forceinline__ REAL mg_prolong_pt(const REAL* x, const REAL* xc, const MgLev& F, const MgLev& Cl, int I, int J, int K) {
+// (fo, co: global index of the local point (0, 0, 0) of the fine and the coarse array; the parent may then be a ghost cell)
+__device__ __forceinline__ REAL mg_prolong_pt(const REAL* x, const REAL* xc, const MgLev& F, const MgLev& Cl, int I, int J, int K, MgG fo = MgG{0, 0, 0},
+                                              MgG co = MgG{0, 0, 0}) {
   const REAL alpha = (REAL)1.8;
-  const REAL c = alpha * xc[mg_at(Cl, I >> 1, J >> 1, K >> 1)];
+  const REAL c = alpha * xc[mg_at(Cl, ((I + fo.i) >> 1) - co.i, ((J + fo.j) >> 1) - co.j, ((K + fo.k) >> 1) - co.k)];
   return x[mg_at(F, I, J, K)] + c;
 }
 
@@ -196,5 +210,71 @@ __global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ 
   {
     const REAL* x0 = lds + T.off[0] + T.len[0];
     mg_each(T.s[0], [&](int I, int J, int K) { xg[mg_at(T.gl, I, J, K)] = x0[mg_at(T.s[0], I, J, K)]; });
+  }
+}
+
+// ---- the distributed levels of a decomposed run ("Decomposed runs"): a brick's array of level l holds the points it owns,
+// in the fine brick's inner-range convention; MgLev's ni, nj, nk are the OWNED points, l and n0 the global ones.  o is the global index of the
+// first owned point, gn the level's global points per direction.  Ghost cells hold the neighbours' values after an exchange.
+struct MgDLev {
+  MgLev L;
+  MgG o;
+  int gni, gnj, gnk;
+};
+
+template <bool ZERO>
+__global__ void __launch_bounds__(256) mgd_smooth_k(const REAL* __restrict__ u, REAL* __restrict__ w, const REAL* __restrict__ b, MgDLev D, REAL omg) {
+  const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
+  if (K >= D.L.nk || I >= D.L.ni) return;
+  w[mg_at(D.L, I, J, K)] = mg_sweep_pt<ZERO>(u, b, D.L, I, J, K, omg, D.o);
+}
+
+// rt = the residual of the first owned layer on the rank-internal - faces (d = 0, 1, 2: I, J, K face; edges and corners belong to the
+// face of the lowest d among the internal ones).  grid: (64-wide blocks along the face's faster free direction, the slower one)
+__global__ void __launch_bounds__(64) mgd_resface_k(REAL* __restrict__ rt, const REAL* __restrict__ x, const REAL* __restrict__ b, MgDLev D, int d,
+                                                    int mi, int mj) {
+  const int a = blockIdx.x * 64 + threadIdx.x, c = blockIdx.y;
+  int I, J, K;
+  if (d == 0) I = 0, K = a, J = c;
+  else if (d == 1) J = 0, K = a, I = c;
+  else K = 0, I = a, J = c;
+  if (I >= D.L.ni || J >= D.L.nj || K >= D.L.nk) return;
+  if ((d >= 1 && mi && I == 0) || (d == 2 && mj && J == 0)) return;  // written by the I (J) face launch
+  rt[mg_at(D.L, I, J, K)] = mg_res_pt(x, b, D.L, I, J, K, D.o);
+}
+
+// bc (owned coarse points) = the children's residual tree; owned children computed here, children on the + neighbours (the brick's
+// ghost layer) read from rt after its exchange.  C.L may be a dense block (no shell): the gathered level's send buffer.
+__global__ void __launch_bounds__(256) mgd_restrict_k(REAL* __restrict__ bc, const REAL* __restrict__ x, const REAL* __restrict__ b, const REAL* __restrict__ rt,
+                                                      MgDLev F, MgDLev C) {
+  const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
+  if (K >= C.L.nk || I >= C.L.ni) return;
+  // global first child, then local (fine array) index
+  const int gi = 2 * (I + C.o.i), gj = 2 * (J + C.o.j), gk = 2 * (K + C.o.k);
+  const bool hi = gi + 1 < F.gni, hj = gj + 1 < F.gnj, hk = gk + 1 < F.gnk;
+  const int li = gi - F.o.i, lj = gj - F.o.j, lk = gk - F.o.k;
+  bc[mg_at(C.L, I, J, K)] = mg_tree(hi, hj, hk, [&](int ib, int jb, int kb) {
+    const int ci = li + ib, cj = lj + jb, ck = lk + kb;
+    if (ci < F.L.ni && cj < F.L.nj && ck < F.L.nk) return mg_res_pt(x, b, F.L, ci, cj, ck, F.o);
+    return rt[mg_at(F.L, ci, cj, ck)];
+  });
+}
+
+// u = x + R(alpha xc(parent)) on the owned points (u may be x); the parent is a ghost cell of xc where it lies on a - neighbour, or a point
+// of the gathered global array (C.o = 0)
+__global__ void __launch_bounds__(256) mgd_prolong_k(REAL* u, const REAL* x, const REAL* __restrict__ xc, MgDLev F, MgDLev C) {
+  const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
+  if (K >= F.L.nk || I >= F.L.ni) return;
+  u[mg_at(F.L, I, J, K)] = mg_prolong_pt(x, xc, F.L, C.L, I, J, K, F.o, C.o);
+}
+
+// one rank's dense block (ni, nj, nk; K fastest) into the gathered global array at global offset o: an exact copy
+__global__ void __launch_bounds__(256) mgd_unpack_k(REAL* __restrict__ X, const REAL* __restrict__ blk, MgLev G, MgG o, int ni, int nj, int nk) {
+  const long long n = (long long)ni * nj * nk;
+  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n; q += (long long)gridDim.x * 256) {
+    const int K = (int)(q % nk);
+    const long long r = q / nk;
+    const int I = (int)(r % ni), J = (int)(r / ni);
+    X[mg_at(G, I + o.i, J + o.j, K + o.k)] = blk[q];
   }
 }

@@ -1693,3 +1693,87 @@ int czhip_mg_apply_async(cz_mg* h, CZ_REAL* z, const CZ_REAL* r, CZ_REAL omg) {
   return 1;
 }
 }  // extern "C"
+
+// ---- the distributed levels (cz_internal.h MgdLevel)
+namespace {
+bool mgd_lev(MgDLev& D, const czhip_internal::MgdLevel& M) {
+  MgLev& L = D.L;
+  if (M.dense) {
+    L.nip = M.sz[0], L.nkp = M.sz[2], L.i0 = L.j0 = L.k0 = 0;
+    L.ni = M.sz[0], L.nj = M.sz[1], L.nk = M.sz[2];
+  } else {
+    const Box b = make_box(M.sz, M.idx, MG_GUIDE);
+    if (b.empty) return false;
+    L.nip = b.nip, L.nkp = b.nkp, L.i0 = b.ii0, L.j0 = b.jj0, L.k0 = b.kk0;
+    L.ni = b.ii1 - b.ii0 + 1, L.nj = b.jj1 - b.jj0 + 1, L.nk = b.kk1 - b.kk0 + 1;
+  }
+  L.l = M.level, L.n0i = M.n0[0], L.n0j = M.n0[1], L.n0k = M.n0[2];
+  D.o = MgG{M.o[0], M.o[1], M.o[2]};
+  D.gni = M.gn[0], D.gnj = M.gn[1], D.gnk = M.gn[2];
+  const int n[3] = {L.ni, L.nj, L.nk};
+  for (int d = 0; d < 3; d++)
+    if (M.o[d] < 0 || n[d] < 0 || M.o[d] + n[d] > M.gn[d]) return false;
+  return M.level >= 0 && M.level < MG_MAXLEV - 1;
+}
+bool mgd_none(const MgDLev& D) { return D.L.ni < 1 || D.L.nj < 1 || D.L.nk < 1; }
+}  // namespace
+
+namespace czhip_internal {
+int mgd_smooth_async(const REAL* u, REAL* w, const REAL* b, const MgdLevel& M, REAL omg) {
+  MgDLev D;
+  if (!w || !b || u == w || !mgd_lev(D, M) || M.dense) return 0;
+  if (mgd_none(D)) return 1;
+  ScopedTimer tm(LBL_MG_SMOOTH);
+  if (u) hipLaunchKernelGGL((mgd_smooth_k<false>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, u, w, b, D, omg);
+  else hipLaunchKernelGGL((mgd_smooth_k<true>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, w, w, b, D, omg);
+  HIP_CHECK(hipGetLastError());
+  return 1;
+}
+
+int mgd_resface_async(REAL* rt, const REAL* x, const REAL* b, const MgdLevel& M, const int* minus) {
+  MgDLev D;
+  if (!rt || !x || !b || rt == x || !mgd_lev(D, M) || M.dense) return 0;
+  if (mgd_none(D)) return 1;
+  ScopedTimer tm(LBL_MG_RESTRICT);
+  for (int d = 0; d < 3; d++) {
+    if (!minus[d]) continue;
+    const int fast = d == 2 ? D.L.ni : D.L.nk, slow = d == 0 ? D.L.nj : d == 1 ? D.L.ni : D.L.nj;
+    hipLaunchKernelGGL(mgd_resface_k, dim3((unsigned)((fast + 63) / 64), (unsigned)slow), dim3(64), 0, ctx.stream, rt, x, b, D, d, minus[0], minus[1]);
+    HIP_CHECK(hipGetLastError());
+  }
+  return 1;
+}
+
+int mgd_restrict_async(REAL* bc, const MgdLevel& MC, const REAL* x, const REAL* b, const REAL* rt, const MgdLevel& MF) {
+  MgDLev F, C;
+  if (!bc || !x || !b || !rt || bc == x || bc == b || !mgd_lev(F, MF) || !mgd_lev(C, MC) || MF.dense || MC.level != MF.level + 1) return 0;
+  if (mgd_none(C)) return 1;
+  ScopedTimer tm(LBL_MG_RESTRICT);
+  hipLaunchKernelGGL(mgd_restrict_k, mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C);
+  HIP_CHECK(hipGetLastError());
+  return 1;
+}
+
+int mgd_prolong_async(REAL* u, const REAL* x, const REAL* xc, const MgdLevel& MC, const MgdLevel& MF) {
+  MgDLev F, C;
+  if (!u || !x || !xc || u == xc || !mgd_lev(F, MF) || !mgd_lev(C, MC) || MF.dense || MC.dense || MC.level != MF.level + 1) return 0;
+  if (mgd_none(F)) return 1;
+  ScopedTimer tm(LBL_MG_PROLONG);
+  hipLaunchKernelGGL(mgd_prolong_k, mg_grid(F.L), dim3(64, 4), 0, ctx.stream, u, x, xc, F, C);
+  HIP_CHECK(hipGetLastError());
+  return 1;
+}
+
+int mgd_unpack_async(REAL* X, const MgdLevel& MG, const REAL* blk, const int* o, const int* cnt) {
+  MgDLev G;
+  if (!X || !blk || !mgd_lev(G, MG) || MG.dense) return 0;
+  for (int d = 0; d < 3; d++)
+    if (o[d] < 0 || cnt[d] < 0 || o[d] + cnt[d] > MG.gn[d]) return 0;
+  const long long n = (long long)cnt[0] * cnt[1] * cnt[2];
+  if (n == 0) return 1;
+  hipLaunchKernelGGL(mgd_unpack_k, dim3((unsigned)std::min<long long>((n + 255) / 256, 1024)), dim3(256), 0, ctx.stream, X, blk, G.L,
+                     MgG{o[0], o[1], o[2]}, cnt[0], cnt[1], cnt[2]);
+  HIP_CHECK(hipGetLastError());
+  return 1;
+}
+}  // namespace czhip_internal

@@ -136,3 +136,46 @@ def pair_plan(idx, nID):
 def sub_first_sweep_range(box, idx1):
     """first-sweep range of a sub-box of the brick: the box grown by one layer, inside the brick's own first-sweep range."""
     return [max(box[f] - 1, idx1[f]) if f % 2 == 0 else min(box[f] + 1, idx1[f]) for f in range(6)]
+
+
+# ---- the distributed V-cycle of pcg ... mg (cz_mg_dist.cpp, DESIGN.md §5.10 "Decomposed runs")
+MG_GATHER_DEFAULT = 32768  # CZ_MG_GATHER unset
+
+
+def mg_own(h: int, m: int, level: int):
+    """comm_mg_own: a brick with the global 0-based level-0 points [h, h+m) along one direction owns that level's points
+    [ceil(h / 2^level), ceil((h+m) / 2^level)) -> (first, count)"""
+    s = 1 << level
+    a, b = -(-h // s), -(-(h + m) // s)
+    return a, b - a
+
+
+def mg_points(gsz, div, rank: int, prec: str = "f32"):
+    """one brick's global 0-based level-0 points per direction: (h[3], m[3])"""
+    d = decompose(gsz, div, div[0] * div[1] * div[2], rank, prec)
+    idx = inner_range(d["size"], d["nID"])
+    h = [d["head"][a] - 1 + idx[2 * a] - 2 for a in range(3)]
+    m = [idx[2 * a + 1] - idx[2 * a] + 1 for a in range(3)]
+    return h, m
+
+
+def mg_level_dims(gsz):
+    """global points per direction of every level (level 0 = the inner box; coarsest: largest extent <= 4)"""
+    dims = [tuple(int(v) - 2 for v in gsz)]
+    while max(dims[-1]) > 4:
+        dims.append(tuple((v + 1) // 2 for v in dims[-1]))
+    return dims
+
+
+def mg_gather_level(gsz, div, gather_points: int = MG_GATHER_DEFAULT, prec: str = "f32"):
+    """G: the first level >= 1 at which some brick owns no point in some direction or whose global points are <= gather_points, at the
+    latest the coarsest; 0 where level 0 is the coarsest"""
+    dims = mg_level_dims(gsz)
+    if len(dims) == 1:
+        return 0
+    pts = [mg_points(gsz, div, r, prec) for r in range(div[0] * div[1] * div[2])]
+    for lev in range(1, len(dims) - 1):
+        empty = any(mg_own(h[a], m[a], lev)[1] < 1 for h, m in pts for a in range(3))
+        if empty or dims[lev][0] * dims[lev][1] * dims[lev][2] <= gather_points:
+            return lev
+    return len(dims) - 1

@@ -35,6 +35,7 @@ class CZ:
         lib.cz_kernel_ms.restype = C.c_double
         lib.czhip_timing_read.argtypes = [C.c_char_p, C.POINTER(C.c_double)]
         lib.cz_info.argtypes = [C.c_void_p, C.c_int]
+        lib.cz_precondition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         if lib.czhip_init(int(device)) != 0:
             raise RuntimeError("czhip_init failed")
         self.h = lib.cz_create()
@@ -100,8 +101,16 @@ class CZ:
     def info(self) -> dict:
         """what a (multi-GPU) run decided (cz_info of include/cz_hip.h)"""
         keys = ("ranks", "fused_pass", "shell_slabs", "overlap", "lagged_reduce", "rccl_ranks", "comm_cus", "pass_kind", "exchange_depth", "buffers", "bicg_fused", "rb4_passes",
-                "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles")
+                "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges")
         return {k: self.lib.cz_info(self.h, i) for i, k in enumerate(keys)}
+
+    def precondition(self, r: np.ndarray) -> np.ndarray:
+        """z = M^-1 r of the set-up pcg ... mg on this rank's brick (dense padded fields as field()); collective in a decomposed run"""
+        r = np.ascontiguousarray(r, dtype=self.real)
+        z = np.zeros_like(r)
+        if self.lib.cz_precondition(self.h, r.ctypes.data_as(C.c_void_p), z.ctypes.data_as(C.c_void_p)) != 1:
+            raise RuntimeError("cz_precondition: no preconditioner set up")
+        return z
 
     def timing(self, enable: bool):
         self.lib.czhip_timing(1 if enable else 0)

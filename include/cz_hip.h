@@ -399,8 +399,13 @@ double cz_last_solve_seconds(const cz_handle*);
  * (a pair of sweeps, or an rb4 pass of two iterations) and were therefore re-run alone from the pass's untouched input to give the converged iterate;
  * 13 iterations of the last PCG solve whose search direction was made inside the SpMV pass (czhip_cg_dir_ax_async); 14 three-sweep
  * Jacobi passes of the last Jacobi solve (czhip_jacobi3_async); 15 levels of the multigrid hierarchy (pcg ... mg; 0 otherwise); 16 V-cycles
- * of the last PCG solve with mg. */
+ * of the last PCG solve with mg; 17 the gather level G of a decomposed pcg ... mg (levels >= G run on every rank from an all-gathered copy;
+ * 0 on a single domain or where level 0 is the coarsest); 18 halo exchanges and all-gathers of the last V-cycle of a decomposed pcg ... mg. */
 int cz_info(const cz_handle*, int what);
+/* pcg ... mg: z = M^-1 r, the set-up solver's V-cycle applied once to host fields of the calling rank's brick in the cz_field layout (the
+ * ghost cells of r are not read).  Collective: every rank of a decomposed run calls it.  Returns 1, or 0 where there is no such
+ * preconditioner (another solver, or not set up). */
+int cz_precondition(cz_handle*, const CZ_REAL* r_dense, CZ_REAL* z_dense);
 double cz_kernel_ms(const cz_handle*, const char* label); /* HIP-event time of a labelled section, ms (avg per launch) */
 
 void cz_set_debug(cz_handle*, int mode);      /* main.cpp:38-42: 1 = run the analytic-error epilogue in cz_evaluate */
