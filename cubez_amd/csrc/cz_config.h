@@ -61,7 +61,7 @@ inline const CzVarDef* cz_var_defs() {
       {"CZ_COMM_ONE_COMM", "0", "one RCCL communicator for halos and all-reduces instead of two"},
       {"CZHIP_TUNING", "", "stencil_k shape \"threads,m,tj,pf\""},
       {"CZHIP_T2", "", "two-stage pass \"enable[,threads,2,tj]\" (0 = chosen per launch by pair_tj_model)"},
-      {"CZHIP_T2_MAP", "1", "two-stage pass: balanced (segment, chunk) table per XCD where bands would idle"},
+      {"CZHIP_T2_MAP", "1", "multi-stage passes: balanced (segment, chunk) table per XCD where bands would idle and row bands of every k window (2: window-major, 0: whole-segment bands)"},
       {"CZHIP_T2_ROWS", "1", "vector kernels take rows whose length is no multiple of the vector width"},
       {"CZHIP_T2_KWIN", "", "two-stage pass: vectors per k window (0 = whole rows where they fit, -1 = chosen per launch)"},
       {"CZHIP_T2_PRE", "1", "two-stage pass on small grids: all operands of a chunk requested before its first plane step (jacobi2p_k<PRE>)"},

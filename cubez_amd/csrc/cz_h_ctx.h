@@ -26,7 +26,8 @@ struct Tuning {
   int jac3_medium = 1;                            // jac3_k FP32: the checked shorter division (mediumdiv) for divisors that passed (CZHIP_JAC3_MEDIUM)
   int unit_coef = 1;                              // the kernels' form for coefficients that are all exactly 1 (offdiag_sum<UNIT>; CZHIP_UNIT_COEF)
   int t2_pre = 1;                                 // two-stage pass on small grids: every operand of a chunk requested before its first step (jacobi2p_k<PRE>; CZHIP_T2_PRE)
-  int t2_map = 1;                                 // two-stage pass: equal shares of (segment, chunk) items per XCD (CZHIP_T2_MAP=0: whole-segment bands)
+  int t2_map = 1;                                 // multi-stage passes: equal shares of (segment, chunk) items per XCD where bands would idle, and row bands of
+                                                  // every k window (pair_xcd_map); 2: window-major, 0: whole-segment bands (CZHIP_T2_MAP, czhip_set_pair_map)
   int use_t2 = 1;                                 // driver may fuse pairs of Jacobi sweeps (single-domain runs)  // 1: residual finalised by the last workgroup of the sweep; 0: separate reduce(+check) launches
 };
 
@@ -66,7 +67,7 @@ struct Ctx {
   Tuning tune;
   std::map<std::vector<double>, REAL*> bc_tabs;  // key: ix, jx, dh, org0, org1
   struct PairMap { int* dev = nullptr; long long nblk = 0; };
-  std::map<long long, PairMap> pair_maps;        // workgroup id -> (segment, chunk) tables of the two-stage pass, key nseg << 32 | nchunk
+  std::map<long long, PairMap> pair_maps;        // workgroup id -> (segment, chunk) tables of the two-stage pass, key nwin << 48 | nsegw << 24 | nchunk
   std::map<unsigned long long, bool> medium_div;  // divisor bits -> did mediumdiv give the bits of n / d for every numerator (jac3_medium)
   std::set<const void*> lds_allowed;             // kernels whose dynamic LDS limit is raised on this context's device (allow_dynamic_lds)
   int num_cu = 256;

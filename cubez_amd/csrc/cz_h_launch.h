@@ -105,7 +105,7 @@ void reduce_partials(int n, double* dst, int accumulate, const int* skip) {
 // the un-overlapped prologue); each XCD serves its band of segments with num_cu/8 * wg_per_cu resident workgroups, so a launch takes
 // ceil(band * nchunk / slots) rounds of that (tools/pair_lab sweeps, profiles/r02/pair_lab_sweep_*.txt: the model ranks the measured
 // times of both shapes and both precisions).  Returns the cost in units of plane steps; *tj_out the best chunk length.
-inline double pair_tj_model(int nseg, int nplanes, int wg_per_cu, bool balanced, int* tj_out, double extra = 3.5) {
+inline double pair_tj_model(int nseg, int nplanes, int wg_per_cu, bool balanced, int* tj_out, double extra = 3.5, bool long_chunks = false) {
   // (decomposed runs: cu_reserved CUs of every XCD stay free for the exchange stream; reserve_comm_cus)
   const int slots = std::max(1, ctx.num_cu / 8 - ctx.cu_reserved) * wg_per_cu;
   double best = 1e300;
@@ -113,11 +113,15 @@ inline double pair_tj_model(int nseg, int nplanes, int wg_per_cu, bool balanced,
   // (chunks from two planes up: on small grids, where one round of short chunks holds every item, the chain of plane steps of a workgroup is
   // the whole launch -- 64^3 FP64: 16 us per pass with chunks of 2 planes against 32 us with 12, the floor of rounds 1-2;
   // profiles/r03/small_grids_chunk_length.txt)
-  for (int tj = std::min(2, nplanes); tj <= std::min(nplanes, 128); tj++) {
+  // (chunks of more than 128 planes only with long_chunks, and only where the whole launch is then ONE round: jac3_k at 512^3 FP32 takes
+  // 3 chunks of 171 planes, 240 workgroups at once, against 16 chunks of 32 in five rounds -- fewer re-read halo planes and redundant
+  // plane steps per point; profiles/r10/pass_planner.txt.  Plans of several rounds keep the cap the other passes were tuned with.)
+  for (int tj = std::min(2, nplanes); tj <= nplanes; tj++) {
     const int nchunk = (nplanes + tj - 1) / tj;
     if (tj > 2 && (nplanes + tj - 2) / (tj - 1) == nchunk) continue;  // a shorter chunk gives the same count: not a candidate
     // items of the busiest XCD: a band of whole segments, or an eighth of all items with the balanced table (pair_xcd_map)
     const long long items = balanced ? ((long long)nseg * nchunk + 7) / 8 : (long long)((nseg + 7) / 8) * nchunk;
+    if (tj > 128 && !(long_chunks && items <= slots)) continue;
     const double cost = (double)((items + slots - 1) / slots) * (tj + extra);
     if (cost < best) best = cost, best_tj = tj;
   }
@@ -133,13 +137,23 @@ inline double pair_tj_model(int nseg, int nplanes, int wg_per_cu, bool balanced,
 // Measured (profiles/r02/ab_xcd_map.txt): +6 % at 256^3 and 384^3, where the bands are 3 against 2 segments; -1 % at 512^3 and -4 % at
 // 640^3, where an XCD that finishes early only hands its share of the HBM bandwidth to the others and shared segments cost L2 hits.  So
 // the table is used where the bands would leave more than a tenth of the XCD slots idle (pair_use_map).
-inline const int* pair_xcd_map(int nseg, int nchunk, long long* nblk_out) {
-  const long long key = ((long long)nseg << 32) | (unsigned)nchunk;
+//
+// ROW BANDS (k-windowed passes, nwin > 1; pair_row_bands).  Segment ids are window-major (Geom2::nsegw), so a run of ids puts ONE window of a
+// set of rows on an XCD and the neighbouring windows of the same rows on others -- and those read the same lines: a window row is not a whole
+// number of 128-byte lines, so the lines at every window boundary were fetched into two L2s.  Here the items are taken in (row segment,
+// window, chunk) order before the cut: an XCD's run is every window of a band of row segments, walked chunk by chunk and inside a chunk by
+// (row segment, window), so that the windows of the same rows start in the same round and share boundary lines and halo rows in one L2.
+// The ids in the table stay window-major; nwin = 1 is the table above.  Cached per (nsegw, nwin, nchunk).
+inline const int* pair_xcd_map(int nsegw, int nchunk, long long* nblk_out, int nwin = 1) {
+  const long long key = ((long long)nwin << 48) | ((long long)nsegw << 24) | (unsigned)nchunk;
   auto it = ctx.pair_maps.find(key);
   if (it == ctx.pair_maps.end()) {
-    const long long T = (long long)nseg * nchunk;
-    std::vector<std::vector<std::pair<int, int>>> own(8);  // (chunk, segment) for the sort
-    for (long long e = 0; e < T; e++) own[(size_t)(e * 8 / T)].push_back({(int)(e % nchunk), (int)(e / nchunk)});
+    const long long nseg = (long long)nsegw * nwin, T = nseg * nchunk;
+    std::vector<std::vector<long long>> own(8);  // chunk << 42 | row segment << 21 | window, for the sort
+    for (long long e = 0; e < T; e++) {
+      const long long q = e / nchunk;  // row segment * nwin + window
+      own[(size_t)(e * 8 / T)].push_back((e % nchunk) << 42 | (q / nwin) << 21 | (q % nwin));
+    }
     size_t most = 0;
     for (auto& v : own) {
       std::sort(v.begin(), v.end());
@@ -149,8 +163,9 @@ inline const int* pair_xcd_map(int nseg, int nchunk, long long* nblk_out) {
     for (size_t r = 0; r < most; r++)
       for (int x = 0; x < 8; x++) {
         const bool has = r < own[x].size();
-        tab[2 * (8 * r + x)] = has ? own[x][r].second : nseg;
-        tab[2 * (8 * r + x) + 1] = has ? own[x][r].first : 0;
+        const long long it3 = has ? own[x][r] : 0;
+        tab[2 * (8 * r + x)] = has ? (int)((it3 & 0x1fffff) * nsegw + ((it3 >> 21) & 0x1fffff)) : (int)nseg;
+        tab[2 * (8 * r + x) + 1] = (int)(it3 >> 42);
       }
     Ctx::PairMap pm;
     pm.nblk = (long long)(8 * most);
@@ -165,6 +180,9 @@ inline const int* pair_xcd_map(int nseg, int nchunk, long long* nblk_out) {
 // (fewer than eight segments -- small planes, boxes long in j -- leave whole XCDs without a band: 40 x 2000 x 40 ran on ONE XCD, at 0.6 of the
 // single-sweep rate, until round 3; profiles/r03/non_cubic_boxes.txt)
 inline bool pair_use_map(int nseg) { return ctx.tune.t2_map && 10 * nseg < 9 * 8 * ((nseg + 7) / 8); }
+// k-windowed passes take the row-band table whatever the balance of the bands (CZHIP_T2_MAP / t2_map: 1 = this, the default; 2 = the
+// window-major order before it, where bands idle, for A/B measurements; 0 = whole-segment bands everywhere; profiles/r10/pass_planner.txt)
+inline bool pair_row_bands(const Geom2& g) { return ctx.tune.t2_map == 1 && g.nwin > 1; }
 
 // k windows of the two-stage pass (Geom2).  A window of KT vectors costs a workgroup (KT + 2) / KT in loads and first-stage work and leaves it
 // rows of R = KT + 2 vectors, i.e. a useful share of (LV - 2R) / LV of its LV = TB MV vectors.  That product peaks near KT = sqrt(LV) = 45 --
@@ -192,6 +210,7 @@ struct PassPlan {
   int wg_per_cu = 0;      // resident workgroups per CU for the chunk model; 0: as many as LDS and threads allow
   double extra = 3.5;     // plane steps a chunk costs beyond its own (pair_tj_model)
   int tj = 0;             // planes per chunk; 0: the model's choice
+  bool long_chunks = false;  // the model may take chunks of more than 128 planes where that makes the launch one round (pair_tj_model)
   int nres = 2;           // residual slots per workgroup in ctx.partials
   int par = 0, zero_u = 0;
   // filled in by plan_pass
@@ -237,7 +256,7 @@ bool plan_pass(PassPlan& p, const Box& b, const Box& ba, LdsBytes lds_bytes, dou
   int tj = p.tj;
   if (tj <= 0 || model_cost) {
     int best = 0;
-    const double cost = pair_tj_model(g.nseg, nplanes, wg_per_cu, pair_use_map(g.nseg), &best, p.extra);
+    const double cost = pair_tj_model(g.nseg, nplanes, wg_per_cu, pair_row_bands(g) || pair_use_map(g.nseg), &best, p.extra, p.long_chunks);
     if (model_cost) *model_cost = cost * wg_per_cu * (double)(p.own + g.S);
     if (tj <= 0) tj = best;
   }
@@ -251,7 +270,8 @@ template <typename... P, typename... A>
 void launch_pass(void (*kernel)(P...), int label, PassPlan& p, const REAL* U, const REAL* B, REAL* W, const Coef& c, const int* skip, Fin2 fin,
                  const A&... extra) {
   long long nblk = 8LL * ((p.g.nseg + 7) / 8) * p.nchunk;
-  if (pair_use_map(p.g.nseg)) p.g.map = pair_xcd_map(p.g.nseg, p.nchunk, &nblk);
+  if (pair_row_bands(p.g)) p.g.map = pair_xcd_map(p.g.nsegw, p.nchunk, &nblk, p.g.nwin);
+  else if (pair_use_map(p.g.nseg)) p.g.map = pair_xcd_map(p.g.nseg, p.nchunk, &nblk);
   ensure_partials((size_t)p.nres * nblk);
   allow_dynamic_lds(kernel, 160 * 1024);
   fin.counter = ctx.counter;
@@ -459,7 +479,7 @@ bool launch_jac3(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box
   p.TB = TB, p.own = TB, p.halo_rows = 4, p.max_R = TB / 8;  // at least half of the workgroup's vectors must be its own
   p.hv = VW == 4 ? 1 : 2;                                    // three stages reach three elements beyond a window
   p.wg_per_cu = 1, p.extra = 5.5;                            // (four redundant planes and a longer prologue per chunk)
-  p.tj = ctx.tune.jac3_tj, p.nres = 3;
+  p.tj = ctx.tune.jac3_tj, p.nres = 3, p.long_chunks = true;
   const int Rfull = (b.nkp + VW - 1) / VW;
   const int want = ctx.tune.jac3_kwin > 0 ? ctx.tune.jac3_kwin : jac3_window(Rfull);
   if (Rfull > want + 2 * p.hv) p.kwin = want;

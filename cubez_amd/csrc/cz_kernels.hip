@@ -589,6 +589,16 @@ int czhip_set_unit_coef(int enable) {
   return before;
 }
 
+// workgroup order of the multi-stage passes (pair_xcd_map, cz_h_launch.h): 0 = whole-segment bands per XCD, 1 = the balanced table where
+// bands would idle and row bands of every k window (default), 2 = the balanced table where bands would idle, window-major; negative: keep.
+// Returns the setting that was in force.  Same bits in every order.
+int czhip_set_pair_map(int order) {
+  ensure_init();
+  const int before = ctx.tune.t2_map;
+  if (order >= 0) ctx.tune.t2_map = order;
+  return before;
+}
+
 // k windows of the two-stage pass (Geom2, cz_k_pair.h): vectors per window; 0 = whole rows wherever they fit, -1 = the launcher's rule
 // (pair_whole_rows_ok), <= -2 = keep.  Returns the setting that was in force.  Same bits whatever the windows.
 int czhip_set_pair_window(int vectors) {

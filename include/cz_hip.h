@@ -301,6 +301,10 @@ int czhip_use_t2(void);
  * extent, and so does the pass since round 4): vectors (16 bytes) per window; 0 = whole rows wherever they fit, -1 = chosen per launch (default),
  * <= -2 = keep.  Returns the previous setting.  Results do not depend on it. */
 int czhip_set_pair_window(int vectors);
+/* Order in which the workgroups of the multi-stage passes (two-sweep, two-iteration red-black and three-sweep) take their (segment, chunk)
+ * items, by XCD: 0 = whole-segment bands, 1 = equal shares where bands would idle and row bands of every k window (default), 2 = equal shares
+ * where bands would idle, window-major (CZHIP_T2_MAP); negative = keep.  Returns the previous setting.  Results do not depend on it. */
+int czhip_set_pair_map(int order);
 /* Small grids (every workgroup of a pass resident at once): the pass requests all operands of a chunk before its first plane step instead of one
  * plane ahead; 1 = on (default), 0 = off, negative = keep.  Returns the previous setting.  Results do not depend on it. */
 int czhip_set_pair_preload(int enable);
