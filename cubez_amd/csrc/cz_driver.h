@@ -203,7 +203,6 @@ class CZ {
 };
 
 // the distributed V-cycle of pcg ... mg (cz_mg_dist.cpp, DESIGN.md §5.10 "Decomposed runs")
-constexpr int MG_DIST_MAXLEV = 32;
 // nullptr on a single domain; gather_points: CZ_MG_GATHER, tail: CZ_MG_TAIL
 MgDist* mgd_create(const CZ& cz, CommCtx* comm0, int gather_points, bool tail);
 void mgd_destroy(MgDist*);

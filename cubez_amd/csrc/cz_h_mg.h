@@ -1,0 +1,305 @@
+// cz_h_mg.h -- part of cz_kernels.hip (ONE translation unit per precision; this file is included at its end, at file scope, and is
+// not a stand-alone header): host side of the multigrid V-cycle preconditioner of PCG: the launches of the level kernels
+// (cz_k_mg.h), the hierarchy handle cz_mg and its operations for the order of a cycle (cz_mg_cycle.h).
+using czhip_internal::MgdLevel;
+
+namespace {
+// the device description of a level from the host one; false if it does not describe level M.level of a grid of M.n0 points
+bool mg_lev(MgDLev& D, const MgdLevel& M) {
+  MgLev& L = D.L;
+  if (M.dense) {
+    L.nip = M.sz[0], L.nkp = M.sz[2], L.i0 = L.j0 = L.k0 = 0;
+    L.ni = M.sz[0], L.nj = M.sz[1], L.nk = M.sz[2];
+  } else {
+    const Box b = make_box(M.sz, M.idx, M.g);
+    if (b.empty) return false;
+    L.nip = b.nip, L.nkp = b.nkp, L.i0 = b.ii0, L.j0 = b.jj0, L.k0 = b.kk0;
+    L.ni = b.ii1 - b.ii0 + 1, L.nj = b.jj1 - b.jj0 + 1, L.nk = b.kk1 - b.kk0 + 1;
+  }
+  if (M.level < 0 || M.level >= MG_MAXLEV - 1) return false;
+  L.l = M.level, L.n0i = M.n0[0], L.n0j = M.n0[1], L.n0k = M.n0[2];
+  D.o = MgG{M.o[0], M.o[1], M.o[2]};
+  D.gni = M.gn[0], D.gnj = M.gn[1], D.gnk = M.gn[2];
+  const int n[3] = {L.ni, L.nj, L.nk};
+  const long long s = 1LL << M.level;
+  for (int d = 0; d < 3; d++)
+    if (M.n0[d] < 1 || (M.n0[d] + s - 1) / s != M.gn[d] || M.o[d] < 0 || n[d] < 0 || M.o[d] + n[d] > M.gn[d]) return false;
+  return true;
+}
+bool mg_none(const MgDLev& D) { return D.L.ni < 1 || D.L.nj < 1 || D.L.nk < 1; }
+bool mg_whole(const MgDLev& D) { return !(D.o.i | D.o.j | D.o.k) && D.L.ni == D.gni && D.L.nj == D.gnj && D.L.nk == D.gnk; }
+bool mg_coarse_of(const MgdLevel& F, const MgdLevel& C) { return C.level == F.level + 1 && std::equal(F.n0, F.n0 + 3, C.n0); }
+
+// a whole level in one array: the inner box of (sz, idx, g) is the level
+MgdLevel mg_array_level(const int* sz, const int* idx, int g, int level, const int* n0) {
+  MgdLevel M = MgdLevel();
+  std::copy(sz, sz + 3, M.sz);
+  std::copy(idx, idx + 6, M.idx);
+  M.g = g, M.level = level;
+  for (int d = 0; d < 3; d++) M.n0[d] = n0[d], M.gn[d] = idx[2 * d + 1] - idx[2 * d] + 1;
+  return M;
+}
+
+// the LDS layout of the levels from fine (level l) down to the coarsest: one zero shell per array, b, x, t per level
+bool mg_tail_plan(MgTail& T, const MgLev& fine, REAL omg) {
+  T = MgTail();
+  T.gl = fine, T.omg = omg;
+  const int n[3] = {fine.ni, fine.nj, fine.nk};
+  int dims[MG_TAIL_MAXLEV][3];
+  T.nlev = mg_level_dims(n, dims, MG_TAIL_MAXLEV);
+  if (!T.nlev) return false;
+  for (int m = 0; m < T.nlev; m++) {
+    MgLev& s = T.s[m] = fine;
+    s.ni = dims[m][0], s.nj = dims[m][1], s.nk = dims[m][2], s.l = fine.l + m;
+    s.nip = s.ni + 2, s.nkp = s.nk + 2, s.i0 = s.j0 = s.k0 = 1;
+    T.len[m] = (s.ni + 2) * (s.nj + 2) * (s.nk + 2);
+    T.off[m] = T.total;
+    T.total += 3 * T.len[m];
+    if ((long long)T.total * (long long)sizeof(REAL) > 160 * 1024) return false;
+  }
+  return true;
+}
+
+void mg_tail_launch(REAL* x, const REAL* b, const MgTail& T) {
+  ScopedTimer tm(LBL_MG_TAIL);
+  const int bytes = T.total * (int)sizeof(REAL);
+  if (bytes > 64 * 1024) allow_dynamic_lds(&mg_tail_k, 160 * 1024);
+  hipLaunchKernelGGL(mg_tail_k, dim3(1), dim3(MG_TAIL_THREADS), bytes, ctx.stream, x, b, T);
+  HIP_CHECK(hipGetLastError());
+}
+
+dim3 mg_grid(const MgLev& L) { return dim3((unsigned)((L.nk + 63) / 64), (unsigned)((L.ni + 3) / 4), (unsigned)L.nj); }
+}  // namespace
+
+// ---- the launches of the level kernels: 0 = refused (nothing launched)
+namespace czhip_internal {
+int mg_smooth_async(const REAL* u, REAL* w, const REAL* b, const MgdLevel& M, REAL omg) {
+  MgDLev D;
+  if (!w || !b || u == w || !mg_lev(D, M) || M.dense) return 0;
+  if (mg_none(D)) return 1;
+  ScopedTimer tm(LBL_MG_SMOOTH);
+  if (u) hipLaunchKernelGGL((mg_smooth_k<false>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, u, w, b, D, omg);
+  else hipLaunchKernelGGL((mg_smooth_k<true>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, w, w, b, D, omg);
+  HIP_CHECK(hipGetLastError());
+  return 1;
+}
+
+int mgd_resface_async(REAL* rt, const REAL* x, const REAL* b, const MgdLevel& M, const int* minus) {
+  MgDLev D;
+  if (!rt || !x || !b || rt == x || !mg_lev(D, M) || M.dense) return 0;
+  if (mg_none(D)) return 1;
+  ScopedTimer tm(LBL_MG_RESTRICT);
+  for (int d = 0; d < 3; d++) {
+    if (!minus[d]) continue;
+    const int fast = d == 2 ? D.L.ni : D.L.nk, slow = d == 0 ? D.L.nj : d == 1 ? D.L.ni : D.L.nj;
+    hipLaunchKernelGGL(mgd_resface_k, dim3((unsigned)((fast + 63) / 64), (unsigned)slow), dim3(64), 0, ctx.stream, rt, x, b, D, d, minus[0], minus[1]);
+    HIP_CHECK(hipGetLastError());
+  }
+  return 1;
+}
+
+// rt = nullptr: every child is a point of F's own array, which then is the whole level
+int mg_restrict_async(REAL* bc, const MgdLevel& MC, const REAL* x, const REAL* b, const REAL* rt, const MgdLevel& MF) {
+  MgDLev F, C;
+  if (!bc || !x || !b || bc == x || bc == b || !mg_lev(F, MF) || !mg_lev(C, MC) || MF.dense || !mg_coarse_of(MF, MC) || (!rt && !(mg_whole(F) && mg_whole(C)))) return 0;
+  if (mg_none(C)) return 1;
+  ScopedTimer tm(LBL_MG_RESTRICT);
+  if (rt) hipLaunchKernelGGL((mg_restrict_k<true>), mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C);
+  else hipLaunchKernelGGL((mg_restrict_k<false>), mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C);
+  HIP_CHECK(hipGetLastError());
+  return 1;
+}
+
+int mg_prolong_async(REAL* u, const REAL* x, const REAL* xc, const MgdLevel& MC, const MgdLevel& MF) {
+  MgDLev F, C;
+  if (!u || !x || !xc || u == xc || !mg_lev(F, MF) || !mg_lev(C, MC) || MF.dense || MC.dense || !mg_coarse_of(MF, MC)) return 0;
+  if (mg_none(F)) return 1;
+  ScopedTimer tm(LBL_MG_PROLONG);
+  hipLaunchKernelGGL(mg_prolong_k, mg_grid(F.L), dim3(64, 4), 0, ctx.stream, u, x, xc, F, C);
+  HIP_CHECK(hipGetLastError());
+  return 1;
+}
+
+int mgd_unpack_async(REAL* X, const MgdLevel& MG, const REAL* blk, const int* o, const int* cnt) {
+  MgDLev G;
+  if (!X || !blk || !mg_lev(G, MG) || MG.dense) return 0;
+  for (int d = 0; d < 3; d++)
+    if (o[d] < 0 || cnt[d] < 0 || o[d] + cnt[d] > MG.gn[d]) return 0;
+  const long long n = (long long)cnt[0] * cnt[1] * cnt[2];
+  if (n == 0) return 1;
+  hipLaunchKernelGGL(mgd_unpack_k, dim3((unsigned)std::min<long long>((n + 255) / 256, 1024)), dim3(256), 0, ctx.stream, X, blk, G.L,
+                     MgG{o[0], o[1], o[2]}, cnt[0], cnt[1], cnt[2]);
+  HIP_CHECK(hipGetLastError());
+  return 1;
+}
+}  // namespace czhip_internal
+
+extern "C" {
+int czhip_mg_smooth_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, int g, int level, const int* n0, CZ_REAL omg) {
+  ensure_init();
+  return czhip_internal::mg_smooth_async(u, w, b, mg_array_level(sz, idx, g, level, n0), omg);
+}
+
+int czhip_mg_restrict_async(CZ_REAL* bc, const int* szc, const int* idxc, const CZ_REAL* x, const CZ_REAL* b, const int* sz, const int* idx, int g, int level,
+                            const int* n0) {
+  ensure_init();
+  return czhip_internal::mg_restrict_async(bc, mg_array_level(szc, idxc, g, level + 1, n0), x, b, nullptr, mg_array_level(sz, idx, g, level, n0));
+}
+
+int czhip_mg_prolong_async(CZ_REAL* u, const CZ_REAL* x, const CZ_REAL* xc, const int* szc, const int* idxc, const int* sz, const int* idx, int g, int level,
+                           const int* n0) {
+  ensure_init();
+  return czhip_internal::mg_prolong_async(u, x, xc, mg_array_level(szc, idxc, g, level + 1, n0), mg_array_level(sz, idx, g, level, n0));
+}
+
+int czhip_mg_tail_async(CZ_REAL* x, const CZ_REAL* b, const int* sz, const int* idx, int g, int level, const int* n0, CZ_REAL omg) {
+  ensure_init();
+  MgDLev D;
+  MgTail T;
+  if (!x || !b || x == b || !mg_lev(D, mg_array_level(sz, idx, g, level, n0)) || !mg_tail_plan(T, D.L, omg)) return 0;
+  mg_tail_launch(x, b, T);
+  return 1;
+}
+}  // extern "C"
+
+// ---- the hierarchy
+namespace czhip_internal {
+cz_mg* mg_create(const int* n0, int l0, bool tail, const int* sz0, const int* idx0) {
+  cz_mg* h = new cz_mg();
+  int dims[MG_MAXLEV][3];
+  h->first = l0, h->nlev = mg_level_dims(n0, dims, MG_MAXLEV - 1);
+  bool ok = std::min(n0[0], std::min(n0[1], n0[2])) >= 1 && l0 >= 0 && l0 < h->nlev;
+  for (int l = l0; ok && l < h->nlev; l++) {  // ceil(n / 2) points per direction, inner box 2 .. n + 1 inside zero faces at 1 and n + 2
+    const int* n = dims[l];
+    const int sz[3] = {n[0] + 2, n[1] + 2, n[2] + 2}, idx[6] = {2, n[0] + 1, 2, n[1] + 1, 2, n[2] + 1};
+    h->lev[l] = l ? mg_array_level(sz, idx, MG_GUIDE, l, n0) : mg_array_level(sz0, idx0, MG_GUIDE, 0, n0);
+    MgDLev D;
+    ok = mg_lev(D, h->lev[l]);
+    if (ok && l) h->b[l] = czhip_alloc_s3d(sz), h->x[l] = czhip_alloc_s3d(sz), h->t[l] = czhip_alloc_s3d(sz);
+  }
+  if (!ok) {
+    czhip_mg_destroy(h);
+    return nullptr;
+  }
+  if (l0 == 0) {
+    h->fine_tmp = czhip_alloc_s3d(sz0);
+    HIP_CHECK(hipMalloc(&h->res, 4 * sizeof(double)));
+  }
+  // the tail starts at the first level >= 1 whose levels down to the coarsest fit one workgroup's LDS (tail off: none)
+  h->tail_from = h->nlev;
+  for (int l = std::max(l0, 1); tail && l < h->nlev; l++) {
+    MgDLev D;
+    MgTail T;
+    mg_lev(D, h->lev[l]);
+    if (mg_tail_plan(T, D.L, (REAL)1)) {
+      h->tail_from = l;
+      break;
+    }
+  }
+  return h;
+}
+}  // namespace czhip_internal
+
+extern "C" {
+cz_mg* czhip_mg_create(const int* sz, const int* idx, int g, const CZ_REAL* cf) {
+  ensure_init();
+  if (g != MG_GUIDE) return nullptr;  // (the coarse arrays and the temporary are S3D arrays: guide 2)
+  for (int c = 0; c < 6; c++)
+    if (cf[c] != (REAL)1) return nullptr;
+  if (cf[6] != (REAL)6) return nullptr;
+  const int n0[3] = {idx[1] - idx[0] + 1, idx[3] - idx[2] + 1, idx[5] - idx[4] + 1};
+  return czhip_internal::mg_create(n0, 0, CzConfig::from_env().on(CZV_MG_TAIL, true), sz, idx);
+}
+
+int czhip_mg_levels(const cz_mg* h) { return h ? h->nlev : 0; }
+
+void czhip_mg_destroy(cz_mg* h) {
+  if (!h) return;
+  czhip_sync();
+  for (int l = 0; l < MG_MAXLEV; l++)
+    for (REAL* a : {h->b[l], h->x[l], h->t[l]})
+      if (a) czhip_free(a);
+  if (h->fine_tmp) czhip_free(h->fine_tmp);
+  if (h->res) (void)hipFree(h->res);
+  delete h;
+}
+}  // extern "C"
+
+namespace {
+// level 0's pairs of sweeps with the unit coefficients, u -> w (u = nullptr: from zero): the fused pass, or where it is not taken two single
+// sweeps through o (an array other than w; it may be u) and a copy back to w
+void mg_fine_pair(cz_mg* h, const REAL* u, REAL* w, REAL* o, const REAL* b, REAL omg) {
+  const int* sz = h->lev[0].sz;
+  const int* idx = h->lev[0].idx;
+  REAL cf[7] = {1, 1, 1, 1, 1, 1, 6};
+  if (u ? czhip_jacobi2_async(u, w, b, sz, idx, nullptr, MG_GUIDE, cf, omg, h->res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr)
+        : czhip_jacobi2_from_zero_async(w, w, b, sz, idx, nullptr, MG_GUIDE, cf, omg, h->res))
+    return;
+  const size_t nbytes = (size_t)(sz[0] + 4) * (sz[1] + 4) * (sz[2] + 4) * sizeof(REAL);
+  if (!u) {
+    HIP_CHECK(hipMemsetAsync(o, 0, nbytes, ctx.stream));
+    u = o;
+  }
+  czhip_jacobi_async(u, w, b, sz, idx, MG_GUIDE, cf, omg, h->res, 0, nullptr);
+  czhip_jacobi_async(w, o, b, sz, idx, MG_GUIDE, cf, omg, h->res, 0, nullptr);
+  HIP_CHECK(hipMemcpyAsync(w, o, nbytes, hipMemcpyDeviceToDevice, ctx.stream));
+}
+
+// the operations of mg_walk on one domain.  Levels >= 1 keep b, x and a temporary t of their own; level 0's b is r, and its pair and
+// prolongation are out of place (the fused pass cannot run in place): its iterate is in x0, or not yet anywhere, and the next one goes to o0
+struct MgOps {
+  cz_mg* h;
+  REAL omg;
+  const REAL* r;
+  REAL *x0, *o0;
+
+  bool whole(int l) {
+    if (l < h->tail_from) return false;
+    MgDLev D;
+    MgTail T;
+    mg_lev(D, h->lev[l]);
+    mg_tail_plan(T, D.L, omg);
+    mg_tail_launch(h->x[l], h->b[l], T);
+    return true;
+  }
+  REAL* x(int l) { return l ? h->x[l] : x0; }
+  static void must(int launched) {
+    if (!launched) cz_fatal(1, "czhip: V-cycle: a level kernel refused its level\n");
+  }
+  void pair(int l, bool zero) {
+    if (l == 0) {
+      mg_fine_pair(h, zero ? nullptr : x0, o0, x0, r, omg);
+      std::swap(x0, o0);
+      return;
+    }
+    must(czhip_internal::mg_smooth_async(zero ? nullptr : h->x[l], h->t[l], h->b[l], h->lev[l], omg));
+    must(czhip_internal::mg_smooth_async(h->t[l], h->x[l], h->b[l], h->lev[l], omg));
+  }
+  void restrict_down(int l) { must(czhip_internal::mg_restrict_async(h->b[l + 1], h->lev[l + 1], x(l), l ? h->b[l] : r, nullptr, h->lev[l])); }
+  void prolong_up(int l) {
+    must(czhip_internal::mg_prolong_async(l ? h->x[l] : o0, x(l), h->x[l + 1], h->lev[l + 1], h->lev[l]));
+    if (l == 0) std::swap(x0, o0);
+  }
+};
+}  // namespace
+
+namespace czhip_internal {
+int mg_cycle_async(cz_mg* h, REAL omg) {
+  if (!h || h->first < 1) return 0;  // (level 0 needs the arrays of czhip_mg_apply_async)
+  MgOps ops{h, omg, nullptr, nullptr, nullptr};
+  mg_walk(ops, h->first, h->nlev - 1);
+  return 1;
+}
+}  // namespace czhip_internal
+
+extern "C" {
+int czhip_mg_apply_async(cz_mg* h, CZ_REAL* z, const CZ_REAL* r, CZ_REAL omg) {
+  ensure_init();
+  if (!h || h->first != 0 || !z || !r || z == r || z == h->fine_tmp) return 0;
+  // level 0's iterate changes array with every step: pair, prolongation, pair, or the coarsest level's four pairs.  The last one writes z
+  const bool four = h->nlev == 1;
+  MgOps ops{h, omg, r, four ? z : h->fine_tmp, four ? h->fine_tmp : z};
+  mg_walk(ops, 0, h->nlev - 1);
+  return 1;
+}
+}  // extern "C"

@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "cz_hip.h"
+#include "cz_mg_cycle.h"
 
 // The reference ABI has no error channel: any failure inside the library is fatal and loud.  Every fatal exit of the library
 // goes through cz_fatal: the message goes to stderr AND, where CZ_FATAL_LOG names a file, is appended to it (a process that dies under
@@ -128,22 +129,39 @@ void copy_shell_async(CZ_REAL* dst, const CZ_REAL* src, const int* sz, const int
 void copy_inner_async(CZ_REAL* dst, const CZ_REAL* src, const int* sz, const int* idx, int g);
 void bc_async(const int* sz, int g, CZ_REAL* p, CZ_REAL dh, const CZ_REAL* org, const int* nID, int ioff = 0, int joff = 0);
 
-// the distributed levels of the V-cycle of a decomposed run (cz_k_mg.h MgDLev): one brick's array of level `level`
-// (guide 2; sz / idx as a fine brick's: inner 1 .. size on rank-internal faces, 2 .. size-1 on physical ones), the global index o of its
-// first owned point, the level's global points gn, the level-0 points n0.  dense: a shell-less block of sz points (idx unused).
+// ---- the multigrid V-cycle of pcg ... mg (cz_h_mg.h, and cz_mg_dist.cpp for decomposed runs)
+// What one domain holds of level `level` of a grid of n0 level-0 points: an array of guide g (sz / idx as a fine brick's: inner 1 .. size on
+// rank-internal faces, 2 .. size-1 on physical ones), the global index o of its first owned point and the level's global points gn (a
+// single domain: o = 0, gn = the inner box).  dense: a shell-less block of sz points (idx and g unused).
 struct MgdLevel {
-  int sz[3], idx[6];
+  int sz[3], idx[6], g;
   int level;
   int n0[3], o[3], gn[3];
   int dense;
 };
-int mgd_smooth_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const MgdLevel& L, CZ_REAL omg);  // u = nullptr: from zero
+// the launches of the level kernels; 0 = refused, nothing launched
+int mg_smooth_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const MgdLevel& L, CZ_REAL omg);  // u = nullptr: from zero
+// rt (nullptr where F is a whole level): the residual of the children on the + neighbours, from mgd_resface_async and its exchange
+int mg_restrict_async(CZ_REAL* bc, const MgdLevel& C, const CZ_REAL* x, const CZ_REAL* b, const CZ_REAL* rt, const MgdLevel& F);
+int mg_prolong_async(CZ_REAL* u, const CZ_REAL* x, const CZ_REAL* xc, const MgdLevel& C, const MgdLevel& F);
 // rt = residual of the first owned layer on the - faces flagged in minus[3]
 int mgd_resface_async(CZ_REAL* rt, const CZ_REAL* x, const CZ_REAL* b, const MgdLevel& L, const int* minus);
-int mgd_restrict_async(CZ_REAL* bc, const MgdLevel& C, const CZ_REAL* x, const CZ_REAL* b, const CZ_REAL* rt, const MgdLevel& F);
-int mgd_prolong_async(CZ_REAL* u, const CZ_REAL* x, const CZ_REAL* xc, const MgdLevel& C, const MgdLevel& F);
 // a dense block of cnt points into the global level array G (o = the block's global offset)
 int mgd_unpack_async(CZ_REAL* X, const MgdLevel& G, const CZ_REAL* blk, const int* o, const int* cnt);
+// levels l0 .. coarsest of the grid of n0 level-0 points, every level a whole array (inner box 2 .. n+1 in n+2; level 0: the caller's sz0,
+// idx0 with guide 2).  tail: run the levels that fit one workgroup's LDS in one launch.  nullptr: no such level
+cz_mg* mg_create(const int* n0, int l0, bool tail, const int* sz0 = nullptr, const int* idx0 = nullptr);
+int mg_cycle_async(cz_mg* h, CZ_REAL omg);  // x[first] = V_first(b[first]) of a hierarchy with first >= 1 (0: refused)
 }  // namespace czhip_internal
+
+// the handle of the public C-ABI: levels first .. nlev-1 of a hierarchy of nlev levels
+struct cz_mg {
+  int first = 0, nlev = 0;
+  czhip_internal::MgdLevel lev[MG_MAXLEV];
+  CZ_REAL *b[MG_MAXLEV] = {}, *x[MG_MAXLEV] = {}, *t[MG_MAXLEV] = {};  // levels >= 1 (level 0: b = r, x = z of the call)
+  CZ_REAL* fine_tmp = nullptr;  // level 0: the second array its iterate alternates with
+  double* res = nullptr;        // the sums the level-0 sweeps write (unused)
+  int tail_from = 0;            // first level run by mg_tail_k (nlev: none)
+};
 
 #endif

@@ -11,7 +11,6 @@
 //
 // Geometry of one level's array (MgLev): padded extents and the padded 0-based index of the first inner point.  The global arrays use the
 // S3D layout with guide g; the tail kernel's LDS arrays the same description with one zero shell (nip = ni + 2, first point at 1).
-constexpr int MG_MAXLEV = 32;       // levels of a hierarchy at most (ceil(log2 n) + 1 for any int extent)
 constexpr int MG_TAIL_MAXLEV = 8;   // levels of the tail at most (its LDS holds far fewer)
 constexpr int MG_TAIL_THREADS = 1024;
 constexpr int MG_GUIDE = 2;         // the guide of the hierarchy's arrays (S3D arrays)
@@ -112,25 +111,76 @@ __device__ __forceinline__ REAL mg_prolong_pt(const REAL* x, const REAL* xc, con
   return x[mg_at(F, I, J, K)] + c;
 }
 
-// ---- the level kernels: one thread per point of the level written; block (64, 4), grid (k, i, j)
+// ---- the level kernels: one thread per point of the level written; block (64, 4), grid (k, i, j).  One array of a level is what a domain
+// owns of it ("Decomposed runs"): MgLev's ni, nj, nk are the OWNED points in the fine brick's inner-range convention, l and
+// n0 the global ones; o is the global index of the first owned point, gn the level's global points per direction.  Ghost cells hold the
+// neighbours' values after an exchange.  A single domain owns every point: o = 0, gn = (ni, nj, nk).
+struct MgDLev {
+  MgLev L;
+  MgG o;
+  int gni, gnj, gnk;
+};
+
 template <bool ZERO>
-__global__ void __launch_bounds__(256) mg_smooth_k(const REAL* __restrict__ u, REAL* __restrict__ w, const REAL* __restrict__ b, MgLev L, REAL omg) {
+__global__ void __launch_bounds__(256) mg_smooth_k(const REAL* __restrict__ u, REAL* __restrict__ w, const REAL* __restrict__ b, MgDLev D, REAL omg) {
   const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
-  if (K >= L.nk || I >= L.ni) return;
-  w[mg_at(L, I, J, K)] = mg_sweep_pt<ZERO>(u, b, L, I, J, K, omg);
+  if (K >= D.L.nk || I >= D.L.ni) return;
+  w[mg_at(D.L, I, J, K)] = mg_sweep_pt<ZERO>(u, b, D.L, I, J, K, omg, D.o);
 }
 
-__global__ void __launch_bounds__(256) mg_restrict_k(REAL* __restrict__ bc, const REAL* __restrict__ x, const REAL* __restrict__ b, MgLev F, MgLev Cl) {
+// bc (owned coarse points) = the children's residual tree; owned children computed here, children on the + neighbours (the brick's
+// ghost layer) read from rt after its exchange.  C.L may be a dense block (no shell): the gathered level's send buffer.  DIST = false: the
+// domain owns the whole level (offsets 0, global extents = the local ones, rt not read) -- the same text with those constants folded in,
+// kept as an instantiation of its own because the FP32 launch measured 1-2 % slower without it (profiles/r11/mg_one_cycle.txt)
+template <bool DIST>
+__global__ void __launch_bounds__(256) mg_restrict_k(REAL* __restrict__ bc, const REAL* __restrict__ x, const REAL* __restrict__ b, const REAL* __restrict__ rt,
+                                                     MgDLev F, MgDLev C) {
   const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
-  if (K >= Cl.nk || I >= Cl.ni) return;
-  bc[mg_at(Cl, I, J, K)] = mg_restrict_pt(x, b, F, I, J, K);
+  if (K >= C.L.nk || I >= C.L.ni) return;
+  const MgG fo = DIST ? F.o : MgG{0, 0, 0}, co = DIST ? C.o : MgG{0, 0, 0};
+  const int gni = DIST ? F.gni : F.L.ni, gnj = DIST ? F.gnj : F.L.nj, gnk = DIST ? F.gnk : F.L.nk;
+  // global first child, then local (fine array) index
+  const int gi = 2 * (I + co.i), gj = 2 * (J + co.j), gk = 2 * (K + co.k);
+  const bool hi = gi + 1 < gni, hj = gj + 1 < gnj, hk = gk + 1 < gnk;
+  const int li = gi - fo.i, lj = gj - fo.j, lk = gk - fo.k;
+  bc[mg_at(C.L, I, J, K)] = mg_tree(hi, hj, hk, [&](int ib, int jb, int kb) {
+    const int ci = li + ib, cj = lj + jb, ck = lk + kb;
+    if (!DIST || (ci < F.L.ni && cj < F.L.nj && ck < F.L.nk)) return mg_res_pt(x, b, F.L, ci, cj, ck, fo);
+    return rt[mg_at(F.L, ci, cj, ck)];
+  });
 }
 
-// u may be x (in place: every point reads its own x and its parent only)
-__global__ void __launch_bounds__(256) mg_prolong_k(REAL* u, const REAL* x, const REAL* __restrict__ xc, MgLev F, MgLev Cl) {
+// u = x + R(alpha xc(parent)) on the owned points (u may be x: every point reads its own x and its parent only); the parent is a ghost cell
+// of xc where it lies on a - neighbour, or a point of the gathered global array (C.o = 0)
+__global__ void __launch_bounds__(256) mg_prolong_k(REAL* u, const REAL* x, const REAL* __restrict__ xc, MgDLev F, MgDLev C) {
   const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
-  if (K >= F.nk || I >= F.ni) return;
-  u[mg_at(F, I, J, K)] = mg_prolong_pt(x, xc, F, Cl, I, J, K);
+  if (K >= F.L.nk || I >= F.L.ni) return;
+  u[mg_at(F.L, I, J, K)] = mg_prolong_pt(x, xc, F.L, C.L, I, J, K, F.o, C.o);
+}
+
+// rt = the residual of the first owned layer on the rank-internal - faces (d = 0, 1, 2: I, J, K face; edges and corners belong to the
+// face of the lowest d among the internal ones).  grid: (64-wide blocks along the face's faster free direction, the slower one)
+__global__ void __launch_bounds__(64) mgd_resface_k(REAL* __restrict__ rt, const REAL* __restrict__ x, const REAL* __restrict__ b, MgDLev D, int d,
+                                                    int mi, int mj) {
+  const int a = blockIdx.x * 64 + threadIdx.x, c = blockIdx.y;
+  int I, J, K;
+  if (d == 0) I = 0, K = a, J = c;
+  else if (d == 1) J = 0, K = a, I = c;
+  else K = 0, I = a, J = c;
+  if (I >= D.L.ni || J >= D.L.nj || K >= D.L.nk) return;
+  if ((d >= 1 && mi && I == 0) || (d == 2 && mj && J == 0)) return;  // written by the I (J) face launch
+  rt[mg_at(D.L, I, J, K)] = mg_res_pt(x, b, D.L, I, J, K, D.o);
+}
+
+// one rank's dense block (ni, nj, nk; K fastest) into the gathered global array at global offset o: an exact copy
+__global__ void __launch_bounds__(256) mgd_unpack_k(REAL* __restrict__ X, const REAL* __restrict__ blk, MgLev G, MgG o, int ni, int nj, int nk) {
+  const long long n = (long long)ni * nj * nk;
+  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n; q += (long long)gridDim.x * 256) {
+    const int K = (int)(q % nk);
+    const long long r = q / nk;
+    const int I = (int)(r % ni), J = (int)(r / ni);
+    X[mg_at(G, I + o.i, J + o.j, K + o.k)] = blk[q];
+  }
 }
 
 // ---- the tail: x = V_t(b) from level t down to the coarsest and back, in ONE workgroup with every level's b, x and t in LDS
@@ -210,71 +260,5 @@ __global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ 
   {
     const REAL* x0 = lds + T.off[0] + T.len[0];
     mg_each(T.s[0], [&](int I, int J, int K) { xg[mg_at(T.gl, I, J, K)] = x0[mg_at(T.s[0], I, J, K)]; });
-  }
-}
-
-// ---- the distributed levels of a decomposed run ("Decomposed runs"): a brick's array of level l holds the points it owns,
-// in the fine brick's inner-range convention; MgLev's ni, nj, nk are the OWNED points, l and n0 the global ones.  o is the global index of the
-// first owned point, gn the level's global points per direction.  Ghost cells hold the neighbours' values after an exchange.
-struct MgDLev {
-  MgLev L;
-  MgG o;
-  int gni, gnj, gnk;
-};
-
-template <bool ZERO>
-__global__ void __launch_bounds__(256) mgd_smooth_k(const REAL* __restrict__ u, REAL* __restrict__ w, const REAL* __restrict__ b, MgDLev D, REAL omg) {
-  const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
-  if (K >= D.L.nk || I >= D.L.ni) return;
-  w[mg_at(D.L, I, J, K)] = mg_sweep_pt<ZERO>(u, b, D.L, I, J, K, omg, D.o);
-}
-
-// rt = the residual of the first owned layer on the rank-internal - faces (d = 0, 1, 2: I, J, K face; edges and corners belong to the
-// face of the lowest d among the internal ones).  grid: (64-wide blocks along the face's faster free direction, the slower one)
-__global__ void __launch_bounds__(64) mgd_resface_k(REAL* __restrict__ rt, const REAL* __restrict__ x, const REAL* __restrict__ b, MgDLev D, int d,
-                                                    int mi, int mj) {
-  const int a = blockIdx.x * 64 + threadIdx.x, c = blockIdx.y;
-  int I, J, K;
-  if (d == 0) I = 0, K = a, J = c;
-  else if (d == 1) J = 0, K = a, I = c;
-  else K = 0, I = a, J = c;
-  if (I >= D.L.ni || J >= D.L.nj || K >= D.L.nk) return;
-  if ((d >= 1 && mi && I == 0) || (d == 2 && mj && J == 0)) return;  // written by the I (J) face launch
-  rt[mg_at(D.L, I, J, K)] = mg_res_pt(x, b, D.L, I, J, K, D.o);
-}
-
-// bc (owned coarse points) = the children's residual tree; owned children computed here, children on the + neighbours (the brick's
-// ghost layer) read from rt after its exchange.  C.L may be a dense block (no shell): the gathered level's send buffer.
-__global__ void __launch_bounds__(256) mgd_restrict_k(REAL* __restrict__ bc, const REAL* __restrict__ x, const REAL* __restrict__ b, const REAL* __restrict__ rt,
-                                                      MgDLev F, MgDLev C) {
-  const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
-  if (K >= C.L.nk || I >= C.L.ni) return;
-  // global first child, then local (fine array) index
-  const int gi = 2 * (I + C.o.i), gj = 2 * (J + C.o.j), gk = 2 * (K + C.o.k);
-  const bool hi = gi + 1 < F.gni, hj = gj + 1 < F.gnj, hk = gk + 1 < F.gnk;
-  const int li = gi - F.o.i, lj = gj - F.o.j, lk = gk - F.o.k;
-  bc[mg_at(C.L, I, J, K)] = mg_tree(hi, hj, hk, [&](int ib, int jb, int kb) {
-    const int ci = li + ib, cj = lj + jb, ck = lk + kb;
-    if (ci < F.L.ni && cj < F.L.nj && ck < F.L.nk) return mg_res_pt(x, b, F.L, ci, cj, ck, F.o);
-    return rt[mg_at(F.L, ci, cj, ck)];
-  });
-}
-
-// u = x + R(alpha xc(parent)) on the owned points (u may be x); the parent is a ghost cell of xc where it lies on a - neighbour, or a point
-// of the gathered global array (C.o = 0)
-__global__ void __launch_bounds__(256) mgd_prolong_k(REAL* u, const REAL* x, const REAL* __restrict__ xc, MgDLev F, MgDLev C) {
-  const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
-  if (K >= F.L.nk || I >= F.L.ni) return;
-  u[mg_at(F.L, I, J, K)] = mg_prolong_pt(x, xc, F.L, C.L, I, J, K, F.o, C.o);
-}
-
-// one rank's dense block (ni, nj, nk; K fastest) into the gathered global array at global offset o: an exact copy
-__global__ void __launch_bounds__(256) mgd_unpack_k(REAL* __restrict__ X, const REAL* __restrict__ blk, MgLev G, MgG o, int ni, int nj, int nk) {
-  const long long n = (long long)ni * nj * nk;
-  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < n; q += (long long)gridDim.x * 256) {
-    const int K = (int)(q % nk);
-    const long long r = q / nk;
-    const int I = (int)(r % ni), J = (int)(r / ni);
-    X[mg_at(G, I + o.i, J + o.j, K + o.k)] = blk[q];
   }
 }

@@ -1455,335 +1455,5 @@ void czhip_cg_dir_ax_async(CZ_REAL* p_new, CZ_REAL* q, const CZ_REAL* z, const C
 }
 }  // extern "C"
 
-// ============================================================================================================
-// Multigrid V-cycle preconditioner of PCG: the level kernels (cz_k_mg.h) and the hierarchy handle
-// ============================================================================================================
-namespace {
-// level l's geometry from its array (sz, idx, g) and the level-0 extents n0; false if the box is not ceil(n0 / 2^l) points per direction
-bool mg_lev(MgLev& L, const int* sz, const int* idx, int g, int l, const int* n0) {
-  const Box b = make_box(sz, idx, g);
-  if (b.empty || l < 0 || l >= MG_MAXLEV - 1) return false;
-  L.nip = b.nip, L.nkp = b.nkp, L.i0 = b.ii0, L.j0 = b.jj0, L.k0 = b.kk0;
-  L.ni = b.ii1 - b.ii0 + 1, L.nj = b.jj1 - b.jj0 + 1, L.nk = b.kk1 - b.kk0 + 1;
-  L.l = l, L.n0i = n0[0], L.n0j = n0[1], L.n0k = n0[2];
-  const long long s = 1LL << l;
-  for (int d = 0; d < 3; d++)
-    if (n0[d] < 1 || (n0[d] + s - 1) / s != (d == 0 ? L.ni : d == 1 ? L.nj : L.nk)) return false;
-  return true;
-}
-
-// the LDS layout of the levels from fine (level l) down to the coarsest: one zero shell per array, b, x, t per level
-bool mg_tail_plan(MgTail& T, const MgLev& fine, REAL omg) {
-  T = MgTail();
-  T.gl = fine, T.omg = omg;
-  MgLev c = fine;
-  int total = 0;
-  for (int m = 0;; m++) {
-    if (m >= MG_TAIL_MAXLEV) return false;
-    MgLev s = c;
-    s.nip = c.ni + 2, s.nkp = c.nk + 2, s.i0 = s.j0 = s.k0 = 1;
-    T.s[m] = s;
-    T.len[m] = (c.ni + 2) * (c.nj + 2) * (c.nk + 2);
-    T.off[m] = total;
-    total += 3 * T.len[m];
-    if ((long long)total * (long long)sizeof(REAL) > 160 * 1024) return false;
-    if (std::max(c.ni, std::max(c.nj, c.nk)) <= 4) {  // the coarsest level
-      T.nlev = m + 1;
-      break;
-    }
-    c.ni = (c.ni + 1) / 2, c.nj = (c.nj + 1) / 2, c.nk = (c.nk + 1) / 2, c.l++;
-  }
-  T.total = total;
-  return true;
-}
-
-dim3 mg_grid(const MgLev& L) { return dim3((unsigned)((L.nk + 63) / 64), (unsigned)((L.ni + 3) / 4), (unsigned)L.nj); }
-
-void mg_smooth_launch(const REAL* u, REAL* w, const REAL* b, const MgLev& L, REAL omg) {
-  ScopedTimer tm(LBL_MG_SMOOTH);
-  if (u) hipLaunchKernelGGL((mg_smooth_k<false>), mg_grid(L), dim3(64, 4), 0, ctx.stream, u, w, b, L, omg);
-  else hipLaunchKernelGGL((mg_smooth_k<true>), mg_grid(L), dim3(64, 4), 0, ctx.stream, w, w, b, L, omg);
-  HIP_CHECK(hipGetLastError());
-}
-
-void mg_restrict_launch(REAL* bc, const REAL* x, const REAL* b, const MgLev& F, const MgLev& Cl) {
-  ScopedTimer tm(LBL_MG_RESTRICT);
-  hipLaunchKernelGGL(mg_restrict_k, mg_grid(Cl), dim3(64, 4), 0, ctx.stream, bc, x, b, F, Cl);
-  HIP_CHECK(hipGetLastError());
-}
-
-void mg_prolong_launch(REAL* u, const REAL* x, const REAL* xc, const MgLev& F, const MgLev& Cl) {
-  ScopedTimer tm(LBL_MG_PROLONG);
-  hipLaunchKernelGGL(mg_prolong_k, mg_grid(F), dim3(64, 4), 0, ctx.stream, u, x, xc, F, Cl);
-  HIP_CHECK(hipGetLastError());
-}
-
-void mg_tail_launch(REAL* x, const REAL* b, const MgTail& T) {
-  ScopedTimer tm(LBL_MG_TAIL);
-  const int bytes = T.total * (int)sizeof(REAL);
-  if (bytes > 64 * 1024) allow_dynamic_lds(&mg_tail_k, 160 * 1024);
-  hipLaunchKernelGGL(mg_tail_k, dim3(1), dim3(MG_TAIL_THREADS), bytes, ctx.stream, x, b, T);
-  HIP_CHECK(hipGetLastError());
-}
-
-bool mg_coarse_of(const MgLev& F, const MgLev& Cl) {
-  return Cl.l == F.l + 1 && Cl.ni == (F.ni + 1) / 2 && Cl.nj == (F.nj + 1) / 2 && Cl.nk == (F.nk + 1) / 2 && Cl.n0i == F.n0i && Cl.n0j == F.n0j &&
-         Cl.n0k == F.n0k;
-}
-}  // namespace
-
-struct cz_mg {
-  int nlev = 0;                  // L: levels 0 .. L-1
-  int sz[MG_MAXLEV][3], idx[MG_MAXLEV][6];
-  MgLev lev[MG_MAXLEV];
-  REAL *b[MG_MAXLEV] = {}, *x[MG_MAXLEV] = {}, *t[MG_MAXLEV] = {};  // levels >= 1 (level 0: b = r, x = z of the call)
-  REAL* fine_tmp = nullptr;      // level 0: the prolonged iterate u, input of the post-smoothing pair
-  double* res = nullptr;         // the sums the level-0 sweeps write (unused)
-  int tail_from = 0;             // first level run by mg_tail_k (nlev: none)
-};
-
-extern "C" {
-
-int czhip_mg_smooth_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, int g, int level, const int* n0, CZ_REAL omg) {
-  ensure_init();
-  MgLev L;
-  if (!w || !b || u == w || !mg_lev(L, sz, idx, g, level, n0)) return 0;
-  mg_smooth_launch(u, w, b, L, omg);
-  return 1;
-}
-
-int czhip_mg_restrict_async(CZ_REAL* bc, const int* szc, const int* idxc, const CZ_REAL* x, const CZ_REAL* b, const int* sz, const int* idx, int g, int level,
-                            const int* n0) {
-  ensure_init();
-  MgLev F, Cl;
-  if (!bc || !x || !b || bc == x || bc == b || !mg_lev(F, sz, idx, g, level, n0) || !mg_lev(Cl, szc, idxc, g, level + 1, n0) || !mg_coarse_of(F, Cl))
-    return 0;
-  mg_restrict_launch(bc, x, b, F, Cl);
-  return 1;
-}
-
-int czhip_mg_prolong_async(CZ_REAL* u, const CZ_REAL* x, const CZ_REAL* xc, const int* szc, const int* idxc, const int* sz, const int* idx, int g, int level,
-                           const int* n0) {
-  ensure_init();
-  MgLev F, Cl;
-  if (!u || !x || !xc || u == xc || !mg_lev(F, sz, idx, g, level, n0) || !mg_lev(Cl, szc, idxc, g, level + 1, n0) || !mg_coarse_of(F, Cl)) return 0;
-  mg_prolong_launch(u, x, xc, F, Cl);
-  return 1;
-}
-
-int czhip_mg_tail_async(CZ_REAL* x, const CZ_REAL* b, const int* sz, const int* idx, int g, int level, const int* n0, CZ_REAL omg) {
-  ensure_init();
-  MgLev L;
-  MgTail T;
-  if (!x || !b || x == b || !mg_lev(L, sz, idx, g, level, n0) || !mg_tail_plan(T, L, omg)) return 0;
-  mg_tail_launch(x, b, T);
-  return 1;
-}
-
-cz_mg* czhip_mg_create(const int* sz, const int* idx, int g, const CZ_REAL* cf) {
-  ensure_init();
-  if (g != MG_GUIDE) return nullptr;  // (the coarse arrays and the temporary are S3D arrays: guide 2)
-  for (int c = 0; c < 6; c++)
-    if (cf[c] != (REAL)1) return nullptr;
-  if (cf[6] != (REAL)6) return nullptr;
-  const int n0[3] = {idx[1] - idx[0] + 1, idx[3] - idx[2] + 1, idx[5] - idx[4] + 1};
-  if (n0[0] < 1 || n0[1] < 1 || n0[2] < 1) return nullptr;
-  cz_mg* h = new cz_mg();
-  for (int l = 0;; l++) {
-    if (l == 0) {
-      std::copy(sz, sz + 3, h->sz[0]);
-      std::copy(idx, idx + 6, h->idx[0]);
-    } else {  // ceil(n / 2) points per direction, inner box 2 .. n + 1 inside zero faces at 1 and n + 2
-      for (int d = 0; d < 3; d++) {
-        const int n = (h->lev[l - 1].ni * (d == 0) + h->lev[l - 1].nj * (d == 1) + h->lev[l - 1].nk * (d == 2) + 1) / 2;
-        h->sz[l][d] = n + 2, h->idx[l][2 * d] = 2, h->idx[l][2 * d + 1] = n + 1;
-      }
-    }
-    if (!mg_lev(h->lev[l], h->sz[l], h->idx[l], g, l, n0)) {
-      czhip_mg_destroy(h);
-      return nullptr;
-    }
-    h->nlev = l + 1;
-    if (l > 0) h->b[l] = czhip_alloc_s3d(h->sz[l]), h->x[l] = czhip_alloc_s3d(h->sz[l]), h->t[l] = czhip_alloc_s3d(h->sz[l]);
-    const MgLev& L = h->lev[l];
-    if (std::max(L.ni, std::max(L.nj, L.nk)) <= 4) break;  // the coarsest level
-  }
-  h->fine_tmp = czhip_alloc_s3d(sz);
-  HIP_CHECK(hipMalloc(&h->res, 4 * sizeof(double)));
-  // the tail starts at the first level >= 1 whose levels down to the coarsest fit one workgroup's LDS (CZ_MG_TAIL=0: none)
-  h->tail_from = h->nlev;
-  if (CzConfig::from_env().on(CZV_MG_TAIL, true)) {
-    MgTail T;
-    for (int l = 1; l < h->nlev; l++)
-      if (mg_tail_plan(T, h->lev[l], (REAL)1)) {
-        h->tail_from = l;
-        break;
-      }
-  }
-  return h;
-}
-
-int czhip_mg_levels(const cz_mg* h) { return h ? h->nlev : 0; }
-
-void czhip_mg_destroy(cz_mg* h) {
-  if (!h) return;
-  czhip_sync();
-  for (int l = 0; l < MG_MAXLEV; l++)
-    for (REAL* a : {h->b[l], h->x[l], h->t[l]})
-      if (a) czhip_free(a);
-  if (h->fine_tmp) czhip_free(h->fine_tmp);
-  if (h->res) (void)hipFree(h->res);
-  delete h;
-}
-}  // extern "C"
-
-namespace {
-// level 0's pairs of sweeps with the unit coefficients, u -> w (u = nullptr: from zero): the fused pass, or where it is not taken two single
-// sweeps through o (an array other than w; it may be u) and a copy back to w
-void mg_fine_pair(cz_mg* h, const REAL* u, REAL* w, REAL* o, const REAL* b, REAL omg) {
-  const int* sz = h->sz[0];
-  const int* idx = h->idx[0];
-  REAL cf[7] = {1, 1, 1, 1, 1, 1, 6};
-  if (u ? czhip_jacobi2_async(u, w, b, sz, idx, nullptr, MG_GUIDE, cf, omg, h->res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr)
-        : czhip_jacobi2_from_zero_async(w, w, b, sz, idx, nullptr, MG_GUIDE, cf, omg, h->res))
-    return;
-  const size_t nbytes = (size_t)(sz[0] + 4) * (sz[1] + 4) * (sz[2] + 4) * sizeof(REAL);
-  if (!u) {
-    HIP_CHECK(hipMemsetAsync(o, 0, nbytes, ctx.stream));
-    u = o;
-  }
-  czhip_jacobi_async(u, w, b, sz, idx, MG_GUIDE, cf, omg, h->res, 0, nullptr);
-  czhip_jacobi_async(w, o, b, sz, idx, MG_GUIDE, cf, omg, h->res, 0, nullptr);
-  HIP_CHECK(hipMemcpyAsync(w, o, nbytes, hipMemcpyDeviceToDevice, ctx.stream));
-}
-
-// x_l = V_l(b_l) for l >= 1, level by level until the tail
-void mg_cycle(cz_mg* h, int l, REAL omg) {
-  const MgLev& L = h->lev[l];
-  REAL *b = h->b[l], *x = h->x[l], *t = h->t[l];
-  if (l >= h->tail_from) {
-    MgTail T;
-    mg_tail_plan(T, L, omg);
-    mg_tail_launch(x, b, T);
-    return;
-  }
-  if (l == h->nlev - 1) {  // the coarsest level: 8 sweeps from zero, b -> t -> x -> ... -> x
-    mg_smooth_launch(nullptr, t, b, L, omg);
-    for (int s = 1; s < 8; s++) mg_smooth_launch((s & 1) ? t : x, (s & 1) ? x : t, b, L, omg);
-    return;
-  }
-  mg_smooth_launch(nullptr, t, b, L, omg);
-  mg_smooth_launch(t, x, b, L, omg);
-  mg_restrict_launch(h->b[l + 1], x, b, L, h->lev[l + 1]);
-  mg_cycle(h, l + 1, omg);
-  mg_prolong_launch(x, x, h->x[l + 1], L, h->lev[l + 1]);
-  mg_smooth_launch(x, t, b, L, omg);
-  mg_smooth_launch(t, x, b, L, omg);
-}
-}  // namespace
-
-extern "C" {
-int czhip_mg_apply_async(cz_mg* h, CZ_REAL* z, const CZ_REAL* r, CZ_REAL omg) {
-  ensure_init();
-  if (!h || !z || !r || z == r || z == h->fine_tmp) return 0;
-  REAL* const tmp = h->fine_tmp;
-  if (h->nlev == 1) {  // level 0 is already the coarsest: the 8 sweeps from zero
-    mg_fine_pair(h, nullptr, tmp, z, r, omg);
-    mg_fine_pair(h, tmp, z, tmp, r, omg);
-    mg_fine_pair(h, z, tmp, z, r, omg);
-    mg_fine_pair(h, tmp, z, tmp, r, omg);
-    return 1;
-  }
-  const MgLev& F = h->lev[0];
-  mg_fine_pair(h, nullptr, z, tmp, r, omg);                 // x = 2 sweeps from zero
-  mg_restrict_launch(h->b[1], z, r, F, h->lev[1]);          // b_1 = restricted b - A x
-  mg_cycle(h, 1, omg);                                      // x_1 = V_1(b_1)
-  mg_prolong_launch(tmp, z, h->x[1], F, h->lev[1]);         // u = x + R(alpha x_1(parent))
-  mg_fine_pair(h, tmp, z, tmp, r, omg);                     // x = 2 sweeps from u
-  return 1;
-}
-}  // extern "C"
-
-// ---- the distributed levels (cz_internal.h MgdLevel)
-namespace {
-bool mgd_lev(MgDLev& D, const czhip_internal::MgdLevel& M) {
-  MgLev& L = D.L;
-  if (M.dense) {
-    L.nip = M.sz[0], L.nkp = M.sz[2], L.i0 = L.j0 = L.k0 = 0;
-    L.ni = M.sz[0], L.nj = M.sz[1], L.nk = M.sz[2];
-  } else {
-    const Box b = make_box(M.sz, M.idx, MG_GUIDE);
-    if (b.empty) return false;
-    L.nip = b.nip, L.nkp = b.nkp, L.i0 = b.ii0, L.j0 = b.jj0, L.k0 = b.kk0;
-    L.ni = b.ii1 - b.ii0 + 1, L.nj = b.jj1 - b.jj0 + 1, L.nk = b.kk1 - b.kk0 + 1;
-  }
-  L.l = M.level, L.n0i = M.n0[0], L.n0j = M.n0[1], L.n0k = M.n0[2];
-  D.o = MgG{M.o[0], M.o[1], M.o[2]};
-  D.gni = M.gn[0], D.gnj = M.gn[1], D.gnk = M.gn[2];
-  const int n[3] = {L.ni, L.nj, L.nk};
-  for (int d = 0; d < 3; d++)
-    if (M.o[d] < 0 || n[d] < 0 || M.o[d] + n[d] > M.gn[d]) return false;
-  return M.level >= 0 && M.level < MG_MAXLEV - 1;
-}
-bool mgd_none(const MgDLev& D) { return D.L.ni < 1 || D.L.nj < 1 || D.L.nk < 1; }
-}  // namespace
-
-namespace czhip_internal {
-int mgd_smooth_async(const REAL* u, REAL* w, const REAL* b, const MgdLevel& M, REAL omg) {
-  MgDLev D;
-  if (!w || !b || u == w || !mgd_lev(D, M) || M.dense) return 0;
-  if (mgd_none(D)) return 1;
-  ScopedTimer tm(LBL_MG_SMOOTH);
-  if (u) hipLaunchKernelGGL((mgd_smooth_k<false>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, u, w, b, D, omg);
-  else hipLaunchKernelGGL((mgd_smooth_k<true>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, w, w, b, D, omg);
-  HIP_CHECK(hipGetLastError());
-  return 1;
-}
-
-int mgd_resface_async(REAL* rt, const REAL* x, const REAL* b, const MgdLevel& M, const int* minus) {
-  MgDLev D;
-  if (!rt || !x || !b || rt == x || !mgd_lev(D, M) || M.dense) return 0;
-  if (mgd_none(D)) return 1;
-  ScopedTimer tm(LBL_MG_RESTRICT);
-  for (int d = 0; d < 3; d++) {
-    if (!minus[d]) continue;
-    const int fast = d == 2 ? D.L.ni : D.L.nk, slow = d == 0 ? D.L.nj : d == 1 ? D.L.ni : D.L.nj;
-    hipLaunchKernelGGL(mgd_resface_k, dim3((unsigned)((fast + 63) / 64), (unsigned)slow), dim3(64), 0, ctx.stream, rt, x, b, D, d, minus[0], minus[1]);
-    HIP_CHECK(hipGetLastError());
-  }
-  return 1;
-}
-
-int mgd_restrict_async(REAL* bc, const MgdLevel& MC, const REAL* x, const REAL* b, const REAL* rt, const MgdLevel& MF) {
-  MgDLev F, C;
-  if (!bc || !x || !b || !rt || bc == x || bc == b || !mgd_lev(F, MF) || !mgd_lev(C, MC) || MF.dense || MC.level != MF.level + 1) return 0;
-  if (mgd_none(C)) return 1;
-  ScopedTimer tm(LBL_MG_RESTRICT);
-  hipLaunchKernelGGL(mgd_restrict_k, mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C);
-  HIP_CHECK(hipGetLastError());
-  return 1;
-}
-
-int mgd_prolong_async(REAL* u, const REAL* x, const REAL* xc, const MgdLevel& MC, const MgdLevel& MF) {
-  MgDLev F, C;
-  if (!u || !x || !xc || u == xc || !mgd_lev(F, MF) || !mgd_lev(C, MC) || MF.dense || MC.dense || MC.level != MF.level + 1) return 0;
-  if (mgd_none(F)) return 1;
-  ScopedTimer tm(LBL_MG_PROLONG);
-  hipLaunchKernelGGL(mgd_prolong_k, mg_grid(F.L), dim3(64, 4), 0, ctx.stream, u, x, xc, F, C);
-  HIP_CHECK(hipGetLastError());
-  return 1;
-}
-
-int mgd_unpack_async(REAL* X, const MgdLevel& MG, const REAL* blk, const int* o, const int* cnt) {
-  MgDLev G;
-  if (!X || !blk || !mgd_lev(G, MG) || MG.dense) return 0;
-  for (int d = 0; d < 3; d++)
-    if (o[d] < 0 || cnt[d] < 0 || o[d] + cnt[d] > MG.gn[d]) return 0;
-  const long long n = (long long)cnt[0] * cnt[1] * cnt[2];
-  if (n == 0) return 1;
-  hipLaunchKernelGGL(mgd_unpack_k, dim3((unsigned)std::min<long long>((n + 255) / 256, 1024)), dim3(256), 0, ctx.stream, X, blk, G.L,
-                     MgG{o[0], o[1], o[2]}, cnt[0], cnt[1], cnt[2]);
-  HIP_CHECK(hipGetLastError());
-  return 1;
-}
-}  // namespace czhip_internal
+// the multigrid V-cycle preconditioner of PCG: launches of cz_k_mg.h and the hierarchy handle
+#include "cz_h_mg.h"

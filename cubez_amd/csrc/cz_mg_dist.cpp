@@ -8,8 +8,11 @@
 //                  CommCtx; a face exchange before every sweep that reads its input, the residual of the first owned layer on the - faces
 //                  exchanged over faces, edges and corners for the children on the + neighbours, the coarse iterate exchanged the same way
 //                  for the parents on the - neighbours
-//   G .. coarsest  the owned blocks of b_G all-gathered (an exact copy) into a global level-G array on every rank; the single-domain level
-//                  kernels and mg_tail_k run there redundantly, and the prolongation from G reads its parents from that copy.
+//   G .. coarsest  the owned blocks of b_G all-gathered (an exact copy) into level G of a single-domain hierarchy (cz_mg) that every rank
+//                  keeps for the levels from G on; its own cycle runs there redundantly, and the prolongation from G reads its parents
+//                  from that copy.
+// The order of the cycle is mg_walk's (cz_mg_cycle.h), the one the single-domain cycle takes; MgdOps below are its operations here, the
+// level kernels those of the single domain (cz_k_mg.h).
 // G = the first level at which some brick owns no point in some direction, the coarsest level, or the first level of at most CZ_MG_GATHER
 // global points, whichever comes first (never below 1).  Every G gives the same bits.
 #include <algorithm>
@@ -23,21 +26,18 @@ using namespace czhip_internal;
 struct MgDist {
   int nlev = 0, G = 0, nproc = 1;
   int n0[3] = {0, 0, 0};
-  int gn[MG_DIST_MAXLEV][3];
-  MgdLevel lev[MG_DIST_MAXLEV];    // distributed levels 0 .. G-1 (level 0: the driver's arrays)
+  MgdLevel lev[MG_MAXLEV];         // distributed levels 0 .. G-1 (level 0: the driver's arrays)
   MgdLevel blk;                    // this brick's owned block of level G (dense: the all-gather's send buffer)
-  MgdLevel glev[MG_DIST_MAXLEV];   // the global levels G .. nlev-1
-  CommCtx* comm[MG_DIST_MAXLEV] = {};  // level 0: the driver's; 1 .. G-1 own ones
-  int minus[MG_DIST_MAXLEV][3];    // rank-internal - faces (the same at every level)
-  REAL_TYPE *b[MG_DIST_MAXLEV] = {}, *x[MG_DIST_MAXLEV] = {}, *t[MG_DIST_MAXLEV] = {}, *rt[MG_DIST_MAXLEV] = {};
-  REAL_TYPE *gb[MG_DIST_MAXLEV] = {}, *gx[MG_DIST_MAXLEV] = {}, *gt[MG_DIST_MAXLEV] = {};
+  cz_mg* g = nullptr;              // levels G .. coarsest: a single-domain hierarchy on every rank
+  CommCtx* comm[MG_MAXLEV] = {};   // level 0: the driver's; 1 .. G-1 own ones
+  int minus[3];                    // rank-internal - faces (the same at every level)
+  REAL_TYPE *b[MG_MAXLEV] = {}, *x[MG_MAXLEV] = {}, *t[MG_MAXLEV] = {}, *rt[MG_MAXLEV] = {};  // levels >= 1 (rt: 0 too)
   REAL_TYPE* tmp0 = nullptr;       // level 0: the second fine array of the sweeps
   REAL_TYPE *send = nullptr, *recv = nullptr;
   size_t blk_max = 0;              // elements per rank in the all-gather (the largest block)
   std::vector<int> bo, bc;         // every rank's level-G block: global offset and points, 3 per rank
   double* res = nullptr;           // the sums the level-0 sweeps write (unused)
   int exchanges = 0;               // halo exchanges + all-gathers of the last cycle
-  bool tail = true;
 };
 
 namespace {
@@ -52,15 +52,6 @@ bool brick_range(const CZ& cz, int rank, int h[3], int m[3], int nid[6]) {
   return true;
 }
 
-void global_level(MgdLevel& L, const int* n, int level, const int* n0) {
-  L = MgdLevel();
-  for (int d = 0; d < 3; d++) {
-    L.sz[d] = n[d] + 2, L.idx[2 * d] = 2, L.idx[2 * d + 1] = n[d] + 1;
-    L.n0[d] = n0[d], L.o[d] = 0, L.gn[d] = n[d];
-  }
-  L.level = level, L.dense = 0;
-}
-
 void fatal_if(bool bad, const char* what) {
   if (bad) cz_fatal(1, "czhip: distributed V-cycle: %s failed\n", what);
 }
@@ -70,17 +61,12 @@ MgDist* mgd_create(const CZ& cz, CommCtx* comm0, int gather_points, bool tail) {
   if (cz.numProc < 2 || !comm0) return nullptr;
   MgDist* h = new MgDist();
   h->nproc = cz.numProc;
-  h->tail = tail;
-  for (int d = 0; d < 3; d++) h->n0[d] = cz.G_size[d] - 2, h->gn[0][d] = h->n0[d];
-  // the levels: those of the single-domain hierarchy (coarsening stops at the first level whose largest extent is <= 4)
-  for (int l = 0;; l++) {
-    if (l >= MG_DIST_MAXLEV) {
-      delete h;
-      return nullptr;
-    }
-    h->nlev = l + 1;
-    if (std::max(h->gn[l][0], std::max(h->gn[l][1], h->gn[l][2])) <= 4) break;
-    for (int d = 0; d < 3; d++) h->gn[l + 1][d] = (h->gn[l][d] + 1) / 2;
+  int gn[MG_MAXLEV][3];
+  for (int d = 0; d < 3; d++) h->n0[d] = cz.G_size[d] - 2;
+  h->nlev = mg_level_dims(h->n0, gn, MG_MAXLEV - 1);  // the levels of the single-domain hierarchy
+  if (!h->nlev) {
+    delete h;
+    return nullptr;
   }
   // the gather level
   std::vector<int> H(3 * h->nproc), M(3 * h->nproc), NID(6 * h->nproc);
@@ -98,7 +84,7 @@ MgDist* mgd_create(const CZ& cz, CommCtx* comm0, int gather_points, bool tail) {
         comm_mg_own(H[3 * r + d], M[3 * r + d], l, &f, &c);
         if (c < 1) empty = true;
       }
-    const double pts = (double)h->gn[l][0] * h->gn[l][1] * h->gn[l][2];
+    const double pts = (double)gn[l][0] * gn[l][1] * gn[l][2];
     if (empty || pts <= (double)gather_points) {
       G = l;
       break;
@@ -112,18 +98,18 @@ MgDist* mgd_create(const CZ& cz, CommCtx* comm0, int gather_points, bool tail) {
   for (int l = 0; l < std::max(G, 1); l++) {
     MgdLevel& L = h->lev[l];
     L = MgdLevel();
-    L.level = l, L.dense = 0;
+    L.level = l, L.g = GUIDE;
     for (int d = 0; d < 3; d++) {
       int f, c;
       comm_mg_own(hm[d], mm[d], l, &f, &c);
       const bool pm = cz.nID[2 * d] < 0, pp = cz.nID[2 * d + 1] < 0;
-      L.n0[d] = h->n0[d], L.o[d] = f, L.gn[d] = h->gn[l][d];
+      L.n0[d] = h->n0[d], L.o[d] = f, L.gn[d] = gn[l][d];
       if (l == 0) {
         L.sz[d] = cz.size[d], L.idx[2 * d] = cz.innerFidx[2 * d], L.idx[2 * d + 1] = cz.innerFidx[2 * d + 1];
       } else {
         L.sz[d] = c + (pm ? 1 : 0) + (pp ? 1 : 0), L.idx[2 * d] = pm ? 2 : 1, L.idx[2 * d + 1] = L.idx[2 * d] + c - 1;
       }
-      h->minus[l][d] = pm ? 0 : 1;
+      h->minus[d] = pm ? 0 : 1;
     }
     if (l == 0) {
       h->comm[0] = comm0;
@@ -136,7 +122,7 @@ MgDist* mgd_create(const CZ& cz, CommCtx* comm0, int gather_points, bool tail) {
     if (l < G) h->rt[l] = czhip_alloc_s3d(L.sz);
   }
   if (G > 0) {
-    // level G: every rank's block, the padded send / receive buffers, the global arrays of G .. coarsest
+    // level G: every rank's block, the padded send / receive buffers, the hierarchy of G .. coarsest
     h->bo.resize(3 * h->nproc), h->bc.resize(3 * h->nproc);
     for (int r = 0; r < h->nproc; r++) {
       size_t n = 1;
@@ -149,14 +135,12 @@ MgDist* mgd_create(const CZ& cz, CommCtx* comm0, int gather_points, bool tail) {
     MgdLevel& B = h->blk;
     B = MgdLevel();
     B.level = G, B.dense = 1;
-    for (int d = 0; d < 3; d++) B.sz[d] = h->bc[3 * me + d], B.o[d] = h->bo[3 * me + d], B.n0[d] = h->n0[d], B.gn[d] = h->gn[G][d];
+    for (int d = 0; d < 3; d++) B.sz[d] = h->bc[3 * me + d], B.o[d] = h->bo[3 * me + d], B.n0[d] = h->n0[d], B.gn[d] = gn[G][d];
     HIP_CHECK(hipMalloc(&h->send, h->blk_max * sizeof(REAL_TYPE)));
     HIP_CHECK(hipMalloc(&h->recv, h->blk_max * h->nproc * sizeof(REAL_TYPE)));
     HIP_CHECK(hipMemset(h->send, 0, h->blk_max * sizeof(REAL_TYPE)));
-    for (int l = G; l < h->nlev; l++) {
-      global_level(h->glev[l], h->gn[l], l, h->n0);
-      h->gb[l] = czhip_alloc_s3d(h->glev[l].sz), h->gx[l] = czhip_alloc_s3d(h->glev[l].sz), h->gt[l] = czhip_alloc_s3d(h->glev[l].sz);
-    }
+    h->g = mg_create(h->n0, G, tail);
+    fatal_if(!h->g, "the hierarchy of the gathered levels");
   }
   HIP_CHECK(hipMalloc(&h->res, 4 * sizeof(double)));
   return h;
@@ -165,11 +149,12 @@ MgDist* mgd_create(const CZ& cz, CommCtx* comm0, int gather_points, bool tail) {
 void mgd_destroy(MgDist* h) {
   if (!h) return;
   czhip_sync();
-  for (int l = 1; l < MG_DIST_MAXLEV; l++)
+  for (int l = 1; l < MG_MAXLEV; l++)
     if (h->comm[l]) comm_destroy(h->comm[l]);
-  for (int l = 0; l < MG_DIST_MAXLEV; l++)
-    for (REAL_TYPE* a : {h->b[l], h->x[l], h->t[l], h->rt[l], h->gb[l], h->gx[l], h->gt[l]})
+  for (int l = 0; l < MG_MAXLEV; l++)
+    for (REAL_TYPE* a : {h->b[l], h->x[l], h->t[l], h->rt[l]})
       if (a) czhip_free(a);
+  czhip_mg_destroy(h->g);
   if (h->tmp0) czhip_free(h->tmp0);
   if (h->send) (void)hipFree(h->send);
   if (h->recv) (void)hipFree(h->recv);
@@ -182,126 +167,78 @@ int mgd_gather_level(const MgDist* h) { return h ? h->G : 0; }
 int mgd_exchanges(const MgDist* h) { return h ? h->exchanges : 0; }
 
 namespace {
-void halo(MgDist* h, int l, REAL_TYPE* X) {
-  fatal_if(!comm_halo(h->comm[l], X, nullptr, stream()), "face exchange");
-  h->exchanges++;
-}
-void halo_full(MgDist* h, int l, REAL_TYPE* X) {
-  fatal_if(!comm_halo_full(h->comm[l], X, stream()), "face + edge + corner exchange");
-  h->exchanges++;
-}
+// the operations of mg_walk on the distributed levels 0 .. G-1 (G = 0: level 0 alone).  Levels >= 1 keep b, x and a temporary t of their own;
+// level 0's b is r and its iterate is in x0, with o0 as the temporary, until the prolongation moves it to o0
+struct MgdOps {
+  MgDist* h;
+  REAL_TYPE omg;
+  const REAL_TYPE* r;
+  REAL_TYPE *x0, *o0;
 
-// level 0's sweep u -> w with the unit coefficients (the decomposed Jacobi sweep of pcg ... jacobi)
-void sweep0(MgDist* h, const REAL_TYPE* u, REAL_TYPE* w, const REAL_TYPE* b, REAL_TYPE omg) {
-  REAL_TYPE cf[7] = {1, 1, 1, 1, 1, 1, 6};
-  czhip_jacobi_async(u, w, b, h->lev[0].sz, h->lev[0].idx, GUIDE, cf, omg, h->res, 0, nullptr);
-}
-
-// x_l = V_l(b_l) on the global copy, l >= G: the single-domain level kernels (czhip_mg_apply_async's mg_cycle)
-void cycle_global(MgDist* h, int l, REAL_TYPE omg) {
-  const MgdLevel& L = h->glev[l];
-  REAL_TYPE *b = h->gb[l], *x = h->gx[l], *t = h->gt[l];
-  if (h->tail && czhip_mg_tail_async(x, b, L.sz, L.idx, GUIDE, l, h->n0, omg)) return;
-  auto smooth = [&](const REAL_TYPE* u, REAL_TYPE* w) { fatal_if(!czhip_mg_smooth_async(u, w, b, L.sz, L.idx, GUIDE, l, h->n0, omg), "smooth"); };
-  if (l == h->nlev - 1) {  // the coarsest level: 8 sweeps from zero
-    smooth(nullptr, t);
-    for (int s = 1; s < 8; s++) smooth((s & 1) ? t : x, (s & 1) ? x : t);
-    return;
+  REAL_TYPE* x(int l) { return l ? h->x[l] : x0; }
+  const REAL_TYPE* b(int l) { return l ? h->b[l] : r; }
+  void halo(int l, REAL_TYPE* X) {
+    fatal_if(!comm_halo(h->comm[l], X, nullptr, stream()), "face exchange");
+    h->exchanges++;
   }
-  const MgdLevel& C = h->glev[l + 1];
-  smooth(nullptr, t);
-  smooth(t, x);
-  fatal_if(!czhip_mg_restrict_async(h->gb[l + 1], C.sz, C.idx, x, b, L.sz, L.idx, GUIDE, l, h->n0), "restrict");
-  cycle_global(h, l + 1, omg);
-  fatal_if(!czhip_mg_prolong_async(x, x, h->gx[l + 1], C.sz, C.idx, L.sz, L.idx, GUIDE, l, h->n0), "prolong");
-  smooth(x, t);
-  smooth(t, x);
-}
-
-// b_G from the restriction (in the send buffer) -> every rank's global copy -> x_G
-void gather_and_cycle(MgDist* h, REAL_TYPE omg) {
-  const int G = h->G;
-  fatal_if(!comm_allgather(h->comm[0], h->send, h->recv, h->blk_max, stream()), "all-gather");
-  h->exchanges++;
-  for (int r = 0; r < h->nproc; r++)
-    fatal_if(!mgd_unpack_async(h->gb[G], h->glev[G], h->recv + (size_t)r * h->blk_max, &h->bo[3 * r], &h->bc[3 * r]), "unpack");
-  cycle_global(h, G, omg);
-}
-
-// the coarse iterate of level l+1 (distributed or gathered) and its geometry, for the prolongation to level l
-void coarse_of(MgDist* h, int l, const REAL_TYPE** xc, const MgdLevel** C) {
-  if (l + 1 < h->G) {
-    halo_full(h, l + 1, h->x[l + 1]);  // parents on the - neighbours
-    *xc = h->x[l + 1], *C = &h->lev[l + 1];
-  } else {
-    *xc = h->gx[h->G], *C = &h->glev[h->G];
+  void halo_full(int l, REAL_TYPE* X) {
+    fatal_if(!comm_halo_full(h->comm[l], X, stream()), "face + edge + corner exchange");
+    h->exchanges++;
   }
-}
+  // w = one sweep from u, after a face exchange of u (zero: u is zero, nothing to exchange).  Level 0: the decomposed Jacobi sweep of
+  // pcg ... jacobi with the unit coefficients, which reads the zeros from u
+  void sweep(int l, REAL_TYPE* u, REAL_TYPE* w, bool zero) {
+    if (!zero) halo(l, u);
+    REAL_TYPE cf[7] = {1, 1, 1, 1, 1, 1, 6};
+    if (l == 0) czhip_jacobi_async(u, w, r, h->lev[0].sz, h->lev[0].idx, GUIDE, cf, omg, h->res, 0, nullptr);
+    else fatal_if(!mg_smooth_async(zero ? nullptr : u, w, h->b[l], h->lev[l], omg), "smooth");
+  }
 
-// b_{l+1} (distributed, or level G's block) = restricted residual of x_l; x's faces are current
-void restrict_down(MgDist* h, int l, const REAL_TYPE* x, const REAL_TYPE* b) {
-  const MgdLevel& F = h->lev[l];
-  fatal_if(!mgd_resface_async(h->rt[l], x, b, F, h->minus[l]), "residual of the - faces");
-  halo_full(h, l, h->rt[l]);  // children on the + neighbours
-  if (l + 1 < h->G) fatal_if(!mgd_restrict_async(h->b[l + 1], h->lev[l + 1], x, b, h->rt[l], F), "restrict");
-  else fatal_if(!mgd_restrict_async(h->send, h->blk, x, b, h->rt[l], F), "restrict into the gathered level");
-}
-
-// x_l = V_l(b_l), 1 <= l < G
-void cycle_dist(MgDist* h, int l, REAL_TYPE omg) {
-  const MgdLevel& L = h->lev[l];
-  REAL_TYPE *b = h->b[l], *x = h->x[l], *t = h->t[l];
-  auto smooth = [&](const REAL_TYPE* u, REAL_TYPE* w) { fatal_if(!mgd_smooth_async(u, w, b, L, omg), "smooth"); };
-  smooth(nullptr, t);
-  halo(h, l, t);
-  smooth(t, x);
-  halo(h, l, x);
-  restrict_down(h, l, x, b);
-  if (l + 1 < h->G) cycle_dist(h, l + 1, omg);
-  else gather_and_cycle(h, omg);
-  const REAL_TYPE* xc;
-  const MgdLevel* C;
-  coarse_of(h, l, &xc, &C);
-  fatal_if(!mgd_prolong_async(x, x, xc, *C, L), "prolong");
-  halo(h, l, x);
-  smooth(x, t);
-  halo(h, l, t);
-  smooth(t, x);
-}
+  // level G: b_G from the restriction (in the send buffer) -> every rank's copy of the whole level -> x_G by the single-domain cycle
+  bool whole(int l) {
+    if (!h->g || l < h->G) return false;
+    fatal_if(!comm_allgather(h->comm[0], h->send, h->recv, h->blk_max, stream()), "all-gather");
+    h->exchanges++;
+    for (int q = 0; q < h->nproc; q++)
+      fatal_if(!mgd_unpack_async(h->g->b[l], h->g->lev[l], h->recv + (size_t)q * h->blk_max, &h->bo[3 * q], &h->bc[3 * q]), "unpack");
+    fatal_if(!mg_cycle_async(h->g, omg), "the cycle of the gathered levels");
+    return true;
+  }
+  void pair(int l, bool zero) {
+    REAL_TYPE* const t = l ? h->t[l] : o0;
+    sweep(l, x(l), t, zero);
+    sweep(l, t, x(l), false);
+  }
+  // b_{l+1} (distributed, or level G's block) = the restricted residual of x_l; the children on the + neighbours come from rt
+  void restrict_down(int l) {
+    halo(l, x(l));
+    fatal_if(!mgd_resface_async(h->rt[l], x(l), b(l), h->lev[l], h->minus), "residual of the - faces");
+    halo_full(l, h->rt[l]);
+    const bool dist = l + 1 < h->G;
+    fatal_if(!mg_restrict_async(dist ? h->b[l + 1] : h->send, dist ? h->lev[l + 1] : h->blk, x(l), b(l), h->rt[l], h->lev[l]), "restrict");
+  }
+  // the parents: level l+1's iterate after its exchange (parents on the - neighbours), or the gathered level
+  void prolong_up(int l) {
+    const bool dist = l + 1 < h->G;
+    if (dist) halo_full(l + 1, h->x[l + 1]);
+    REAL_TYPE* const u = l ? h->x[l] : o0;
+    fatal_if(!mg_prolong_async(u, x(l), dist ? h->x[l + 1] : h->g->x[l + 1], dist ? h->lev[l + 1] : h->g->lev[l + 1], h->lev[l]), "prolong");
+    if (l == 0) std::swap(x0, o0);
+  }
+};
 }  // namespace
 
 // z = V_0(r) on this rank's brick; collective.  r's ghost cells are not read.
 int mgd_apply(MgDist* h, REAL_TYPE* z, const REAL_TYPE* r, REAL_TYPE omg) {
   if (!h || !z || !r || z == r) return 0;
   h->exchanges = 0;
-  REAL_TYPE* const tmp = h->tmp0;
+  // level 0's iterate ends in z: it starts there where nothing moves it (level 0 the coarsest), else in the temporary.  The array it starts
+  // in is cleared for the sweep from zero; the other one is written on its owned points and rank-internal ghost cells only, so tmp0's
+  // physical faces keep the zeros of its allocation, as z's do by the caller's contract
+  const bool stays = h->nlev == 1;
+  MgdOps ops{h, omg, r, stays ? z : h->tmp0, stays ? h->tmp0 : z};
   const MgdLevel& F = h->lev[0];
-  const size_t nbytes = (size_t)(F.sz[0] + 2 * GUIDE) * (F.sz[1] + 2 * GUIDE) * (F.sz[2] + 2 * GUIDE) * sizeof(REAL_TYPE);
-  HIP_CHECK(hipMemsetAsync(tmp, 0, nbytes, stream()));
-  if (h->nlev == 1) {  // level 0 is already the coarsest: 8 sweeps from zero
-    sweep0(h, tmp, z, r, omg);
-    for (int s = 1; s < 8; s++) {
-      REAL_TYPE* u = (s & 1) ? z : tmp;
-      halo(h, 0, u);
-      sweep0(h, u, (s & 1) ? tmp : z, r, omg);
-    }
-    HIP_CHECK(hipMemcpyAsync(z, tmp, nbytes, hipMemcpyDeviceToDevice, stream()));  // (the eighth sweep wrote tmp)
-    return 1;
-  }
-  sweep0(h, tmp, z, r, omg);  // x = 2 sweeps from zero (in tmp)
-  halo(h, 0, z);
-  sweep0(h, z, tmp, r, omg);
-  halo(h, 0, tmp);
-  restrict_down(h, 0, tmp, r);
-  if (h->G > 1) cycle_dist(h, 1, omg);
-  else gather_and_cycle(h, omg);
-  const REAL_TYPE* xc;
-  const MgdLevel* C;
-  coarse_of(h, 0, &xc, &C);
-  fatal_if(!mgd_prolong_async(z, tmp, xc, *C, F), "prolong");  // u = x + R(alpha x_1(parent)), in z
-  halo(h, 0, z);
-  sweep0(h, z, tmp, r, omg);  // x = 2 sweeps from u
-  halo(h, 0, tmp);
-  sweep0(h, tmp, z, r, omg);
+  HIP_CHECK(hipMemsetAsync(ops.x0, 0, (size_t)(F.sz[0] + 2 * GUIDE) * (F.sz[1] + 2 * GUIDE) * (F.sz[2] + 2 * GUIDE) * sizeof(REAL_TYPE), stream()));
+  mg_walk(ops, 0, h->nlev - 1);
   return 1;
 }

@@ -179,3 +179,9 @@ def mg_gather_level(gsz, div, gather_points: int = MG_GATHER_DEFAULT, prec: str 
         if empty or dims[lev][0] * dims[lev][1] * dims[lev][2] <= gather_points:
             return lev
     return len(dims) - 1
+
+
+def mg_exchanges(gather_level: int) -> int:
+    """halo exchanges + all-gathers of one distributed V-cycle (cz_info 18): 6 per distributed level, 7 where level 0 is the coarsest
+    (G = 0).  DESIGN.md §5.10.1, "Exchanges per V-cycle", derives the count from the order of the cycle"""
+    return 6 * gather_level if gather_level else 7

@@ -64,16 +64,30 @@ def rank_main(rank, world, outdir, n):
     lib.cz_comm_shutdown()
 
 
-def single(n, pc, itmax):
+def single(n, pc, itmax, prec="f64"):
     from cubez_amd import CZ
     out = []
     for _ in range(2):  # the second solve is reported (the first one pays the launches' first-use costs)
-        cz = CZ("f64", quiet=True)
+        cz = CZ(prec, quiet=True)
         assert cz.setup([n, n, n, "pcg", itmax, 0.8, pc]) == 1
         itr = cz.solve()
         out.append((itr, cz.lib.cz_last_solve_seconds(cz.h)))
         cz.close()
     return out[-1]
+
+
+def level_kernels(n, prec):
+    """HIP-event time of the level kernels over one solve: label -> (launches, ms per launch)"""
+    from cubez_amd import CZ
+    cz = CZ(prec, quiet=True)
+    assert cz.setup([n, n, n, "pcg", 1000, 0.8, "mg"]) == 1
+    cz.solve()
+    cz.timing(True)
+    cz.solve()
+    out = {k: cz.timing_read(k) for k in ("mg_smooth", "mg_restrict", "mg_prolong", "mg_tail")}
+    cz.timing(False)
+    cz.close()
+    return {k: (c, ms / max(c, 1)) for k, (c, ms) in out.items()}
 
 
 def bytes_model(n, div, rank):
@@ -97,12 +111,15 @@ def main():
     from test_gpu_rccl import rank_env
     lines = []
     P = lines.append
-    P("single domain, FP64, coefficient 0.8, eps 1e-5 (second of two solves, cz_last_solve_seconds)")
+    P("single domain, coefficient 0.8, eps 1e-5 (second of two solves, cz_last_solve_seconds)")
     for n, itmax in ((128, 1000), (512, 1000)):
-        for pc in ("mg", "jacobi"):
-            itr, s = single(n, pc, itmax if pc == "mg" or n == 128 else 40)
-            P(f"  {n}^3 pcg {pc:6s}: {itr:4d} iterations{' (ItrMax 40)' if pc == 'jacobi' and n == 512 else ''}  {s * 1e3:9.2f} ms  "
+        for pc, prec in (("mg", "f64"), ("jacobi", "f64"), ("mg", "f32")):
+            itr, s = single(n, pc, itmax if pc == "mg" or n == 128 else 40, prec)
+            P(f"  {n}^3 {prec} pcg {pc:6s}: {itr:4d} iterations{' (ItrMax 40)' if pc == 'jacobi' and n == 512 else ''}  {s * 1e3:9.2f} ms  "
               f"{s / itr * 1e3:8.3f} ms/iteration")
+    for prec in ("f64", "f32"):
+        P(f"  512^3 {prec} pcg mg, ms per launch (launches): "
+          + ", ".join(f"{k} {ms:.4f} ({c})" for k, (c, ms) in level_kernels(512, prec).items()))
     n = 128
     with tempfile.TemporaryDirectory(prefix="cz_mgd_") as out:
         procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "rank", str(r), "2", out, str(n)], env=rank_env(r),
