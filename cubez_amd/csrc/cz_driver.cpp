@@ -61,6 +61,7 @@ const char* printMethod(int t) {
     case LS_BICGSTAB_MAF: return "PBiCGSTAB_MAF";
     case LS_PCG: return "PCG";
     case LS_MG: return "MG";
+    case LS_MGRB: return "MGRB";
     default: return "NONE";
   }
 }
@@ -220,6 +221,7 @@ void CZ::setLS(const char* q) {
     if (!strcasecmp(precon.c_str(), "none")) pc_type = LS_NONE;
     else if (!strcasecmp(precon.c_str(), "jacobi")) pc_type = LS_JACOBI;
     else if (!strcasecmp(precon.c_str(), "mg")) pc_type = LS_MG;
+    else if (!strcasecmp(precon.c_str(), "mgrb")) pc_type = LS_MGRB;
     else {
       Hostonly_ printf("Invalid preconditioner for pcg '%s' (none | jacobi)\n", precon.c_str());
       exit(0);
@@ -228,6 +230,20 @@ void CZ::setLS(const char* q) {
     if (pc_type == LS_MG && !(ac1 > (REAL_TYPE)0 && ac1 <= (REAL_TYPE)1)) {
       Hostonly_ printf("Invalid coefficient for pcg with mg '%g' (0 < coef <= 1: a symmetric definite preconditioner)\n", (double)ac1);
       exit(0);
+    }
+    // the red-black V-cycle is symmetric by its colour order; definite as far as the Ritz estimates of M A were taken
+    if (pc_type == LS_MGRB && !(ac1 > (REAL_TYPE)0 && ac1 <= (REAL_TYPE)1.2)) {
+      Hostonly_ printf("Invalid coefficient for pcg with mgrb '%g' (0 < coef <= 1.2: a symmetric definite preconditioner)\n", (double)ac1);
+      exit(0);
+    }
+    // under a cut a colour sweep needs an exchange per colour and the two-iteration pass four ghost layers: not built
+    if (pc_type == LS_MGRB && numProc > 1) {
+      Hostonly_ printf("pcg with mgrb runs on a single domain only (%d ranks); use mg\n", numProc);
+      fflush(stdout);
+      // ranks may be threads of one process that all arrive here with the GPU open: no exit handlers (as cz_fatal_quick), and the ranks that
+      // print nothing leave the process to rank 0 for a moment, so that its line is out before the first of them ends it
+      if (myRank != 0) sleep(2);
+      _exit(0);
     }
     // k relaxed Jacobi sweeps from zero are a polynomial in A: symmetric, and definite with A's sign for 0 < omega <= 1
     if (pc_type == LS_JACOBI && !(ac1 > (REAL_TYPE)0 && ac1 <= (REAL_TYPE)1)) {
@@ -369,10 +385,10 @@ int CZ::Setup(int argc, char** argv) {
     pcg_r0 = czhip_alloc_s3d(size), pcg_q = czhip_alloc_s3d(size), pcg_s = czhip_alloc_s3d(size);
     pcg_s_ = czhip_alloc_s3d(size), pcg_t_ = czhip_alloc_s3d(size);
   }
-  const int narr = bicg ? 11 : ls_type == LS_PCG ? (pc_type == LS_JACOBI ? 8 : pc_type == LS_MG ? 9 : 7) : 3;
+  const int narr = bicg ? 11 : ls_type == LS_PCG ? (pc_type == LS_JACOBI ? 8 : pc_type == LS_MG || pc_type == LS_MGRB ? 9 : 7) : 3;
   if (ls_type == LS_PCG) {  // zero-filled; only their inner boxes are ever written (the fused passes read the shells as zeros)
     cg_r = czhip_alloc_s3d(size), cg_q = czhip_alloc_s3d(size), cg_p[0] = czhip_alloc_s3d(size), cg_p[1] = czhip_alloc_s3d(size);
-    if (pc_type == LS_JACOBI || pc_type == LS_MG) cg_z = czhip_alloc_s3d(size);
+    if (pc_type == LS_JACOBI || pc_type == LS_MG || pc_type == LS_MGRB) cg_z = czhip_alloc_s3d(size);
     // (a decomposed run: the distributed cycle, DESIGN.md §5.10 "Decomposed runs"; the coefficients are the unit ones of the command line)
     if (pc_type == LS_MG && numProc > 1 && !(mgd = mgd_create(*this, comm, cfg.num(CZV_MG_GATHER, 32768), cfg.on(CZV_MG_TAIL, true)))) {
       Hostonly_ printf("pcg with mg: the distributed V-cycle could not be set up\n");
@@ -382,13 +398,17 @@ int CZ::Setup(int argc, char** argv) {
       Hostonly_ printf("pcg with mg: unsupported coefficients (c1 .. c6 = 1, dd = 6 only)\n");
       return 0;
     }
+    if (pc_type == LS_MGRB && !(mg = czhip_mg_create_rb(size, innerFidx, GUIDE, cf))) {
+      Hostonly_ printf("pcg with mgrb: unsupported coefficients (c1 .. c6 = 1, dd = 6 only)\n");
+      return 0;
+    }
   }
   if (!quiet) Hostonly_ {
     const double arr = (double)(size[0] + 2 * gc) * (size[1] + 2 * gc) * (size[2] + 2 * gc) * sizeof(REAL_TYPE);
     printf("\n----------\n\n\tDevice memory per rank : %.1f MiB in %d arrays of (%d+4)x(%d+4)x(%d+4) %s\n", arr *
            narr / 1048576.0, narr, size[0], size[1], size[2],
            sizeof(REAL_TYPE) == 4 ? "float" : "double");
-    if (mg) printf("\tMultigrid levels       : %d (coarse arrays about 3/7 of one array more)\n", czhip_mg_levels(mg));
+    if (mg) printf("\tMultigrid levels       : %d (coarse arrays about %s of one array more)\n", czhip_mg_levels(mg), pc_type == LS_MGRB ? "2/7" : "3/7");
     if (mgd) printf("\tMultigrid levels       : %d, gathered from level %d on\n", mgd_levels(mgd), mgd_gather_level(mgd));
   }
 
@@ -1520,7 +1540,7 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   hipStream_t st = stream();
   const size_t nbytes = (size_t)(size[0] + 2 * gc) * (size[1] + 2 * gc) * (size[2] + 2 * gc) * sizeof(REAL_TYPE);
   const double n = npts();
-  const bool pc = pc_type == LS_JACOBI || pc_type == LS_MG;
+  const bool pc = pc_type == LS_JACOBI || pc_type == LS_MG || pc_type == LS_MGRB;
   const bool fuse = cfg.on(CZV_CG_FUSE, true);
   const bool fuse_dir = fuse && numProc == 1;  // the direction pass reads z's and p's shells as zeros: single domain only
   REAL_TYPE* const sc = reinterpret_cast<REAL_TYPE*>(d_res + 12);  // alpha, -alpha, beta, rho (cg_scal_k)
@@ -1651,6 +1671,7 @@ void CZ::WriteProfile(FILE* fp) const {
       {"MG Jacobi sweep (coarse level)", "mg_smooth", 0.0},
       {"MG prolongation", "mg_prolong", 0.0},
       {"MG tail (coarse levels in LDS)", "mg_tail", 0.0},
+      {"MG red-black colour sweep (coarse level)", "mg_rb", 0.0},
   };
   char host[256] = "unknown";
   gethostname(host, sizeof(host) - 1);
@@ -1862,6 +1883,7 @@ int cz_info(const cz_handle* h, int what) {
     case 16: return c.mg_cycles;
     case 17: return mgd_gather_level(c.mgd);
     case 18: return mgd_exchanges(c.mgd);
+    case 19: return c.mg ? czhip_mg_kind(c.mg) : c.mgd ? 1 : 0;
     case 5: return comm_transport_ranks(c.comm);
     case 6: return c.comm_cus;
     case 7: return c.last_plan.kind;

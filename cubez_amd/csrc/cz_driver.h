@@ -15,7 +15,7 @@ typedef CZ_REAL REAL_TYPE;  // cz_Define.h:28-37
 #define GUIDE 2             // cz_Define.h:40
 
 // cz_Define.h:68-89 (only the solvers of the hot path are accepted; the others are rejected by setLS)
-enum LinearSolver { LS_NONE = 0, LS_PSOR = 1, LS_SOR2SMA, LS_BICGSTAB, LS_JACOBI, LS_PCR = 5, LS_PCR_EDA, LS_PCR_ESA, LS_PCR_RB, LS_PCR_RB_ESA, LS_PCR_J_ESA, LS_PSOR_MAF = 11, LS_SOR2SMA_MAF, LS_BICGSTAB_MAF, LS_JACOBI_MAF, LS_PCR_MAF, LS_PCR_EDA_MAF, LS_PCR_ESA_MAF, LS_PCR_RB_MAF, LS_PCR_RB_ESA_MAF, LS_PCG, LS_MG };  // (LS_PCG, LS_MG: beyond the reference)
+enum LinearSolver { LS_NONE = 0, LS_PSOR = 1, LS_SOR2SMA, LS_BICGSTAB, LS_JACOBI, LS_PCR = 5, LS_PCR_EDA, LS_PCR_ESA, LS_PCR_RB, LS_PCR_RB_ESA, LS_PCR_J_ESA, LS_PSOR_MAF = 11, LS_SOR2SMA_MAF, LS_BICGSTAB_MAF, LS_JACOBI_MAF, LS_PCR_MAF, LS_PCR_EDA_MAF, LS_PCR_ESA_MAF, LS_PCR_RB_MAF, LS_PCR_RB_ESA_MAF, LS_PCG, LS_MG, LS_MGRB };  // (LS_PCG, LS_MG, LS_MGRB: beyond the reference)
 
 // CB_Define_stub.h:64-70 / cz_fparam.fi:10-16
 enum { I_minus = 0, I_plus, J_minus, J_plus, K_minus, K_plus };
@@ -58,7 +58,7 @@ class CZ {
             *pcg_s_ = nullptr, *pcg_t_ = nullptr;
   // PCG's work vectors (the pcg_* above are BiCGSTAB's, named as in the reference); allocated only when pcg is selected
   REAL_TYPE *cg_r = nullptr, *cg_z = nullptr, *cg_p[2] = {nullptr, nullptr}, *cg_q = nullptr;
-  cz_mg* mg = nullptr;           // the multigrid hierarchy of pcg ... mg, allocated only then
+  cz_mg* mg = nullptr;           // the multigrid hierarchy of pcg ... mg | mgrb, allocated only then
   struct MgDist* mgd = nullptr;  // decomposed runs: the distributed V-cycle of pcg ... mg instead (cz_mg_dist.cpp)
 
   // ---- build-specific state

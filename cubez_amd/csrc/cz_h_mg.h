@@ -40,8 +40,9 @@ MgdLevel mg_array_level(const int* sz, const int* idx, int g, int level, const i
   return M;
 }
 
-// the LDS layout of the levels from fine (level l) down to the coarsest: one zero shell per array, b, x, t per level
-bool mg_tail_plan(MgTail& T, const MgLev& fine, REAL omg) {
+// the LDS layout of the levels from fine (level l) down to the coarsest: one zero shell per array, b, x, t per level (rb: b and x, the
+// red-black iterations run in place)
+bool mg_tail_plan(MgTail& T, const MgLev& fine, REAL omg, bool rb = false) {
   T = MgTail();
   T.gl = fine, T.omg = omg;
   const int n[3] = {fine.ni, fine.nj, fine.nk};
@@ -54,19 +55,21 @@ bool mg_tail_plan(MgTail& T, const MgLev& fine, REAL omg) {
     s.nip = s.ni + 2, s.nkp = s.nk + 2, s.i0 = s.j0 = s.k0 = 1;
     T.len[m] = (s.ni + 2) * (s.nj + 2) * (s.nk + 2);
     T.off[m] = T.total;
-    T.total += 3 * T.len[m];
+    T.total += (rb ? 2 : 3) * T.len[m];
     if ((long long)T.total * (long long)sizeof(REAL) > 160 * 1024) return false;
   }
   return true;
 }
 
+template <bool RB>
 void mg_tail_launch(REAL* x, const REAL* b, const MgTail& T) {
   ScopedTimer tm(LBL_MG_TAIL);
   const int bytes = T.total * (int)sizeof(REAL);
-  if (bytes > 64 * 1024) allow_dynamic_lds(&mg_tail_k, 160 * 1024);
-  hipLaunchKernelGGL(mg_tail_k, dim3(1), dim3(MG_TAIL_THREADS), bytes, ctx.stream, x, b, T);
+  if (bytes > 64 * 1024) allow_dynamic_lds(&mg_tail_k<RB>, 160 * 1024);
+  hipLaunchKernelGGL((mg_tail_k<RB>), dim3(1), dim3(MG_TAIL_THREADS), bytes, ctx.stream, x, b, T);
   HIP_CHECK(hipGetLastError());
 }
+void mg_tail_launch(REAL* x, const REAL* b, const MgTail& T, bool rb) { rb ? mg_tail_launch<true>(x, b, T) : mg_tail_launch<false>(x, b, T); }
 
 dim3 mg_grid(const MgLev& L) { return dim3((unsigned)((L.nk + 63) / 64), (unsigned)((L.ni + 3) / 4), (unsigned)L.nj); }
 }  // namespace
@@ -80,6 +83,20 @@ int mg_smooth_async(const REAL* u, REAL* w, const REAL* b, const MgdLevel& M, RE
   ScopedTimer tm(LBL_MG_SMOOTH);
   if (u) hipLaunchKernelGGL((mg_smooth_k<false>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, u, w, b, D, omg);
   else hipLaunchKernelGGL((mg_smooth_k<true>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, w, w, b, D, omg);
+  HIP_CHECK(hipGetLastError());
+  return 1;
+}
+
+// (a whole level only: the colour is that of the global index, and a cut would need an exchange per colour)
+int mg_rb_async(REAL* x, const REAL* b, const MgdLevel& M, REAL omg, int colour, int zero) {
+  MgDLev D;
+  if (!x || !b || x == b || !mg_lev(D, M) || M.dense || !mg_whole(D) || M.level < 1 || (colour | 1) != 1 || zero < 0 || zero > 2) return 0;
+  if (mg_none(D)) return 1;
+  ScopedTimer tm(LBL_MG_RB);
+  const dim3 grid((unsigned)(((D.L.nk + 1) / 2 + 63) / 64), (unsigned)((D.L.ni + 3) / 4), (unsigned)D.L.nj);
+  if (zero == 0) hipLaunchKernelGGL((mg_rb_k<0>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
+  else if (zero == 1) hipLaunchKernelGGL((mg_rb_k<1>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
+  else hipLaunchKernelGGL((mg_rb_k<2>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
   HIP_CHECK(hipGetLastError());
   return 1;
 }
@@ -157,15 +174,30 @@ int czhip_mg_tail_async(CZ_REAL* x, const CZ_REAL* b, const int* sz, const int* 
   MgDLev D;
   MgTail T;
   if (!x || !b || x == b || !mg_lev(D, mg_array_level(sz, idx, g, level, n0)) || !mg_tail_plan(T, D.L, omg)) return 0;
-  mg_tail_launch(x, b, T);
+  mg_tail_launch(x, b, T, false);
+  return 1;
+}
+
+int czhip_mg_rb_async(CZ_REAL* x, const CZ_REAL* b, const int* sz, const int* idx, int g, int level, const int* n0, CZ_REAL omg, int colour, int zero) {
+  ensure_init();
+  return czhip_internal::mg_rb_async(x, b, mg_array_level(sz, idx, g, level, n0), omg, colour, zero);
+}
+
+int czhip_mg_tail_rb_async(CZ_REAL* x, const CZ_REAL* b, const int* sz, const int* idx, int g, int level, const int* n0, CZ_REAL omg) {
+  ensure_init();
+  MgDLev D;
+  MgTail T;
+  if (!x || !b || x == b || level < 1 || !mg_lev(D, mg_array_level(sz, idx, g, level, n0)) || !mg_tail_plan(T, D.L, omg, true)) return 0;
+  mg_tail_launch(x, b, T, true);
   return 1;
 }
 }  // extern "C"
 
 // ---- the hierarchy
 namespace czhip_internal {
-cz_mg* mg_create(const int* n0, int l0, bool tail, const int* sz0, const int* idx0) {
+cz_mg* mg_create(const int* n0, int l0, bool tail, const int* sz0, const int* idx0, bool rb) {
   cz_mg* h = new cz_mg();
+  h->rb = rb;
   int dims[MG_MAXLEV][3];
   h->first = l0, h->nlev = mg_level_dims(n0, dims, MG_MAXLEV - 1);
   bool ok = std::min(n0[0], std::min(n0[1], n0[2])) >= 1 && l0 >= 0 && l0 < h->nlev;
@@ -175,7 +207,8 @@ cz_mg* mg_create(const int* n0, int l0, bool tail, const int* sz0, const int* id
     h->lev[l] = l ? mg_array_level(sz, idx, MG_GUIDE, l, n0) : mg_array_level(sz0, idx0, MG_GUIDE, 0, n0);
     MgDLev D;
     ok = mg_lev(D, h->lev[l]);
-    if (ok && l) h->b[l] = czhip_alloc_s3d(sz), h->x[l] = czhip_alloc_s3d(sz), h->t[l] = czhip_alloc_s3d(sz);
+    if (ok && l) h->b[l] = czhip_alloc_s3d(sz), h->x[l] = czhip_alloc_s3d(sz);
+    if (ok && l && !rb) h->t[l] = czhip_alloc_s3d(sz);
   }
   if (!ok) {
     czhip_mg_destroy(h);
@@ -191,7 +224,7 @@ cz_mg* mg_create(const int* n0, int l0, bool tail, const int* sz0, const int* id
     MgDLev D;
     MgTail T;
     mg_lev(D, h->lev[l]);
-    if (mg_tail_plan(T, D.L, (REAL)1)) {
+    if (mg_tail_plan(T, D.L, (REAL)1, rb)) {
       h->tail_from = l;
       break;
     }
@@ -201,17 +234,27 @@ cz_mg* mg_create(const int* n0, int l0, bool tail, const int* sz0, const int* id
 }  // namespace czhip_internal
 
 extern "C" {
-cz_mg* czhip_mg_create(const int* sz, const int* idx, int g, const CZ_REAL* cf) {
+}  // extern "C"
+namespace {
+cz_mg* mg_create_public(const int* sz, const int* idx, int g, const CZ_REAL* cf, bool rb) {
   ensure_init();
   if (g != MG_GUIDE) return nullptr;  // (the coarse arrays and the temporary are S3D arrays: guide 2)
   for (int c = 0; c < 6; c++)
     if (cf[c] != (REAL)1) return nullptr;
   if (cf[6] != (REAL)6) return nullptr;
   const int n0[3] = {idx[1] - idx[0] + 1, idx[3] - idx[2] + 1, idx[5] - idx[4] + 1};
-  return czhip_internal::mg_create(n0, 0, CzConfig::from_env().on(CZV_MG_TAIL, true), sz, idx);
+  const CzConfig cfg = CzConfig::from_env();
+  cz_mg* h = czhip_internal::mg_create(n0, 0, cfg.on(CZV_MG_TAIL, true), sz, idx, rb);
+  if (h) h->zero4 = cfg.on(CZV_MGRB_ZERO4, true);  // (measured: profiles/r12/mgrb.txt)
+  return h;
 }
+}  // namespace
+extern "C" {
+cz_mg* czhip_mg_create(const int* sz, const int* idx, int g, const CZ_REAL* cf) { return mg_create_public(sz, idx, g, cf, false); }
+cz_mg* czhip_mg_create_rb(const int* sz, const int* idx, int g, const CZ_REAL* cf) { return mg_create_public(sz, idx, g, cf, true); }
 
 int czhip_mg_levels(const cz_mg* h) { return h ? h->nlev : 0; }
+int czhip_mg_kind(const cz_mg* h) { return h ? 1 + h->rb : 0; }
 
 void czhip_mg_destroy(cz_mg* h) {
   if (!h) return;
@@ -258,15 +301,56 @@ struct MgOps {
     MgDLev D;
     MgTail T;
     mg_lev(D, h->lev[l]);
-    mg_tail_plan(T, D.L, omg);
-    mg_tail_launch(h->x[l], h->b[l], T);
+    mg_tail_plan(T, D.L, omg, h->rb);
+    mg_tail_launch(h->x[l], h->b[l], T, h->rb);
     return true;
   }
   REAL* x(int l) { return l ? h->x[l] : x0; }
   static void must(int launched) {
     if (!launched) cz_fatal(1, "czhip: V-cycle: a level kernel refused its level\n");
   }
-  void pair(int l, bool zero) {
+  // ---- mgrb.  Level 0 takes the red-black passes that exist (two iterations per pass where the planner takes the box, else one per pass, else
+  // the colour sweeps in place); ofst 0 runs colour 0 first, ofst 1 colour 1.  moves: how often such a pair hands the iterate to the other array
+  int fine_rb_moves(bool zero) const {
+    const int* sz = h->lev[0].sz;
+    const int* idx = h->lev[0].idx;
+    const REAL cf[7] = {1, 1, 1, 1, 1, 1, 6};
+    if ((!zero || h->zero4) && czhip_rbsor4_async(x0, o0, r, sz, idx, MG_GUIDE, cf, 0, omg, h->res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 1)) return 1;
+    return czhip_internal::pair_probe(x0, o0, r, sz, idx, idx, MG_GUIDE, (REAL)6, 0) ? 2 : 0;
+  }
+  void fine_rb_pair(bool zero, bool post) {
+    const int* sz = h->lev[0].sz;
+    const int* idx = h->lev[0].idx;
+    const REAL cf[7] = {1, 1, 1, 1, 1, 1, 6};
+    const int ofst = post ? 1 : 0, moves = fine_rb_moves(zero);
+    if (zero && moves != 2) HIP_CHECK(hipMemsetAsync(x0, 0, (size_t)(sz[0] + 4) * (sz[1] + 4) * (sz[2] + 4) * sizeof(REAL), ctx.stream));
+    if (moves == 1) {
+      must(czhip_rbsor4_async(x0, o0, r, sz, idx, MG_GUIDE, cf, ofst, omg, h->res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 0));
+      std::swap(x0, o0);
+    } else if (moves == 2) {
+      for (int it = 0; it < 2; it++) {
+        must(zero && it == 0 ? czhip_jacobi2_from_zero_made_async(x0, o0, const_cast<REAL*>(r), 0, nullptr, nullptr, nullptr, (REAL)0, (REAL)0, sz, idx, nullptr, MG_GUIDE, cf,
+                                                                  omg, ofst, h->res, 0)
+                             : czhip_rbsor2_async(x0, o0, r, sz, idx, nullptr, MG_GUIDE, cf, ofst, omg, h->res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr));
+        std::swap(x0, o0);
+      }
+    } else {
+      for (int s = 0; s < 4; s++) czhip_rbsor_async(x0, r, sz, idx, MG_GUIDE, cf, ofst, s & 1, omg, h->res, 0, nullptr);
+    }
+  }
+  void rb_pair(int l, bool zero, bool post) {
+    if (l == 0) return fine_rb_pair(zero, post);
+    const int c0 = post ? 1 : 0;
+    for (int s = 0; s < 4; s++) must(czhip_internal::mg_rb_async(h->x[l], h->b[l], h->lev[l], omg, (c0 + s) & 1, zero && s < 2 ? s + 1 : 0));
+  }
+  // level 0's iterate must end in z: how many times the walk moves it
+  int fine_moves() const {
+    if (!h->rb) return h->nlev == 1 ? 4 : 3;
+    return h->nlev == 1 ? fine_rb_moves(true) + 3 * fine_rb_moves(false) : fine_rb_moves(true) + 1 + fine_rb_moves(false);
+  }
+
+  void pair(int l, bool zero, bool post) {
+    if (h->rb) return rb_pair(l, zero, post);
     if (l == 0) {
       mg_fine_pair(h, zero ? nullptr : x0, o0, x0, r, omg);
       std::swap(x0, o0);
@@ -296,9 +380,10 @@ extern "C" {
 int czhip_mg_apply_async(cz_mg* h, CZ_REAL* z, const CZ_REAL* r, CZ_REAL omg) {
   ensure_init();
   if (!h || h->first != 0 || !z || !r || z == r || z == h->fine_tmp) return 0;
-  // level 0's iterate changes array with every step: pair, prolongation, pair, or the coarsest level's four pairs.  The last one writes z
-  const bool four = h->nlev == 1;
-  MgOps ops{h, omg, r, four ? z : h->fine_tmp, four ? h->fine_tmp : z};
+  // level 0's iterate changes array with every step: pair, prolongation, pair, or the coarsest level's four pairs (mgrb: a pair moves it
+  // once, twice or not at all).  The last step writes z
+  MgOps ops{h, omg, r, z, h->fine_tmp};
+  if (ops.fine_moves() & 1) std::swap(ops.x0, ops.o0);
   mg_walk(ops, 0, h->nlev - 1);
   return 1;
 }

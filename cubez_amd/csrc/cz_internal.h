@@ -144,13 +144,17 @@ int mg_smooth_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const MgdLev
 // rt (nullptr where F is a whole level): the residual of the children on the + neighbours, from mgd_resface_async and its exchange
 int mg_restrict_async(CZ_REAL* bc, const MgdLevel& C, const CZ_REAL* x, const CZ_REAL* b, const CZ_REAL* rt, const MgdLevel& F);
 int mg_prolong_async(CZ_REAL* u, const CZ_REAL* x, const CZ_REAL* xc, const MgdLevel& C, const MgdLevel& F);
+// pcg ... mgrb: one colour sweep of a whole level >= 1 in place (colour = (I + J + K) & 1); zero: 0 from the iterate, 1 the first colour of an
+// iteration from zero (x not read), 2 its second colour (only the fresh colour read)
+int mg_rb_async(CZ_REAL* x, const CZ_REAL* b, const MgdLevel& L, CZ_REAL omg, int colour, int zero);
 // rt = residual of the first owned layer on the - faces flagged in minus[3]
 int mgd_resface_async(CZ_REAL* rt, const CZ_REAL* x, const CZ_REAL* b, const MgdLevel& L, const int* minus);
 // a dense block of cnt points into the global level array G (o = the block's global offset)
 int mgd_unpack_async(CZ_REAL* X, const MgdLevel& G, const CZ_REAL* blk, const int* o, const int* cnt);
 // levels l0 .. coarsest of the grid of n0 level-0 points, every level a whole array (inner box 2 .. n+1 in n+2; level 0: the caller's sz0,
-// idx0 with guide 2).  tail: run the levels that fit one workgroup's LDS in one launch.  nullptr: no such level
-cz_mg* mg_create(const int* n0, int l0, bool tail, const int* sz0 = nullptr, const int* idx0 = nullptr);
+// idx0 with guide 2).  tail: run the levels that fit one workgroup's LDS in one launch.  rb: the red-black smoother of pcg ... mgrb (level 0 on
+// a single domain only).  nullptr: no such level
+cz_mg* mg_create(const int* n0, int l0, bool tail, const int* sz0 = nullptr, const int* idx0 = nullptr, bool rb = false);
 int mg_cycle_async(cz_mg* h, CZ_REAL omg);  // x[first] = V_first(b[first]) of a hierarchy with first >= 1 (0: refused)
 }  // namespace czhip_internal
 
@@ -162,6 +166,8 @@ struct cz_mg {
   CZ_REAL* fine_tmp = nullptr;  // level 0: the second array its iterate alternates with
   double* res = nullptr;        // the sums the level-0 sweeps write (unused)
   int tail_from = 0;            // first level run by mg_tail_k (nlev: none)
+  int rb = 0;                   // the smoother: 0 relaxed Jacobi (mg), 1 symmetric red-black (mgrb; t stays unallocated)
+  int zero4 = 0;                // mgrb, level 0: the two iterations from zero as one two-iteration pass over a cleared array (CZ_MGRB_ZERO4)
 };
 
 #endif

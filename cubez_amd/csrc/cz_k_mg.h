@@ -57,11 +57,12 @@ __device__ __forceinline__ REAL mg_ss(const REAL* u, const MgLev& L, const MgW& 
 }
 
 // one relaxed Jacobi sweep at a point (cz_solver.f90:334-351 with the level's weights): pn = pp + ((ss - bb)/D - pp) omg, IEEE division
-template <bool ZERO>
+// (ZPP: the point's own value is a literal zero although its neighbours are read -- the second colour of a red-black iteration from zero)
+template <bool ZERO, bool ZPP = ZERO>
 __device__ __forceinline__ REAL mg_sweep_pt(const REAL* u, const REAL* b, const MgLev& L, int I, int J, int K, REAL omg, MgG o = MgG{0, 0, 0}) {
   const MgW w = mg_weights(L, I + o.i, J + o.j, K + o.k);
   const long long p = mg_at(L, I, J, K);
-  const REAL pp = ZERO ? (REAL)0 : u[p];
+  const REAL pp = ZPP ? (REAL)0 : u[p];
   const REAL ss = mg_ss<ZERO>(u, L, w, p);
   const REAL dp = ((ss - b[p]) / w.d - pp) * omg;
   return pp + dp;
@@ -128,6 +129,24 @@ __global__ void __launch_bounds__(256) mg_smooth_k(const REAL* __restrict__ u, R
   w[mg_at(D.L, I, J, K)] = mg_sweep_pt<ZERO>(u, b, D.L, I, J, K, omg, D.o);
 }
 
+// ---- pcg ... mgrb: one colour sweep of a level >= 1, IN PLACE.  The colour of a point is (I + J + K) & 1; the points of
+// one colour read only points of the other one (and their own value), so the sweep is deterministic in place.  One thread per UPDATED point:
+// thread kk of row (I, J) owns K = 2 kk + ((I + J + c) & 1).  A workgroup is (64, 4) with one row per wave, so that offset is wave-uniform and
+// the colour c a launch argument: no lane selects operands.  Z: 0 = from the iterate; 1 = the first colour of an iteration from zero (x is not
+// read); 2 = its second colour (reads the freshly written colour, its own value is a literal zero).  The same bits as a sweep from a cleared x.
+template <int Z>
+__device__ __forceinline__ REAL mg_rb_pt(const REAL* x, const REAL* b, const MgLev& L, int I, int J, int K, REAL omg) {
+  return mg_sweep_pt<Z == 1, Z != 0>(x, b, L, I, J, K, omg);
+}
+
+template <int Z>
+__global__ void __launch_bounds__(256) mg_rb_k(REAL* x, const REAL* __restrict__ b, MgLev L, REAL omg, int c) {
+  const int I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
+  const int K = 2 * (blockIdx.x * 64 + threadIdx.x) + ((I + J + c) & 1);
+  if (K >= L.nk || I >= L.ni) return;
+  x[mg_at(L, I, J, K)] = mg_rb_pt<Z>(x, b, L, I, J, K, omg);
+}
+
 // bc (owned coarse points) = the children's residual tree; owned children computed here, children on the + neighbours (the brick's
 // ghost layer) read from rt after its exchange.  C.L may be a dense block (no shell): the gathered level's send buffer.  DIST = false: the
 // domain owns the whole level (offsets 0, global extents = the local ones, rt not read) -- the same text with those constants folded in,
@@ -188,7 +207,7 @@ struct MgTail {
   int nlev;                // levels t .. t + nlev - 1 (the last is the coarsest)
   MgLev gl;                // the global arrays of level t (b read, x written)
   MgLev s[MG_TAIL_MAXLEV];      // the LDS arrays of every tail level (one zero shell)
-  int off[MG_TAIL_MAXLEV];      // REAL offset of level m's b in LDS; x and t follow at + len[m], + 2 len[m]
+  int off[MG_TAIL_MAXLEV];      // REAL offset of level m's b in LDS; x and t follow at + len[m], + 2 len[m] (mgrb: no t)
   int len[MG_TAIL_MAXLEV];      // REALs per LDS array of level m
   int total;               // REALs of LDS in all
   REAL omg;
@@ -204,6 +223,44 @@ __device__ __forceinline__ void mg_each(const MgLev& L, F f) {
   }
 }
 
+// the points of colour c of level L, by the workgroup (K = 2 kk + the row's offset)
+template <class F>
+__device__ __forceinline__ void mg_each_colour(const MgLev& L, int c, F f) {
+  const int nh = (L.nk + 1) / 2, n = L.ni * L.nj * nh;
+  for (int q = threadIdx.x; q < n; q += blockDim.x) {
+    const int kk = q % nh, r = q / nh, I = r % L.ni, J = r / L.ni;
+    const int K = 2 * kk + ((I + J + c) & 1);
+    if (K < L.nk) f(I, J, K);
+  }
+}
+
+// x <- two smoothing iterations of the level (zero: from zero); RB: red-black in place, backward (colours 1, 0) where post; else relaxed
+// Jacobi through t.  Ends with the workgroup in step
+template <bool RB>
+__device__ __forceinline__ void mg_tail_pair(const MgLev& L, const REAL* b, REAL* x, REAL* t, bool zero, bool post, REAL omg) {
+  if (RB) {
+    const int c0 = post ? 1 : 0;
+    if (zero) {
+      mg_each_colour(L, c0, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<1>(x, b, L, I, J, K, omg); });
+      __syncthreads();
+      mg_each_colour(L, 1 - c0, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<2>(x, b, L, I, J, K, omg); });
+      __syncthreads();
+    }
+    for (int s = zero ? 2 : 0; s < 4; s++) {
+      mg_each_colour(L, (c0 + s) & 1, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<0>(x, b, L, I, J, K, omg); });
+      __syncthreads();
+    }
+    return;
+  }
+  if (zero) mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<true>(t, b, L, I, J, K, omg); });
+  else mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<false>(x, b, L, I, J, K, omg); });
+  __syncthreads();
+  mg_each(L, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_sweep_pt<false>(t, b, L, I, J, K, omg); });
+  __syncthreads();
+}
+
+// RB: the cycle of pcg ... mgrb (its levels keep b and x only: T.len[m] apart, no t)
+template <bool RB>
 __global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ xg, const REAL* __restrict__ bg, MgTail T) {
   extern __shared__ __align__(16) unsigned char mg_lds_raw[];
   REAL* const lds = reinterpret_cast<REAL*>(mg_lds_raw);
@@ -215,33 +272,22 @@ __global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ 
   }
   __syncthreads();
   const REAL omg = T.omg;
-  // down: pre-smoothing pair from zero (b -> t -> x), residual restricted into the next level's b
+  // down: pre-smoothing pair from zero, residual restricted into the next level's b
   for (int m = 0; m + 1 < T.nlev; m++) {
     const MgLev& L = T.s[m];
     REAL *b = lds + T.off[m], *x = b + T.len[m], *t = x + T.len[m];
-    mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<true>(t, b, L, I, J, K, omg); });
-    __syncthreads();
-    mg_each(L, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_sweep_pt<false>(t, b, L, I, J, K, omg); });
-    __syncthreads();
+    mg_tail_pair<RB>(L, b, x, t, true, false, omg);
     const MgLev& Cl = T.s[m + 1];
     REAL* bc = lds + T.off[m + 1];
     mg_each(Cl, [&](int I, int J, int K) { bc[mg_at(Cl, I, J, K)] = mg_restrict_pt(x, b, L, I, J, K); });
     __syncthreads();
   }
-  {  // the coarsest level: 8 sweeps from zero, b -> t -> x -> t ... -> x
+  {  // the coarsest level: four pairs from zero, the last two post (mg_walk's order)
     const int m = T.nlev - 1;
-    const MgLev& L = T.s[m];
     REAL *b = lds + T.off[m], *x = b + T.len[m], *t = x + T.len[m];
-    mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<true>(t, b, L, I, J, K, omg); });
-    __syncthreads();
-    for (int s = 1; s < 8; s++) {
-      const REAL* src = (s & 1) ? t : x;
-      REAL* dst = (s & 1) ? x : t;
-      mg_each(L, [&](int I, int J, int K) { dst[mg_at(L, I, J, K)] = mg_sweep_pt<false>(src, b, L, I, J, K, omg); });
-      __syncthreads();
-    }
+    for (int s = 0; s < 4; s++) mg_tail_pair<RB>(T.s[m], b, x, t, s == 0, s >= 2, omg);
   }
-  // up: x += R(alpha x_c(parent)) in place, post-smoothing pair x -> t -> x
+  // up: x += R(alpha x_c(parent)) in place, post-smoothing pair
   for (int m = T.nlev - 2; m >= 0; m--) {
     const MgLev& L = T.s[m];
     const MgLev& Cl = T.s[m + 1];
@@ -252,10 +298,7 @@ __global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ 
       x[p] = mg_prolong_pt(x, xc, L, Cl, I, J, K);
     });
     __syncthreads();
-    mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<false>(x, b, L, I, J, K, omg); });
-    __syncthreads();
-    mg_each(L, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_sweep_pt<false>(t, b, L, I, J, K, omg); });
-    __syncthreads();
+    mg_tail_pair<RB>(L, b, x, t, false, true, omg);
   }
   {
     const REAL* x0 = lds + T.off[0] + T.len[0];

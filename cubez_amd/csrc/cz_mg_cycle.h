@@ -1,4 +1,4 @@
-// cz_mg_cycle.h -- the V-cycle of pcg ... mg as far as the single-domain hierarchy (cz_h_mg.h) and the distributed one
+// cz_mg_cycle.h -- the V-cycle of pcg ... mg and pcg ... mgrb as far as the single-domain hierarchy (cz_h_mg.h) and the distributed one
 // (cz_mg_dist.cpp) share it: which levels there are, and the order of a cycle.  The order is stated here and nowhere else on the host
 // (mg_tail_k states it once more on the device, for the levels it runs from LDS).
 #ifndef CZ_MG_CYCLE_H_
@@ -22,22 +22,25 @@ inline int mg_level_dims(const int* n, int (*dims)[3], int max) {
 
 // x_l = V_l(b_l).  Ops names the arrays and launches (and, decomposed, exchanges):
 //   whole(l)          true if it ran levels l .. coarsest in one go (the tail kernel; the gathered levels of a decomposed run)
-//   pair(l, zero)     x_l <- two relaxed Jacobi sweeps from x_l (zero: from zero)
+//   pair(l, zero, post)  x_l <- two smoothing iterations from x_l (zero: from zero).  mg: relaxed Jacobi sweeps, post is not looked at.
+//                     mgrb: red-black iterations, forward (colour 0, 1) before the coarse correction and backward (colour 1, 0: post) after it,
+//                     which makes the post-smoother the adjoint of the pre-smoother
 //   restrict_down(l)  b_{l+1} <- the residual of x_l summed over the children
 //   prolong_up(l)     x_l <- x_l + alpha x_{l+1}(parent)
 template <class Ops>
 void mg_walk(Ops& ops, int l, int coarsest) {
   if (ops.whole(l)) return;
-  if (l == coarsest) {  // eight sweeps from zero
-    ops.pair(l, true);
-    for (int s = 0; s < 3; s++) ops.pair(l, false);
+  if (l == coarsest) {  // eight iterations from zero: four as before a correction, four as after one
+    ops.pair(l, true, false);
+    ops.pair(l, false, false);
+    for (int s = 0; s < 2; s++) ops.pair(l, false, true);
     return;
   }
-  ops.pair(l, true);
+  ops.pair(l, true, false);
   ops.restrict_down(l);
   mg_walk(ops, l + 1, coarsest);
   ops.prolong_up(l);
-  ops.pair(l, false);
+  ops.pair(l, false, true);
 }
 
 #endif

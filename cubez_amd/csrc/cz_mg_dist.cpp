@@ -204,7 +204,7 @@ struct MgdOps {
     fatal_if(!mg_cycle_async(h->g, omg), "the cycle of the gathered levels");
     return true;
   }
-  void pair(int l, bool zero) {
+  void pair(int l, bool zero, bool /*post: Jacobi sweeps are the same before and after the correction*/) {
     REAL_TYPE* const t = l ? h->t[l] : o0;
     sweep(l, x(l), t, zero);
     sweep(l, t, x(l), false);

@@ -18,7 +18,7 @@ ABI_SYMBOLS = [
     "czhip_real_bytes", "czhip_arch", "czhip_init", "czhip_finalize", "czhip_alloc_s3d", "czhip_free", "czhip_h2d",
     "czhip_d2h", "czhip_sync", "czhip_stream", "czhip_set_tuning", "czhip_get_tuning",
     "czhip_jacobi_async", "czhip_rbsor_async", "czhip_check_async", "czhip_jacobi_checked_async",
-    "czhip_rbsor_checked_async", "czhip_jacobi2_async", "czhip_set_tuning2", "czhip_set_pcr_mode", "czhip_set_pcr_lex", "czhip_set_pcr_lex_timeout", "czhip_set_pcr_lex_limits", "czhip_set_psor", "czhip_set_psor_ahead", "czhip_use_t2", "czhip_set_pair_window", "czhip_set_pair_map", "czhip_set_pair_preload", "czhip_set_unit_coef", "czhip_config_describe", "czhip_set_comm_cus", "czhip_selftest_fastdiv", "czhip_selftest_mediumdiv", "czhip_pair_maf_async", "czhip_rbsor2_async", "czhip_rbsor4_async", "czhip_set_rb4", "czhip_jacobi3_async", "czhip_set_jac3", "czhip_set_jac3_medium", "czhip_jac3_division", "czhip_jacobi2_from_zero_async", "czhip_jacobi2_from_zero_made_async", "czhip_check2_async", "czhip_pair_split_async", "czhip_cg_update_async", "czhip_cg_dir_ax_async", "czhip_mg_smooth_async", "czhip_mg_restrict_async", "czhip_mg_prolong_async", "czhip_mg_tail_async", "czhip_mg_create", "czhip_mg_levels", "czhip_mg_apply_async", "czhip_mg_destroy", "psor_", "psor_maf_", "pcr_", "pcr_eda_", "pcr_esa_", "pcr_rb_esa_", "pcr_j_esa_", "pcr_rb_maf_", "pcr_rb_esa_maf_", "pcr_maf_", "pcr_eda_maf_", "pcr_esa_maf_",
+    "czhip_rbsor_checked_async", "czhip_jacobi2_async", "czhip_set_tuning2", "czhip_set_pcr_mode", "czhip_set_pcr_lex", "czhip_set_pcr_lex_timeout", "czhip_set_pcr_lex_limits", "czhip_set_psor", "czhip_set_psor_ahead", "czhip_use_t2", "czhip_set_pair_window", "czhip_set_pair_map", "czhip_set_pair_preload", "czhip_set_unit_coef", "czhip_config_describe", "czhip_set_comm_cus", "czhip_selftest_fastdiv", "czhip_selftest_mediumdiv", "czhip_pair_maf_async", "czhip_rbsor2_async", "czhip_rbsor4_async", "czhip_set_rb4", "czhip_jacobi3_async", "czhip_set_jac3", "czhip_set_jac3_medium", "czhip_jac3_division", "czhip_jacobi2_from_zero_async", "czhip_jacobi2_from_zero_made_async", "czhip_check2_async", "czhip_pair_split_async", "czhip_cg_update_async", "czhip_cg_dir_ax_async", "czhip_mg_smooth_async", "czhip_mg_restrict_async", "czhip_mg_prolong_async", "czhip_mg_tail_async", "czhip_mg_create", "czhip_mg_levels", "czhip_mg_apply_async", "czhip_mg_destroy", "czhip_mg_rb_async", "czhip_mg_tail_rb_async", "czhip_mg_create_rb", "czhip_mg_kind", "psor_", "psor_maf_", "pcr_", "pcr_eda_", "pcr_esa_", "pcr_rb_esa_", "pcr_j_esa_", "pcr_rb_maf_", "pcr_rb_esa_maf_", "pcr_maf_", "pcr_eda_maf_", "pcr_esa_maf_",
     "cz_create", "cz_destroy", "cz_evaluate", "cz_setup", "cz_solve", "cz_sweeps", "cz_result_iter", "cz_result_res",
     "cz_history", "cz_field", "cz_local_size", "cz_error_max", "cz_set_quiet", "cz_last_solve_seconds", "cz_kernel_ms",
     "cz_set_debug", "cz_set_profile", "cz_info", "cz_precondition", "czhip_timing", "czhip_timing_read",
@@ -522,6 +522,31 @@ class CzHip:
         self.lib.czhip_mg_create.restype = C.c_void_p
         self.lib.czhip_mg_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         return self.lib.czhip_mg_create(szp, idxp, GUIDE, cfp)
+
+    # -- the same cycle with the symmetric red-black smoother (pcg ... mgrb)
+    def mg_rb(self, x, b, sz, idx, level, n0, omg, colour, zero=0) -> bool:
+        """one colour sweep of level `level` (>= 1) in place on x; zero: 0 from the iterate, 1 / 2 the first / second colour from zero"""
+        (_, szp), (_, idxp), (_, n0p) = self._i(sz), self._i(idx), self._i(n0)
+        f = self.lib.czhip_mg_rb_async
+        f.argtypes = [C.c_void_p] * 2 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, self.creal, C.c_int, C.c_int]
+        return bool(f(x.ptr, b.ptr, szp, idxp, GUIDE, int(level), n0p, float(omg), int(colour), int(zero)))
+
+    def mg_tail_rb(self, x, b, sz, idx, level, n0, omg) -> bool:
+        (_, szp), (_, idxp), (_, n0p) = self._i(sz), self._i(idx), self._i(n0)
+        f = self.lib.czhip_mg_tail_rb_async
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, self.creal]
+        return bool(f(x.ptr, b.ptr, szp, idxp, GUIDE, int(level), n0p, float(omg)))
+
+    def mg_create_rb(self, sz, idx, cf=(1, 1, 1, 1, 1, 1, 6)):
+        """the hierarchy handle with the red-black smoother (None when refused); mg_levels, mg_apply and mg_destroy serve it too"""
+        (_, szp), (_, idxp), (_, cfp) = self._i(sz), self._i(idx), self._r(cf)
+        self.lib.czhip_mg_create_rb.restype = C.c_void_p
+        self.lib.czhip_mg_create_rb.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        return self.lib.czhip_mg_create_rb(szp, idxp, GUIDE, cfp)
+
+    def mg_kind(self, h) -> int:
+        self.lib.czhip_mg_kind.argtypes = [C.c_void_p]
+        return self.lib.czhip_mg_kind(h)
 
     def mg_levels(self, h) -> int:
         self.lib.czhip_mg_levels.argtypes = [C.c_void_p]

@@ -361,6 +361,21 @@ cz_mg* czhip_mg_create(const int* sz, const int* idx, int g, const CZ_REAL* cf);
 int czhip_mg_levels(const cz_mg* h);
 int czhip_mg_apply_async(cz_mg* h, CZ_REAL* z, const CZ_REAL* r, CZ_REAL omg);
 void czhip_mg_destroy(cz_mg* h);
+/* The same cycle with a symmetric red-black smoother (pcg ... mgrb): the colour of a point is (I + J + K) & 1 of its 0-based
+ * indices in the level's inner box, a colour sweep updates the points of one colour in place, a forward iteration is colour 0 then 1, a backward
+ * one colour 1 then 0; V_l = 2 forward iterations from zero, restrict, V_{l+1}, prolong, 2 backward iterations (the coarsest level: 4 forward from
+ * zero, 4 backward).  Levels, weights, restriction and prolongation are those above.
+ * czhip_mg_rb_async: one colour sweep of a whole level >= 1 in place on x; zero: 0 = from the iterate, 1 = the first colour of an iteration from
+ *   zero (x is not read), 2 = its second colour (reads the other colour only).  0 at level 0: that level runs czhip_rbsor2_async /
+ *   czhip_rbsor4_async / czhip_jacobi2_from_zero_made_async with ofst 0 (forward) and 1 (backward).
+ * czhip_mg_tail_rb_async: czhip_mg_tail_async for this cycle (its levels keep two arrays in LDS, not three: it may start one level earlier).
+ * czhip_mg_create_rb: the hierarchy of czhip_mg_create with this smoother (no temporaries on the coarse levels); czhip_mg_apply_async,
+ *   czhip_mg_levels and czhip_mg_destroy serve both kinds of handle.  0 < omg <= 1.2 (the range the preconditioner was checked to be definite on).
+ * czhip_mg_kind: 0 = no handle, 1 = relaxed Jacobi (czhip_mg_create), 2 = red-black (czhip_mg_create_rb). */
+int czhip_mg_rb_async(CZ_REAL* x, const CZ_REAL* b, const int* sz, const int* idx, int g, int level, const int* n0, CZ_REAL omg, int colour, int zero);
+int czhip_mg_tail_rb_async(CZ_REAL* x, const CZ_REAL* b, const int* sz, const int* idx, int g, int level, const int* n0, CZ_REAL omg);
+cz_mg* czhip_mg_create_rb(const int* sz, const int* idx, int g, const CZ_REAL* cf);
+int czhip_mg_kind(const cz_mg* h);
 
 /* Convergence bookkeeping on the device (cz_Poisson.cpp:67-77): res = sqrt(res_dev[0]*res_normal);
  * hist_dev[itr] = res; if (res < eps && !*flag) { *flag = 1; conv_itr_dev[0] = itr; }.  No-op when
@@ -404,9 +419,10 @@ double cz_last_solve_seconds(const cz_handle*);
  * 13 iterations of the last PCG solve whose search direction was made inside the SpMV pass (czhip_cg_dir_ax_async); 14 three-sweep
  * Jacobi passes of the last Jacobi solve (czhip_jacobi3_async); 15 levels of the multigrid hierarchy (pcg ... mg; 0 otherwise); 16 V-cycles
  * of the last PCG solve with mg; 17 the gather level G of a decomposed pcg ... mg (levels >= G run on every rank from an all-gathered copy;
- * 0 on a single domain or where level 0 is the coarsest); 18 halo exchanges and all-gathers of the last V-cycle of a decomposed pcg ... mg. */
+ * 0 on a single domain or where level 0 is the coarsest); 18 halo exchanges and all-gathers of the last V-cycle of a decomposed pcg ... mg;
+ * 19 the smoother of the multigrid preconditioner (0 none, 1 relaxed Jacobi: mg, 2 symmetric red-black: mgrb; 15 and 16 count for both). */
 int cz_info(const cz_handle*, int what);
-/* pcg ... mg: z = M^-1 r, the set-up solver's V-cycle applied once to host fields of the calling rank's brick in the cz_field layout (the
+/* pcg ... mg | mgrb: z = M^-1 r, the set-up solver's V-cycle applied once to host fields of the calling rank's brick in the cz_field layout (the
  * ghost cells of r are not read).  Collective: every rank of a decomposed run calls it.  Returns 1, or 0 where there is no such
  * preconditioner (another solver, or not set up). */
 int cz_precondition(cz_handle*, const CZ_REAL* r_dense, CZ_REAL* z_dense);
