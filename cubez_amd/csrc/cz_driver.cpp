@@ -16,10 +16,14 @@
 //   * bc_k_ after each checked iteration (cz_Poisson.cpp:74) is skipped: sweeps write the inner box only, the
 //     Dirichlet faces set at start-up are never touched, so the call is an identity.
 //   * the CBrick/MPI domain decomposition is replaced by cell-ownership decomposition + RCCL (cz_comm.cpp).
+//
+// What a solver or preconditioner name means is stated once, as a row of cz_solvers.h: spelling, printed name, where it is accepted, MAF
+// flag, loop family, what Preconditioner does with it, a line solver's iteration.  setLS / setStrPre look the name up, CZ::run turns the
+// family into the loop (for Solve, Sweeps and Preconditioner alike).  A new solver is one enumerator and one row; it needs a loop here and
+// a case in CZ::run only if its family is new.  Conditions that belong to one loop's own reasoning (the literal zero start, pcg's
+// coefficient ranges) stay with that loop.
 #include "cz_driver.h"
 
-#include <strings.h>
-#include <ctype.h>
 #include <unistd.h>
 
 #include <cfloat>
@@ -38,33 +42,7 @@ using namespace czhip_internal;
 #define Hostonly_ if (myRank == 0)
 
 namespace {
-const char* printMethod(int t) {
-  switch (t) {
-    case LS_JACOBI: return "JACOBI";
-    case LS_SOR2SMA: return "SOR2SMA";
-    case LS_BICGSTAB: return "PBiCGSTAB";
-    case LS_PSOR: return "PSOR";
-    case LS_PCR_RB: return "PCR_RB";
-    case LS_PCR: return "PCR";
-    case LS_PCR_ESA: return "PCR_ESA";
-    case LS_PCR_EDA: return "PCR_EDA";
-    case LS_PCR_RB_ESA: return "PCR_RB_ESA";
-    case LS_PCR_J_ESA: return "PCR_J_ESA";
-    case LS_PSOR_MAF: return "PSOR_MAF";
-    case LS_PCR_MAF: return "PCR_MAF";
-    case LS_PCR_EDA_MAF: return "PCR_EDA_MAF";
-    case LS_PCR_ESA_MAF: return "PCR_ESA_MAF";
-    case LS_PCR_RB_MAF: return "PCR_RB_MAF";
-    case LS_PCR_RB_ESA_MAF: return "PCR_RB_ESA_MAF";
-    case LS_JACOBI_MAF: return "JACOBI_MAF";
-    case LS_SOR2SMA_MAF: return "SOR2SMA_MAF";
-    case LS_BICGSTAB_MAF: return "PBiCGSTAB_MAF";
-    case LS_PCG: return "PCG";
-    case LS_MG: return "MG";
-    case LS_MGRB: return "MGRB";
-    default: return "NONE";
-  }
-}
+const char* printMethod(int t) { return cz_solvers::row(t).printed; }
 double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -113,6 +91,8 @@ CZ::~CZ() {
   if (fph) fclose(fph);
 }
 
+size_t CZ::padded_cells() const { return (size_t)(size[0] + 2 * GUIDE) * (size[1] + 2 * GUIDE) * (size[2] + 2 * GUIDE); }
+
 double CZ::npts() const {
   return (double)(innerFidx[I_plus] - innerFidx[I_minus] + 1) * (double)(innerFidx[J_plus] - innerFidx[J_minus] + 1) *
          (double)(innerFidx[K_plus] - innerFidx[K_minus] + 1);
@@ -134,98 +114,37 @@ double CZ::range_inner_index() {
   return (double)(ied - ist + 1) * (double)(jed - jst + 1) * (double)(ked - kst + 1);
 }
 
-// cz_Evaluate.cpp:571-581
+// cz_Evaluate.cpp:571-681: the preconditioner of pbicgstab[_maf] (a MAF preconditioner alone sets SW_maf as well)
 void CZ::setStrPre() {
-  if (!strcasecmp(precon.c_str(), "jacobi")) pc_type = LS_JACOBI;
-  else if (!strcasecmp(precon.c_str(), "sor2sma")) pc_type = LS_SOR2SMA;
-  else if (!strcasecmp(precon.c_str(), "jacobi_maf")) pc_type = LS_JACOBI_MAF, SW_maf = 1;
-  else if (!strcasecmp(precon.c_str(), "sor2sma_maf")) pc_type = LS_SOR2SMA_MAF, SW_maf = 1;
-  else if (!strcasecmp(precon.c_str(), "pcr_rb")) pc_type = LS_PCR_RB;
-  else if (!strcasecmp(precon.c_str(), "pcr_rb_esa")) pc_type = LS_PCR_RB_ESA;  // :585-587
-  else if (!strcasecmp(precon.c_str(), "pcr_j_esa")) pc_type = LS_PCR_J_ESA;    // :588-590 (CZ::Preconditioner has no case for it: acts as none)
-  else if (!strcasecmp(precon.c_str(), "pcr")) pc_type = LS_PCR;                // :591-593
-  else if (!strcasecmp(precon.c_str(), "pcr_eda")) pc_type = LS_PCR_EDA;        // :594-596
-  else if (!strcasecmp(precon.c_str(), "psor")) pc_type = LS_PSOR;
-  else if (!strcasecmp(precon.c_str(), "psor_maf")) pc_type = LS_PSOR_MAF, SW_maf = 1;
-  else if (!strcasecmp(precon.c_str(), "pcr_rb_maf")) pc_type = LS_PCR_RB_MAF, SW_maf = 1;          // :606-617
-  else if (!strcasecmp(precon.c_str(), "pcr_rb_esa_maf")) pc_type = LS_PCR_RB_ESA_MAF, SW_maf = 1;
-  else if (!strcasecmp(precon.c_str(), "pcr_maf")) pc_type = LS_PCR_MAF, SW_maf = 1;
-  else if (!strcasecmp(precon.c_str(), "pcr_eda_maf")) pc_type = LS_PCR_EDA_MAF, SW_maf = 1;
-  else if (!strcasecmp(precon.c_str(), "none")) pc_type = LS_NONE;
-  else {
-    Hostonly_ printf("Invalid preconditioner '%s' (this build: none | jacobi | psor | sor2sma | pcr | pcr_eda | pcr_rb | pcr_rb_esa | pcr_j_esa | jacobi_maf | psor_maf | sor2sma_maf | pcr_maf | pcr_eda_maf | pcr_rb_maf | pcr_rb_esa_maf)\n", precon.c_str());
+  const cz_solvers::Row* r = cz_solvers::find(precon.c_str(), cz_solvers::PRE_BICG);
+  if (!r) {
+    Hostonly_ printf("Invalid preconditioner '%s' (this build: %s)\n", precon.c_str(), cz_solvers::list(cz_solvers::PRE_BICG).c_str());
     exit(0);
   }
+  pc_type = r->id;
+  if (r->maf) SW_maf = 1;
 }
 
-// cz_Evaluate.cpp:684-803 (hot-path solvers only; see DESIGN.md "out of scope")
+// cz_Evaluate.cpp:684-803 (hot-path solvers only; see DESIGN.md "out of scope").  What a name means is its row in cz_solvers.h; what is
+// left here are pcg's rules.
 void CZ::setLS(const char* q) {
-  if (!strcasecmp(q, "jacobi")) {
-    ls_type = LS_JACOBI;
-    hist_name = "jacobi.txt";
-  } else if (!strcasecmp(q, "sor2sma")) {
-    ls_type = LS_SOR2SMA;
-    hist_name = "sor2sma.txt";
-  } else if (!strcasecmp(q, "pbicgstab")) {
-    ls_type = LS_BICGSTAB;
-    hist_name = "pbicgstab.txt";
-    setStrPre();
-  } else if (!strcasecmp(q, "psor")) {  // :691-694, lexicographic point SOR
-    ls_type = LS_PSOR;
-    hist_name = "psor.txt";
-  } else if (!strcasecmp(q, "psor_maf")) {  // :748-751
-    ls_type = LS_PSOR_MAF;
-    hist_name = "psor_maf.txt";
-    SW_maf = 1;
-  } else if (!strcasecmp(q, "pcr_rb_maf") || !strcasecmp(q, "pcr_rb_esa_maf") || !strcasecmp(q, "pcr_maf") || !strcasecmp(q, "pcr_eda_maf") ||
-             !strcasecmp(q, "pcr_esa_maf")) {  // :767-797, the MAF line solvers
-    ls_type = !strcasecmp(q, "pcr_rb_maf") ? LS_PCR_RB_MAF : !strcasecmp(q, "pcr_rb_esa_maf") ? LS_PCR_RB_ESA_MAF
-              : !strcasecmp(q, "pcr_maf") ? LS_PCR_MAF : !strcasecmp(q, "pcr_eda_maf") ? LS_PCR_EDA_MAF : LS_PCR_ESA_MAF;
-    hist_name = std::string(q) + ".txt";
-    for (char& ch : hist_name) ch = (char)tolower((unsigned char)ch);
-    SW_maf = 1;
-  } else if (!strcasecmp(q, "pcr_rb_esa")) {  // :712-716
-    ls_type = LS_PCR_RB_ESA;
-    hist_name = "pcr_rb_esa.txt";
-  } else if (!strcasecmp(q, "pcr_j_esa")) {  // :718-722
-    ls_type = LS_PCR_J_ESA;
-    hist_name = "pcr_j_esa.txt";
-  } else if (!strcasecmp(q, "pcr")) {  // :724-727
-    ls_type = LS_PCR;
-    hist_name = "pcr.txt";
-  } else if (!strcasecmp(q, "pcr_eda")) {  // :729-732
-    ls_type = LS_PCR_EDA;
-    hist_name = "pcr_eda.txt";
-  } else if (!strcasecmp(q, "pcr_esa")) {  // :734-737
-    ls_type = LS_PCR_ESA;
-    hist_name = "pcr_esa.txt";
-  } else if (!strcasecmp(q, "pcr_rb")) {  // :707-710, line SOR by parallel cyclic reduction
-    ls_type = LS_PCR_RB;
-    hist_name = "pcr_rb.txt";
-  } else if (!strcasecmp(q, "jacobi_maf")) {  // :738-760, the MAF flavours
-    ls_type = LS_JACOBI_MAF;
-    hist_name = "jacobi_maf.txt";
-    SW_maf = 1;
-  } else if (!strcasecmp(q, "sor2sma_maf")) {
-    ls_type = LS_SOR2SMA_MAF;
-    hist_name = "sor2sma_maf.txt";
-    SW_maf = 1;
-  } else if (!strcasecmp(q, "pbicgstab_maf")) {
-    ls_type = LS_BICGSTAB_MAF;
-    hist_name = "pbicgstab_maf.txt";
-    setStrPre();
-    SW_maf = 1;
-  } else if (!strcasecmp(q, "pcg")) {  // beyond the reference (DESIGN.md "PCG"): symmetric preconditioners only
-    ls_type = LS_PCG;
-    hist_name = "pcg.txt";
-    if (!strcasecmp(precon.c_str(), "none")) pc_type = LS_NONE;
-    else if (!strcasecmp(precon.c_str(), "jacobi")) pc_type = LS_JACOBI;
-    else if (!strcasecmp(precon.c_str(), "mg")) pc_type = LS_MG;
-    else if (!strcasecmp(precon.c_str(), "mgrb")) pc_type = LS_MGRB;
-    else {
+  const cz_solvers::Row* r = cz_solvers::find(q, cz_solvers::SOLVER);
+  if (!r) {
+    printf("Invalid solver\n");  // :799-802
+    exit(0);
+  }
+  ls_type = r->id;
+  hist_name = std::string(r->name) + ".txt";
+  if (r->family == cz_solvers::BICGSTAB) setStrPre();
+  if (r->maf) SW_maf = 1;
+  if (r->family == cz_solvers::PCG) {  // beyond the reference (DESIGN.md "PCG"): symmetric preconditioners only
+    const cz_solvers::Row* pre = cz_solvers::find(precon.c_str(), cz_solvers::PRE_PCG);
+    if (!pre) {
+      // (a literal, not cz_solvers::list: the text is older than mg and mgrb, and tests/test_gpu_pcg.py pins it)
       Hostonly_ printf("Invalid preconditioner for pcg '%s' (none | jacobi)\n", precon.c_str());
       exit(0);
     }
+    pc_type = pre->id;
     // the V-cycle's smoothers are relaxed Jacobi sweeps: the same range keeps it symmetric and definite
     if (pc_type == LS_MG && !(ac1 > (REAL_TYPE)0 && ac1 <= (REAL_TYPE)1)) {
       Hostonly_ printf("Invalid coefficient for pcg with mg '%g' (0 < coef <= 1: a symmetric definite preconditioner)\n", (double)ac1);
@@ -250,9 +169,6 @@ void CZ::setLS(const char* q) {
       Hostonly_ printf("Invalid coefficient for pcg with jacobi '%g' (0 < coef <= 1: a symmetric definite preconditioner)\n", (double)ac1);
       exit(0);
     }
-  } else {
-    printf("Invalid solver\n");  // :799-802
-    exit(0);
   }
 }
 
@@ -304,14 +220,15 @@ int CZ::Setup(int argc, char** argv) {
   }
 
   const char* q = argv[4];
-  if (!strcasecmp(q, "pbicgstab") || !strcasecmp(q, "pbicgstab_maf")) {  // :63-70
+  const cz_solvers::Row* named = cz_solvers::find(q, cz_solvers::SOLVER);  // (an unknown name is refused by setLS, after the checks in between)
+  if (named && named->family == cz_solvers::BICGSTAB) {  // :63-70
     if (argc != 8 && argc != 11) {
       Hostonly_ printf("command line error : pbicgstab\n");
       exit(0);
     }
     precon = argv[7];
   }
-  if (!strcasecmp(q, "pcg")) precon = (argc == 8 || argc == 11) ? argv[7] : "none";  // [none | jacobi]
+  if (named && named->family == cz_solvers::PCG) precon = (argc == 8 || argc == 11) ? argv[7] : "none";
   if (argc == 10) {  // :73-78
     div_type = 1;
     G_div[0] = atoi(argv[7]), G_div[1] = atoi(argv[8]), G_div[2] = atoi(argv[9]);
@@ -338,7 +255,7 @@ int CZ::Setup(int argc, char** argv) {
   setLS(q);
   if (!quiet) Hostonly_ {
     printf("Iterative Mehtod = %s\n", printMethod(ls_type));  // :194 (sic)
-    if (ls_type == LS_BICGSTAB || ls_type == LS_BICGSTAB_MAF || ls_type == LS_PCG) printf("Preconditioner = %s\n", printMethod(pc_type));
+    if (cz_solvers::krylov(cz_solvers::row(ls_type))) printf("Preconditioner = %s\n", printMethod(pc_type));
   }
 
   if (!quiet) Hostonly_ {  // :210-218
@@ -379,7 +296,7 @@ int CZ::Setup(int argc, char** argv) {
       }
     }
   }
-  const bool bicg = ls_type == LS_BICGSTAB || ls_type == LS_BICGSTAB_MAF;
+  const bool bicg = cz_solvers::row(ls_type).family == cz_solvers::BICGSTAB;
   if (bicg) {
     pcg_p = czhip_alloc_s3d(size), pcg_p_ = czhip_alloc_s3d(size), pcg_r = czhip_alloc_s3d(size);
     pcg_r0 = czhip_alloc_s3d(size), pcg_q = czhip_alloc_s3d(size), pcg_s = czhip_alloc_s3d(size);
@@ -404,7 +321,7 @@ int CZ::Setup(int argc, char** argv) {
     }
   }
   if (!quiet) Hostonly_ {
-    const double arr = (double)(size[0] + 2 * gc) * (size[1] + 2 * gc) * (size[2] + 2 * gc) * sizeof(REAL_TYPE);
+    const double arr = (double)padded_cells() * sizeof(REAL_TYPE);
     printf("\n----------\n\n\tDevice memory per rank : %.1f MiB in %d arrays of (%d+4)x(%d+4)x(%d+4) %s\n", arr *
            narr / 1048576.0, narr, size[0], size[1], size[2],
            sizeof(REAL_TYPE) == 4 ? "float" : "double");
@@ -414,9 +331,7 @@ int CZ::Setup(int argc, char** argv) {
 
   ItrMax = atoi(argv[5]);  // :330
 
-  auto is_line = [](int t) {
-    return (t >= LS_PCR && t <= LS_PCR_J_ESA) || (t >= LS_PCR_MAF && t <= LS_PCR_RB_ESA_MAF);
-  };
+  auto is_line = [](int t) { return cz_solvers::row(t).family == cz_solvers::LINE; };
   if (is_line(ls_type) || is_line(pc_type)) {
     // Decomposed line SOR.  The colour and Jacobi orders exchange ghost columns after each colour / iteration: with whole k-lines per
     // brick (gdv_z = 1) they reproduce the single-domain run bit for bit.  What cannot: (a) a cut along k -- every brick then solves ITS
@@ -464,46 +379,7 @@ int CZ::Solve() {
   if (profile) czhip_timing(1);  // restart the section timers (the reference's PM.start/stop around the kernels)
   czhip_sync();
   const double t0 = now_s();
-  switch (ls_type) {  // :415-488
-    case LS_JACOBI:
-    case LS_JACOBI_MAF:
-      if (0 == (itr = JACOBI(res, P, RHS, ItrMax, flop, ls_type))) return 0;
-      break;
-    case LS_SOR2SMA:
-    case LS_SOR2SMA_MAF:
-      if (0 == (itr = RBSOR(res, P, RHS, ItrMax, flop, ls_type))) return 0;
-      break;
-    case LS_BICGSTAB:
-    case LS_BICGSTAB_MAF:
-      if (0 == (itr = PBiCGSTAB(res, P, RHS, flop, ls_type))) return 0;
-      break;
-    case LS_PCG:
-      if (0 == (itr = PCG(res, P, RHS, flop))) return 0;
-      break;
-    case LS_PCR_RB:
-      if (0 == (itr = LSOR_PCR_RB(res, P, RHS, ItrMax, flop, ls_type))) return 0;
-      break;
-    case LS_PSOR:
-    case LS_PSOR_MAF:
-      if (0 == (itr = PSOR(res, P, RHS, ItrMax, flop, ls_type))) return 0;
-      break;
-    case LS_PCR:
-    case LS_PCR_EDA:
-    case LS_PCR_ESA:
-    case LS_PCR_RB_ESA:
-    case LS_PCR_J_ESA:
-      if (0 == (itr = LSOR_PCR_VARIANT(res, P, RHS, ItrMax, flop, ls_type))) return 0;
-      break;
-    case LS_PCR_MAF:
-    case LS_PCR_EDA_MAF:
-    case LS_PCR_ESA_MAF:
-    case LS_PCR_RB_MAF:
-    case LS_PCR_RB_ESA_MAF:
-      if (0 == (itr = LSOR_PCR_MAF(res, P, RHS, ItrMax, flop, ls_type))) return 0;
-      break;
-    default:
-      break;
-  }
+  if (0 == (itr = run(ls_type, res, P, RHS, ItrMax, flop))) return 0;  // :415-488
   czhip_sync();
   solve_seconds = now_s() - t0;
   result_itr = itr;
@@ -526,7 +402,7 @@ int CZ::Evaluate(int argc, char** argv) {
   if (!Solve()) return 0;
   if (!quiet) Hostonly_ {
     const double lups = 1.0 / res_normal * (double)(result_itr > ItrMax ? ItrMax : result_itr);
-    if (ls_type != LS_BICGSTAB && ls_type != LS_BICGSTAB_MAF && ls_type != LS_PCG)
+    if (!cz_solvers::krylov(cz_solvers::row(ls_type)))
       printf("\n\tGPU time = %.6f s   %.1f MLUPS\n", solve_seconds, lups / solve_seconds * 1e-6);
     else
       printf("\n\tGPU time = %.6f s\n", solve_seconds);
@@ -549,7 +425,7 @@ int CZ::Evaluate(int argc, char** argv) {
     char fname[32];
     if (dump) {
       snprintf(fname, sizeof(fname), "p_%05d.sph", myRank);  // :553-554
-      std::vector<REAL_TYPE> p((size_t)(size[0] + 2 * GUIDE) * (size[1] + 2 * GUIDE) * (size[2] + 2 * GUIDE));
+      std::vector<REAL_TYPE> p(padded_cells());
       Field(p.data());
       if (!WriteSph(fname, p.data())) return 0;
     }
@@ -568,25 +444,32 @@ int CZ::Evaluate(int argc, char** argv) {
 // Bench leg: n more iterations of the stationary solver, with the complete per-iteration work of the checked loop
 // (sweep, residual reduction, convergence bookkeeping) but eps disabled so that nothing is skipped.
 int CZ::Sweeps(int n) {
-  if (!set_up || (ls_type != LS_JACOBI && ls_type != LS_SOR2SMA && ls_type != LS_JACOBI_MAF && ls_type != LS_SOR2SMA_MAF &&
-                  ls_type != LS_PCR_RB && ls_type != LS_PSOR && ls_type != LS_PSOR_MAF && ls_type != LS_PCR && ls_type != LS_PCR_EDA && ls_type != LS_PCR_ESA &&
-                  ls_type != LS_PCR_RB_ESA && ls_type != LS_PCR_J_ESA && !(ls_type >= LS_PCR_MAF && ls_type <= LS_PCR_RB_ESA_MAF)))
-    return 0;
+  const cz_solvers::Family f = cz_solvers::row(ls_type).family;
+  if (!set_up || !(f == cz_solvers::JACOBI || f == cz_solvers::RBSOR || f == cz_solvers::PSOR || f == cz_solvers::LINE)) return 0;
   const double keep = eps;
   eps = -1.0;
   double res = 0.0, flop = 0.0;
   history.clear();
-  if (ls_type == LS_PCR || ls_type == LS_PCR_EDA || ls_type == LS_PCR_ESA || ls_type == LS_PCR_RB_ESA || ls_type == LS_PCR_J_ESA)
-    LSOR_PCR_VARIANT(res, P, RHS, n, flop, ls_type);
-  else if (ls_type >= LS_PCR_MAF && ls_type <= LS_PCR_RB_ESA_MAF) LSOR_PCR_MAF(res, P, RHS, n, flop, ls_type);
-  else if (ls_type == LS_PSOR || ls_type == LS_PSOR_MAF) PSOR(res, P, RHS, n, flop, ls_type);
-  else if (ls_type == LS_PCR_RB) LSOR_PCR_RB(res, P, RHS, n, flop, ls_type);
-  else if (ls_type == LS_JACOBI || ls_type == LS_JACOBI_MAF) JACOBI(res, P, RHS, n, flop, ls_type);
-  else RBSOR(res, P, RHS, n, flop, ls_type);
+  run(ls_type, res, P, RHS, n, flop);
   eps = keep;
   sweeps_done += n;
   result_res = res;
   return n;
+}
+
+// The one place where a solver's family (cz_solvers.h) becomes the loop that runs it: Solve and Sweeps (checked), Preconditioner (unchecked,
+// perhaps from a literal zero and making its right-hand side).  0: failed, as every loop returns it.
+int CZ::run(int s_type, double& res, REAL_TYPE* X, REAL_TYPE* B, int itr_max, double& flop, bool converge_check, bool x_is_zero, const BMade* made) {
+  switch (cz_solvers::row(s_type).family) {
+    case cz_solvers::JACOBI: return JACOBI(res, X, B, itr_max, flop, s_type, converge_check, x_is_zero, made);
+    case cz_solvers::RBSOR: return RBSOR(res, X, B, itr_max, flop, s_type, converge_check, x_is_zero, made);
+    case cz_solvers::PSOR: return PSOR(res, X, B, itr_max, flop, s_type, converge_check);
+    case cz_solvers::LINE: return LSOR(res, X, B, itr_max, flop, s_type, converge_check);
+    case cz_solvers::BICGSTAB: return PBiCGSTAB(res, X, B, flop, s_type);  // (the Krylov loops run to ItrMax)
+    case cz_solvers::PCG: return PCG(res, X, B, flop);
+    case cz_solvers::NO_LOOP: break;
+  }
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -749,7 +632,7 @@ bool CZ::sweep_failed(const char* solver) {
 // differ from brick to brick (a brick too thin to split): the same exchanges and all-reduces in the same order either way.
 CZ::PassPlan CZ::plan_pass(REAL_TYPE* X, REAL_TYPE* B, int s_type, int itr_max, bool converge_check, bool x_is_zero, bool rb, bool probe_only) {
   PassPlan p;
-  p.maf = (s_type == LS_JACOBI_MAF || s_type == LS_SOR2SMA_MAF) ? 1 : 0;
+  p.maf = cz_solvers::row(s_type).maf ? 1 : 0;
   p.rb = rb ? 1 : 0;
   p.comm_cus = comm_cus;
   bool fused = czhip_use_t2() != 0 && (rb || itr_max >= 2);
@@ -855,8 +738,7 @@ bool CZ::fused_begin(FusedLoop& L, REAL_TYPE* X, int itr_max, bool x_is_zero, co
   if (x_is_zero && !plan.zero_start) {
     // the caller skipped its blas_clear_ (cz_Poisson.cpp:405, 441) and this solve does not take the zero as a literal: clear now
     // (guide cells / faces are zero already)
-    const size_t nbytes = (size_t)(size[0] + 2 * GUIDE) * (size[1] + 2 * GUIDE) * (size[2] + 2 * GUIDE) * sizeof(REAL_TYPE);
-    HIP_CHECK(hipMemsetAsync(X, 0, nbytes, stream()));
+    HIP_CHECK(hipMemsetAsync(X, 0, padded_cells() * sizeof(REAL_TYPE), stream()));
   }
   reset_ticket();
   if (L.converge_check) {
@@ -1119,7 +1001,7 @@ int CZ::RBSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double
 
 // cz_Poisson.cpp:95-146.  Lexicographic point SOR, in place; one sweep = the launches of psor_async (tile hyperplanes).
 int CZ::PSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double& flop, int s_type, bool converge_check) {
-  const bool maf = (s_type == LS_PSOR_MAF);  // :108-114
+  const bool maf = cz_solvers::row(s_type).maf;  // :108-114
   const int gc = GUIDE;
   reset_ticket();
   const int* skip = nullptr;
@@ -1176,84 +1058,50 @@ int CZ::line_finish(int itr, int itr_max, bool converge_check, double& res, int 
   return itr;
 }
 
-// cz_Poisson.cpp:621-742 (pcr_rb_esa), :745-826 (pcr), :910-1005 (pcr_esa), :1008-1095 (pcr_j_esa): the line-SOR variants that end
-// in 4x4 systems and / or visit the columns in another order; one loop, the variant picks order and final stage.
-int CZ::LSOR_PCR_VARIANT(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double& flop, int s_type, bool converge_check) {
+// One iteration of a line solver as its row describes it (cz_solvers.h): the launches of a kernel family in a column order, with the
+// exchanges that follow them.  false: an exchange failed.
+//   order 0  colour 0 then colour 1, in place (cz_Poisson.cpp:573-578, 685-690).  mod(i+j, 2) == colour is meant in GLOBAL indices: the
+//            brick's local rule is shifted by its head (the reference's MPI path ignores this, cz_solver.f90:534 "unused variable"; here
+//            decomposed == single domain), and the ghost columns are exchanged after each colour, like the two-colour RB-SOR
+//   order 1  one lexicographic sweep (:783-786, :966-969), exchange :794 (decomposed: block-local, see CZ::Setup)
+//   order 2  Jacobi order into WRK (:1061-1064), copied back, exchange :1068
+bool CZ::line_iteration(const cz_solvers::Line& d, REAL_TYPE* X, REAL_TYPE* B, int pn) {
   const int gc = GUIDE;
-  reset_ticket();
-  const int n = innerFidx[K_plus] - innerFidx[K_minus] + 1;
-  const int pn = line_stages();
-  const int final4 = (s_type == LS_PCR_J_ESA || s_type == LS_PCR_EDA) ? 0 : 1;
-  const int order = (s_type == LS_PCR_RB_ESA) ? 0 : (s_type == LS_PCR_J_ESA) ? 2 : 1;
-  const int stages = final4 ? pn - 2 : pn - 1;
-  const double fin = final4 ? (double)(1 << (pn - 2)) * (s_type == LS_PCR ? 74.0 : 78.0) : (double)(1 << (pn - 1)) * 9.0;
-  if (converge_check) {
-    ensure_hist(itr_max + 2);
-    HIP_CHECK(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), stream()));
-  }
-  int itr;
-  for (itr = 1; itr <= itr_max; itr++) {
-    if (order == 0) {
-      for (int color = 0; color < 2; color++) {  // :685-690; global colouring and an exchange per colour as in LSOR_PCR_RB
-        pcr_variant_async(X, nullptr, MSK, B, size, innerFidx, gc, pn, 0, (color + head[0] + head[1]) & 1, final4, ac1, d_res, color);
-        if (!Comm_S(X)) return 0;
-      }
-    } else if (order == 1) {
-      pcr_variant_async(X, nullptr, MSK, B, size, innerFidx, gc, pn, 1, 0, final4, ac1, d_res, 0);  // :783-786, :966-969
-      if (!Comm_S(X)) return 0;  // :794 (decomposed: block-local, see CZ::Setup)
-    } else {
-      pcr_variant_async(X, WRK, MSK, B, size, innerFidx, gc, pn, 2, 0, final4, ac1, d_res, 0);  // :1061-1064
-      copy_inner_async(X, WRK, size, innerFidx, gc);
-      if (!Comm_S(X)) return 0;  // :1068
+  auto launch = [&](int par, int slot) {
+    switch (d.kernel) {
+      case cz_solvers::PCR_RB: pcr_rb_async(X, MSK, B, size, innerFidx, gc, pn, par, ac1, d_res, slot); break;
+      case cz_solvers::PCR_VARIANT: pcr_variant_async(X, d.order == 2 ? WRK : nullptr, MSK, B, size, innerFidx, gc, pn, d.order, par, d.final4, ac1, d_res, slot); break;
+      case cz_solvers::PCR_MAF: pcr_maf_async(X, MSK, B, size, innerFidx, gc, pn, d.order, par, d_xc, d_yc, d_zc, ac1, d_res, slot); break;
+      case cz_solvers::NO_LINE: break;
     }
-    flop += (npts() / n) * (n * 6.0 + n * (double)stages * 14.0 + fin + n * 6.0 + 6.0);
-    if (converge_check) {
-      const int t = line_test(itr, s_type);
-      if (t < 0) return 0;
-      if (t > 0) break;
+  };
+  if (d.order == 0) {
+    for (int color = 0; color < 2; color++) {
+      launch((color + head[0] + head[1]) & 1, color);
+      if (!Comm_S(X)) return false;
     }
+    return true;
   }
-  return line_finish(itr, itr_max, converge_check, res, s_type);
+  launch(0, 0);
+  if (d.order == 2) copy_inner_async(X, WRK, size, innerFidx, gc);
+  return Comm_S(X);
 }
 
-// The line solvers of the MAF flavour (cz_Poisson.cpp:549-557, 665-683, 770-776, 853-859, 940-946 call pcr_rb_maf_, pcr_rb_esa_maf_,
-// pcr_maf_, pcr_eda_maf_, pcr_esa_maf_): coefficients from the metrics of the 1-D grids, pn-1 stages + 2x2 systems.
-int CZ::LSOR_PCR_MAF(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double& flop, int s_type, bool converge_check) {
-  const int gc = GUIDE;
-  reset_ticket();
+// The reference's operation count of one iteration, per kernel family: pcr_rb (cz_Poisson.cpp:580), the variants that end in 4x4 systems
+// and / or visit the columns in another order (:692, :788, :971, :1066), the MAF flavour (pn-1 stages + 2x2 systems, :559)
+double CZ::line_flop(const cz_solvers::Line& d, int pn) const {
   const int n = innerFidx[K_plus] - innerFidx[K_minus] + 1;
-  const int pn = line_stages();
-  const bool rb = (s_type == LS_PCR_RB_MAF || s_type == LS_PCR_RB_ESA_MAF);
-  const double fin = (s_type == LS_PCR_EDA_MAF || s_type == LS_PCR_ESA_MAF) ? 9.0 : 11.0;
-  if (converge_check) {
-    ensure_hist(itr_max + 2);
-    HIP_CHECK(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), stream()));
-  }
-  int itr;
-  for (itr = 1; itr <= itr_max; itr++) {
-    if (rb) {
-      for (int color = 0; color < 2; color++) {  // global colouring, exchange per colour (as LSOR_PCR_RB)
-        pcr_maf_async(X, MSK, B, size, innerFidx, gc, pn, 0, (color + head[0] + head[1]) & 1, d_xc, d_yc, d_zc, ac1, d_res, color);
-        if (!Comm_S(X)) return 0;
-      }
-    } else {
-      pcr_maf_async(X, MSK, B, size, innerFidx, gc, pn, 1, 0, d_xc, d_yc, d_zc, ac1, d_res, 0);
-      if (!Comm_S(X)) return 0;
-    }
-    flop += (npts() / n) * ((24.0 + 6.0 + 12.0) + n * 21.0 + (n - 2.0) * 6.0 + n * (double)(pn - 1) * 16.0 + (double)(1 << (pn - 1)) * fin + n * 6.0);
-    if (converge_check) {
-      const int t = line_test(itr, s_type);
-      if (t < 0) return 0;
-      if (t > 0) break;
-    }
-  }
-  return line_finish(itr, itr_max, converge_check, res, s_type);
+  if (d.kernel == cz_solvers::PCR_RB) return npts() * (12.0 + (pn - 1) * 14.0);
+  if (d.kernel == cz_solvers::PCR_MAF)
+    return (npts() / n) * ((24.0 + 6.0 + 12.0) + n * 21.0 + (n - 2.0) * 6.0 + n * (double)(pn - 1) * 16.0 + (double)(1 << (pn - 1)) * d.fin + n * 6.0);
+  const int stages = d.final4 ? pn - 2 : pn - 1;
+  return (npts() / n) * (n * 6.0 + n * (double)stages * 14.0 + (double)(1 << stages) * d.fin + n * 6.0 + 6.0);
 }
 
-// cz_Poisson.cpp:518-611.  Line SOR: every (i,j) column of one checkerboard colour is solved along k by parallel cyclic
-// reduction (pcr_rb_k), colour 0 then colour 1, in place.  Single-domain.
-int CZ::LSOR_PCR_RB(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double& flop, int s_type, bool converge_check) {
-  const int gc = GUIDE;
+// cz_Poisson.cpp:518-611 (pcr_rb), :621-742 (pcr_rb_esa), :745-826 (pcr), :829-907 (pcr_eda), :910-1005 (pcr_esa), :1008-1095 (pcr_j_esa) and
+// their MAF flavours: line SOR, every (i,j) column solved along k by parallel cyclic reduction.  One loop; the row says what an iteration is.
+int CZ::LSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double& flop, int s_type, bool converge_check) {
+  const cz_solvers::Line& d = cz_solvers::row(s_type).line;
   reset_ticket();
   const int pn = line_stages();
   if (converge_check) {
@@ -1262,13 +1110,8 @@ int CZ::LSOR_PCR_RB(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, 
   }
   int itr;
   for (itr = 1; itr <= itr_max; itr++) {
-    for (int color = 0; color < 2; color++) {  // :573-578
-      // mod(i+j, 2) == color is meant in GLOBAL indices: the brick's local rule is shifted by its head (the reference's
-      // MPI path ignores this, cz_solver.f90:534 "unused variable"; here decomposed == single domain)
-      pcr_rb_async(X, MSK, B, size, innerFidx, gc, pn, (color + head[0] + head[1]) & 1, ac1, d_res, color);
-      if (!Comm_S(X)) return 0;  // after each colour, like the two-colour RB-SOR path
-    }
-    flop += npts() * (12.0 + (pn - 1) * 14.0);
+    if (!line_iteration(d, X, B, pn)) return 0;
+    flop += line_flop(d, pn);
     if (converge_check) {
       const int t = line_test(itr, s_type);
       if (t < 0) return 0;
@@ -1282,15 +1125,16 @@ int CZ::LSOR_PCR_RB(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, 
 // partial sums are all-reduced and rounded to REAL once.
 REAL_TYPE CZ::Fdot1(REAL_TYPE* x, double& flop) {
   dot1_async(x, size, innerFidx, GUIDE, d_res + 1);
-  flop += 2.0 * npts();
-  if (!Comm_SUM_dev(d_res + 1, 1)) exit(0);
-  HIP_CHECK(hipMemcpyAsync(h_scal + 1, d_res + 1, sizeof(double), hipMemcpyDeviceToHost, stream()));
-  HIP_CHECK(hipStreamSynchronize(stream()));
-  return (REAL_TYPE)h_scal[1];
+  return dot_read(flop);
 }
 
 REAL_TYPE CZ::Fdot2(REAL_TYPE* x, REAL_TYPE* y, double& flop) {
   dot2_async(x, y, size, innerFidx, GUIDE, d_res + 1);
+  return dot_read(flop);
+}
+
+// the partial sums of the dot product just launched: all-reduced, read back, rounded
+REAL_TYPE CZ::dot_read(double& flop) {
   flop += 2.0 * npts();
   if (!Comm_SUM_dev(d_res + 1, 1)) exit(0);
   HIP_CHECK(hipMemcpyAsync(h_scal + 1, d_res + 1, sizeof(double), hipMemcpyDeviceToHost, stream()));
@@ -1319,7 +1163,7 @@ bool CZ::bicg_fusable(int pc_type) {
 void CZ::Preconditioner(REAL_TYPE* xx, REAL_TYPE* bb, double& flop, int s_type, const BMade* made) {
   double res = 0.0;
   const int lc_max = 8;  // :280
-  const size_t nbytes = (size_t)(size[0] + 2 * GUIDE) * (size[1] + 2 * GUIDE) * (size[2] + 2 * GUIDE) * sizeof(REAL_TYPE);
+  const size_t nbytes = padded_cells() * sizeof(REAL_TYPE);
   // blas_clear_(xx) of the caller (cz_Poisson.cpp:405, 441) is folded in here.  With the plain Jacobi preconditioner on
   // the fused-pair path the clear is not even executed: xx's guide cells / faces are zero from allocation on (sweeps only
   // ever write its inner box) and the first pair takes "u == 0" as a literal instead of reading it.
@@ -1331,46 +1175,17 @@ void CZ::Preconditioner(REAL_TYPE* xx, REAL_TYPE* bb, double& flop, int s_type, 
     explicit Scope(bool& x) : f(x) { f = true; }
     ~Scope() { f = false; }
   } scope(in_precond);
-  switch (s_type) {
-    case LS_JACOBI:
-    case LS_JACOBI_MAF:
-      JACOBI(res, xx, bb, lc_max, flop, s_type, false, zero_start, made);
-      break;
-    case LS_SOR2SMA:
-    case LS_SOR2SMA_MAF:
-      RBSOR(res, xx, bb, lc_max, flop, s_type, false, zero_start, made);
-      break;
-    case LS_PCR_RB:
-      LSOR_PCR_RB(res, xx, bb, lc_max, flop, s_type, false);
-      break;
-    case LS_PSOR:
-    case LS_PSOR_MAF:
-      PSOR(res, xx, bb, lc_max, flop, s_type, false);
-      break;
-    case LS_PCR:
-    case LS_PCR_EDA:
-    case LS_PCR_RB_ESA:  // (LS_PCR_J_ESA has no case in the reference either, cz_Poisson.cpp:282-321: it falls to the copy)
-      LSOR_PCR_VARIANT(res, xx, bb, lc_max, flop, s_type, false);
-      break;
-    case LS_PCR_MAF:
-    case LS_PCR_EDA_MAF:
-    case LS_PCR_RB_MAF:
-    case LS_PCR_RB_ESA_MAF:  // :300-316
-      LSOR_PCR_MAF(res, xx, bb, lc_max, flop, s_type, false);
-      break;
-    default: {
-      const size_t n = (size_t)(size[0] + 2 * GUIDE) * (size[1] + 2 * GUIDE) * (size[2] + 2 * GUIDE);
-      HIP_CHECK(hipMemcpyAsync(xx, bb, n * sizeof(REAL_TYPE), hipMemcpyDeviceToDevice, stream()));  // blas_copy_
-    }
-  }
+  // (a name without a loop here -- none, and pcr_j_esa as in the reference, cz_Poisson.cpp:282-321 -- is a copy)
+  if (cz_solvers::row(s_type).precond_runs) run(s_type, res, xx, bb, lc_max, flop, false, zero_start, made);
+  else HIP_CHECK(hipMemcpyAsync(xx, bb, nbytes, hipMemcpyDeviceToDevice, stream()));  // blas_copy_
 }
 
 // cz_Poisson.cpp:332-504
 int CZ::PBiCGSTAB(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop, int s_type) {
-  const bool maf = (s_type == LS_BICGSTAB_MAF);
+  const bool maf = cz_solvers::row(s_type).maf;
   const int gc = GUIDE;
   hipStream_t st = stream();
-  const size_t nbytes = (size_t)(size[0] + 2 * gc) * (size[1] + 2 * gc) * (size[2] + 2 * gc) * sizeof(REAL_TYPE);
+  const size_t nbytes = padded_cells() * sizeof(REAL_TYPE);
   int itr;
   double flop_count = 0.0;
   res = 0.0;
@@ -1404,15 +1219,7 @@ int CZ::PBiCGSTAB(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop, int s_t
   // as REALs.  CZ_BICG_DEVSC=0: the host computes them from read-back dot products as in rounds 1-2 (and as the reference does).
   REAL_TYPE* const d_bs = reinterpret_cast<REAL_TYPE*>(d_res + 12);
   const bool devsc = cfg.on(CZV_BICG_DEVSC, true);
-  bool pc_copy;  // Preconditioner() has no case for pc_type: it copies (cz_Poisson.cpp:282-321)
-  switch (pc_type) {
-    case LS_JACOBI: case LS_JACOBI_MAF: case LS_SOR2SMA: case LS_SOR2SMA_MAF: case LS_PCR_RB: case LS_PSOR: case LS_PSOR_MAF: case LS_PCR:
-    case LS_PCR_EDA: case LS_PCR_RB_ESA: case LS_PCR_MAF: case LS_PCR_EDA_MAF: case LS_PCR_RB_MAF: case LS_PCR_RB_ESA_MAF:
-      pc_copy = false;
-      break;
-    default:
-      pc_copy = true;
-  }
+  bool pc_copy = !cz_solvers::row(pc_type).precond_runs;  // Preconditioner() would copy (cz_Poisson.cpp:318-320)
   if (!cfg.on(CZV_BICG_ALIAS, true)) pc_copy = false;  // (the copy is made: A/B and the bit-equality test)
 
   for (itr = 1; itr < ItrMax; itr++) {  // :373
@@ -1538,7 +1345,7 @@ int CZ::PBiCGSTAB(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop, int s_t
 int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   const int gc = GUIDE;
   hipStream_t st = stream();
-  const size_t nbytes = (size_t)(size[0] + 2 * gc) * (size[1] + 2 * gc) * (size[2] + 2 * gc) * sizeof(REAL_TYPE);
+  const size_t nbytes = padded_cells() * sizeof(REAL_TYPE);
   const double n = npts();
   const bool pc = pc_type == LS_JACOBI || pc_type == LS_MG || pc_type == LS_MGRB;
   const bool fuse = cfg.on(CZV_CG_FUSE, true);
@@ -1635,8 +1442,7 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
 
 // ------------------------------------------------------------------------------------------------------------
 void CZ::Field(REAL_TYPE* host) const {
-  const size_t n = (size_t)(size[0] + 2 * GUIDE) * (size[1] + 2 * GUIDE) * (size[2] + 2 * GUIDE);
-  czhip_d2h(host, P, n * sizeof(REAL_TYPE));
+  czhip_d2h(host, P, padded_cells() * sizeof(REAL_TYPE));
 }
 
 // profiling.txt (cz_Evaluate.cpp:506-545).  The reference prints PMlib's "Basic Report" (PMlib 6.4.x is a third-party

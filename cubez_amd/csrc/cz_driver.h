@@ -10,12 +10,10 @@
 
 #include "cz_config.h"
 #include "cz_internal.h"
+#include "cz_solvers.h"  // enum LinearSolver (cz_Define.h:68-89) and the table of the names accepted: one row each
 
 typedef CZ_REAL REAL_TYPE;  // cz_Define.h:28-37
 #define GUIDE 2             // cz_Define.h:40
-
-// cz_Define.h:68-89 (only the solvers of the hot path are accepted; the others are rejected by setLS)
-enum LinearSolver { LS_NONE = 0, LS_PSOR = 1, LS_SOR2SMA, LS_BICGSTAB, LS_JACOBI, LS_PCR = 5, LS_PCR_EDA, LS_PCR_ESA, LS_PCR_RB, LS_PCR_RB_ESA, LS_PCR_J_ESA, LS_PSOR_MAF = 11, LS_SOR2SMA_MAF, LS_BICGSTAB_MAF, LS_JACOBI_MAF, LS_PCR_MAF, LS_PCR_EDA_MAF, LS_PCR_ESA_MAF, LS_PCR_RB_MAF, LS_PCR_RB_ESA_MAF, LS_PCG, LS_MG, LS_MGRB };  // (LS_PCG, LS_MG, LS_MGRB: beyond the reference)
 
 // CB_Define_stub.h:64-70 / cz_fparam.fi:10-16
 enum { I_minus = 0, I_plus, J_minus, J_plus, K_minus, K_plus };
@@ -155,9 +153,11 @@ class CZ {
   int RBSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, int itr_max, double& flop, int s_type, bool converge_check = true, bool x_is_zero = false,
             const BMade* made = nullptr);
   int PSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, int itr_max, double& flop, int s_type, bool converge_check = true);
-  int LSOR_PCR_VARIANT(double& res, REAL_TYPE* X, REAL_TYPE* B, int itr_max, double& flop, int s_type, bool converge_check = true);
-  int LSOR_PCR_MAF(double& res, REAL_TYPE* X, REAL_TYPE* B, int itr_max, double& flop, int s_type, bool converge_check = true);
-  int LSOR_PCR_RB(double& res, REAL_TYPE* X, REAL_TYPE* B, int itr_max, double& flop, int s_type, bool converge_check = true);
+  int LSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, int itr_max, double& flop, int s_type, bool converge_check = true);
+  // the loop of s_type's family (cz_solvers.h): what Solve, Sweeps and Preconditioner call
+  int run(int s_type, double& res, REAL_TYPE* X, REAL_TYPE* B, int itr_max, double& flop, bool converge_check = true, bool x_is_zero = false,
+          const BMade* made = nullptr);
+  REAL_TYPE dot_read(double& flop);
   REAL_TYPE Fdot1(REAL_TYPE* x, double& flop);
   REAL_TYPE Fdot2(REAL_TYPE* x, REAL_TYPE* y, double& flop);
   void Preconditioner(REAL_TYPE* xx, REAL_TYPE* bb, double& flop, int s_type, const BMade* made = nullptr);
@@ -191,8 +191,11 @@ class CZ {
 
   int finish_stationary(int itr_max, bool converge_check, double& res);
   void read_history(int n_exec, double& res);
-  // line solvers: the stage count of the k lines (exits when there is none), the test after an iteration, the end of the solve
+  // line solvers: the stage count of the k lines (exits when there is none), the launches and exchanges of one iteration and its operation
+  // count, the test after an iteration, the end of the solve
   int line_stages();
+  bool line_iteration(const cz_solvers::Line& d, REAL_TYPE* X, REAL_TYPE* B, int pn);
+  double line_flop(const cz_solvers::Line& d, int pn) const;
   int line_test(int itr, int s_type);
   int line_finish(int itr, int itr_max, bool converge_check, double& res, int s_type);
   // line solvers: the one-launch lexicographic sweep reports a lost hand-off between its workgroups as a NaN residual (every wait inside
@@ -200,6 +203,7 @@ class CZ {
   bool sweep_failed(const char* solver);
   bool line_error = false;       // set by sweep_failed; PBiCGSTAB gives up when a line-solver preconditioner set it
   double npts() const;
+  size_t padded_cells() const;   // cells of an array with its guide layers
 };
 
 // the distributed V-cycle of pcg ... mg (cz_mg_dist.cpp, DESIGN.md §5.10 "Decomposed runs")
