@@ -61,6 +61,7 @@ CZ::CZ() {
   cfg = CzConfig::from_env();  // the environment as this driver was created in (cz_config.h); nothing below asks it again
   overlap = cfg.num(CZV_OVERLAP, overlap);
   lag_reduce = cfg.num(CZV_LAG_REDUCE, lag_reduce);
+  field_form = cfg.num(CZV_FIELD_FORM, field_form);
   if (const char* sk = cfg.str(CZV_TEST_SKEW)) sscanf(sk, "%d,%d", &skew_rank, &skew_ms);  // tests: "rank,milliseconds"
 }
 
@@ -88,6 +89,8 @@ CZ::~CZ() {
   for (hipEvent_t e : ev_chk)
     if (e) (void)hipEventDestroy(e);
   if (comm_stream) (void)hipStreamDestroy(comm_stream);
+  if (ev_io) (void)hipEventDestroy(ev_io);
+  if (io_stage) (void)hipFree(io_stage);
   if (fph) fclose(fph);
 }
 
@@ -375,7 +378,11 @@ int CZ::Solve() {
   if (!set_up) return 0;
   double res = 0.0, flop = 0.0;
   int itr = 0;
+  // every solve starts from the current P with the bookkeeping a fresh set-up leaves (the loops clear the device flag and their counters
+  // themselves; the lagged tests of an earlier solve were drained by its fused_end)
   history.clear();
+  sweeps_done = 0;
+  line_error = false;
   if (profile) czhip_timing(1);  // restart the section timers (the reference's PM.start/stop around the kernels)
   czhip_sync();
   const double t0 = now_s();
@@ -1445,6 +1452,98 @@ void CZ::Field(REAL_TYPE* host) const {
   czhip_d2h(host, P, padded_cells() * sizeof(REAL_TYPE));
 }
 
+// The caller's problem: import into RHS / P, export of P (cz_set_rhs, cz_set_field, cz_get_field).  Device arrays are handed
+// over by events (the compute stream waits for what the caller's stream holds, the kernel runs, the caller's stream waits for the kernel): no
+// device-wide wait.  user_stream NULL: nothing to wait for before, the host waits for the compute stream after.  Host arrays: the span the
+// strides cover goes through a device buffer and the same kernels; of an export only the brick's cells reach the caller's array.
+int CZ::FieldIO(int which, REAL_TYPE* a, const long long* stride, int on_device, void* user_stream, bool to_user, const char* who) {
+  auto refuse = [&](const char* why) {
+    fprintf(stderr, "%s: %s\n", who, why);
+    return 0;
+  };
+  if (!set_up) return refuse("no problem is set up (cz_setup first)");
+  if (!a || !stride) return refuse("NULL pointer");
+  if (reinterpret_cast<uintptr_t>(a) & (sizeof(REAL_TYPE) - 1)) return refuse("the array is not aligned to its element size");
+  for (int d = 0; d < 3; d++)
+    if (stride[d] < 1) return refuse("strides must be positive (elements)");
+  long long span = 1;
+  for (int d = 0; d < 3; d++) span += (long long)(size[d] - 1) * stride[d];
+  if (to_user) {
+    // two cells of a destination must not share an element.  Accepted: ordered by stride, every stride is at least the span of the
+    // directions below it (dense arrays in any order of the directions, and slices of them); directions of one cell do not count
+    int o[3] = {0, 1, 2};
+    std::sort(o, o + 3, [&](int x, int y) { return stride[x] < stride[y]; });
+    long long below = 1;  // span of the directions already passed
+    for (int n = 0; n < 3; n++) {
+      const int d = o[n];
+      if (size[d] == 1) continue;
+      if (stride[d] < below) return refuse("two cells of the destination share an element under these strides");
+      below += (long long)(size[d] - 1) * stride[d];
+    }
+  }
+  hipStream_t st = stream();
+  REAL_TYPE* arr = which == 0 ? RHS : P;
+  REAL_TYPE* dev = a;
+  if (on_device) {
+    hipPointerAttribute_t at;
+    int cur = -1;
+    HIP_CHECK(hipGetDevice(&cur));
+    if (hipPointerGetAttributes(&at, a) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != cur) {
+      (void)hipGetLastError();
+      return refuse("not a pointer to memory of the handle's device");
+    }
+    if (user_stream) {
+      if (!ev_io) HIP_CHECK(hipEventCreateWithFlags(&ev_io, hipEventDisableTiming));
+      HIP_CHECK(hipEventRecord(ev_io, (hipStream_t)user_stream));
+      HIP_CHECK(hipStreamWaitEvent(st, ev_io, 0));
+    }
+  } else {
+    if ((size_t)span > io_stage_cap) {
+      if (io_stage) {
+        HIP_CHECK(hipStreamSynchronize(st));
+        HIP_CHECK(hipFree(io_stage));
+      }
+      HIP_CHECK(hipMalloc(&io_stage, (size_t)span * sizeof(REAL_TYPE)));
+      io_stage_cap = (size_t)span;
+    }
+    dev = io_stage;
+    // (an export fills the brick's cells of the device span only; the host copies exactly those cells below -- the other elements of the
+    // caller's span are not the library's to touch: they may be another rank's cells of one shared array)
+    if (!to_user) HIP_CHECK(hipMemcpyAsync(dev, a, (size_t)span * sizeof(REAL_TYPE), hipMemcpyHostToDevice, st));
+  }
+  last_field_form = field_copy_async(arr, dev, size, GUIDE, stride, to_user ? 1 : 0, field_form == 3 ? 3 : 0);
+  if (!last_field_form) return refuse("no kernel form takes these strides");
+  if (!to_user) {
+    // the ghost layers as Setup fills them; WRK's copy of P's shell is stale
+    if (!Comm_S2(arr)) return 0;
+    if (which == 1) wrk_shell_tag = 0;
+  }
+  if (!on_device) {
+    std::vector<REAL_TYPE> tmp;
+    if (to_user) {
+      tmp.resize((size_t)span);
+      HIP_CHECK(hipMemcpyAsync(tmp.data(), dev, (size_t)span * sizeof(REAL_TYPE), hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (to_user) {  // the brick's cells and nothing else, the direction of the smallest stride innermost
+      int o[3] = {0, 1, 2};
+      std::sort(o, o + 3, [&](int x, int y) { return stride[x] > stride[y]; });
+      const long long s0 = stride[o[0]], s1 = stride[o[1]], s2 = stride[o[2]];
+      for (int x = 0; x < size[o[0]]; x++)
+        for (int y = 0; y < size[o[1]]; y++) {
+          const long long base = x * s0 + y * s1;
+          for (int z = 0; z < size[o[2]]; z++) a[base + z * s2] = tmp[(size_t)(base + z * s2)];
+        }
+    }
+  } else if (user_stream) {
+    HIP_CHECK(hipEventRecord(ev_io, st));
+    HIP_CHECK(hipStreamWaitEvent((hipStream_t)user_stream, ev_io, 0));
+  } else {
+    HIP_CHECK(hipStreamSynchronize(st));
+  }
+  return 1;
+}
+
 // profiling.txt (cz_Evaluate.cpp:506-545).  The reference prints PMlib's "Basic Report" (PMlib 6.4.x is a third-party
 // library that is not part of the reference tree); this is the same table -- one line per measured section with call
 // count, accumulated time, share, time per call, operation count and rate -- filled from the library's HIP-event timing
@@ -1663,6 +1762,31 @@ int cz_history(const cz_handle* h, double* out, int cap) {
   return n;
 }
 void cz_field(const cz_handle* h, CZ_REAL* host_out) { h->cz.Field(host_out); }
+int cz_set_rhs(cz_handle* h, const CZ_REAL* src, const long long* stride, int on_device, void* ready_stream) {
+  return h ? h->cz.FieldIO(0, const_cast<CZ_REAL*>(src), stride, on_device, ready_stream, false, "cz_set_rhs") : 0;
+}
+int cz_set_field(cz_handle* h, const CZ_REAL* src, const long long* stride, int on_device, void* ready_stream) {
+  return h ? h->cz.FieldIO(1, const_cast<CZ_REAL*>(src), stride, on_device, ready_stream, false, "cz_set_field") : 0;
+}
+int cz_get_field(cz_handle* h, CZ_REAL* dst, const long long* stride, int on_device, void* done_stream) {
+  return h ? h->cz.FieldIO(1, dst, stride, on_device, done_stream, true, "cz_get_field") : 0;
+}
+int cz_set_eps(cz_handle* h, double eps) {
+  if (!h || !h->cz.set_up || !(eps > 0.0)) {
+    fprintf(stderr, "cz_set_eps: %s\n", h && h->cz.set_up ? "the tolerance must be positive" : "no problem is set up (cz_setup first)");
+    return 0;
+  }
+  h->cz.eps = eps;
+  return 1;
+}
+int cz_set_itr_max(cz_handle* h, int n) {
+  if (!h || !h->cz.set_up || n < 1) {
+    fprintf(stderr, "cz_set_itr_max: %s\n", h && h->cz.set_up ? "at least one iteration" : "no problem is set up (cz_setup first)");
+    return 0;
+  }
+  h->cz.ItrMax = n;
+  return 1;
+}
 void cz_local_size(const cz_handle* h, int* size3, int* head3, int* nID6, int* inner6) {
   for (int a = 0; a < 3; a++) size3[a] = h->cz.size[a], head3[a] = h->cz.head[a];
   for (int f = 0; f < 6; f++) nID6[f] = h->cz.nID[f], inner6[f] = h->cz.innerFidx[f];
@@ -1695,6 +1819,7 @@ int cz_info(const cz_handle* h, int what) {
     case 7: return c.last_plan.kind;
     case 8: return c.last_plan.depth;
     case 9: return c.last_plan.buffers;
+    case 20: return c.last_field_form;
     default: return -1;
   }
 }

@@ -81,6 +81,11 @@ class CZ {
   int bicg_fused = 0;            // vector updates of the last BiCGSTAB solve that were made inside the first pair of a preconditioner solve (cz_info 10)
   bool in_precond = false;       // inside Preconditioner: an unchecked solve does not drain the queue (the caller's next launch follows in stream order)
   int last_lag = 0;              // the last stationary solve ran its all-reduce + test one pass behind (cz_info)
+  int field_form = 0;            // CZ_FIELD_FORM: 3 = the generic import / export kernel whatever the strides
+  int last_field_form = 0;       // the kernel form of the last import / export (cz_info 20: 1 k rows, 2 tile transpose, 3 generic)
+  hipEvent_t ev_io = nullptr;    // the hand-over between the caller's stream and the compute stream
+  REAL_TYPE* io_stage = nullptr; // device copy of a host array's span
+  size_t io_stage_cap = 0;
   CzConfig cfg;  // the environment as read when this object was created (cz_config.h)
   int skew_rank = -1, skew_ms = 0;  // CZ_TEST_SKEW=rank,ms: that rank sleeps before each look at the convergence flag (tests)
   void skew_wait() const;
@@ -124,6 +129,9 @@ class CZ {
   int Sweeps(int n);
   double ErrorMax(int loc[3]);          //   :550-563
   void Field(REAL_TYPE* host) const;
+  // the caller's own problem (part 4 of cz_hip.h): this rank's brick, cell (i, j, k) at a[i stride[0] + j stride[1] + k stride[2]],
+  // into RHS (which 0) or P (which 1), or P out into it (to_user); 1 / 0
+  int FieldIO(int which, REAL_TYPE* a, const long long* stride, int on_device, void* user_stream, bool to_user, const char* who);
   void WriteProfile(FILE* fp) const;                                             // cz_Evaluate.cpp:506-545
   bool WriteSph(const char* fname, const REAL_TYPE* padded_host_field) const;  // cz_utility.f90:17-47
   void Exact(std::vector<REAL_TYPE>& e) const;                                   // cz_utility.f90:52-82

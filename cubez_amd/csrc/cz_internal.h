@@ -127,6 +127,9 @@ int pair_box_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz
                    const CZ_REAL* cf, CZ_REAL omg, int rb, double* res_dev, int with_shell, const int* skip, const MafPtrs* maf);
 void copy_shell_async(CZ_REAL* dst, const CZ_REAL* src, const int* sz, const int* idx, int g);
 void copy_inner_async(CZ_REAL* dst, const CZ_REAL* src, const int* sz, const int* idx, int g);
+// a caller's brick (cell (i, j, k) at user[i stride[0] + j stride[1] + k stride[2]], elements) into (to_user 0) or out of (1) the padded array arr;
+// form 0: chosen from the strides, 1 row / 2 transpose / 3 generic asked for; returns the form taken, 0 = refused (cz_k_field.h, cz_h_field.h)
+int field_copy_async(CZ_REAL* arr, CZ_REAL* user, const int* sz, int g, const long long* stride, int to_user, int form);
 void bc_async(const int* sz, int g, CZ_REAL* p, CZ_REAL dh, const CZ_REAL* org, const int* nID, int ioff = 0, int joff = 0);
 
 // ---- the multigrid V-cycle of pcg ... mg (cz_h_mg.h, and cz_mg_dist.cpp for decomposed runs)

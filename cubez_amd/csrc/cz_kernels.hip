@@ -50,6 +50,7 @@ namespace {
 #include "cz_k_psor.h"
 #include "cz_k_blas.h"
 #include "cz_k_mg.h"
+#include "cz_k_field.h"
 #include "cz_h_ctx.h"
 #include "cz_h_launch.h"
 
@@ -1390,6 +1391,7 @@ void bc_async(const int* sz, int g, REAL* p, REAL dh, const REAL* org, const int
   }
   HIP_CHECK(hipGetLastError());
 }
+#include "cz_h_field.h"
 }  // namespace czhip_internal
 
 // ------------------------------------------------------------------------------------------------------------

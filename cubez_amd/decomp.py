@@ -41,6 +41,12 @@ def inner_range(size, nID):
     return idx
 
 
+def brick_slice(size, head):
+    """the cells a rank owns within an array of the whole domain indexed [i, j, k] (head: 1-based global index of the brick's first cell):
+    what CZ.set_rhs / set_field take and get_field returns is ``whole[brick_slice(size, head)]``"""
+    return tuple(slice(h - 1, h - 1 + n) for n, h in zip(size, head))
+
+
 def rb_offset(head, idx, nproc):
     """colour offset passed to psor2sma_core so that colour 0 = even GLOBAL i+j+k (CZ::RBSOR)."""
     return 0 if nproc == 1 else (head[0] + head[1] + head[2] + 1 + idx[4]) % 2

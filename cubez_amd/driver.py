@@ -36,6 +36,11 @@ class CZ:
         lib.czhip_timing_read.argtypes = [C.c_char_p, C.POINTER(C.c_double)]
         lib.cz_info.argtypes = [C.c_void_p, C.c_int]
         lib.cz_precondition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ("cz_set_rhs", "cz_set_field", "cz_get_field"):
+            getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_int, C.c_void_p]
+        lib.cz_set_eps.argtypes = [C.c_void_p, C.c_double]
+        lib.cz_set_itr_max.argtypes = [C.c_void_p, C.c_int]
+        self.device = int(device)
         if lib.czhip_init(int(device)) != 0:
             raise RuntimeError("czhip_init failed")
         self.h = lib.cz_create()
@@ -93,6 +98,74 @@ class CZ:
         self.lib.cz_field(self.h, out.ctypes.data_as(C.c_void_p))
         return out
 
+    # -- the caller's own problem (cz_set_rhs / cz_set_field / cz_get_field of include/cz_hip.h): arrays of this rank's brick, shape
+    # local()["size"] = (ni, nj, nk), indexed [i, j, k], any positive strides.  A numpy array goes the host path; anything with data_ptr(),
+    # stride(), dtype, device and is_cuda (a torch tensor on the handle's GPU) is read / written in place on the device, handed over on
+    # torch's current stream.
+    def _brick(self, a, what):
+        shape = tuple(self.local()["size"])
+        if isinstance(a, np.ndarray):
+            if a.dtype != self.real:
+                raise ValueError(f"{what}: dtype {a.dtype}, this handle is {np.dtype(self.real)}")
+            if tuple(a.shape) != shape:
+                raise ValueError(f"{what}: shape {tuple(a.shape)}, this rank's brick is {shape}")
+            if any(st % a.itemsize or st < a.itemsize for st in a.strides):
+                raise ValueError(f"{what}: strides {a.strides} are not positive multiples of the element size")
+            return a.ctypes.data, [st // a.itemsize for st in a.strides], 0, None, None
+        if not all(hasattr(a, n) for n in ("data_ptr", "stride", "dtype", "device", "is_cuda")):
+            raise ValueError(f"{what}: a numpy array or a device tensor (data_ptr, stride, dtype, device, is_cuda) is needed")
+        if str(a.dtype).split(".")[-1] != np.dtype(self.real).name:
+            raise ValueError(f"{what}: dtype {a.dtype}, this handle is {np.dtype(self.real)}")
+        if tuple(a.shape) != shape:
+            raise ValueError(f"{what}: shape {tuple(a.shape)}, this rank's brick is {shape}")
+        import torch  # (only on this path: the package imports without it)
+        mine = self.device if self.device >= 0 else torch.cuda.current_device()
+        if not a.is_cuda or a.device.index != mine:
+            raise ValueError(f"{what}: tensor on {a.device}, this handle runs on GPU {mine}")
+        strides = [int(v) for v in a.stride()]
+        if min(strides) < 1:
+            raise ValueError(f"{what}: strides {strides} must be positive")
+        ts = torch.cuda.current_stream(a.device)
+        # torch's default stream is handle 0, which the C interface reads as "no stream to hand over on": wait for that stream (not the device)
+        # before an import, and let the library wait for its kernel after an export
+        return a.data_ptr(), strides, 1, ts.cuda_stream or None, ts
+
+    def _io(self, fn, a, what):
+        ptr, strides, on_dev, stream, ts = self._brick(a, what)
+        if on_dev and stream is None:
+            ts.synchronize()
+        if fn(self.h, C.c_void_p(ptr), (C.c_longlong * 3)(*strides), on_dev, C.c_void_p(stream) if stream else None) != 1:
+            raise RuntimeError(f"{what}: refused (see stderr)")
+
+    def set_rhs(self, a):
+        """the right-hand side b of  sum of the six neighbours - 6 p = b  on this rank's brick (collective in a decomposed run)"""
+        self._io(self.lib.cz_set_rhs, a, "set_rhs")
+
+    def set_field(self, a):
+        """Dirichlet values (the layers on physical sides) and the initial guess (collective in a decomposed run)"""
+        self._io(self.lib.cz_set_field, a, "set_field")
+
+    def get_field(self, out=None):
+        """the current iterate of this rank's brick into `out` (default: a new C-order numpy array [i, j, k]); returns it"""
+        if out is None:
+            out = np.empty(tuple(self.local()["size"]), dtype=self.real)
+        self._io(self.lib.cz_get_field, out, "get_field")
+        return out
+
+    def set_eps(self, eps: float):
+        if self.lib.cz_set_eps(self.h, float(eps)) != 1:
+            raise ValueError(f"set_eps({eps}): refused")
+
+    def set_itr_max(self, n: int):
+        if self.lib.cz_set_itr_max(self.h, int(n)) != 1:
+            raise ValueError(f"set_itr_max({n}): refused")
+
+    def global_slice(self):
+        """this rank's brick within an array of the whole domain indexed [i, j, k]"""
+        from .decomp import brick_slice
+        loc = self.local()
+        return brick_slice(loc["size"], loc["head"])
+
     def error_max(self):
         loc = (C.c_int * 3)()
         d = self.lib.cz_error_max(self.h, loc)
@@ -101,7 +174,7 @@ class CZ:
     def info(self) -> dict:
         """what a (multi-GPU) run decided (cz_info of include/cz_hip.h)"""
         keys = ("ranks", "fused_pass", "shell_slabs", "overlap", "lagged_reduce", "rccl_ranks", "comm_cus", "pass_kind", "exchange_depth", "buffers", "bicg_fused", "rb4_passes",
-                "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother")
+                "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother", "field_form")
         return {k: self.lib.cz_info(self.h, i) for i, k in enumerate(keys)}
 
     def precondition(self, r: np.ndarray) -> np.ndarray:

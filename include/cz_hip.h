@@ -396,7 +396,42 @@ void cz_destroy(cz_handle*);
 int cz_evaluate(cz_handle*, int argc, char** argv);
 /* Split form used by bench.py / tests: setup (parse + allocate + boundary conditions), then solve. */
 int cz_setup(cz_handle*, int argc, char** argv);
-int cz_solve(cz_handle*);                      /* runs the selected solver to ItrMax / eps; returns Iter (0 = error) */
+int cz_solve(cz_handle*);                      /* runs the selected solver to ItrMax / eps; returns Iter (0 = error).  Repeatable: every call
+                                                  starts from the current P with the history and the counters of cz_info a fresh set-up leaves */
+/* A caller's own problem (INTEGRATION.md "Level 3").  After cz_setup (sizes, solver, ItrMax, coefficient, preconditioner,
+ * division as on the command line) the built-in test case in P and RHS is replaced by the caller's:
+ *   cz_set_rhs    the right-hand side b,
+ *   cz_set_field  the Dirichlet values and the initial guess,
+ *   cz_get_field  the current iterate / the solution, into the caller's array,
+ *   cz_set_eps    the tolerance of the residual test (> 0; 1.0e-5 after cz_setup),  cz_set_itr_max  the iteration limit (>= 1).
+ * The system solved is the one the kernels state, with the unit coefficients of the command line:
+ *   p[i+1] + p[i-1] + p[j+1] + p[j-1] + p[k+1] + p[k-1] - 6 p = b        at every inner cell
+ * -- for the Poisson equation on a mesh of width h, b = h^2 f: scaling is the caller's business.  The MAF solvers take the entries too; their
+ * grid stays the built-in one.
+ * The array covers the calling rank's brick, cells 1 .. size[d] of cz_local_size, without guide cells: cell [i, j, k] (0-based) is element
+ * i stride[0] + j stride[1] + k stride[2], strides in elements, any positive values -- a C-order tensor [ni][nj][nk] has strides
+ * {nj nk, nk, 1}, the reference's Fortran array p[i,j,k] has {1, ni, ni nj}, a slice of a larger array keeps the larger array's strides.
+ * On a physical side of the domain layer 1 / size[d] of the field is the Dirichlet face: no solver writes it.  Every other cell of
+ * cz_set_field is the initial guess.  Values of b on physical faces are copied but never read: every pass reads b at the cells it updates
+ * (inner cells; in a decomposed run also inner cells of the neighbour, through the ghost layer), so the solution does not depend on them.
+ * After an import the ghost layers are filled from the neighbours as cz_setup does: in a decomposed run cz_set_rhs and cz_set_field are
+ * collective, every rank calls them with its own brick, and needs to do nothing more.
+ * on_device = 1: the pointer is memory of the handle's device, read or written in place by kernels on the library's compute stream (no copy
+ * through the host).  stream is the hipStream_t on which the caller produced the data (cz_set_*) or will consume it (cz_get_field): the
+ * compute stream waits for an event recorded there, and that stream waits for the kernel, so the caller neither synchronises nor has to keep
+ * its hands off the array afterwards.  NULL: the data must be complete at the call, which returns when the kernel has finished.  Nothing on
+ * this path waits for the whole device.  on_device = 0: host memory; the elements the strides span go through a device buffer and the same
+ * kernels, and the call returns when done.  Either way cz_get_field writes the brick's cells and no other element of dst -- ranks that are
+ * threads of one process may export their bricks into one shared array at the same time.
+ * Return 1, or 0 with one line on stderr and nothing changed: before cz_setup, a NULL pointer, a stride < 1, a pointer that is not on the
+ * handle's device, a destination under whose strides two cells share an element (accepted: ordered by stride, each stride is at least the
+ * span of the directions below it -- dense arrays in any order of directions, and their slices).
+ * cz_error_max keeps comparing with the analytic solution of the built-in test case. */
+int cz_set_rhs(cz_handle*, const CZ_REAL* src, const long long* stride, int on_device, void* ready_stream);
+int cz_set_field(cz_handle*, const CZ_REAL* src, const long long* stride, int on_device, void* ready_stream);
+int cz_get_field(cz_handle*, CZ_REAL* dst, const long long* stride, int on_device, void* done_stream);
+int cz_set_eps(cz_handle*, double eps);
+int cz_set_itr_max(cz_handle*, int n);
 int cz_sweeps(cz_handle*, int n);              /* bench leg: n more iterations of the selected stationary solver with the
                                                   full per-iteration work (sweep + residual + convergence bookkeeping),
                                                   never stopping early; returns n */
@@ -420,7 +455,8 @@ double cz_last_solve_seconds(const cz_handle*);
  * Jacobi passes of the last Jacobi solve (czhip_jacobi3_async); 15 levels of the multigrid hierarchy (pcg ... mg; 0 otherwise); 16 V-cycles
  * of the last PCG solve with mg; 17 the gather level G of a decomposed pcg ... mg (levels >= G run on every rank from an all-gathered copy;
  * 0 on a single domain or where level 0 is the coarsest); 18 halo exchanges and all-gathers of the last V-cycle of a decomposed pcg ... mg;
- * 19 the smoother of the multigrid preconditioner (0 none, 1 relaxed Jacobi: mg, 2 symmetric red-black: mgrb; 15 and 16 count for both). */
+ * 19 the smoother of the multigrid preconditioner (0 none, 1 relaxed Jacobi: mg, 2 symmetric red-black: mgrb; 15 and 16 count for both);
+ * 20 the kernel form of the last cz_set_rhs / cz_set_field / cz_get_field (1 k rows, 2 tile transpose, 3 generic; CZ_FIELD_FORM=3 forces 3). */
 int cz_info(const cz_handle*, int what);
 /* pcg ... mg | mgrb: z = M^-1 r, the set-up solver's V-cycle applied once to host fields of the calling rank's brick in the cz_field layout (the
  * ghost cells of r are not read).  Collective: every rank of a decomposed run calls it.  Returns 1, or 0 where there is no such
