@@ -391,7 +391,7 @@ void build_pattern(CommCtx* c, Pattern& p, int depth, bool edges, bool corners =
         const bool vec_rows = (nkp * c->eb) % 16 == 0;  // every padded k-row starts 16-byte aligned (hipMalloc'ed arrays)
         int kind = BOX_GENERIC;
         size_t cnt = (size_t)ext[0] * ext[1] * ext[2];
-        if (nz == 1 && dj != 0 && !c->cfg.has(CZV_COMM_PACK_J)) {
+        if (nz == 1 && dj != 0 && !c->cfg.on(CZV_COMM_PACK_J, false)) {
           kind = BOX_DIRECT;  // dep whole padded planes
           cnt = (size_t)dep * nkp * nip;
         } else if (nz == 1 && di != 0 && vec_rows) {
@@ -620,6 +620,20 @@ int comm_transport_ranks(const CommCtx* c) {
   int n = 0;
   NCCL_CHECK(ncclCommCount(c->nccl, &n));
   return n;
+}
+
+int comm_setting(const CommCtx* c, int what) {
+  if (!c) return -1;
+  switch (what) {
+    case 0: return c->cfg.on(CZV_COMM_PACK_J, false) ? 1 : 0;
+    case 1: {
+      int n = 0;
+      for (int m = 0; m < c->deep.nmsg; m++) n += c->deep.direct[m] ? 1 : 0;
+      return n;
+    }
+    case 2: return c->tr == T_RCCL && c->nccl_red == c->nccl ? 1 : 0;
+    default: return -1;
+  }
 }
 
 // ============================================================================================================

@@ -38,5 +38,8 @@ bool comm_allreduce_sum(CommCtx*, double* d_val, int count, hipStream_t st);
 double comm_allreduce_max_host(CommCtx*, double v);
 // ranks of the RCCL communicator behind the context (ncclCommCount); 0 for the LOCAL transport or no context
 int comm_transport_ranks(const CommCtx*);
+// what the communicator made of its own switches: 0 CZ_COMM_PACK_J as parsed, 1 messages of the two-layer exchange that go from / into the
+// array itself (J faces; 0 with CZ_COMM_PACK_J=1), 2 one RCCL communicator for halos and all-reduces (CZ_COMM_ONE_COMM); -1 no context
+int comm_setting(const CommCtx*, int what);
 
 #endif

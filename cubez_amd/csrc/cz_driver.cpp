@@ -1823,6 +1823,20 @@ int cz_info(const cz_handle* h, int what) {
     default: return -1;
   }
 }
+// the driver's and its communicator's copies of their own switches, name=value, one per line (the string lives until the next call on this thread)
+const char* cz_config_in_force(const cz_handle* h) {
+  static thread_local std::string text;
+  const CZ& c = h->cz;
+  const std::pair<const char*, int> rows[] = {
+      {"overlap", c.overlap}, {"lag_reduce", c.lag_reduce}, {"comm_cus", c.numProc > 1 ? c.cfg.num(CZV_COMM_CUS, 2) : 0},
+      {"comm_cus_reserved", c.comm_cus}, {"bicg_fuse", c.cfg.on(CZV_BICG_FUSE, true)}, {"bicg_devsc", c.cfg.on(CZV_BICG_DEVSC, true)},
+      {"bicg_alias", c.cfg.on(CZV_BICG_ALIAS, true)}, {"cg_fuse", c.cfg.on(CZV_CG_FUSE, true)}, {"mg_tail", c.cfg.on(CZV_MG_TAIL, true)},
+      {"mg_gather", c.cfg.num(CZV_MG_GATHER, 32768)}, {"mgrb_zero4", c.cfg.on(CZV_MGRB_ZERO4, true)}, {"field_form", c.field_form},
+      {"comm_pack_j", comm_setting(c.comm, 0)}, {"comm_direct_messages", comm_setting(c.comm, 1)}, {"comm_one_comm", comm_setting(c.comm, 2)}};
+  text.clear();
+  for (const auto& r : rows) text += std::string(r.first) + "=" + std::to_string(r.second) + "\n";
+  return text.c_str();
+}
 int cz_precondition(cz_handle* h, const CZ_REAL* r_dense, CZ_REAL* z_dense) {
   CZ& c = h->cz;
   if (!c.set_up || !(c.mg || c.mgd)) return 0;

@@ -145,6 +145,25 @@ const char* czhip_config_describe(int only_set) {
 }
 const char* czhip_arch(void) { return "gfx950"; }
 
+// what czhip_init and the setters made of the kernel switches: the calling thread's Tuning and its CU reservation, name=value, one per line
+// (ready=0: the context has not started yet, the values are the built-in defaults); the string lives until the next call on this thread
+const char* czhip_tuning_describe(void) {
+  static thread_local std::string text;
+  const Tuning& t = ctx.tune;
+  const std::pair<const char*, long long> rows[] = {
+      {"ready", ctx.ready ? 1 : 0}, {"threads", t.threads}, {"m", t.m}, {"tj", t.tj}, {"pf", t.pf}, {"fuse_fin", t.fuse_fin},
+      {"use_t2", t.use_t2}, {"t2_threads", t.t2_threads}, {"t2_mv", t.t2_mv}, {"t2_tj", t.t2_tj}, {"t2_map", t.t2_map},
+      {"t2_any_rows", t.t2_any_rows}, {"t2_kwin", t.t2_kwin}, {"t2_pre", t.t2_pre}, {"rb4", t.rb4}, {"rb4_kwin", t.rb4_kwin},
+      {"rb4_tj", t.rb4_tj}, {"jac3", t.jac3}, {"jac3_kwin", t.jac3_kwin}, {"jac3_tj", t.jac3_tj}, {"jac3_medium", t.jac3_medium},
+      {"unit_coef", t.unit_coef}, {"pcr_fast", t.pcr_fast}, {"pcr_variant", t.pcr_variant}, {"pcr_pipe", t.pcr_pipe},
+      {"pipe_spin_ticks", t.pipe_spin_ticks}, {"pcr_rows", t.pcr_rows}, {"pcr_q", t.pcr_q}, {"pcr_wg_per_cu", t.pcr_wg_per_cu},
+      {"pcr_max_wg", t.pcr_max_wg}, {"pcr_slots", t.pcr_slots}, {"psor_col", t.psor_col}, {"psor_wg_per_cu", t.psor_wg_per_cu},
+      {"psor_ahead", t.psor_ahead}, {"num_cu", ctx.num_cu}, {"cu_reserved", ctx.cu_reserved}};
+  text.clear();
+  for (const auto& r : rows) text += std::string(r.first) + "=" + std::to_string(r.second) + "\n";
+  return text.c_str();
+}
+
 int czhip_init(int device) {
   if (ctx.ready) return 0;
   int ndev = 0;

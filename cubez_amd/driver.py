@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from .lib import GUIDE, load
+from .lib import GUIDE, LABELS, _pairs, load, tuning_in_force
 
 
 class CZ:
@@ -35,6 +35,8 @@ class CZ:
         lib.cz_kernel_ms.restype = C.c_double
         lib.czhip_timing_read.argtypes = [C.c_char_p, C.POINTER(C.c_double)]
         lib.cz_info.argtypes = [C.c_void_p, C.c_int]
+        lib.cz_config_in_force.argtypes = [C.c_void_p]
+        lib.cz_config_in_force.restype = C.c_char_p
         lib.cz_precondition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ("cz_set_rhs", "cz_set_field", "cz_get_field"):
             getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_int, C.c_void_p]
@@ -177,6 +179,14 @@ class CZ:
                 "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother", "field_form")
         return {k: self.lib.cz_info(self.h, i) for i, k in enumerate(keys)}
 
+    def config_in_force(self) -> dict:
+        """the driver's and its communicator's copies of their own switches (cz_config_in_force of include/cz_hip.h)"""
+        return _pairs(self.lib.cz_config_in_force(self.h))
+
+    def tuning(self) -> dict:
+        """the calling thread's kernel switches as parsed (czhip_tuning_describe)"""
+        return tuning_in_force(self.lib)
+
     def precondition(self, r: np.ndarray) -> np.ndarray:
         """z = M^-1 r of the set-up pcg ... mg on this rank's brick (dense padded fields as field()); collective in a decomposed run"""
         r = np.ascontiguousarray(r, dtype=self.real)
@@ -192,6 +202,10 @@ class CZ:
         tot = C.c_double(0.0)
         n = self.lib.czhip_timing_read(label.encode(), C.byref(tot))
         return n, tot.value
+
+    def launches(self) -> dict:
+        """launches recorded under every label since timing was enabled on the calling thread"""
+        return {k: self.timing_read(k)[0] for k in LABELS}
 
     def close(self):
         if self.h:

@@ -315,6 +315,12 @@ int czhip_set_unit_coef(int enable);
 /* Every environment variable the library and the cz command line read (one table, cubez_amd/csrc/cz_config.h), one per line: NAME=value where set,
  * NAME (unset; default ...) otherwise; only_set != 0 lists the former only.  The string lives until the next call on the calling thread. */
 const char* czhip_config_describe(int only_set);
+/* What czhip_init and the setters made of the kernel switches: the calling thread's tuning (threads, m, tj, pf, fuse_fin, use_t2, t2_threads,
+ * t2_mv, t2_tj, t2_map, t2_any_rows, t2_kwin, t2_pre, rb4, rb4_kwin, rb4_tj, jac3, jac3_kwin, jac3_tj, jac3_medium, unit_coef, pcr_fast,
+ * pcr_variant, pcr_pipe, pipe_spin_ticks, pcr_rows, pcr_q, pcr_wg_per_cu, pcr_max_wg, pcr_slots, psor_col, psor_wg_per_cu, psor_ahead), num_cu
+ * and cu_reserved (the CU reservation of czhip_set_comm_cus), as name=value, one per line.  ready=0: the thread's context has not started,
+ * the values are the built-in defaults (the call does not start it).  Read-only; the string lives until the next call on the calling thread. */
+const char* czhip_tuning_describe(void);
 /* Decomposed runs keep k CUs of every XCD free of the sweeps (CZ_COMM_CUS, default 2) so that RCCL's send/recv kernels run while an interior
  * sweep fills the chip -- through the launch geometry (the launches count those CUs out).  Measurement aid: put that reservation in force by
  * hand (the driver does it itself in decomposed runs and undoes it in single-domain ones at set-up); returns the reservation in force. */
@@ -458,6 +464,11 @@ double cz_last_solve_seconds(const cz_handle*);
  * 19 the smoother of the multigrid preconditioner (0 none, 1 relaxed Jacobi: mg, 2 symmetric red-black: mgrb; 15 and 16 count for both);
  * 20 the kernel form of the last cz_set_rhs / cz_set_field / cz_get_field (1 k rows, 2 tile transpose, 3 generic; CZ_FIELD_FORM=3 forces 3). */
 int cz_info(const cz_handle*, int what);
+/* The driver's and its communicator's own copies of their switches, as name=value, one per line: overlap, lag_reduce, comm_cus (as asked for;
+ * 0 on a single domain), comm_cus_reserved (in force after set-up), bicg_fuse, bicg_devsc, bicg_alias, cg_fuse, mg_tail, mg_gather, mgrb_zero4,
+ * field_form; of the communicator (-1 on a single domain): comm_pack_j, comm_direct_messages (messages of the two-layer exchange sent from /
+ * received into the array itself: the J faces unless CZ_COMM_PACK_J=1), comm_one_comm.  The string lives until the next call on the thread. */
+const char* cz_config_in_force(const cz_handle*);
 /* pcg ... mg | mgrb: z = M^-1 r, the set-up solver's V-cycle applied once to host fields of the calling rank's brick in the cz_field layout (the
  * ghost cells of r are not read).  Collective: every rank of a decomposed run calls it.  Returns 1, or 0 where there is no such
  * preconditioner (another solver, or not set up). */

@@ -57,7 +57,8 @@ wall = time.time() - t0
 loc = cz.local()
 rec = dict(rank=rank, itr=itr, res=cz.res, history=cz.history(), local=loc, info=cz.info(), wall_s=wall,
            fused_pairs=cz.timing_read("jacobi2")[0] + cz.timing_read("rbsor2")[0], shell_launches=cz.timing_read("pair_shell")[0],
-           pair_ms=cz.timing_read("jacobi2"), rb_ms=cz.timing_read("rbsor2"))
+           pair_ms=cz.timing_read("jacobi2"), rb_ms=cz.timing_read("rbsor2"), launches=cz.launches(), in_force=cz.config_in_force(),
+           tuning=cz.tuning())
 cz.timing(False)
 np.save(os.path.join(outdir, f"field_{rank}.npy"), cz.field())
 with open(os.path.join(outdir, f"rank_{rank}.json"), "w") as f:

@@ -68,6 +68,7 @@ def _decomposed_run(prec, gsz, solver, itmax, coef, div, pc, solves):
                 loc["fused_pairs"] = cz.timing_read("jacobi2")[0] + cz.timing_read("rbsor2")[0]
                 loc["shell_launches"] = cz.timing_read("pair_shell")[0]
                 loc["info"] = cz.info()
+                loc["launches"], loc["in_force"], loc["tuning"] = cz.launches(), cz.config_in_force(), cz.tuning()  # (tests/switch_worker.py)
                 cz.timing(False)
                 out = (itr, cz.res, cz.history(), cz.field(), loc)
                 if results[r] is not None:  # every solve must repeat the first one exactly
