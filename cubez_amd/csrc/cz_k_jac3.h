@@ -2,7 +2,8 @@
 // jac3_k, THREE relaxed-Jacobi sweeps (cz_solver.f90:334-351 three times) per pass over memory.  Single-domain runs, constant coefficients.
 // ------------------------------------------------------------------------------------------------------------
 // Why: the two-sweep pass (jacobi2p_k) moves 1.11 x the bytes of one fused pass at 0.88 of the copy ceiling (profiles/hbm_traffic.json), so
-// the only lever left on a large Jacobi solve is fewer bytes per sweep.  The arrangement is rb4_k's (cz_k_rb4.h) one stage shorter:
+// the only lever left on a large Jacobi solve is fewer bytes per sweep.  On the frame of cz_k_pass.h (work item, addresses, masks, outer rows, masked
+// store, epilogue); the arrangement is rb4_k's (cz_k_rb4.h) one stage shorter:
 //     fields      u on E3 = own segment +- 3 rows, f1 (after sweep n+1) on E2, f2 (after sweep n+2) on E1, f3 = output on the segment
 //     threads     one per vector of E2 (TB = LV = S + 4R), dealt in order (x = t): a Jacobi stage has no colour, so rows need no dealing by parity
 //     stages      1 on all of E2; 2 on the waves that hold a vector of E1; 3 on the waves that own a vector (wave-uniform branches: the waves at
@@ -15,39 +16,6 @@
 // converges, the driver re-runs one sweep or one pair from the untouched input (out of place, like the pair).
 // ------------------------------------------------------------------------------------------------------------
 
-// the three-sum form of pair_finalize: the bookkeeping of cz_Poisson.cpp:67-77 for iterations itr, itr+1, itr+2 in order
-template <int TB>
-__device__ __forceinline__ void jac3_finalize(const double* partials, int nblk, const Fin2& fin, double* wsum) {
-  const int t = threadIdx.x;
-  double x[3] = {0.0, 0.0, 0.0};
-  for (int i = t; i < nblk; i += TB) {
-#pragma unroll
-    for (int s = 0; s < 3; s++) x[s] += __hip_atomic_load(&partials[s * nblk + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  double tot[3];
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    __syncthreads();
-    tot[s] = block_sum<TB>(x[s], wsum);
-  }
-  if (t == 0) {
-#pragma unroll
-    for (int s = 0; s < 3; s++) fin.dst[s] = tot[s];
-    if (fin.do_check) {
-      for (int s = 0; s < 3; s++) {
-        const double r = sqrt(tot[s] * fin.res_normal);
-        fin.hist[fin.itr + s] = r;
-        if (r < fin.eps) {
-          *fin.flag = 1;
-          *fin.conv_itr = fin.itr + s;
-          break;
-        }
-      }
-    }
-    *fin.counter = 0u;
-  }
-}
-
 // MED = 1 (FP32): the division with one correction step (mediumdiv, cz_k_fastdiv.h), taken only for a divisor that passed the exhaustive
 // comparison with `n / d` on this context (jac3_medium, cz_h_launch.h)
 template <int V, int TB, int UNIT, int MED>
@@ -58,87 +26,33 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = threadIdx.x;
   const int R = g.R;
-  constexpr int LV = TB;      // E2: own segment +- two rows (S = LV - 4R); one vector per thread
-  const int LU = LV + 2 * R;  // E3
-  // (R vectors of padding in front of the u buffers and behind the last field buffer: stages 1 and 2 are evaluated on whole waves and the
-  // lanes beyond their sets read +-R outside them -- inside the allocation, never used)
-  Vec<V>* ldsU = reinterpret_cast<Vec<V>*>(smem) + R;  // 2 buffers of LU vectors: plane p in buffer p & 1
-  Vec<V>* ldsF = ldsU + (size_t)2 * LU;                 // f1, f2: [field][plane & 1][LV]
-  double* wsum = reinterpret_cast<double*>(ldsF + (size_t)4 * LV + R);
+  constexpr int LV = TB;  // E2: own segment +- two rows (S = LV - 4R); one vector per thread; u on E3
+  const DeepLds<V> lds = deep_lds<V, LV, 3>(smem, R);
+  const int LU = lds.LU;
+  Vec<V>* ldsU = lds.U;
+  Vec<V>* ldsF = lds.F;
+  double* wsum = lds.wsum;
 
-  // ---- workgroup -> (window, segment, chunk): as jacobi2p_k
-  const int lb = blockIdx.x;
-  const int nblk = gridDim.x;
-  int seg, chunk;
-  if (g.map != nullptr) {
-    seg = g.map[2 * lb];
-    chunk = g.map[2 * lb + 1];
-  } else {
-    const int xc = lb & 7, r = lb >> 3;
-    const int base = g.nseg >> 3, rem = g.nseg & 7, bmax = base + (rem ? 1 : 0);
-    const int blen = base + (xc < rem ? 1 : 0);
-    const int sl = r % bmax;
-    chunk = r / bmax;
-    seg = (sl < blen) ? xc * base + min(xc, rem) + sl : g.nseg;  // nseg = no work
-  }
-  int win = 0;
-  if (seg < g.nseg) {
-    win = seg / g.nsegw;
-    seg -= win * g.nsegw;
-  } else {
-    seg = g.nsegw;
-  }
-  const int kw0 = win * g.KW - g.hv * V;
-  const long long fb = (seg < g.nsegw) ? g.F0 + (long long)seg * g.S : g.Fend;
-  const int ja = g.jj0 + chunk * g.TJ;
-  int jb = ja + g.TJ - 1;
-  if (jb > g.jj1) jb = g.jj1;
+  const PassItem it = pass_item<V>(g);
+  const int ja = it.ja, jb = it.jb;
 
   double acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
   const typename std::conditional<MED != 0, MediumDiv, HoistedDiv>::type dv{fastdiv_init(c.dd)};
 
-  if (ja <= jb && fb < g.Fend) {
-    const long long e2_0 = fb - 2 * (long long)R;  // first vector of E2
-    const long long vlast = g.PSV - 1;
+  if (it.work) {
+    const long long e2_0 = it.fb - 2 * (long long)R;  // first vector of E2
     const size_t PB = (size_t)g.PSB;
-    auto off_of = [&](long long f) -> unsigned {  // (see jacobi2p_k: clamped below the plane, not beyond it; `lim` for the array's last plane)
-      if (f < 0) f = 0;
-      if (f > vlast) f = vlast;
-      const long long r = f / R;
-      long long el = r * g.nkp + kw0 + (f - r * R) * V;
-      el = el < 0 ? 0 : el;
-      return (unsigned)(el * (long long)sizeof(REAL));
-    };
-    auto lim = [&](unsigned off, int plane) -> unsigned { return plane == g.jlast ? (off < g.last_off ? off : g.last_off) : off; };
-    auto pl = [&](int p) -> int { return p < 0 ? 0 : (p > g.jlast ? g.jlast : p); };  // planes beyond the array are never used: clamped
+    const RowView<V> rv = row_view<V>(g, it);
     const int x = t;  // this thread's vector: index in E2
     const long long f = e2_0 + x;
-    const unsigned bo = off_of(f);
-    unsigned inbox = 0;  // components inside the inner box (every stage updates only those)
-    unsigned own = 0;    // ... of a vector this workgroup owns (stores, residual counts)
-    {
-      const long long fc = f < 0 ? 0 : f;
-      const long long row = fc / R;
-      const int kv = (int)(fc - row * R);
-      const int kb = kw0 + kv * V;
-      unsigned bits = 0;
-#pragma unroll
-      for (int cc = 0; cc < V; cc++) {
-        const int kk = kb + cc;
-        if (kk >= g.kk0 && kk <= g.kk1) bits |= 1u << cc;
-      }
-      const bool rows_in = f >= g.F0 && f < g.Fend;
-      inbox = rows_in ? bits : 0u;
-      const bool kown = kv >= g.hv && kv < g.hv + g.KT;
-      own = (x >= 2 * R && x < LV - 2 * R && rows_in && kown) ? bits : 0u;
-    }
+    const unsigned bo = rv.off_of(f);
+    const VecMask mk = vec_mask<V>(g, it, f);
+    const unsigned inbox = mk.rows ? mk.bits : 0u;                                                     // components inside the inner box (every stage updates only those)
+    const unsigned own = (x >= 2 * R && x < LV - 2 * R && mk.rows && mk.kown) ? mk.bits : 0u;  // ... of a vector this workgroup owns (stores, residual counts)
     // wave-uniform: does this wave hold a vector of E1 (stage 2) / an owned vector (stage 3)?
     const bool wave2 = __builtin_amdgcn_ballot_w64(x >= R && x < LV - R) != 0ull;
     const bool wave3 = __builtin_amdgcn_ballot_w64(own != 0) != 0ull;
-    // the outer rows of E3: the first R threads stage the lower one, the last R threads the upper one
-    const bool has_halo = (t < R) || (t >= TB - R);
-    const int hl = (t < R) ? t : (LV + R + (t - (TB - R)));  // index inside an LDS u buffer (E3 coordinates)
-    const unsigned hbo = off_of(has_halo ? (fb - 3 * (long long)R + hl) : f);
+    const OuterRow h = outer_row<V, TB>(rv, LV, it.fb - 3 * (long long)R, f);  // the outer rows of E3
     const char* Ub = reinterpret_cast<const char*>(U);
     const char* Bb = reinterpret_cast<const char*>(B);
     char* Wb = reinterpret_cast<char*>(W);
@@ -147,14 +61,14 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
     const int q0 = ja - 2;
     Vec<V> uA, uB, bA, bB, hx;
     {
-      const Vec<V> t2 = ld16<V>(Ub + (size_t)pl(q0 - 1) * PB, lim(bo, pl(q0 - 1)));
-      const Vec<V> t1 = ld16<V>(Ub + (size_t)pl(q0) * PB, lim(bo, pl(q0)));
-      const Vec<V> h1 = ld16<V>(Ub + (size_t)pl(q0) * PB, lim(hbo, pl(q0)));
-      uA = ld16<V>(Ub + (size_t)pl(q0 + 1) * PB, lim(bo, pl(q0 + 1)));
-      bA = ld16<V>(Bb + (size_t)pl(q0) * PB, lim(bo, pl(q0)));
+      const Vec<V> t2 = ld16<V>(Ub + (size_t)rv.pl(q0 - 1) * PB, rv.lim(bo, rv.pl(q0 - 1)));
+      const Vec<V> t1 = ld16<V>(Ub + (size_t)rv.pl(q0) * PB, rv.lim(bo, rv.pl(q0)));
+      const Vec<V> h1 = ld16<V>(Ub + (size_t)rv.pl(q0) * PB, rv.lim(h.bo, rv.pl(q0)));
+      uA = ld16<V>(Ub + (size_t)rv.pl(q0 + 1) * PB, rv.lim(bo, rv.pl(q0 + 1)));
+      bA = ld16<V>(Bb + (size_t)rv.pl(q0) * PB, rv.lim(bo, rv.pl(q0)));
       ldsU[(size_t)((q0 - 1) & 1) * LU + R + x] = t2;
       ldsU[(size_t)(q0 & 1) * LU + R + x] = t1;
-      if (has_halo) ldsU[(size_t)(q0 & 1) * LU + hl] = h1;
+      if (h.has) ldsU[(size_t)(q0 & 1) * LU + h.hl] = h1;
     }
     Vec<V> bq1 = zerov<V>(), bq2 = zerov<V>();  // b of the planes of stages 2, 3
     __syncthreads();
@@ -177,10 +91,10 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
     // One plane step q.  uc = u(q+1) and b1 = b(q) were requested one step ago; un / bn receive this step's requests.
     auto step = [&](const int q, Vec<V>& uc, Vec<V>& un, Vec<V>& b1, Vec<V>& bn) __attribute__((always_inline)) {
       {
-        const int qu = pl(q + 2 <= jb + 3 ? q + 2 : jb + 3), qb = pl(q + 1 <= jb + 2 ? q + 1 : jb + 2);
-        hx = ld16<V>(Ub + (size_t)pl(q + 1) * PB, lim(hbo, pl(q + 1)));
-        un = ld16<V>(Ub + (size_t)qu * PB, lim(bo, qu));
-        bn = ld16<V>(Bb + (size_t)qb * PB, lim(bo, qb));
+        const int qu = rv.pl(q + 2 <= jb + 3 ? q + 2 : jb + 3), qb = rv.pl(q + 1 <= jb + 2 ? q + 1 : jb + 2);
+        hx = ld16<V>(Ub + (size_t)rv.pl(q + 1) * PB, rv.lim(h.bo, rv.pl(q + 1)));
+        un = ld16<V>(Ub + (size_t)qu * PB, rv.lim(bo, qu));
+        bn = ld16<V>(Bb + (size_t)qb * PB, rv.lim(bo, qb));
       }
       // planes of the three stages; masks: inside the inner box a stage updates, inside the chunk the owner counts the residual
       const int p1 = q, p2 = q - 1, p3 = q - 2;
@@ -199,22 +113,14 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
       // lane next to the first owned vector of a window holds a halo vector -- it owns nothing but must take part.
       if (p3 >= ja && wave3) {
         const Vec<V> o = stage(F2 + (size_t)(p3 & 1) * LV, F2 + (size_t)((p3 - 1) & 1) * LV, v2, bq2, own, own, acc3);
-        char* Wq = Wb + (size_t)p3 * PB;
-        if (own == (1u << V) - 1) {
-          st16<V>(Wq, bo, o);
-        } else if (own != 0) {
-          REAL* wp = reinterpret_cast<REAL*>(Wq + bo);
-#pragma unroll
-          for (int cc = 0; cc < V; cc++)
-            if (own & (1u << cc)) wp[cc] = o.v[cc];
-        }
+        store_owned<V>(Wb + (size_t)p3 * PB, bo, own, o);
       }
       // ---- publish: f1(p1), f2(p2) and the next u centre plane u(q+1) with its outer rows
       F1[(size_t)(p1 & 1) * LV + x] = v1;
       F2[(size_t)(p2 & 1) * LV + x] = v2;
       Vec<V>* nU = ldsU + (size_t)((p1 + 1) & 1) * LU;
       nU[R + x] = uc;
-      if (has_halo) nU[hl] = hx;
+      if (h.has) nU[h.hl] = hx;
       bq2 = bq1, bq1 = b1;  // (b1 is complete: stage 1 used it)
       __syncthreads();
     };
@@ -228,20 +134,7 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
     }
   }
 
-  // ---- residuals of the three sweeps: per-workgroup partials, finalised by the last workgroup (see jacobi2p_k)
-  __syncthreads();
-  const double s1 = block_sum<TB>(acc1, wsum);
-  __syncthreads();
-  const double s2 = block_sum<TB>(acc2, wsum);
-  __syncthreads();
-  const double s3 = block_sum<TB>(acc3, wsum);
-  int* last_flag = reinterpret_cast<int*>(wsum + 16);
-  if (t == 0) {
-    __hip_atomic_store(&partials[lb], s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&partials[nblk + lb], s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&partials[2 * nblk + lb], s3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *last_flag = arrive_and_test_last(fin.counter, nblk);
-  }
-  __syncthreads();
-  if (*last_flag) jac3_finalize<TB>(partials, nblk, fin, wsum);
+  // ---- residuals of the three sweeps: per-workgroup partials, finalised by the last workgroup
+  const double acc[3] = {acc1, acc2, acc3};
+  pass_epilogue<TB, 3>(acc, partials, fin, wsum);
 }

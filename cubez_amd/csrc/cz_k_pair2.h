@@ -1,10 +1,13 @@
 // cz_k_pair2.h -- part of cz_kernels.hip (ONE translation unit per precision; included inside its anonymous namespace after
-// cz_k_pair.h): jacobi2p_k, the software-pipelined form of the two-stage pass (two Jacobi sweeps / one red-black iteration
-// per pass over memory; cz_solver.f90:334-351, 466-480).
+// cz_k_pair.h): jacobi2p_k, the two-stage pass (two Jacobi sweeps / one red-black iteration per pass over memory;
+// cz_solver.f90:334-351, 466-480) on the frame of cz_k_pass.h, MV vectors per thread.
 // ------------------------------------------------------------------------------------------------------------
-// Same tiling, same per-point arithmetic and the same results as jacobi2_k (cz_k_pair.h) -- what changes is WHEN things move:
+//     stage 1 at plane q   : v(q)   = relax(u(q-1), u(q), u(q+1))     on E1 = own segment +- one k-row (R vectors)
+//     stage 2 at plane q-1 : w(q-1) = relax(v(q-2), v(q-1), v(q))     on the own segment
+// Software-pipelined: the tiling and the per-point arithmetic are those of round 1's kernel (tools/pair_lab_v1.h keeps it as the A/B partner
+// of tools/pair_lab.hip) -- what changed in round 2 is WHEN things move:
 //   * the loads of plane q+2 of u and of plane q+1 of b are issued at the top of step q and consumed in step q+1 (one plane
-//     of prefetch).  jacobi2_k issued the loads of a step and waited for them a few instructions later, and the compiler's
+//     of prefetch).  Round 1 issued the loads of a step and waited for them a few instructions later, and the compiler's
 //     s_waitcnt vmcnt(0) in front of the LDS publish drained the step's W stores as well: a memory round trip and a store
 //     round trip on the critical path of every plane (profiles/r02/isa_notes.md).  Here every global access of the main loop
 //     is unconditional (clamped addresses instead of predicates), so the compiler can count the younger loads and wait with
@@ -14,41 +17,10 @@
 //     of being carried in two register queues.
 //   * the vector-crossing k neighbours come from the lane next door (DPP wave shift) with one broadcast LDS read per wave for
 //     the lane at the end of the wave, instead of two stride-4 ds_read_b32 per vector (4-way bank conflicts, 32 % of all LDS
-//     cycles in jacobi2_k, profiles/r01/pmc_jacobi2_512_f32.csv).
+//     cycles in round 1, profiles/r01/pmc_jacobi2_512_f32.csv).
 // LDS: u(q) on E2 = own segment +- 2 rows and u(q-1), v(q-1) on E1 = own +- 1 row and v(q-2); two buffers each, one barrier
 // per plane.
 // ------------------------------------------------------------------------------------------------------------
-// global accesses of the pass: a vector is REAL-aligned in memory (16-byte aligned where the row length is a multiple of the vector width)
-template <int V>
-__device__ __forceinline__ Vec<V> ld16(const char* plane, unsigned byte_off) {
-  typedef typename NatVec<V>::type nv;
-  typedef nv unv __attribute__((aligned(sizeof(REAL))));
-  const nv x = *reinterpret_cast<const unv*>(plane + byte_off);
-  Vec<V> r;
-  __builtin_memcpy(&r, &x, sizeof(r));
-  return r;
-}
-template <int V>
-__device__ __forceinline__ void st16(char* plane, unsigned byte_off, const Vec<V>& x) {
-  typedef typename NatVec<V>::type nv;
-  typedef nv unv __attribute__((aligned(sizeof(REAL))));
-  nv y;
-  __builtin_memcpy(&y, &x, sizeof(y));
-  *reinterpret_cast<unv*>(plane + byte_off) = y;
-}
-
-// one ds_read_b128 per vector: left to itself the compiler re-reads overlapping pieces of a vector with ds_read_b32 / ds_read2_b32
-// (operand pairs for packed FP32 math) -- stride-16-byte scalar reads, i.e. the 4-way bank conflicts this kernel set out to remove
-template <int V>
-__device__ __forceinline__ Vec<V> lds_ld(const Vec<V>* p) {
-  typedef typename NatVec<V>::type nv;
-  nv x = *reinterpret_cast<const nv*>(p);
-  asm("" : "+v"(x));  // the value is needed whole, in consecutive registers: keeps the read one ds_read_b128
-  Vec<V> r;
-  __builtin_memcpy(&r, &x, sizeof(r));
-  return r;
-}
-
 // value of `x` in the previous (SHR) / next (SHL) lane of the wave; lane 0 / lane 63 receive `edge`
 __device__ __forceinline__ float lane_shr1(float edge, float x) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge), __builtin_bit_cast(int, x), 0x138, 0xf, 0xf, false));
@@ -178,38 +150,8 @@ jacobi2p_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restr
   double* wsum = reinterpret_cast<double*>(ldsV + (size_t)2 * LV);   // 16 doubles + flag
   REAL* ztab = reinterpret_cast<REAL*>(wsum + 18);                   // MAF: ZT[k], then ZTT[k], k = 0 .. nkp-1
 
-  int lb = blockIdx.x;
-  const int nblk = gridDim.x;
-  int seg, chunk;
-  if (g.map != nullptr) {
-    // balanced shares: the (segment, chunk) items in segment-major order are cut into eight equal runs, one per XCD (the hardware deals
-    // workgroup ids round-robin over the XCDs), each walked chunk by chunk -- see pair_xcd_map
-    seg = g.map[2 * lb];
-    chunk = g.map[2 * lb + 1];
-  } else {
-    // XCD bands: XCD x owns a contiguous band of whole segments of every chunk (row-adjacent segments share their halo rows in one L2)
-    // and walks it chunk by chunk
-    const int x = lb & 7, r = lb >> 3;
-    const int base = g.nseg >> 3, rem = g.nseg & 7, bmax = base + (rem ? 1 : 0);
-    const int blen = base + (x < rem ? 1 : 0);
-    const int sl = r % bmax;
-    chunk = r / bmax;
-    seg = (sl < blen) ? x * base + min(x, rem) + sl : g.nseg;  // nseg = no work
-  }
-  // k window of this segment (Geom2): ids are window-major, so the band / run of an XCD is a set of row-adjacent segments of ONE window
-  int win = 0;
-  if (g.nwin > 1 && seg < g.nseg) {
-    win = seg / g.nsegw;
-    seg -= win * g.nsegw;
-  } else if (g.nwin > 1) {
-    seg = g.nsegw;  // no work
-  }
-  const int nseg_w = (g.nwin > 1) ? g.nsegw : g.nseg;
-  const int kw0 = win * g.KW - g.hv * V;  // element of the row that vector 0 of the window's view starts at (-V: the left halo of window 0)
-  const long long fb = (seg < nseg_w) ? g.F0 + (long long)seg * g.S : g.Fend;
-  const int ja = g.jj0 + chunk * g.TJ;
-  int jb = ja + g.TJ - 1;
-  if (jb > g.jj1) jb = g.jj1;
+  const PassItem it = pass_item<V>(g);
+  const int ja = it.ja, jb = it.jb;
 
   double acc1 = 0.0, acc2 = 0.0;
 #ifdef CZ_P2_PLAIN_DIV  // tools/pair_lab A/B only
@@ -222,23 +164,11 @@ jacobi2p_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restr
   const HoistedDiv dv{fastdiv_init(c.dd)};  // exact IEEE quotients, the divisor's share of the work done once (cz_k_fastdiv.h)
 #endif
 
-  if (ja <= jb && fb < g.Fend) {
-    const long long e1_0 = fb - R;      // first vector of E1
-    const long long e2_0 = fb - 2 * R;  // first vector of E2
-    const long long vlast = g.PSV - 1;
-    const size_t PB = (size_t)g.PSB;  // bytes per plane
-    // byte offset of vector f of the (window's) row view inside a plane in memory.  Below the plane (row 0's left halo vector of window 0:
-    // masked, and no unmasked point reads it) it is clamped to 0.  Beyond the plane's end it is NOT clamped here: the last vector of the last
-    // row of a plane whose rows are no multiple of the vector width hangs over by a few elements and IS read by the first stage of a
-    // decomposed brick (row nip-1 is the second ghost layer); the elements behind the plane are the next plane's, masked -- only in the
-    // array's last plane must the access stay inside, and there the vector is never used (lim, Geom2::last_off).
-    auto off_of = [&](long long f) -> unsigned {
-      const long long r = f / R;
-      long long el = r * g.nkp + kw0 + (f - r * R) * V;
-      el = el < 0 ? 0 : el;
-      return (unsigned)(el * (long long)sizeof(REAL));
-    };
-    auto lim = [&](unsigned off, int plane) -> unsigned { return plane == g.jlast ? (off < g.last_off ? off : g.last_off) : off; };
+  if (it.work) {
+    const long long e1_0 = it.fb - R;      // first vector of E1
+    const long long e2_0 = it.fb - 2 * R;  // first vector of E2
+    const size_t PB = (size_t)g.PSB;       // bytes per plane
+    const RowView<V> rv = row_view<V>(g, it);
     unsigned bo[MV];   // byte offset of the thread's m-th vector inside a plane (clamped into the plane: such lanes are masked)
     unsigned ka[MV];   // stage-1 bits: components of the vector inside the stage-1 box (0 when the row is outside)
     unsigned own[MV];  // stage-2 bits if this workgroup owns the vector (stores, residual counts), else 0
@@ -247,27 +177,16 @@ jacobi2p_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restr
     for (int m = 0; m < MV; m++) {
       const int e = t + m * TB;
       const long long f = e1_0 + e;
-      const long long fc = f < vlast ? f : vlast;
-      bo[m] = off_of(fc);
-      const long long row = f / R;
-      const int kv = (int)(f - row * R);
-      const int kb = kw0 + kv * V;  // k of component 0
-      unsigned bits1 = 0, bits2 = 0;
-#pragma unroll
-      for (int cc = 0; cc < V; cc++) {
-        const int kk = kb + cc;
-        if (kk >= g.kk0a && kk <= g.kk1a) bits1 |= 1u << cc;
-        if (kk >= g.kk0 && kk <= g.kk1) bits2 |= 1u << cc;
-      }
-      pbase[m] = kb + (int)row + g.par;
-      ka[m] = (f >= g.F0a && f < g.Fenda) ? bits1 : 0u;
-      const bool kown = kv >= g.hv && kv < g.hv + g.KT;  // the window that holds the vector owns it (its halo vectors belong to the windows next door)
-      own[m] = (e >= R && e < LV - R && f >= g.F0 && f < g.Fend && kown) ? bits2 : 0u;
+      bo[m] = rv.off_of(f);
+      const VecMask mk = vec_mask<V>(g, it, f);
+      pbase[m] = mk.pbase;
+      ka[m] = mk.rows1 ? mk.bits1 : 0u;
+      own[m] = (e >= R && e < LV - R && mk.rows && mk.kown) ? mk.bits : 0u;
     }
     REAL XG[MAF ? MV : 1], XGG[MAF ? MV : 1];  // MAF: metric terms of the rows of the thread's vectors
     int kvo[MAF ? MV : 1];                      // MAF: first k of the vector (offset into ztab)
     if (MAF) {
-      const int nkp = R * V;  // (the row view of the window: element kk of it is k = kw0 + kk of the row)
+      const int nkp = R * V;  // (the row view of the window: element kk of it is k = it.kw0 + kk of the row)
 #pragma unroll
       for (int m = 0; m < MV; m++) {
         const long long f = e1_0 + t + m * TB;
@@ -282,23 +201,14 @@ jacobi2p_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restr
         XGG[m] = xp - (REAL)2.0 * x0 + xm;
       }
       for (int kk = t; kk < nkp; kk += TB) {
-        int kc = kw0 + kk < 1 ? 1 : kw0 + kk;
+        int kc = it.kw0 + kk < 1 ? 1 : it.kw0 + kk;
         if (kc > g.nkp - 2) kc = g.nkp - 2;
         const REAL zm = ma.zc[kc - 1], z0 = ma.zc[kc], zp = ma.zc[kc + 1];
         ztab[kk] = (REAL)0.5 * (zp - zm);
         ztab[nkp + kk] = zp - (REAL)2.0 * z0 + zm;
       }
     }
-    // the two outer rows of E2: the first R threads stage the lower one, the last R threads the upper one (2R <= TB)
-    const bool has_halo = (t < R) || (t >= TB - R);
-    const int hl = (t < R) ? t : (LV + R + (t - (TB - R)));  // index inside an LDS u buffer
-    unsigned hbo;
-    {
-      long long fh = e2_0 + hl;
-      if (!has_halo) fh = e1_0 + t;
-      if (fh > vlast) fh = vlast;
-      hbo = off_of(fh);
-    }
+    const OuterRow h = outer_row<V, TB>(rv, LV, e2_0, e1_0 + t);  // the two outer rows of E2
     const char* Ub = reinterpret_cast<const char*>(U);
     const char* Bb = reinterpret_cast<const char*>(B);
     char* Wb = reinterpret_cast<char*>(W);
@@ -313,7 +223,7 @@ jacobi2p_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restr
     Vec<V> uA[MV], uB[MV], bA[MV], bB[MV], b2[MV], vc[MV], hx;
     Vec<V> rx[BS ? MV : 1], ry[BS ? MV : 1], rz[BS == 2 ? MV : 1];  // BS: the operands of b(q), asked for one step ahead (ONE set: b(q) is made
                                                                      // from them at the top of step q, before the requests of that step)
-    // PRE: every operand of the chunk.  UP[p] = u(ja-2+p), HP[p] its outer rows (the has_halo threads), BP[p] = b(ja-1+p); planes beyond
+    // PRE: every operand of the chunk.  UP[p] = u(ja-2+p), HP[p] its outer rows (the threads that stage one), BP[p] = b(ja-1+p); planes beyond
     // jb+2 / jb+1 (a last chunk shorter than PRE) are clamped and never used.
     Vec<V> UP[PRE ? PRE + 4 : 1][MV], HP[PRE ? PRE + 4 : 1], BP[PRE ? PRE + 2 : 1][MV];
     if (PRE) {
@@ -322,8 +232,8 @@ jacobi2p_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restr
         const int pl = (ja - 2 + p <= jb + 2) ? ja - 2 + p : jb + 2;
         const char* Pp = Ub + (size_t)pl * PB;
 #pragma unroll
-        for (int m = 0; m < MV; m++) UP[p][m] = ld16<V>(Pp, lim(bo[m], pl));
-        HP[p] = ld16<V>(Pp, lim(hbo, pl));
+        for (int m = 0; m < MV; m++) UP[p][m] = ld16<V>(Pp, rv.lim(bo[m], pl));
+        HP[p] = ld16<V>(Pp, rv.lim(h.bo, pl));
       }
 #pragma unroll
       for (int p = 0; p < PRE + 2; p++) {
@@ -338,7 +248,7 @@ jacobi2p_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restr
         ldsU[R + t + m * TB] = UP[1][m];
         b2[m] = zerov<V>();
       }
-      if (has_halo) ldsU[hl] = HP[1];
+      if (h.has) ldsU[h.hl] = HP[1];
     } else
     // prologue: LDS_U[1] <- u(ja-2) (own vectors), LDS_U[0] <- u(ja-1) on E2; in flight: u(ja) and b(ja-1)
     {
@@ -349,13 +259,13 @@ jacobi2p_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restr
       Vec<V> t2[MV], t1[MV], h1;
 #pragma unroll
       for (int m = 0; m < MV; m++) {
-        t2[m] = ZU ? zerov<V>() : ld16<V>(P2, lim(bo[m], ja - 2));
-        t1[m] = ZU ? zerov<V>() : ld16<V>(P1, lim(bo[m], ja - 1));
+        t2[m] = ZU ? zerov<V>() : ld16<V>(P2, rv.lim(bo[m], ja - 2));
+        t1[m] = ZU ? zerov<V>() : ld16<V>(P1, rv.lim(bo[m], ja - 1));
       }
-      h1 = ZU ? zerov<V>() : ld16<V>(P1, lim(hbo, ja - 1));
+      h1 = ZU ? zerov<V>() : ld16<V>(P1, rv.lim(h.bo, ja - 1));
 #pragma unroll
       for (int m = 0; m < MV; m++) {
-        uA[m] = ZU ? zerov<V>() : ld16<V>(P0, lim(bo[m], ja));
+        uA[m] = ZU ? zerov<V>() : ld16<V>(P0, rv.lim(bo[m], ja));
         if (BS) {
           rx[m] = ld16<V>(SXb + (size_t)(ja - 1) * PB, bo[m]);
           ry[m] = ld16<V>(SYb + (size_t)(ja - 1) * PB, bo[m]);
@@ -371,7 +281,7 @@ jacobi2p_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restr
         ldsU[LU + R + t + m * TB] = t2[m];
         ldsU[R + t + m * TB] = t1[m];
       }
-      if (has_halo) ldsU[hl] = h1;
+      if (h.has) ldsU[h.hl] = h1;
     }
     __syncthreads();
 
@@ -394,16 +304,7 @@ jacobi2p_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restr
         if (count1) {  // the planes of this chunk, the vectors of this segment: every point of the inner box has exactly one owner
           char* Sq = SOb + (size_t)q * PB;
 #pragma unroll
-          for (int m = 0; m < MV; m++) {
-            if (own[m] == (1u << V) - 1) {
-              st16<V>(Sq, bo[m], b1[m]);
-            } else if (own[m] != 0) {
-              REAL* sp = reinterpret_cast<REAL*>(Sq + bo[m]);
-#pragma unroll
-              for (int cc = 0; cc < V; cc++)
-                if (own[m] & (1u << cc)) sp[cc] = b1[m].v[cc];
-            }
-          }
+          for (int m = 0; m < MV; m++) store_owned<V>(Sq, bo[m], own[m], b1[m]);
         }
       }
       // ---- requests for the NEXT step (the last step re-reads a plane it already has: no branch around a load)
@@ -415,9 +316,9 @@ jacobi2p_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restr
         const char* Un = Ub + (size_t)qu * PB;
         const char* Bn = Bb + (size_t)qb * PB;
         // the outer rows of u(q+1) go to LDS at the end of THIS step (one register set; the oldest request of the step)
-        hx = ZU ? zerov<V>() : ld16<V>(Ub + (size_t)(q + 1) * PB, lim(hbo, q + 1));
+        hx = ZU ? zerov<V>() : ld16<V>(Ub + (size_t)(q + 1) * PB, rv.lim(h.bo, q + 1));
 #pragma unroll
-        for (int m = 0; m < MV; m++) un[m] = ZU ? zerov<V>() : ld16<V>(Un, lim(bo[m], qu));
+        for (int m = 0; m < MV; m++) un[m] = ZU ? zerov<V>() : ld16<V>(Un, rv.lim(bo[m], qu));
         if (BS) {
           const size_t po = (size_t)qb * PB;
 #pragma unroll
@@ -539,14 +440,7 @@ jacobi2p_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restr
             } else {
               o = relax_vec<V, UNIT>(vb, im, ip, pm, vc[m], kl, kr, b2[m], c, dv, m2, m2, acc2);
             }
-            if (own[m] == (1u << V) - 1) {
-              st16<V>(Wq, bo[m], o);
-            } else {
-              REAL* wp = reinterpret_cast<REAL*>(Wq + bo[m]);
-#pragma unroll
-              for (int cc = 0; cc < V; cc++)
-                if (own[m] & (1u << cc)) wp[cc] = o.v[cc];
-            }
+            store_owned<V>(Wq, bo[m], own[m], o);
           }
         }
       }
@@ -556,7 +450,7 @@ jacobi2p_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restr
       for (int m = 0; m < MV; m++) pV[t + m * TB] = vc[m];
 #pragma unroll
       for (int m = 0; m < MV; m++) pU[R + t + m * TB] = uc[m];
-      if (has_halo) pU[hl] = hx;
+      if (h.has) pU[h.hl] = hx;
 #pragma unroll
       for (int m = 0; m < MV; m++) b2[m] = b1[m];  // b(q) for the next step's stage 2 (complete: stage 1 used it)
       __syncthreads();
@@ -579,17 +473,7 @@ jacobi2p_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restr
     }
   }
 
-  // ---- residuals: per-workgroup partials, finalised by the last workgroup (write-through hand-off, see stencil_k)
-  __syncthreads();
-  const double s1 = block_sum<TB>(acc1, wsum);
-  __syncthreads();
-  const double s2 = block_sum<TB>(acc2, wsum);
-  int* last_flag = reinterpret_cast<int*>(wsum + 16);
-  if (t == 0) {
-    __hip_atomic_store(&partials[lb], s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&partials[nblk + lb], s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *last_flag = arrive_and_test_last(fin.counter, nblk);
-  }
-  __syncthreads();
-  if (*last_flag) pair_finalize<TB>(partials, nblk, fin, wsum);
+  // ---- residuals: per-workgroup partials, finalised by the last workgroup
+  const double acc[2] = {acc1, acc2};
+  pass_epilogue<TB, 2>(acc, partials, fin, wsum);
 }

@@ -12,6 +12,7 @@
 //     LDS         u: 2 x (LV + 2R), f1..f3: 2 x LV each (E3 coordinates), one barrier per plane step   = 133 KB for R = 34
 //     k windows   KT vectors + hv halo vectors per side; four stages reach 3 elements beyond a window: hv = 1 (FP32), 2 (FP64)
 //     planes      stage s at step q works on plane q - s + 1: f1(q) from u(q-1..q+1), f2(q-1) from f1, f3(q-2), f4(q-3) -> W
+// Work item, addresses, masks, outer rows, masked store and epilogue are the frame's (cz_k_pass.h).
 // Same per-point operations on the same values as four psor2sma_core_ calls => the same bits (relax_vec_rb is the stage of jacobi2p_k).
 // Threads -> vectors: which components of a vector a stage updates depends on the parity of its ROW (k of component 0 is even in every window);
 // E3 is therefore dealt out by row parity -- threads 0 .. nA-1 take the first row of E3 and every second one after it, the others the rows in
@@ -29,59 +30,23 @@ rb4_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict__
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = threadIdx.x;
   const int R = g.R;
-  constexpr int LV = TB;      // E3: own segment +- three rows (S = LV - 6R); one vector per thread
-  const int LU = LV + 2 * R;  // E4
-  // (R vectors of padding in front of the u buffers and behind the last field buffer: stages 2 and 3 are evaluated on all of E3 and read
-  // +-R beyond their sets -- inside the allocation, never used)
-  Vec<V>* ldsU = reinterpret_cast<Vec<V>*>(smem) + R;   // 2 buffers of LU vectors: plane p in buffer p & 1
-  Vec<V>* ldsF = ldsU + (size_t)2 * LU;                  // f1, f2, f3: [field][plane & 1][LV]
-  double* wsum = reinterpret_cast<double*>(ldsF + (size_t)6 * LV + R);
+  constexpr int LV = TB;  // E3: own segment +- three rows (S = LV - 6R); one vector per thread; u on E4
+  const DeepLds<V> lds = deep_lds<V, LV, 4>(smem, R);
+  const int LU = lds.LU;
+  Vec<V>* ldsU = lds.U;
+  Vec<V>* ldsF = lds.F;
+  double* wsum = lds.wsum;
 
-  // ---- workgroup -> (window, segment, chunk): as jacobi2p_k
-  const int lb = blockIdx.x;
-  const int nblk = gridDim.x;
-  int seg, chunk;
-  if (g.map != nullptr) {
-    seg = g.map[2 * lb];
-    chunk = g.map[2 * lb + 1];
-  } else {
-    const int x = lb & 7, r = lb >> 3;
-    const int base = g.nseg >> 3, rem = g.nseg & 7, bmax = base + (rem ? 1 : 0);
-    const int blen = base + (x < rem ? 1 : 0);
-    const int sl = r % bmax;
-    chunk = r / bmax;
-    seg = (sl < blen) ? x * base + min(x, rem) + sl : g.nseg;  // nseg = no work
-  }
-  int win = 0;
-  if (seg < g.nseg) {
-    win = seg / g.nsegw;
-    seg -= win * g.nsegw;
-  } else {
-    seg = g.nsegw;
-  }
-  const int kw0 = win * g.KW - g.hv * V;
-  const long long fb = (seg < g.nsegw) ? g.F0 + (long long)seg * g.S : g.Fend;
-  const int ja = g.jj0 + chunk * g.TJ;
-  int jb = ja + g.TJ - 1;
-  if (jb > g.jj1) jb = g.jj1;
+  const PassItem it = pass_item<V>(g);
+  const int ja = it.ja, jb = it.jb;
 
   double acc1 = 0.0, acc2 = 0.0;
   const HoistedDiv dv{fastdiv_init(c.dd)};
 
-  if (ja <= jb && fb < g.Fend) {
-    const long long e3_0 = fb - 3 * (long long)R;  // first vector of E3
-    const long long vlast = g.PSV - 1;
+  if (it.work) {
+    const long long e3_0 = it.fb - 3 * (long long)R;  // first vector of E3
     const size_t PB = (size_t)g.PSB;
-    auto off_of = [&](long long f) -> unsigned {  // (see jacobi2p_k: clamped below the plane, not beyond it; `lim` for the array's last plane)
-      if (f < 0) f = 0;
-      if (f > vlast) f = vlast;
-      const long long r = f / R;
-      long long el = r * g.nkp + kw0 + (f - r * R) * V;
-      el = el < 0 ? 0 : el;
-      return (unsigned)(el * (long long)sizeof(REAL));
-    };
-    auto lim = [&](unsigned off, int plane) -> unsigned { return plane == g.jlast ? (off < g.last_off ? off : g.last_off) : off; };
-    auto pl = [&](int p) -> int { return p < 0 ? 0 : (p > g.jlast ? g.jlast : p); };  // planes beyond the array are never used: clamped
+    const RowView<V> rv = row_view<V>(g, it);
     // this thread's vector: x = its index in E3, rows dealt by parity (see the head of the file)
     int x;
     {
@@ -98,31 +63,12 @@ rb4_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict__
       }
     }
     const long long f = e3_0 + x;
-    const unsigned bo = off_of(f);
-    unsigned inbox = 0;  // components inside the inner box (every stage updates only those)
-    unsigned own = 0;    // ... of a vector this workgroup owns (stores, residual counts)
-    int pbase;
-    {
-      const long long fc = f < 0 ? 0 : f;
-      const long long row = fc / R;
-      const int kv = (int)(fc - row * R);
-      const int kb = kw0 + kv * V;
-      unsigned bits = 0;
-#pragma unroll
-      for (int cc = 0; cc < V; cc++) {
-        const int kk = kb + cc;
-        if (kk >= g.kk0 && kk <= g.kk1) bits |= 1u << cc;
-      }
-      pbase = kb + (int)row + g.par;
-      const bool rows_in = f >= g.F0 && f < g.Fend;
-      inbox = rows_in ? bits : 0u;
-      const bool kown = kv >= g.hv && kv < g.hv + g.KT;
-      own = (x >= 3 * R && x < LV - 3 * R && rows_in && kown) ? bits : 0u;
-    }
-    // the outer rows of E4: the first R threads stage the lower one, the last R threads the upper one
-    const bool has_halo = (t < R) || (t >= TB - R);
-    const int hl = (t < R) ? t : (LV + R + (t - (TB - R)));  // index inside an LDS u buffer (E4 coordinates)
-    const unsigned hbo = off_of(has_halo ? (fb - 4 * (long long)R + hl) : f);
+    const unsigned bo = rv.off_of(f);
+    const VecMask mk = vec_mask<V>(g, it, f);
+    const int pbase = mk.pbase;
+    const unsigned inbox = mk.rows ? mk.bits : 0u;                                                     // components inside the inner box (every stage updates only those)
+    const unsigned own = (x >= 3 * R && x < LV - 3 * R && mk.rows && mk.kown) ? mk.bits : 0u;  // ... of a vector this workgroup owns (stores, residual counts)
+    const OuterRow h = outer_row<V, TB>(rv, LV, it.fb - 4 * (long long)R, f);  // the outer rows of E4
     const char* Ub = reinterpret_cast<const char*>(U);
     const char* Bb = reinterpret_cast<const char*>(B);
     char* Wb = reinterpret_cast<char*>(W);
@@ -131,14 +77,14 @@ rb4_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict__
     const int q0 = ja - 3;
     Vec<V> uA, uB, bA, bB, hx;
     {
-      const Vec<V> t2 = ld16<V>(Ub + (size_t)pl(q0 - 1) * PB, lim(bo, pl(q0 - 1)));
-      const Vec<V> t1 = ld16<V>(Ub + (size_t)pl(q0) * PB, lim(bo, pl(q0)));
-      const Vec<V> h1 = ld16<V>(Ub + (size_t)pl(q0) * PB, lim(hbo, pl(q0)));
-      uA = ld16<V>(Ub + (size_t)pl(q0 + 1) * PB, lim(bo, pl(q0 + 1)));
-      bA = ld16<V>(Bb + (size_t)pl(q0) * PB, lim(bo, pl(q0)));
+      const Vec<V> t2 = ld16<V>(Ub + (size_t)rv.pl(q0 - 1) * PB, rv.lim(bo, rv.pl(q0 - 1)));
+      const Vec<V> t1 = ld16<V>(Ub + (size_t)rv.pl(q0) * PB, rv.lim(bo, rv.pl(q0)));
+      const Vec<V> h1 = ld16<V>(Ub + (size_t)rv.pl(q0) * PB, rv.lim(h.bo, rv.pl(q0)));
+      uA = ld16<V>(Ub + (size_t)rv.pl(q0 + 1) * PB, rv.lim(bo, rv.pl(q0 + 1)));
+      bA = ld16<V>(Bb + (size_t)rv.pl(q0) * PB, rv.lim(bo, rv.pl(q0)));
       ldsU[(size_t)((q0 - 1) & 1) * LU + R + x] = t2;
       ldsU[(size_t)(q0 & 1) * LU + R + x] = t1;
-      if (has_halo) ldsU[(size_t)(q0 & 1) * LU + hl] = h1;
+      if (h.has) ldsU[(size_t)(q0 & 1) * LU + h.hl] = h1;
     }
     Vec<V> bq1 = zerov<V>(), bq2 = zerov<V>(), bq3 = zerov<V>();  // b of the planes of stages 2, 3, 4
     __syncthreads();
@@ -182,10 +128,10 @@ rb4_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict__
     // One plane step q.  uc = u(q+1) and b1 = b(q) were requested one step ago; un / bn receive this step's requests.
     auto step = [&](const int q, Vec<V>& uc, Vec<V>& un, Vec<V>& b1, Vec<V>& bn) __attribute__((always_inline)) {
       {
-        const int qu = pl(q + 2 <= jb + 4 ? q + 2 : jb + 4), qb = pl(q + 1 <= jb + 3 ? q + 1 : jb + 3);
-        hx = ld16<V>(Ub + (size_t)pl(q + 1) * PB, lim(hbo, pl(q + 1)));
-        un = ld16<V>(Ub + (size_t)qu * PB, lim(bo, qu));
-        bn = ld16<V>(Bb + (size_t)qb * PB, lim(bo, qb));
+        const int qu = rv.pl(q + 2 <= jb + 4 ? q + 2 : jb + 4), qb = rv.pl(q + 1 <= jb + 3 ? q + 1 : jb + 3);
+        hx = ld16<V>(Ub + (size_t)rv.pl(q + 1) * PB, rv.lim(h.bo, rv.pl(q + 1)));
+        un = ld16<V>(Ub + (size_t)qu * PB, rv.lim(bo, qu));
+        bn = ld16<V>(Bb + (size_t)qb * PB, rv.lim(bo, qb));
       }
       // planes of the four stages; masks: inside the inner box a stage updates, inside the chunk the owner counts the residual
       const int p1 = q, p2 = q - 1, p3 = q - 2, p4 = q - 3;
@@ -210,15 +156,7 @@ rb4_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict__
       // shifts, and the lane next to the first owned vector of a window holds a halo vector -- it owns nothing but must take part.
       if (p4 >= ja && __builtin_amdgcn_ballot_w64(own != 0) != 0ull) {
         const Vec<V> o = compute(o4, nullptr, F3 + (size_t)((p4 - 1) & 1) * LV, v3, bq3, p4, 1, own, own, acc2);
-        char* Wq = Wb + (size_t)p4 * PB;
-        if (own == (1u << V) - 1) {
-          st16<V>(Wq, bo, o);
-        } else if (own != 0) {
-          REAL* wp = reinterpret_cast<REAL*>(Wq + bo);
-#pragma unroll
-          for (int cc = 0; cc < V; cc++)
-            if (own & (1u << cc)) wp[cc] = o.v[cc];
-        }
+        store_owned<V>(Wb + (size_t)p4 * PB, bo, own, o);
       }
       // ---- publish: f1(p1), f2(p2), f3(p3) and the next u centre plane u(q+1) with its outer rows
       F1[(size_t)(p1 & 1) * LV + x] = v1;
@@ -226,7 +164,7 @@ rb4_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict__
       F3[(size_t)(p3 & 1) * LV + x] = v3;
       Vec<V>* nU = ldsU + (size_t)((p1 + 1) & 1) * LU;
       nU[R + x] = uc;
-      if (has_halo) nU[hl] = hx;
+      if (h.has) nU[h.hl] = hx;
       bq3 = bq2, bq2 = bq1, bq1 = b1;  // (b1 is complete: stage 1 used it)
       __syncthreads();
     };
@@ -241,17 +179,7 @@ rb4_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict__
     }
   }
 
-  // ---- residuals of the two iterations: per-workgroup partials, finalised by the last workgroup (see jacobi2p_k)
-  __syncthreads();
-  const double s1 = block_sum<TB>(acc1, wsum);
-  __syncthreads();
-  const double s2 = block_sum<TB>(acc2, wsum);
-  int* last_flag = reinterpret_cast<int*>(wsum + 16);
-  if (t == 0) {
-    __hip_atomic_store(&partials[lb], s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&partials[nblk + lb], s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *last_flag = arrive_and_test_last(fin.counter, nblk);
-  }
-  __syncthreads();
-  if (*last_flag) pair_finalize<TB>(partials, nblk, fin, wsum);
+  // ---- residuals of the two iterations: per-workgroup partials, finalised by the last workgroup
+  const double acc[2] = {acc1, acc2};
+  pass_epilogue<TB, 2>(acc, partials, fin, wsum);
 }

@@ -41,6 +41,7 @@ constexpr int VW = 4;
 namespace {
 #include "cz_k_common.h"
 #include "cz_k_fastdiv.h"
+#include "cz_k_pass.h"
 #include "cz_k_stencil.h"
 #include "cz_k_pair.h"
 #include "cz_k_pair2.h"
@@ -554,7 +555,7 @@ int czhip_set_rb4(int enable, int window, int planes) {
 }
 
 // The fused pass split the way a decomposed brick runs it: the slabs behind the faces with nID[f] >= 0 first
-// (pair_shell_k), then the interior (jacobi2_k) -- same result as the unsplit launch.  rb_ofst < 0: two Jacobi sweeps,
+// (pair_shell_k), then the interior (jacobi2p_k) -- same result as the unsplit launch.  rb_ofst < 0: two Jacobi sweeps,
 // res_dev[0..1]; rb_ofst >= 0: one red-black iteration with that ofst, res_dev[0].  Returns 0 when nothing was launched.
 int czhip_pair_split_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, const int* idx1,
                            const int* nID, int g, const CZ_REAL* cf, CZ_REAL omg, int rb_ofst, double* res_dev) {

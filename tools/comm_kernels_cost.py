@@ -1,6 +1,6 @@
 """GPU-side cost of the exchange kernels (pack / unpack of the two-layer pattern) and of the shell / interior launches of a decomposed
 512^3-per-rank run, measured on ONE GPU with two ranks as host threads (LOCAL transport): run under
-`rocprofv3 --kernel-trace -- python3 tools/comm_kernels_cost.py <di> <dj> <dk>` and read box_copy_k / pair_shell_k / jacobi2_k."""
+`rocprofv3 --kernel-trace -- python3 tools/comm_kernels_cost.py <di> <dj> <dk>` and read box_copy_k / pair_shell_k / jacobi2p_k."""
 import ctypes as C
 import os
 import sys

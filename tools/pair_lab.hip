@@ -24,6 +24,7 @@ constexpr int VW = 4;
 namespace {
 #include "cz_k_common.h"
 #include "cz_k_fastdiv.h"
+#include "cz_k_pass.h"
 #include "cz_k_pair.h"
 #include "pair_lab_v1.h"
 #include "cz_k_pair2.h"

@@ -1,6 +1,6 @@
 // tools/pair_lab_v1.h -- round 1's two-stage pass kernel (jacobi2_k), kept ONLY as the A/B partner of tools/pair_lab.hip: the library
 // runs jacobi2p_k (cubez_amd/csrc/cz_k_pair2.h), which must reproduce this kernel's output bit for bit.  Included inside pair_lab.hip's
-// anonymous namespace after cz_k_pair.h (Geom2, Fin2, relax_vec, pair_finalize).  Loads are issued at the top of a plane step and waited
+// anonymous namespace after cz_k_pass.h (Geom2, Fin2, relax_vec, pass_finalize) and cz_k_pair.h.  Loads are issued at the top of a plane step and waited
 // for a few instructions later; j-1 operands ride in register queues; k neighbours across vectors are stride-4 ds_read_b32.
 // RB = 0: two Jacobi sweeps.  RB = 1: one red-black SOR iteration (cz_solver.f90:466-480 for colour 0 then colour 1):
 // stage 1 updates the points of colour 0, stage 2 those of colour 1 from the freshly updated colour-0 neighbours; the
@@ -207,6 +207,6 @@ jacobi2_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restri
     *last_flag = (ticket == (unsigned)nblk - 1u);
   }
   __syncthreads();
-  if (*last_flag) pair_finalize<TB>(partials, nblk, fin, wsum);
+  if (*last_flag) pass_finalize<TB, 2>(partials, nblk, fin, wsum);
 }
 
