@@ -6,6 +6,7 @@ loops.  This package is only the thin ctypes binding used by the tests, ``bench.
 Python launcher; there is no CPU fallback -- loading fails loudly when the library is missing.
 """
 from .driver import CZ  # noqa: F401
+from .refine import Refined  # noqa: F401
 from .lib import CzHip, DeviceArray, GUIDE, lib_path, load  # noqa: F401
 
-__all__ = ["CZ", "CzHip", "DeviceArray", "GUIDE", "lib_path", "load"]
+__all__ = ["CZ", "Refined", "CzHip", "DeviceArray", "GUIDE", "lib_path", "load"]

@@ -1452,23 +1452,39 @@ void CZ::Field(REAL_TYPE* host) const {
   czhip_d2h(host, P, padded_cells() * sizeof(REAL_TYPE));
 }
 
-// The caller's problem: import into RHS / P, export of P (cz_set_rhs, cz_set_field, cz_get_field).  Device arrays are handed
+// The caller's problem: import into RHS / P, export of P (cz_set_rhs, cz_set_field, cz_get_field), and the two operations of
+// mixed-precision refinement, the residual of P out and a correction into P (cz_get_residual, cz_add_field), whose caller's
+// side holds float or double (abytes).  Device arrays are handed
 // over by events (the compute stream waits for what the caller's stream holds, the kernel runs, the caller's stream waits for the kernel): no
 // device-wide wait.  user_stream NULL: nothing to wait for before, the host waits for the compute stream after.  Host arrays: the span the
 // strides cover goes through a device buffer and the same kernels; of an export only the brick's cells reach the caller's array.
-int CZ::FieldIO(int which, REAL_TYPE* a, const long long* stride, int on_device, void* user_stream, bool to_user, const char* who) {
+// Every refusal comes before the first launch.
+int CZ::FieldIO(int which, void* a, int abytes, const long long* stride, int on_device, void* user_stream, int op, double scale, double* sumsq,
+                const char* who) {
   auto refuse = [&](const char* why) {
     fprintf(stderr, "%s: %s\n", who, why);
     return 0;
   };
+  const bool to_user = op == FIO_EXPORT || op == FIO_RESIDUAL;
+  const bool refine = op == FIO_RESIDUAL || op == FIO_ADD;
+  const bool none = op == FIO_RESIDUAL && !a;  // the norm only
   if (!set_up) return refuse("no problem is set up (cz_setup first)");
-  if (!a || !stride) return refuse("NULL pointer");
-  if (reinterpret_cast<uintptr_t>(a) & (sizeof(REAL_TYPE) - 1)) return refuse("the array is not aligned to its element size");
-  for (int d = 0; d < 3; d++)
-    if (stride[d] < 1) return refuse("strides must be positive (elements)");
+  if (refine) {
+    if (SW_maf) return refuse("the handle's operator is a MAF one, not the unit-coefficient operator");
+    const REAL_TYPE rs = (REAL_TYPE)scale;
+    if (!(scale > 0.0) || !std::isfinite(scale) || !(rs > (REAL_TYPE)0) || !std::isfinite(rs)) return refuse("the scale must be finite and positive");
+    if (op == FIO_RESIDUAL && !sumsq) return refuse("NULL pointer");
+    if (!none && abytes != 4 && abytes != 8) return refuse("the element size must be 4 or 8 bytes");
+  }
   long long span = 1;
-  for (int d = 0; d < 3; d++) span += (long long)(size[d] - 1) * stride[d];
-  if (to_user) {
+  if (!none) {
+    if (!a || !stride) return refuse("NULL pointer");
+    if (reinterpret_cast<uintptr_t>(a) & (uintptr_t)(abytes - 1)) return refuse("the array is not aligned to its element size");
+    for (int d = 0; d < 3; d++)
+      if (stride[d] < 1) return refuse("strides must be positive (elements)");
+    for (int d = 0; d < 3; d++) span += (long long)(size[d] - 1) * stride[d];
+  }
+  if (to_user && !none) {
     // two cells of a destination must not share an element.  Accepted: ordered by stride, every stride is at least the span of the
     // directions below it (dense arrays in any order of the directions, and slices of them); directions of one cell do not count
     int o[3] = {0, 1, 2};
@@ -1483,8 +1499,10 @@ int CZ::FieldIO(int which, REAL_TYPE* a, const long long* stride, int on_device,
   }
   hipStream_t st = stream();
   REAL_TYPE* arr = which == 0 ? RHS : P;
-  REAL_TYPE* dev = a;
-  if (on_device) {
+  void* dev = a;
+  const size_t span_bytes = (size_t)span * (size_t)abytes;
+  if (none) {
+  } else if (on_device) {
     hipPointerAttribute_t at;
     int cur = -1;
     HIP_CHECK(hipGetDevice(&cur));
@@ -1498,49 +1516,67 @@ int CZ::FieldIO(int which, REAL_TYPE* a, const long long* stride, int on_device,
       HIP_CHECK(hipStreamWaitEvent(st, ev_io, 0));
     }
   } else {
-    if ((size_t)span > io_stage_cap) {
+    if (span_bytes > io_stage_cap) {
       if (io_stage) {
         HIP_CHECK(hipStreamSynchronize(st));
         HIP_CHECK(hipFree(io_stage));
       }
-      HIP_CHECK(hipMalloc(&io_stage, (size_t)span * sizeof(REAL_TYPE)));
-      io_stage_cap = (size_t)span;
+      HIP_CHECK(hipMalloc(&io_stage, span_bytes));
+      io_stage_cap = span_bytes;
     }
     dev = io_stage;
     // (an export fills the brick's cells of the device span only; the host copies exactly those cells below -- the other elements of the
     // caller's span are not the library's to touch: they may be another rank's cells of one shared array)
-    if (!to_user) HIP_CHECK(hipMemcpyAsync(dev, a, (size_t)span * sizeof(REAL_TYPE), hipMemcpyHostToDevice, st));
+    if (!to_user) HIP_CHECK(hipMemcpyAsync(dev, a, span_bytes, hipMemcpyHostToDevice, st));
   }
-  last_field_form = field_copy_async(arr, dev, size, GUIDE, stride, to_user ? 1 : 0, field_form == 3 ? 3 : 0);
+  const int form = field_form == 3 ? 3 : 0;
+  if (op == FIO_RESIDUAL) {
+    // (the stencil reads one ghost layer of P; a solve may have left it one exchange behind)
+    if (!Comm_S(P)) return 0;
+    last_field_form = field_residual_async(P, RHS, WRK, dev, abytes, size, innerFidx, GUIDE, stride, cf, scale, form, d_res + 10);
+  } else if (op == FIO_ADD) {
+    last_field_form = field_add_async(P, dev, abytes, size, innerFidx, GUIDE, stride, scale, form);
+  } else {
+    last_field_form = field_copy_async(arr, static_cast<REAL_TYPE*>(dev), size, GUIDE, stride, to_user ? 1 : 0, form);
+  }
   if (!last_field_form) return refuse("no kernel form takes these strides");
   if (!to_user) {
     // the ghost layers as Setup fills them; WRK's copy of P's shell is stale
     if (!Comm_S2(arr)) return 0;
     if (which == 1) wrk_shell_tag = 0;
   }
-  if (!on_device) {
-    std::vector<REAL_TYPE> tmp;
+  if (op == FIO_RESIDUAL) {
+    if (!Comm_SUM_dev(d_res + 10, 1)) return 0;
+    HIP_CHECK(hipMemcpyAsync(h_scal + 10, d_res + 10, sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  if (none) {
+    HIP_CHECK(hipStreamSynchronize(st));
+  } else if (!on_device) {
+    std::vector<unsigned char> tmp;
     if (to_user) {
-      tmp.resize((size_t)span);
-      HIP_CHECK(hipMemcpyAsync(tmp.data(), dev, (size_t)span * sizeof(REAL_TYPE), hipMemcpyDeviceToHost, st));
+      tmp.resize(span_bytes);
+      HIP_CHECK(hipMemcpyAsync(tmp.data(), dev, span_bytes, hipMemcpyDeviceToHost, st));
     }
     HIP_CHECK(hipStreamSynchronize(st));
     if (to_user) {  // the brick's cells and nothing else, the direction of the smallest stride innermost
       int o[3] = {0, 1, 2};
       std::sort(o, o + 3, [&](int x, int y) { return stride[x] > stride[y]; });
       const long long s0 = stride[o[0]], s1 = stride[o[1]], s2 = stride[o[2]];
+      unsigned char* out = static_cast<unsigned char*>(a);
       for (int x = 0; x < size[o[0]]; x++)
         for (int y = 0; y < size[o[1]]; y++) {
           const long long base = x * s0 + y * s1;
-          for (int z = 0; z < size[o[2]]; z++) a[base + z * s2] = tmp[(size_t)(base + z * s2)];
+          for (int z = 0; z < size[o[2]]; z++) memcpy(out + (size_t)(base + z * s2) * abytes, tmp.data() + (size_t)(base + z * s2) * abytes, (size_t)abytes);
         }
     }
   } else if (user_stream) {
     HIP_CHECK(hipEventRecord(ev_io, st));
     HIP_CHECK(hipStreamWaitEvent((hipStream_t)user_stream, ev_io, 0));
+    if (op == FIO_RESIDUAL) HIP_CHECK(hipStreamSynchronize(st));  // (the one wait: the sum is a host value on return)
   } else {
     HIP_CHECK(hipStreamSynchronize(st));
   }
+  if (op == FIO_RESIDUAL) *sumsq = h_scal[10];
   return 1;
 }
 
@@ -1763,13 +1799,19 @@ int cz_history(const cz_handle* h, double* out, int cap) {
 }
 void cz_field(const cz_handle* h, CZ_REAL* host_out) { h->cz.Field(host_out); }
 int cz_set_rhs(cz_handle* h, const CZ_REAL* src, const long long* stride, int on_device, void* ready_stream) {
-  return h ? h->cz.FieldIO(0, const_cast<CZ_REAL*>(src), stride, on_device, ready_stream, false, "cz_set_rhs") : 0;
+  return h ? h->cz.FieldIO(0, const_cast<CZ_REAL*>(src), (int)sizeof(CZ_REAL), stride, on_device, ready_stream, CZ::FIO_IMPORT, 1.0, nullptr, "cz_set_rhs") : 0;
 }
 int cz_set_field(cz_handle* h, const CZ_REAL* src, const long long* stride, int on_device, void* ready_stream) {
-  return h ? h->cz.FieldIO(1, const_cast<CZ_REAL*>(src), stride, on_device, ready_stream, false, "cz_set_field") : 0;
+  return h ? h->cz.FieldIO(1, const_cast<CZ_REAL*>(src), (int)sizeof(CZ_REAL), stride, on_device, ready_stream, CZ::FIO_IMPORT, 1.0, nullptr, "cz_set_field") : 0;
 }
 int cz_get_field(cz_handle* h, CZ_REAL* dst, const long long* stride, int on_device, void* done_stream) {
-  return h ? h->cz.FieldIO(1, dst, stride, on_device, done_stream, true, "cz_get_field") : 0;
+  return h ? h->cz.FieldIO(1, dst, (int)sizeof(CZ_REAL), stride, on_device, done_stream, CZ::FIO_EXPORT, 1.0, nullptr, "cz_get_field") : 0;
+}
+int cz_get_residual(cz_handle* h, void* dst, int dst_real_bytes, const long long* stride, int on_device, void* done_stream, double scale, double* sumsq) {
+  return h ? h->cz.FieldIO(1, dst, dst_real_bytes, stride, on_device, done_stream, CZ::FIO_RESIDUAL, scale, sumsq, "cz_get_residual") : 0;
+}
+int cz_add_field(cz_handle* h, const void* src, int src_real_bytes, const long long* stride, int on_device, void* ready_stream, double scale) {
+  return h ? h->cz.FieldIO(1, const_cast<void*>(src), src_real_bytes, stride, on_device, ready_stream, CZ::FIO_ADD, scale, nullptr, "cz_add_field") : 0;
 }
 int cz_set_eps(cz_handle* h, double eps) {
   if (!h || !h->cz.set_up || !(eps > 0.0)) {

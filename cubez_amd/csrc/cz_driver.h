@@ -84,8 +84,8 @@ class CZ {
   int field_form = 0;            // CZ_FIELD_FORM: 3 = the generic import / export kernel whatever the strides
   int last_field_form = 0;       // the kernel form of the last import / export (cz_info 20: 1 k rows, 2 tile transpose, 3 generic)
   hipEvent_t ev_io = nullptr;    // the hand-over between the caller's stream and the compute stream
-  REAL_TYPE* io_stage = nullptr; // device copy of a host array's span
-  size_t io_stage_cap = 0;
+  void* io_stage = nullptr;      // device copy of a host array's span
+  size_t io_stage_cap = 0;       // ... its bytes
   CzConfig cfg;  // the environment as read when this object was created (cz_config.h)
   int skew_rank = -1, skew_ms = 0;  // CZ_TEST_SKEW=rank,ms: that rank sleeps before each look at the convergence flag (tests)
   void skew_wait() const;
@@ -130,8 +130,12 @@ class CZ {
   double ErrorMax(int loc[3]);          //   :550-563
   void Field(REAL_TYPE* host) const;
   // the caller's own problem (part 4 of cz_hip.h): this rank's brick, cell (i, j, k) at a[i stride[0] + j stride[1] + k stride[2]],
-  // into RHS (which 0) or P (which 1), or P out into it (to_user); 1 / 0
-  int FieldIO(int which, REAL_TYPE* a, const long long* stride, int on_device, void* user_stream, bool to_user, const char* who);
+  // into RHS (which 0) or P (which 1), or P out into it; elements of abytes bytes (REAL_TYPE's for the import and the export); 1 / 0.
+  // FIO_RESIDUAL: (T)(r scale) of r = RHS - A P out into it (a NULL: no destination) and *sumsq = sum r^2 over the whole domain;
+  // FIO_ADD: P = P + (REAL_TYPE)a scale on the cells every sweep updates
+  enum { FIO_IMPORT = 0, FIO_EXPORT = 1, FIO_RESIDUAL = 2, FIO_ADD = 3 };
+  int FieldIO(int which, void* a, int abytes, const long long* stride, int on_device, void* user_stream, int op, double scale, double* sumsq,
+              const char* who);
   void WriteProfile(FILE* fp) const;                                             // cz_Evaluate.cpp:506-545
   bool WriteSph(const char* fname, const REAL_TYPE* padded_host_field) const;  // cz_utility.f90:17-47
   void Exact(std::vector<REAL_TYPE>& e) const;                                   // cz_utility.f90:52-82

@@ -130,6 +130,13 @@ void copy_inner_async(CZ_REAL* dst, const CZ_REAL* src, const int* sz, const int
 // a caller's brick (cell (i, j, k) at user[i stride[0] + j stride[1] + k stride[2]], elements) into (to_user 0) or out of (1) the padded array arr;
 // form 0: chosen from the strides, 1 row / 2 transpose / 3 generic asked for; returns the form taken, 0 = refused (cz_k_field.h, cz_h_field.h)
 int field_copy_async(CZ_REAL* arr, CZ_REAL* user, const int* sz, int g, const long long* stride, int to_user, int form);
+// cz_get_residual / cz_add_field (cz_k_resid.h, cz_h_field.h): the caller's brick holds float or double (user_bytes 4 | 8).
+// field_residual_async: (T)(r scale) of r = rhs - A p at the cells of idx and 0 at the brick's other cells into user (nullptr: none), sum r^2
+// into sumsq_dev[0]; wrk: a padded array whose inner box is scratch.  field_add_async: p = p + (REAL)user (REAL)scale at the cells of idx.
+// form and return value as field_copy_async.
+int field_residual_async(const CZ_REAL* p, const CZ_REAL* rhs, CZ_REAL* wrk, void* user, int user_bytes, const int* sz, const int* idx, int g,
+                         const long long* stride, const CZ_REAL* cf, double scale, int form, double* sumsq_dev);
+int field_add_async(CZ_REAL* p, const void* user, int user_bytes, const int* sz, const int* idx, int g, const long long* stride, double scale, int form);
 void bc_async(const int* sz, int g, CZ_REAL* p, CZ_REAL dh, const CZ_REAL* org, const int* nID, int ioff = 0, int joff = 0);
 
 // ---- the multigrid V-cycle of pcg ... mg (cz_h_mg.h, and cz_mg_dist.cpp for decomposed runs)

@@ -13,6 +13,27 @@
 //                 take two banks each) further per lane -- no two lanes of a 32-lane group share a bank.
 //   field_any_k   every other stride triple: one cell per thread, k fastest on A's side.  Correct; no performance claim.
 // Offsets are long long throughout (1024^3 and beyond).
+// The transpose and generic forms also serve cz_get_residual and cz_add_field (their row forms are cz_k_resid.h): the caller's
+// side has element type T (float | double, whatever REAL is), and OP 1 is the scaled, boxed form of the copy -- DIR 1: U = (T)(A scale) at
+// the cells of the box and 0 at the brick's other cells (the residual in WRK out to the caller); DIR 0: A = A + (REAL)U scale at the cells of
+// the box, A's other cells untouched (the correction into P).  The product is one REAL multiplication, the conversion comes after it.
+// OP 0 is the plain copy, T = REAL.
+struct FieldBox {  // the cells every sweep updates, 0-based in the brick, inclusive
+  int lo0, hi0, lo1, hi1, lo2, hi2;
+};
+__device__ __forceinline__ bool field_in(const FieldBox& b, int c0, int c1, int c2) {
+  return c0 >= b.lo0 && c0 <= b.hi0 && c1 >= b.lo1 && c1 <= b.hi1 && c2 >= b.lo2 && c2 <= b.hi2;
+}
+template <int DIR, class T>
+struct FieldSides {  // element types of the destination and the source
+  typedef REAL D;
+  typedef T S;
+};
+template <class T>
+struct FieldSides<1, T> {
+  typedef T D;
+  typedef REAL S;
+};
 struct FieldGeom {
   int ni, nj, nk, g;
   int nkp;               // elements per k row of A
@@ -51,8 +72,10 @@ struct FieldTGeom {
 };
 constexpr int FIELD_TS = 64, FIELD_TP = FIELD_TS + 1;
 
-template <int DIR>
-__global__ __launch_bounds__(256) void field_tr_k(REAL* __restrict__ dst, const REAL* __restrict__ src, const FieldTGeom g) {
+// bx (OP 1): the box in the tile's directions (u, w, k)
+template <int DIR, class T = REAL, int OP = 0>
+__global__ __launch_bounds__(256) void field_tr_k(typename FieldSides<DIR, T>::D* __restrict__ dst, const typename FieldSides<DIR, T>::S* __restrict__ src,
+                                                  const FieldTGeom g, const FieldBox bx, const REAL scale) {
   __shared__ REAL tile[FIELD_TS * FIELD_TP];  // tile[kk * FIELD_TP + uu]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int u0 = blockIdx.x * FIELD_TS, k0 = blockIdx.y * FIELD_TS;
@@ -60,7 +83,7 @@ __global__ __launch_bounds__(256) void field_tr_k(REAL* __restrict__ dst, const 
     if (DIR == 0) {  // U's rows run along u
       if (u0 + lane < g.nu) {
         const long long ub = (long long)(u0 + lane) + (long long)w * g.u_ws;
-        for (int kk = wave; kk < FIELD_TS && k0 + kk < g.nk; kk += 4) tile[kk * FIELD_TP + lane] = src[ub + (long long)(k0 + kk) * g.u_ks];
+        for (int kk = wave; kk < FIELD_TS && k0 + kk < g.nk; kk += 4) tile[kk * FIELD_TP + lane] = (REAL)src[ub + (long long)(k0 + kk) * g.u_ks];
       }
     } else {  // A's rows run along k
       if (k0 + lane < g.nk) {
@@ -72,28 +95,43 @@ __global__ __launch_bounds__(256) void field_tr_k(REAL* __restrict__ dst, const 
     if (DIR == 0) {
       if (k0 + lane < g.nk) {
         const long long ab = g.a0 + (long long)w * g.a_ws + (k0 + lane);
-        for (int uu = wave; uu < FIELD_TS && u0 + uu < g.nu; uu += 4) dst[ab + (long long)(u0 + uu) * g.a_us] = tile[lane * FIELD_TP + uu];
+        for (int uu = wave; uu < FIELD_TS && u0 + uu < g.nu; uu += 4) {
+          const long long d = ab + (long long)(u0 + uu) * g.a_us;
+          if (!OP) dst[d] = tile[lane * FIELD_TP + uu];
+          else if (field_in(bx, u0 + uu, w, k0 + lane)) dst[d] = dst[d] + tile[lane * FIELD_TP + uu] * scale;
+        }
       }
     } else {
       if (u0 + lane < g.nu) {
         const long long ub = (long long)(u0 + lane) + (long long)w * g.u_ws;
-        for (int kk = wave; kk < FIELD_TS && k0 + kk < g.nk; kk += 4) dst[ub + (long long)(k0 + kk) * g.u_ks] = tile[kk * FIELD_TP + lane];
+        for (int kk = wave; kk < FIELD_TS && k0 + kk < g.nk; kk += 4) {
+          const long long d = ub + (long long)(k0 + kk) * g.u_ks;
+          if (!OP) dst[d] = (T)tile[kk * FIELD_TP + lane];
+          else dst[d] = field_in(bx, u0 + lane, w, k0 + kk) ? (T)(tile[kk * FIELD_TP + lane] * scale) : (T)0;
+        }
       }
     }
     __syncthreads();  // (the next line's tile)
   }
 }
 
-template <int DIR>
-__global__ __launch_bounds__(256) void field_any_k(REAL* __restrict__ dst, const REAL* __restrict__ src, const FieldGeom g) {
+template <int DIR, class T = REAL, int OP = 0>
+__global__ __launch_bounds__(256) void field_any_k(typename FieldSides<DIR, T>::D* __restrict__ dst, const typename FieldSides<DIR, T>::S* __restrict__ src,
+                                                   const FieldGeom g, const FieldBox bx, const REAL scale) {
   const long long per_plane = (long long)g.ni * g.nk;
   for (int j = blockIdx.y; j < g.nj; j += gridDim.y) {
     for (long long it = (long long)blockIdx.x * 256 + threadIdx.x; it < per_plane; it += (long long)gridDim.x * 256) {
       const int i = (int)(it / g.nk), k = (int)(it - (long long)i * g.nk);
       const long long a = (long long)(j + g.g) * g.PSE + (long long)(i + g.g) * g.nkp + (k + g.g);
       const long long u = (long long)i * g.s0 + (long long)j * g.s1 + (long long)k * g.s2;
-      if (DIR) dst[u] = src[a];
-      else dst[a] = src[u];
+      if (!OP) {
+        if (DIR) dst[u] = (T)src[a];
+        else dst[a] = (REAL)src[u];
+      } else if (DIR) {
+        dst[u] = field_in(bx, i, j, k) ? (T)(src[a] * scale) : (T)0;
+      } else if (field_in(bx, i, j, k)) {
+        dst[a] = dst[a] + (REAL)src[u] * scale;
+      }
     }
   }
 }

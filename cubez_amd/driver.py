@@ -40,6 +40,8 @@ class CZ:
         lib.cz_precondition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ("cz_set_rhs", "cz_set_field", "cz_get_field"):
             getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_int, C.c_void_p]
+        lib.cz_get_residual.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_double, C.POINTER(C.c_double)]
+        lib.cz_add_field.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_double]
         lib.cz_set_eps.argtypes = [C.c_void_p, C.c_double]
         lib.cz_set_itr_max.argtypes = [C.c_void_p, C.c_int]
         self.device = int(device)
@@ -104,10 +106,12 @@ class CZ:
     # local()["size"] = (ni, nj, nk), indexed [i, j, k], any positive strides.  A numpy array goes the host path; anything with data_ptr(),
     # stride(), dtype, device and is_cuda (a torch tensor on the handle's GPU) is read / written in place on the device, handed over on
     # torch's current stream.
-    def _brick(self, a, what):
+    # any_real (get_residual, add_field): the array may hold float32 or float64 whatever the handle's precision.
+    def _brick(self, a, what, any_real=False):
         shape = tuple(self.local()["size"])
+        names = ("float32", "float64") if any_real else (np.dtype(self.real).name,)
         if isinstance(a, np.ndarray):
-            if a.dtype != self.real:
+            if a.dtype.name not in names:
                 raise ValueError(f"{what}: dtype {a.dtype}, this handle is {np.dtype(self.real)}")
             if tuple(a.shape) != shape:
                 raise ValueError(f"{what}: shape {tuple(a.shape)}, this rank's brick is {shape}")
@@ -116,7 +120,7 @@ class CZ:
             return a.ctypes.data, [st // a.itemsize for st in a.strides], 0, None, None
         if not all(hasattr(a, n) for n in ("data_ptr", "stride", "dtype", "device", "is_cuda")):
             raise ValueError(f"{what}: a numpy array or a device tensor (data_ptr, stride, dtype, device, is_cuda) is needed")
-        if str(a.dtype).split(".")[-1] != np.dtype(self.real).name:
+        if str(a.dtype).split(".")[-1] not in names:
             raise ValueError(f"{what}: dtype {a.dtype}, this handle is {np.dtype(self.real)}")
         if tuple(a.shape) != shape:
             raise ValueError(f"{what}: shape {tuple(a.shape)}, this rank's brick is {shape}")
@@ -153,6 +157,41 @@ class CZ:
             out = np.empty(tuple(self.local()["size"]), dtype=self.real)
         self._io(self.lib.cz_get_field, out, "get_field")
         return out
+
+    # -- mixed-precision refinement (cz_get_residual / cz_add_field of include/cz_hip.h)
+    def get_residual(self, out=None, dtype=None, scale=1.0):
+        """(out, sumsq): out = (r * scale) of the true residual r = b - A p of the iterate in the handle on this rank's brick (0 on Dirichlet
+        faces), as float32 or float64 whatever the handle's precision; sumsq = the sum of r^2 (unscaled, in double) over the whole domain.
+        out: a numpy array or a device tensor; None with a dtype: a new C-order numpy array; None without: the norm only, (None, sumsq).
+        Collective in a decomposed run."""
+        if out is None and dtype is not None:
+            out = np.empty(tuple(self.local()["size"]), dtype=np.dtype(dtype))
+        ss = C.c_double(0.0)
+        if out is None:
+            ok = self.lib.cz_get_residual(self.h, None, 0, None, 0, None, float(scale), C.byref(ss))
+        else:
+            ptr, strides, on_dev, stream, ts = self._brick(out, "get_residual", any_real=True)
+            if on_dev and stream is None:
+                ts.synchronize()
+            ok = self.lib.cz_get_residual(self.h, C.c_void_p(ptr), self._itemsize(out), (C.c_longlong * 3)(*strides), on_dev,
+                                          C.c_void_p(stream) if stream else None, float(scale), C.byref(ss))
+        if ok != 1:
+            raise RuntimeError("get_residual: refused (see stderr)")
+        return out, ss.value
+
+    def add_field(self, a, scale=1.0):
+        """p = p + a * scale on the cells every sweep updates (a: float32 or float64, numpy array or device tensor); Dirichlet faces are not
+        written (collective in a decomposed run)"""
+        ptr, strides, on_dev, stream, ts = self._brick(a, "add_field", any_real=True)
+        if on_dev and stream is None:
+            ts.synchronize()
+        if self.lib.cz_add_field(self.h, C.c_void_p(ptr), self._itemsize(a), (C.c_longlong * 3)(*strides), on_dev,
+                                 C.c_void_p(stream) if stream else None, float(scale)) != 1:
+            raise RuntimeError("add_field: refused (see stderr)")
+
+    @staticmethod
+    def _itemsize(a):
+        return a.itemsize if isinstance(a, np.ndarray) else a.element_size()
 
     def set_eps(self, eps: float):
         if self.lib.cz_set_eps(self.h, float(eps)) != 1:

@@ -436,6 +436,21 @@ int cz_solve(cz_handle*);                      /* runs the selected solver to It
 int cz_set_rhs(cz_handle*, const CZ_REAL* src, const long long* stride, int on_device, void* ready_stream);
 int cz_set_field(cz_handle*, const CZ_REAL* src, const long long* stride, int on_device, void* ready_stream);
 int cz_get_field(cz_handle*, CZ_REAL* dst, const long long* stride, int on_device, void* done_stream);
+/* Mixed-precision refinement: the true residual of the iterate in the handle, and a correction into it.  The caller's brick is
+ * laid out and handed over as for cz_get_field / cz_set_field, but its elements are float or double, chosen by *_real_bytes (4 | 8), whatever
+ * the library's precision -- the FP64 library's residual goes out as the FP32 library's right-hand side, and that library's solution comes back.
+ *   cz_get_residual  r = b - (ss - 6 p) of the current P and RHS -- the unit-coefficient operator above, with the arithmetic, the operation
+ *     order and the type (CZ_REAL) of blas_calc_rk_ -- at the cells every sweep updates and 0 on physical (Dirichlet) faces, written as
+ *     (T)(r * (CZ_REAL)scale): one multiplication, then one conversion (FP64 -> FP32 rounds to nearest, FP32 -> FP64 is exact).  *sumsq (a host
+ *     pointer, written on return) = the sum of r^2 of the unscaled r, every square and the sum in double, over the whole domain (a decomposed
+ *     run all-reduces it: the same value on every rank); its bits do not depend on the destination, and two calls give the same bits.
+ *     dst = NULL: the sum only.  Collective in a decomposed run: the ghost layer of P is exchanged first.
+ *   cz_add_field     P = P + (CZ_REAL)src * (CZ_REAL)scale at the cells every sweep updates -- one multiplication and one addition, each
+ *     rounded once; Dirichlet faces and guide cells are not written.  Afterwards the ghost layers are filled as cz_set_field fills them.
+ * Return 1, or 0 with one line on stderr and nothing changed: every case cz_get_field / cz_set_field refuse, a byte size other than 4 or 8,
+ * a scale that is not finite and positive (as given and as CZ_REAL), a handle set up with a _maf solver (its operator is not the unit one). */
+int cz_get_residual(cz_handle*, void* dst, int dst_real_bytes, const long long* stride, int on_device, void* done_stream, double scale, double* sumsq);
+int cz_add_field(cz_handle*, const void* src, int src_real_bytes, const long long* stride, int on_device, void* ready_stream, double scale);
 int cz_set_eps(cz_handle*, double eps);
 int cz_set_itr_max(cz_handle*, int n);
 int cz_sweeps(cz_handle*, int n);              /* bench leg: n more iterations of the selected stationary solver with the
