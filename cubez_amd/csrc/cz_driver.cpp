@@ -212,6 +212,10 @@ int CZ::Setup(int argc, char** argv) {
   const int gc = GUIDE;
   if (argc != 7 && argc != 8 && argc != 10 && argc != 11) return 0;  // main.cpp:19
 
+  // a set-up starts with Dirichlet faces: the hierarchy it builds knows no mask (cz_set_neumann comes after cz_setup)
+  std::fill(neumann, neumann + 6, 0);
+  neumann_mask = 0;
+
   comm_world(&myRank, &numProc);  // rank/size from the launcher environment (replaces MPI_Comm_rank/size, :44-50)
 
   G_size[0] = atoi(argv[1]);
@@ -374,8 +378,15 @@ int CZ::Setup(int argc, char** argv) {
   return 1;
 }
 
+// Zero-flux faces are built for pcg (none | jacobi | mg | mgrb) alone: every other loop would sweep with Dirichlet faces
+bool CZ::neumann_refused(const char* who, int s_type) const {
+  if (!neumann_mask || s_type == LS_PCG) return false;
+  fprintf(stderr, "%s: Neumann faces are set (cz_set_neumann) and the solver is not pcg\n", who);
+  return true;
+}
+
 int CZ::Solve() {
-  if (!set_up) return 0;
+  if (!set_up || neumann_refused("cz_solve", ls_type)) return 0;
   double res = 0.0, flop = 0.0;
   int itr = 0;
   // every solve starts from the current P with the bookkeeping a fresh set-up leaves (the loops clear the device flag and their counters
@@ -405,6 +416,10 @@ int CZ::Solve() {
 }
 
 int CZ::Evaluate(int argc, char** argv) {
+  if (neumann_mask && argc > 4) {
+    const cz_solvers::Row* named = cz_solvers::find(argv[4], cz_solvers::SOLVER);
+    if (neumann_refused("cz_evaluate", named ? named->id : LS_NONE)) return 0;
+  }
   if (!Setup(argc, argv)) return 0;
   if (!Solve()) return 0;
   if (!quiet) Hostonly_ {
@@ -452,6 +467,7 @@ int CZ::Evaluate(int argc, char** argv) {
 // (sweep, residual reduction, convergence bookkeeping) but eps disabled so that nothing is skipped.
 int CZ::Sweeps(int n) {
   const cz_solvers::Family f = cz_solvers::row(ls_type).family;
+  if (set_up && neumann_refused("cz_sweeps", ls_type)) return 0;
   if (!set_up || !(f == cz_solvers::JACOBI || f == cz_solvers::RBSOR || f == cz_solvers::PSOR || f == cz_solvers::LINE)) return 0;
   const double keep = eps;
   eps = -1.0;
@@ -1356,7 +1372,8 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   const double n = npts();
   const bool pc = pc_type == LS_JACOBI || pc_type == LS_MG || pc_type == LS_MGRB;
   const bool fuse = cfg.on(CZV_CG_FUSE, true);
-  const bool fuse_dir = fuse && numProc == 1;  // the direction pass reads z's and p's shells as zeros: single domain only
+  // the direction pass reads z's and p's shells as zeros: single domain only, and no Neumann face (whose layer of p is the mirror)
+  const bool fuse_dir = fuse && numProc == 1 && !neumann_mask;
   REAL_TYPE* const sc = reinterpret_cast<REAL_TYPE*>(d_res + 12);  // alpha, -alpha, beta, rho (cg_scal_k)
   double* const d_rr = d_res + 5;
   double* const d_pq = d_res + 3;                 // (the unfused SpMV writes q.q to d_res[4])
@@ -1366,6 +1383,7 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   cg_fused = 0;
   mg_cycles = 0;
 
+  mirror(X);
   calc_rk_async(cg_r, X, B, size, innerFidx, gc, cf);
   flop += 14.0 * n;
   if (!Comm_S(cg_r)) return 0;
@@ -1390,6 +1408,20 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
       if (mg || mgd) {
         if (mg ? !czhip_mg_apply_async(mg, cg_z, cg_r, ac1) : !mgd_apply(mgd, cg_z, cg_r, ac1)) return 0;  // z = V_0(r)
         mg_cycles++;
+      } else if (neumann_mask) {
+        // the 8 relaxed sweeps from zero as single sweeps between cg_z and cg_p[1] (free: the direction is not fused), the exchange and the
+        // mirror before every sweep that reads its input
+        HIP_CHECK(hipMemsetAsync(cg_z, 0, nbytes, st));
+        REAL_TYPE *src = cg_z, *dst = cg_p[1];
+        for (int s = 0; s < 8; s++) {
+          if (s) {
+            if (!Comm_S(src)) return 0;
+            mirror(src);
+          }
+          czhip_jacobi_async(src, dst, cg_r, size, innerFidx, gc, cf, ac1, d_res, 0, nullptr);
+          std::swap(src, dst);
+        }
+        flop += 8 * 18.0 * n;
       } else {
         double fc = 0.0;
         Preconditioner(cg_z, cg_r, fc, LS_JACOBI);
@@ -1408,6 +1440,7 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
       if (itr == 1) HIP_CHECK(hipMemcpyAsync(cg_p[cur], z, nbytes, hipMemcpyDeviceToDevice, st));
       else triad_async(cg_p[cur], cg_p[cur], z, (REAL_TYPE)0, size, innerFidx, gc, sc + 2);  // p = beta p + z
       if (!Comm_S(cg_p[cur])) return 0;
+      mirror(cg_p[cur]);
       calc_ax_dots_async(cg_q, cg_p[cur], cg_p[cur], size, innerFidx, gc, cf, nullptr, d_pq);
     }
     if (itr > 1) flop += 2.0 * n;
@@ -1444,10 +1477,40 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   }
   if (itr > ItrMax) itr = ItrMax;
   if (!Comm_S(X)) return 0;  // (the ghost layers of the result, as PBiCGSTAB leaves them)
+  mirror(X);
   return itr;
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Zero-flux (Neumann) faces.  The mask is global and the same on every rank; a brick mirrors the faces that are physical on it
+void CZ::mirror(REAL_TYPE* X) {
+  if (!neumann_mask) return;
+  if (!czhip_mirror_faces_async(X, size, innerFidx, GUIDE, neumann)) cz_fatal(1, "czhip: the mirror of the Neumann faces was refused\n");
+}
+
+int CZ::SetNeumann(const int* faces) {
+  auto refuse = [&](const char* why) {
+    fprintf(stderr, "cz_set_neumann: %s\n", why);
+    return 0;
+  };
+  if (!set_up) return refuse("no problem is set up (cz_setup first)");
+  if (!faces) return refuse("NULL pointer");
+  int nm = 0;
+  for (int f = 0; f < 6; f++) nm |= faces[f] ? 1 << f : 0;
+  if (nm == 63) return refuse("at least one face must stay a Dirichlet face (the all-Neumann problem is singular)");
+  if (SW_maf) return refuse("the handle's operator is a MAF one, not the unit-coefficient operator");
+  if ((mg && !czhip_mg_set_neumann(mg, faces)) || (mgd && !mgd_set_neumann(mgd, faces))) return refuse("the multigrid hierarchy refused the mask");
+  for (int f = 0; f < 6; f++) neumann[f] = faces[f] ? 1 : 0;
+  neumann_mask = nm;
+  // the work vectors whose face layers carried the mirrors of an earlier mask: zeros again, as the unmasked passes read them
+  for (REAL_TYPE* a : {cg_z, cg_p[0], cg_p[1]})
+    if (a) HIP_CHECK(hipMemsetAsync(a, 0, padded_cells() * sizeof(REAL_TYPE), stream()));
+  mirror(P);
+  wrk_shell_tag = 0;
+  czhip_sync();
+  return 1;
+}
+
 void CZ::Field(REAL_TYPE* host) const {
   czhip_d2h(host, P, padded_cells() * sizeof(REAL_TYPE));
 }
@@ -1533,6 +1596,7 @@ int CZ::FieldIO(int which, void* a, int abytes, const long long* stride, int on_
   if (op == FIO_RESIDUAL) {
     // (the stencil reads one ghost layer of P; a solve may have left it one exchange behind)
     if (!Comm_S(P)) return 0;
+    mirror(P);
     last_field_form = field_residual_async(P, RHS, WRK, dev, abytes, size, innerFidx, GUIDE, stride, cf, scale, form, d_res + 10);
   } else if (op == FIO_ADD) {
     last_field_form = field_add_async(P, dev, abytes, size, innerFidx, GUIDE, stride, scale, form);
@@ -1543,7 +1607,10 @@ int CZ::FieldIO(int which, void* a, int abytes, const long long* stride, int on_
   if (!to_user) {
     // the ghost layers as Setup fills them; WRK's copy of P's shell is stale
     if (!Comm_S2(arr)) return 0;
-    if (which == 1) wrk_shell_tag = 0;
+    if (which == 1) {  // (Neumann faces: what the caller passed there is not data)
+      mirror(P);
+      wrk_shell_tag = 0;
+    }
   }
   if (op == FIO_RESIDUAL) {
     if (!Comm_SUM_dev(d_res + 10, 1)) return 0;
@@ -1813,6 +1880,7 @@ int cz_get_residual(cz_handle* h, void* dst, int dst_real_bytes, const long long
 int cz_add_field(cz_handle* h, const void* src, int src_real_bytes, const long long* stride, int on_device, void* ready_stream, double scale) {
   return h ? h->cz.FieldIO(1, const_cast<void*>(src), src_real_bytes, stride, on_device, ready_stream, CZ::FIO_ADD, scale, nullptr, "cz_add_field") : 0;
 }
+int cz_set_neumann(cz_handle* h, const int* faces) { return h ? h->cz.SetNeumann(faces) : 0; }
 int cz_set_eps(cz_handle* h, double eps) {
   if (!h || !h->cz.set_up || !(eps > 0.0)) {
     fprintf(stderr, "cz_set_eps: %s\n", h && h->cz.set_up ? "the tolerance must be positive" : "no problem is set up (cz_setup first)");
@@ -1862,6 +1930,7 @@ int cz_info(const cz_handle* h, int what) {
     case 8: return c.last_plan.depth;
     case 9: return c.last_plan.buffers;
     case 20: return c.last_field_form;
+    case 21: return c.neumann_mask;
     default: return -1;
   }
 }

@@ -81,6 +81,8 @@ class CZ {
   int bicg_fused = 0;            // vector updates of the last BiCGSTAB solve that were made inside the first pair of a preconditioner solve (cz_info 10)
   bool in_precond = false;       // inside Preconditioner: an unchecked solve does not drain the queue (the caller's next launch follows in stream order)
   int last_lag = 0;              // the last stationary solve ran its all-reduce + test one pass behind (cz_info)
+  int neumann[6] = {0, 0, 0, 0, 0, 0};  // zero-flux (Neumann) physical faces of the global box, X-, X+, Y-, Y+, Z-, Z+ (cz_set_neumann)
+  int neumann_mask = 0;          // ... as bits (cz_info 21); non-zero: P's face layers there hold the mirror of the first inner layer
   int field_form = 0;            // CZ_FIELD_FORM: 3 = the generic import / export kernel whatever the strides
   int last_field_form = 0;       // the kernel form of the last import / export (cz_info 20: 1 k rows, 2 tile transpose, 3 generic)
   hipEvent_t ev_io = nullptr;    // the hand-over between the caller's stream and the compute stream
@@ -136,6 +138,8 @@ class CZ {
   enum { FIO_IMPORT = 0, FIO_EXPORT = 1, FIO_RESIDUAL = 2, FIO_ADD = 3 };
   int FieldIO(int which, void* a, int abytes, const long long* stride, int on_device, void* user_stream, int op, double scale, double* sumsq,
               const char* who);
+  int SetNeumann(const int* faces);  // cz_set_neumann: 1, or 0 with one line on stderr and nothing changed
+  void mirror(REAL_TYPE* X);         // the Neumann face layers of X from its first inner layers (nothing without a mask)
   void WriteProfile(FILE* fp) const;                                             // cz_Evaluate.cpp:506-545
   bool WriteSph(const char* fname, const REAL_TYPE* padded_host_field) const;  // cz_utility.f90:17-47
   void Exact(std::vector<REAL_TYPE>& e) const;                                   // cz_utility.f90:52-82
@@ -175,6 +179,7 @@ class CZ {
   void Preconditioner(REAL_TYPE* xx, REAL_TYPE* bb, double& flop, int s_type, const BMade* made = nullptr);
   int PBiCGSTAB(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop, int s_type);
   int PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop);  // beyond the reference (DESIGN.md "PCG")
+  bool neumann_refused(const char* who, int s_type) const;          // a mask is set and the solver is not pcg: one line, true
 
   // cz_comm.cpp replacements (no-ops when numProc == 1, like cz_comm.cpp:25,76,104)
   bool Comm_S(REAL_TYPE* X, const int* skip_flag = nullptr);
@@ -223,6 +228,7 @@ class CZ {
 MgDist* mgd_create(const CZ& cz, CommCtx* comm0, int gather_points, bool tail);
 void mgd_destroy(MgDist*);
 int mgd_apply(MgDist*, REAL_TYPE* z, const REAL_TYPE* r, REAL_TYPE omg);  // z = V_0(r) on this rank's brick, collective
+int mgd_set_neumann(MgDist*, const int* faces6);  // the global mask of zero-flux faces, on every rank; 0 = refused
 int mgd_levels(const MgDist*);
 int mgd_gather_level(const MgDist*);
 int mgd_exchanges(const MgDist*);  // halo exchanges + all-gathers of the last cycle

@@ -18,6 +18,7 @@ bool mg_lev(MgDLev& D, const MgdLevel& M) {
   }
   if (M.level < 0 || M.level >= MG_MAXLEV - 1) return false;
   L.l = M.level, L.n0i = M.n0[0], L.n0j = M.n0[1], L.n0k = M.n0[2];
+  L.nm = M.level >= 1 ? M.nm & 63 : 0;  // (level 0 keeps 1 and 6: there the mirrored face layer carries the condition)
   D.o = MgG{M.o[0], M.o[1], M.o[2]};
   D.gni = M.gn[0], D.gnj = M.gn[1], D.gnk = M.gn[2];
   const int n[3] = {L.ni, L.nj, L.nk};
@@ -61,15 +62,19 @@ bool mg_tail_plan(MgTail& T, const MgLev& fine, REAL omg, bool rb = false) {
   return true;
 }
 
-template <bool RB>
+// (NM: the level kernels' instantiation for a level with Neumann faces, chosen here from the level's mask -- cz_k_mg.h, mg_weights)
+template <bool RB, bool NM>
 void mg_tail_launch(REAL* x, const REAL* b, const MgTail& T) {
   ScopedTimer tm(LBL_MG_TAIL);
   const int bytes = T.total * (int)sizeof(REAL);
-  if (bytes > 64 * 1024) allow_dynamic_lds(&mg_tail_k<RB>, 160 * 1024);
-  hipLaunchKernelGGL((mg_tail_k<RB>), dim3(1), dim3(MG_TAIL_THREADS), bytes, ctx.stream, x, b, T);
+  if (bytes > 64 * 1024) allow_dynamic_lds(&mg_tail_k<RB, NM>, 160 * 1024);
+  hipLaunchKernelGGL((mg_tail_k<RB, NM>), dim3(1), dim3(MG_TAIL_THREADS), bytes, ctx.stream, x, b, T);
   HIP_CHECK(hipGetLastError());
 }
-void mg_tail_launch(REAL* x, const REAL* b, const MgTail& T, bool rb) { rb ? mg_tail_launch<true>(x, b, T) : mg_tail_launch<false>(x, b, T); }
+void mg_tail_launch(REAL* x, const REAL* b, const MgTail& T, bool rb) {
+  if (T.gl.nm) rb ? mg_tail_launch<true, true>(x, b, T) : mg_tail_launch<false, true>(x, b, T);
+  else rb ? mg_tail_launch<true, false>(x, b, T) : mg_tail_launch<false, false>(x, b, T);
+}
 
 dim3 mg_grid(const MgLev& L) { return dim3((unsigned)((L.nk + 63) / 64), (unsigned)((L.ni + 3) / 4), (unsigned)L.nj); }
 }  // namespace
@@ -81,8 +86,11 @@ int mg_smooth_async(const REAL* u, REAL* w, const REAL* b, const MgdLevel& M, RE
   if (!w || !b || u == w || !mg_lev(D, M) || M.dense) return 0;
   if (mg_none(D)) return 1;
   ScopedTimer tm(LBL_MG_SMOOTH);
-  if (u) hipLaunchKernelGGL((mg_smooth_k<false>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, u, w, b, D, omg);
-  else hipLaunchKernelGGL((mg_smooth_k<true>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, w, w, b, D, omg);
+  if (D.L.nm) {
+    if (u) hipLaunchKernelGGL((mg_smooth_k<false, true>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, u, w, b, D, omg);
+    else hipLaunchKernelGGL((mg_smooth_k<true, true>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, w, w, b, D, omg);
+  } else if (u) hipLaunchKernelGGL((mg_smooth_k<false, false>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, u, w, b, D, omg);
+  else hipLaunchKernelGGL((mg_smooth_k<true, false>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, w, w, b, D, omg);
   HIP_CHECK(hipGetLastError());
   return 1;
 }
@@ -94,9 +102,13 @@ int mg_rb_async(REAL* x, const REAL* b, const MgdLevel& M, REAL omg, int colour,
   if (mg_none(D)) return 1;
   ScopedTimer tm(LBL_MG_RB);
   const dim3 grid((unsigned)(((D.L.nk + 1) / 2 + 63) / 64), (unsigned)((D.L.ni + 3) / 4), (unsigned)D.L.nj);
-  if (zero == 0) hipLaunchKernelGGL((mg_rb_k<0>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
-  else if (zero == 1) hipLaunchKernelGGL((mg_rb_k<1>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
-  else hipLaunchKernelGGL((mg_rb_k<2>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
+  if (D.L.nm) {
+    if (zero == 0) hipLaunchKernelGGL((mg_rb_k<0, true>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
+    else if (zero == 1) hipLaunchKernelGGL((mg_rb_k<1, true>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
+    else hipLaunchKernelGGL((mg_rb_k<2, true>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
+  } else if (zero == 0) hipLaunchKernelGGL((mg_rb_k<0, false>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
+  else if (zero == 1) hipLaunchKernelGGL((mg_rb_k<1, false>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
+  else hipLaunchKernelGGL((mg_rb_k<2, false>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
   HIP_CHECK(hipGetLastError());
   return 1;
 }
@@ -109,7 +121,9 @@ int mgd_resface_async(REAL* rt, const REAL* x, const REAL* b, const MgdLevel& M,
   for (int d = 0; d < 3; d++) {
     if (!minus[d]) continue;
     const int fast = d == 2 ? D.L.ni : D.L.nk, slow = d == 0 ? D.L.nj : d == 1 ? D.L.ni : D.L.nj;
-    hipLaunchKernelGGL(mgd_resface_k, dim3((unsigned)((fast + 63) / 64), (unsigned)slow), dim3(64), 0, ctx.stream, rt, x, b, D, d, minus[0], minus[1]);
+    const dim3 grid((unsigned)((fast + 63) / 64), (unsigned)slow);
+    if (D.L.nm) hipLaunchKernelGGL(mgd_resface_k<true>, grid, dim3(64), 0, ctx.stream, rt, x, b, D, d, minus[0], minus[1]);
+    else hipLaunchKernelGGL(mgd_resface_k<false>, grid, dim3(64), 0, ctx.stream, rt, x, b, D, d, minus[0], minus[1]);
     HIP_CHECK(hipGetLastError());
   }
   return 1;
@@ -121,8 +135,12 @@ int mg_restrict_async(REAL* bc, const MgdLevel& MC, const REAL* x, const REAL* b
   if (!bc || !x || !b || bc == x || bc == b || !mg_lev(F, MF) || !mg_lev(C, MC) || MF.dense || !mg_coarse_of(MF, MC) || (!rt && !(mg_whole(F) && mg_whole(C)))) return 0;
   if (mg_none(C)) return 1;
   ScopedTimer tm(LBL_MG_RESTRICT);
-  if (rt) hipLaunchKernelGGL((mg_restrict_k<true>), mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C);
-  else hipLaunchKernelGGL((mg_restrict_k<false>), mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C);
+  // (the children's residual takes the FINE level's weights: its mask)
+  if (F.L.nm) {
+    if (rt) hipLaunchKernelGGL((mg_restrict_k<true, true>), mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C);
+    else hipLaunchKernelGGL((mg_restrict_k<false, true>), mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C);
+  } else if (rt) hipLaunchKernelGGL((mg_restrict_k<true, false>), mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C);
+  else hipLaunchKernelGGL((mg_restrict_k<false, false>), mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C);
   HIP_CHECK(hipGetLastError());
   return 1;
 }
@@ -254,6 +272,21 @@ cz_mg* czhip_mg_create(const int* sz, const int* idx, int g, const CZ_REAL* cf) 
 cz_mg* czhip_mg_create_rb(const int* sz, const int* idx, int g, const CZ_REAL* cf) { return mg_create_public(sz, idx, g, cf, true); }
 
 int czhip_mg_levels(const cz_mg* h) { return h ? h->nlev : 0; }
+
+// zero-flux (Neumann) faces for the hierarchy's cycles from now on (faces[6]: X-, X+, Y-, Y+, Z-, Z+; all zero: none); 0 = refused (all six)
+int czhip_mg_set_neumann(cz_mg* h, const int* faces) {
+  if (!h || !faces) return 0;
+  int nm = 0;
+  for (int f = 0; f < 6; f++) nm |= faces[f] ? 1 << f : 0;
+  if (nm == 63) return 0;
+  h->nm = nm;
+  for (int l = h->first; l < h->nlev; l++) h->lev[l].nm = nm;
+  if (h->fine_tmp) {  // (its face layers may hold the mirrors of an earlier mask: zeros again, as the unmasked passes read them)
+    const int* sz = h->lev[0].sz;
+    HIP_CHECK(hipMemsetAsync(h->fine_tmp, 0, (size_t)(sz[0] + 4) * (sz[1] + 4) * (sz[2] + 4) * sizeof(REAL), ctx.stream));
+  }
+  return 1;
+}
 int czhip_mg_kind(const cz_mg* h) { return h ? 1 + h->rb : 0; }
 
 void czhip_mg_destroy(cz_mg* h) {
@@ -269,21 +302,32 @@ void czhip_mg_destroy(cz_mg* h) {
 }  // extern "C"
 
 namespace {
+// the Neumann face layers of a level-0 array from its first inner layers
+void mg_mirror(cz_mg* h, REAL* x) {
+  int faces[6];
+  for (int f = 0; f < 6; f++) faces[f] = (h->nm >> f) & 1;
+  if (!czhip_mirror_faces_async(x, h->lev[0].sz, h->lev[0].idx, MG_GUIDE, faces)) cz_fatal(1, "czhip: V-cycle: the mirror of the Neumann faces was refused\n");
+}
+
 // level 0's pairs of sweeps with the unit coefficients, u -> w (u = nullptr: from zero): the fused pass, or where it is not taken two single
 // sweeps through o (an array other than w; it may be u) and a copy back to w
-void mg_fine_pair(cz_mg* h, const REAL* u, REAL* w, REAL* o, const REAL* b, REAL omg) {
+// (Neumann faces: two single sweeps, the face layers mirrored before each sweep that reads its input -- DESIGN.md §5.13)
+void mg_fine_pair(cz_mg* h, REAL* u, REAL* w, REAL* o, const REAL* b, REAL omg) {
   const int* sz = h->lev[0].sz;
   const int* idx = h->lev[0].idx;
   REAL cf[7] = {1, 1, 1, 1, 1, 1, 6};
-  if (u ? czhip_jacobi2_async(u, w, b, sz, idx, nullptr, MG_GUIDE, cf, omg, h->res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr)
-        : czhip_jacobi2_from_zero_async(w, w, b, sz, idx, nullptr, MG_GUIDE, cf, omg, h->res))
+  if (!h->nm && (u ? czhip_jacobi2_async(u, w, b, sz, idx, nullptr, MG_GUIDE, cf, omg, h->res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr)
+                   : czhip_jacobi2_from_zero_async(w, w, b, sz, idx, nullptr, MG_GUIDE, cf, omg, h->res)))
     return;
   const size_t nbytes = (size_t)(sz[0] + 4) * (sz[1] + 4) * (sz[2] + 4) * sizeof(REAL);
   if (!u) {
     HIP_CHECK(hipMemsetAsync(o, 0, nbytes, ctx.stream));
     u = o;
+  } else if (h->nm) {
+    mg_mirror(h, u);
   }
   czhip_jacobi_async(u, w, b, sz, idx, MG_GUIDE, cf, omg, h->res, 0, nullptr);
+  if (h->nm) mg_mirror(h, w);
   czhip_jacobi_async(w, o, b, sz, idx, MG_GUIDE, cf, omg, h->res, 0, nullptr);
   HIP_CHECK(hipMemcpyAsync(w, o, nbytes, hipMemcpyDeviceToDevice, ctx.stream));
 }
@@ -296,6 +340,7 @@ struct MgOps {
   const REAL* r;
   REAL *x0, *o0;
 
+  void mirror(REAL* X) { mg_mirror(h, X); }
   bool whole(int l) {
     if (l < h->tail_from) return false;
     MgDLev D;
@@ -315,6 +360,7 @@ struct MgOps {
     const int* sz = h->lev[0].sz;
     const int* idx = h->lev[0].idx;
     const REAL cf[7] = {1, 1, 1, 1, 1, 1, 6};
+    if (h->nm) return 0;  // (Neumann faces: the colour sweeps in place, a mirror after each)
     if ((!zero || h->zero4) && czhip_rbsor4_async(x0, o0, r, sz, idx, MG_GUIDE, cf, 0, omg, h->res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 1)) return 1;
     return czhip_internal::pair_probe(x0, o0, r, sz, idx, idx, MG_GUIDE, (REAL)6, 0) ? 2 : 0;
   }
@@ -335,7 +381,13 @@ struct MgOps {
         std::swap(x0, o0);
       }
     } else {
-      for (int s = 0; s < 4; s++) czhip_rbsor_async(x0, r, sz, idx, MG_GUIDE, cf, ofst, s & 1, omg, h->res, 0, nullptr);
+      // (Neumann faces: the ghost of a cell is read by that cell alone, so one mirror after every colour sweep serves the next one; the
+      // prolongation moved the iterate to an array whose face layers are stale)
+      if (h->nm && !zero) mirror(x0);
+      for (int s = 0; s < 4; s++) {
+        czhip_rbsor_async(x0, r, sz, idx, MG_GUIDE, cf, ofst, s & 1, omg, h->res, 0, nullptr);
+        if (h->nm) mirror(x0);
+      }
     }
   }
   void rb_pair(int l, bool zero, bool post) {
@@ -359,7 +411,10 @@ struct MgOps {
     must(czhip_internal::mg_smooth_async(zero ? nullptr : h->x[l], h->t[l], h->b[l], h->lev[l], omg));
     must(czhip_internal::mg_smooth_async(h->t[l], h->x[l], h->b[l], h->lev[l], omg));
   }
-  void restrict_down(int l) { must(czhip_internal::mg_restrict_async(h->b[l + 1], h->lev[l + 1], x(l), l ? h->b[l] : r, nullptr, h->lev[l])); }
+  void restrict_down(int l) {
+    if (l == 0 && h->nm && !h->rb) mirror(x0);  // (mgrb: mirrored after its last colour sweep)
+    must(czhip_internal::mg_restrict_async(h->b[l + 1], h->lev[l + 1], x(l), l ? h->b[l] : r, nullptr, h->lev[l]));
+  }
   void prolong_up(int l) {
     must(czhip_internal::mg_prolong_async(l ? h->x[l] : o0, x(l), h->x[l + 1], h->lev[l + 1], h->lev[l]));
     if (l == 0) std::swap(x0, o0);

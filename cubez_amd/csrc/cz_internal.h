@@ -148,6 +148,7 @@ struct MgdLevel {
   int level;
   int n0[3], o[3], gn[3];
   int dense;
+  int nm;  // zero-flux (Neumann) faces of the global box, bit f = X-, X+, Y-, Y+, Z-, Z+: the diagonal of levels >= 1
 };
 // the launches of the level kernels; 0 = refused, nothing launched
 int mg_smooth_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const MgdLevel& L, CZ_REAL omg);  // u = nullptr: from zero
@@ -177,6 +178,7 @@ struct cz_mg {
   double* res = nullptr;        // the sums the level-0 sweeps write (unused)
   int tail_from = 0;            // first level run by mg_tail_k (nlev: none)
   int rb = 0;                   // the smoother: 0 relaxed Jacobi (mg), 1 symmetric red-black (mgrb; t stays unallocated)
+  int nm = 0;                   // zero-flux (Neumann) faces, bit f of the six (czhip_mg_set_neumann): level 0 mirrors, levels >= 1 take the masked diagonal
   int zero4 = 0;                // mgrb, level 0: the two iterations from zero as one two-iteration pass over a cleared array (CZ_MGRB_ZERO4)
 };
 

@@ -386,6 +386,37 @@ __global__ void bc_jface_k(REAL* p, int ix, int kx, int jface, int g, int nkp, i
   p[(size_t)(k + g - 1) + (size_t)(i + g - 1) * nkp + (size_t)(jface + g - 1) * nkp * nip] = (REAL)0;
 }
 
+// Zero-flux (Neumann) faces: the face layer of a physical face is the mirror of the first inner layer, p(1, j, k) = p(2, j, k)
+// on a - side and p(size, j, k) = p(size-1, j, k) on a + side, j and k over the inner box (edges and corners are neither read by a 7-point
+// kernel nor written here).  One launch fills every face listed: blockIdx.y picks the face (0 .. 5: X-, X+, Y-, Y+, Z-, Z+), one wave per row.
+// X and Y faces copy k-rows with the lanes along k; a Z face has one element per k-row, so its lanes run along i.  Padded 0-based indices.
+struct MirrorFaces {
+  int nkp, nip;
+  int ii0, ii1, jj0, jj1, kk0, kk1;  // the inner box (inclusive)
+  int n, face[6];                    // the faces to fill
+};
+__global__ void __launch_bounds__(256) mirror_faces_k(REAL* p, MirrorFaces m) {
+  const int f = m.face[blockIdx.y], d = f >> 1, plus = f & 1;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const long long si = m.nkp, sj = (long long)m.nkp * m.nip;
+  if (d == 0) {  // row = j; from layer ii0 (ii1) to ii0 - 1 (ii1 + 1)
+    const int jj = m.jj0 + row, is = plus ? m.ii1 : m.ii0;
+    if (jj > m.jj1) return;
+    const long long src = jj * sj + is * si, dst = src + (plus ? si : -si);
+    for (int kk = m.kk0 + lane; kk <= m.kk1; kk += 64) p[dst + kk] = p[src + kk];
+  } else if (d == 1) {  // row = i
+    const int ii = m.ii0 + row, js = plus ? m.jj1 : m.jj0;
+    if (ii > m.ii1) return;
+    const long long src = js * sj + ii * si, dst = src + (plus ? sj : -sj);
+    for (int kk = m.kk0 + lane; kk <= m.kk1; kk += 64) p[dst + kk] = p[src + kk];
+  } else {  // row = j, lanes along i
+    const int jj = m.jj0 + row, ks = plus ? m.kk1 : m.kk0;
+    if (jj > m.jj1) return;
+    const long long src = jj * sj + ks, dst = src + (plus ? 1 : -1);
+    for (int ii = m.ii0 + lane; ii <= m.ii1; ii += 64) p[dst + ii * si] = p[src + ii * si];
+  }
+}
+
 // copy every element OUTSIDE the inner box (guide cells, Dirichlet faces) from src to dst: one wave per k-row.
 // Used to give the ping-pong partner buffer of a Jacobi solve the same boundary data as the solution array.
 __global__ void __launch_bounds__(256)

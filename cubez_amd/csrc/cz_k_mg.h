@@ -21,6 +21,7 @@ struct MgLev {
   int ni, nj, nk;      // points of the level per direction
   int l;               // level
   int n0i, n0j, n0k;   // level-0 points per direction (the extents E)
+  int nm;              // zero-flux (Neumann) physical faces of the box, bit f = face X-, X+, Y-, Y+, Z-, Z+; level 0: always 0
 };
 
 // global index of a level array's local point (0, 0, 0): zero on a single domain, the brick's first owned point of the level in the
@@ -40,10 +41,21 @@ __device__ __forceinline__ int mg_ext(int I, int l, int n0) {
 struct MgW {
   REAL wx, wy, wz, d;
 };
+// the links of global point I in one direction that exist: 2, less the one across a Neumann face (nm: bit 0 the - face, bit 1 the + face) at
+// the level's first / last point -- there the Galerkin operator has no link, the correction being zero outside the box either way
+__device__ __forceinline__ int mg_links(int I, int l, int n0, int nm) {
+  return 2 - ((nm & 1) && I == 0 ? 1 : 0) - ((nm & 2) && ((I + 1) << l) >= n0 ? 1 : 0);
+}
+// (I, J, K): the GLOBAL index.  NM: the level has Neumann faces (L.nm != 0), D = Wx cx + Wy cy + Wz cz; else 2 (Wx + Wy + Wz), which is the
+// same integer for a mask of zero.  A template parameter, chosen by the launcher from L.nm, as DIST is: the instantiations without a mask are
+// the text and the code from before there was one (the one-workgroup tail measured 2-3 us slower with the test inside, profiles/r16/neumann.txt)
+template <bool NM>
 __device__ __forceinline__ MgW mg_weights(const MgLev& L, int I, int J, int K) {
   const int ex = mg_ext(I, L.l, L.n0i), ey = mg_ext(J, L.l, L.n0j), ez = mg_ext(K, L.l, L.n0k);
   const int wx = ey * ez, wy = ex * ez, wz = ex * ey;
-  return MgW{(REAL)wx, (REAL)wy, (REAL)wz, (REAL)(2 * (wx + wy + wz))};
+  const int d = NM ? wx * mg_links(I, L.l, L.n0i, L.nm) + wy * mg_links(J, L.l, L.n0j, L.nm >> 2) + wz * mg_links(K, L.l, L.n0k, L.nm >> 4)
+                   : 2 * (wx + wy + wz);
+  return MgW{(REAL)wx, (REAL)wy, (REAL)wz, (REAL)d};
 }
 
 // the six weighted neighbours, in the reference's c1 .. c6 order; ZERO: u is identically zero (literal zeros, the same arithmetic)
@@ -58,9 +70,9 @@ __device__ __forceinline__ REAL mg_ss(const REAL* u, const MgLev& L, const MgW& 
 
 // one relaxed Jacobi sweep at a point (cz_solver.f90:334-351 with the level's weights): pn = pp + ((ss - bb)/D - pp) omg, IEEE division
 // (ZPP: the point's own value is a literal zero although its neighbours are read -- the second colour of a red-black iteration from zero)
-template <bool ZERO, bool ZPP = ZERO>
+template <bool NM, bool ZERO, bool ZPP = ZERO>
 __device__ __forceinline__ REAL mg_sweep_pt(const REAL* u, const REAL* b, const MgLev& L, int I, int J, int K, REAL omg, MgG o = MgG{0, 0, 0}) {
-  const MgW w = mg_weights(L, I + o.i, J + o.j, K + o.k);
+  const MgW w = mg_weights<NM>(L, I + o.i, J + o.j, K + o.k);
   const long long p = mg_at(L, I, J, K);
   const REAL pp = ZPP ? (REAL)0 : u[p];
   const REAL ss = mg_ss<ZERO>(u, L, w, p);
@@ -69,8 +81,9 @@ __device__ __forceinline__ REAL mg_sweep_pt(const REAL* u, const REAL* b, const 
 }
 
 // residual at a point, written like blas_calc_rk_ (cz_blas.f90:705-711): b - (ss - D x)
+template <bool NM>
 __device__ __forceinline__ REAL mg_res_pt(const REAL* x, const REAL* b, const MgLev& L, int I, int J, int K, MgG o = MgG{0, 0, 0}) {
-  const MgW w = mg_weights(L, I + o.i, J + o.j, K + o.k);
+  const MgW w = mg_weights<NM>(L, I + o.i, J + o.j, K + o.k);
   const long long p = mg_at(L, I, J, K);
   const REAL ss = mg_ss<false>(x, L, w, p);
   return b[p] - (ss - w.d * x[p]);
@@ -97,10 +110,11 @@ __device__ __forceinline__ REAL mg_tree(bool hi, bool hj, bool hk, R res) {
   return hj ? t[0] + t[1] : t[0];
 }
 
+template <bool NM>
 __device__ __forceinline__ REAL mg_restrict_pt(const REAL* x, const REAL* b, const MgLev& F, int I, int J, int K) {
   const int i0 = 2 * I, j0 = 2 * J, k0 = 2 * K;
   const bool hi = i0 + 1 < F.ni, hj = j0 + 1 < F.nj, hk = k0 + 1 < F.nk;
-  return mg_tree(hi, hj, hk, [&](int ib, int jb, int kb) { return mg_res_pt(x, b, F, i0 + ib, j0 + jb, k0 + kb); });
+  return mg_tree(hi, hj, hk, [&](int ib, int jb, int kb) { return mg_res_pt<NM>(x, b, F, i0 + ib, j0 + jb, k0 + kb); });
 }
 
 // u = x + R(alpha xc(parent)), alpha = R(1.8): one rounding per operation (no contraction: the build has -ffp-contract=off)
@@ -122,11 +136,11 @@ struct MgDLev {
   int gni, gnj, gnk;
 };
 
-template <bool ZERO>
+template <bool ZERO, bool NM>
 __global__ void __launch_bounds__(256) mg_smooth_k(const REAL* __restrict__ u, REAL* __restrict__ w, const REAL* __restrict__ b, MgDLev D, REAL omg) {
   const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
   if (K >= D.L.nk || I >= D.L.ni) return;
-  w[mg_at(D.L, I, J, K)] = mg_sweep_pt<ZERO>(u, b, D.L, I, J, K, omg, D.o);
+  w[mg_at(D.L, I, J, K)] = mg_sweep_pt<NM, ZERO>(u, b, D.L, I, J, K, omg, D.o);
 }
 
 // ---- pcg ... mgrb: one colour sweep of a level >= 1, IN PLACE.  The colour of a point is (I + J + K) & 1; the points of
@@ -134,24 +148,24 @@ __global__ void __launch_bounds__(256) mg_smooth_k(const REAL* __restrict__ u, R
 // thread kk of row (I, J) owns K = 2 kk + ((I + J + c) & 1).  A workgroup is (64, 4) with one row per wave, so that offset is wave-uniform and
 // the colour c a launch argument: no lane selects operands.  Z: 0 = from the iterate; 1 = the first colour of an iteration from zero (x is not
 // read); 2 = its second colour (reads the freshly written colour, its own value is a literal zero).  The same bits as a sweep from a cleared x.
-template <int Z>
+template <int Z, bool NM>
 __device__ __forceinline__ REAL mg_rb_pt(const REAL* x, const REAL* b, const MgLev& L, int I, int J, int K, REAL omg) {
-  return mg_sweep_pt<Z == 1, Z != 0>(x, b, L, I, J, K, omg);
+  return mg_sweep_pt<NM, Z == 1, Z != 0>(x, b, L, I, J, K, omg);
 }
 
-template <int Z>
+template <int Z, bool NM>
 __global__ void __launch_bounds__(256) mg_rb_k(REAL* x, const REAL* __restrict__ b, MgLev L, REAL omg, int c) {
   const int I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
   const int K = 2 * (blockIdx.x * 64 + threadIdx.x) + ((I + J + c) & 1);
   if (K >= L.nk || I >= L.ni) return;
-  x[mg_at(L, I, J, K)] = mg_rb_pt<Z>(x, b, L, I, J, K, omg);
+  x[mg_at(L, I, J, K)] = mg_rb_pt<Z, NM>(x, b, L, I, J, K, omg);
 }
 
 // bc (owned coarse points) = the children's residual tree; owned children computed here, children on the + neighbours (the brick's
 // ghost layer) read from rt after its exchange.  C.L may be a dense block (no shell): the gathered level's send buffer.  DIST = false: the
 // domain owns the whole level (offsets 0, global extents = the local ones, rt not read) -- the same text with those constants folded in,
 // kept as an instantiation of its own because the FP32 launch measured 1-2 % slower without it (profiles/r11/mg_one_cycle.txt)
-template <bool DIST>
+template <bool DIST, bool NM>
 __global__ void __launch_bounds__(256) mg_restrict_k(REAL* __restrict__ bc, const REAL* __restrict__ x, const REAL* __restrict__ b, const REAL* __restrict__ rt,
                                                      MgDLev F, MgDLev C) {
   const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
@@ -164,7 +178,7 @@ __global__ void __launch_bounds__(256) mg_restrict_k(REAL* __restrict__ bc, cons
   const int li = gi - fo.i, lj = gj - fo.j, lk = gk - fo.k;
   bc[mg_at(C.L, I, J, K)] = mg_tree(hi, hj, hk, [&](int ib, int jb, int kb) {
     const int ci = li + ib, cj = lj + jb, ck = lk + kb;
-    if (!DIST || (ci < F.L.ni && cj < F.L.nj && ck < F.L.nk)) return mg_res_pt(x, b, F.L, ci, cj, ck, fo);
+    if (!DIST || (ci < F.L.ni && cj < F.L.nj && ck < F.L.nk)) return mg_res_pt<NM>(x, b, F.L, ci, cj, ck, fo);
     return rt[mg_at(F.L, ci, cj, ck)];
   });
 }
@@ -179,6 +193,7 @@ __global__ void __launch_bounds__(256) mg_prolong_k(REAL* u, const REAL* x, cons
 
 // rt = the residual of the first owned layer on the rank-internal - faces (d = 0, 1, 2: I, J, K face; edges and corners belong to the
 // face of the lowest d among the internal ones).  grid: (64-wide blocks along the face's faster free direction, the slower one)
+template <bool NM>
 __global__ void __launch_bounds__(64) mgd_resface_k(REAL* __restrict__ rt, const REAL* __restrict__ x, const REAL* __restrict__ b, MgDLev D, int d,
                                                     int mi, int mj) {
   const int a = blockIdx.x * 64 + threadIdx.x, c = blockIdx.y;
@@ -188,7 +203,7 @@ __global__ void __launch_bounds__(64) mgd_resface_k(REAL* __restrict__ rt, const
   else K = 0, I = a, J = c;
   if (I >= D.L.ni || J >= D.L.nj || K >= D.L.nk) return;
   if ((d >= 1 && mi && I == 0) || (d == 2 && mj && J == 0)) return;  // written by the I (J) face launch
-  rt[mg_at(D.L, I, J, K)] = mg_res_pt(x, b, D.L, I, J, K, D.o);
+  rt[mg_at(D.L, I, J, K)] = mg_res_pt<NM>(x, b, D.L, I, J, K, D.o);
 }
 
 // one rank's dense block (ni, nj, nk; K fastest) into the gathered global array at global offset o: an exact copy
@@ -236,31 +251,31 @@ __device__ __forceinline__ void mg_each_colour(const MgLev& L, int c, F f) {
 
 // x <- two smoothing iterations of the level (zero: from zero); RB: red-black in place, backward (colours 1, 0) where post; else relaxed
 // Jacobi through t.  Ends with the workgroup in step
-template <bool RB>
+template <bool RB, bool NM>
 __device__ __forceinline__ void mg_tail_pair(const MgLev& L, const REAL* b, REAL* x, REAL* t, bool zero, bool post, REAL omg) {
   if (RB) {
     const int c0 = post ? 1 : 0;
     if (zero) {
-      mg_each_colour(L, c0, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<1>(x, b, L, I, J, K, omg); });
+      mg_each_colour(L, c0, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<1, NM>(x, b, L, I, J, K, omg); });
       __syncthreads();
-      mg_each_colour(L, 1 - c0, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<2>(x, b, L, I, J, K, omg); });
+      mg_each_colour(L, 1 - c0, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<2, NM>(x, b, L, I, J, K, omg); });
       __syncthreads();
     }
     for (int s = zero ? 2 : 0; s < 4; s++) {
-      mg_each_colour(L, (c0 + s) & 1, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<0>(x, b, L, I, J, K, omg); });
+      mg_each_colour(L, (c0 + s) & 1, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<0, NM>(x, b, L, I, J, K, omg); });
       __syncthreads();
     }
     return;
   }
-  if (zero) mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<true>(t, b, L, I, J, K, omg); });
-  else mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<false>(x, b, L, I, J, K, omg); });
+  if (zero) mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<NM, true>(t, b, L, I, J, K, omg); });
+  else mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<NM, false>(x, b, L, I, J, K, omg); });
   __syncthreads();
-  mg_each(L, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_sweep_pt<false>(t, b, L, I, J, K, omg); });
+  mg_each(L, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_sweep_pt<NM, false>(t, b, L, I, J, K, omg); });
   __syncthreads();
 }
 
 // RB: the cycle of pcg ... mgrb (its levels keep b and x only: T.len[m] apart, no t)
-template <bool RB>
+template <bool RB, bool NM>
 __global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ xg, const REAL* __restrict__ bg, MgTail T) {
   extern __shared__ __align__(16) unsigned char mg_lds_raw[];
   REAL* const lds = reinterpret_cast<REAL*>(mg_lds_raw);
@@ -276,16 +291,16 @@ __global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ 
   for (int m = 0; m + 1 < T.nlev; m++) {
     const MgLev& L = T.s[m];
     REAL *b = lds + T.off[m], *x = b + T.len[m], *t = x + T.len[m];
-    mg_tail_pair<RB>(L, b, x, t, true, false, omg);
+    mg_tail_pair<RB, NM>(L, b, x, t, true, false, omg);
     const MgLev& Cl = T.s[m + 1];
     REAL* bc = lds + T.off[m + 1];
-    mg_each(Cl, [&](int I, int J, int K) { bc[mg_at(Cl, I, J, K)] = mg_restrict_pt(x, b, L, I, J, K); });
+    mg_each(Cl, [&](int I, int J, int K) { bc[mg_at(Cl, I, J, K)] = mg_restrict_pt<NM>(x, b, L, I, J, K); });
     __syncthreads();
   }
   {  // the coarsest level: four pairs from zero, the last two post (mg_walk's order)
     const int m = T.nlev - 1;
     REAL *b = lds + T.off[m], *x = b + T.len[m], *t = x + T.len[m];
-    for (int s = 0; s < 4; s++) mg_tail_pair<RB>(T.s[m], b, x, t, s == 0, s >= 2, omg);
+    for (int s = 0; s < 4; s++) mg_tail_pair<RB, NM>(T.s[m], b, x, t, s == 0, s >= 2, omg);
   }
   // up: x += R(alpha x_c(parent)) in place, post-smoothing pair
   for (int m = T.nlev - 2; m >= 0; m--) {
@@ -298,7 +313,7 @@ __global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ 
       x[p] = mg_prolong_pt(x, xc, L, Cl, I, J, K);
     });
     __syncthreads();
-    mg_tail_pair<RB>(L, b, x, t, false, true, omg);
+    mg_tail_pair<RB, NM>(L, b, x, t, false, true, omg);
   }
   {
     const REAL* x0 = lds + T.off[0] + T.len[0];

@@ -1415,6 +1415,33 @@ void bc_async(const int* sz, int g, REAL* p, REAL dh, const REAL* org, const int
 #include "cz_h_field.h"
 }  // namespace czhip_internal
 
+extern "C" {
+// the mirror of the first inner layer into the face layer of every face flagged in faces[6] that is a physical face of the brick (idx starts at 2
+// / ends at size - 1 there: the inner-range convention of a brick), in one launch (mirror_faces_k); 0 = refused, nothing launched
+int czhip_mirror_faces_async(CZ_REAL* p, const int* sz, const int* idx, int g, const int* faces) {
+  ensure_init();
+  if (!p || !sz || !idx || !faces) return 0;
+  const Box b = make_box(sz, idx, g);
+  if (b.empty) return 1;
+  MirrorFaces m;
+  m.nkp = b.nkp, m.nip = b.nip, m.ii0 = b.ii0, m.ii1 = b.ii1, m.jj0 = b.jj0, m.jj1 = b.jj1, m.kk0 = b.kk0, m.kk1 = b.kk1, m.n = 0;
+  int rows = 0;
+  for (int f = 0; f < 6; f++) {
+    const int d = f >> 1;
+    const bool physical = (f & 1) ? idx[2 * d + 1] == sz[d] - 1 : idx[2 * d] == 2;
+    if (!faces[f] || !physical) continue;
+    m.face[m.n++] = f;
+    rows = std::max(rows, d == 1 ? b.ii1 - b.ii0 + 1 : b.jj1 - b.jj0 + 1);
+  }
+  for (int q = m.n; q < 6; q++) m.face[q] = 0;
+  if (!m.n) return 1;
+  ScopedTimer tm(LBL_BC_MIRROR);
+  hipLaunchKernelGGL(mirror_faces_k, dim3((unsigned)((rows + 3) / 4), (unsigned)m.n), dim3(256), 0, ctx.stream, p, m);
+  HIP_CHECK(hipGetLastError());
+  return 1;
+}
+}  // extern "C"
+
 // ------------------------------------------------------------------------------------------------------------
 // PCG (beyond the reference; CZ::PCG, DESIGN.md "PCG"): the update pass, the direction + SpMV pass and the scalars
 // ------------------------------------------------------------------------------------------------------------

@@ -38,6 +38,8 @@ struct MgDist {
   std::vector<int> bo, bc;         // every rank's level-G block: global offset and points, 3 per rank
   double* res = nullptr;           // the sums the level-0 sweeps write (unused)
   int exchanges = 0;               // halo exchanges + all-gathers of the last cycle
+  int faces[6] = {0, 0, 0, 0, 0, 0};  // zero-flux (Neumann) faces of the global box (mgd_set_neumann)
+  bool masked = false;
 };
 
 namespace {
@@ -162,6 +164,21 @@ void mgd_destroy(MgDist* h) {
   delete h;
 }
 
+// the global mask, the same on every rank: every distributed level, the gathered block and the hierarchy of the gathered levels learn it
+int mgd_set_neumann(MgDist* h, const int* faces) {
+  if (!h || !faces) return 0;
+  int nm = 0;
+  for (int f = 0; f < 6; f++) nm |= faces[f] ? 1 << f : 0;
+  if (nm == 63 || (h->g && !czhip_mg_set_neumann(h->g, faces))) return 0;
+  for (int f = 0; f < 6; f++) h->faces[f] = faces[f] ? 1 : 0;
+  h->masked = nm != 0;
+  for (int l = 0; l < MG_MAXLEV; l++) h->lev[l].nm = nm;
+  h->blk.nm = nm;
+  const MgdLevel& F = h->lev[0];
+  HIP_CHECK(hipMemsetAsync(h->tmp0, 0, (size_t)(F.sz[0] + 2 * GUIDE) * (F.sz[1] + 2 * GUIDE) * (F.sz[2] + 2 * GUIDE) * sizeof(REAL_TYPE), stream()));
+  return 1;
+}
+
 int mgd_levels(const MgDist* h) { return h ? h->nlev : 0; }
 int mgd_gather_level(const MgDist* h) { return h ? h->G : 0; }
 int mgd_exchanges(const MgDist* h) { return h ? h->exchanges : 0; }
@@ -177,9 +194,11 @@ struct MgdOps {
 
   REAL_TYPE* x(int l) { return l ? h->x[l] : x0; }
   const REAL_TYPE* b(int l) { return l ? h->b[l] : r; }
+  // (level 0 with Neumann faces: the mirror of the brick's physical faces stands beside the exchange; it is not one)
   void halo(int l, REAL_TYPE* X) {
     fatal_if(!comm_halo(h->comm[l], X, nullptr, stream()), "face exchange");
     h->exchanges++;
+    if (l == 0 && h->masked) fatal_if(!czhip_mirror_faces_async(X, h->lev[0].sz, h->lev[0].idx, GUIDE, h->faces), "mirror of the Neumann faces");
   }
   void halo_full(int l, REAL_TYPE* X) {
     fatal_if(!comm_halo_full(h->comm[l], X, stream()), "face + edge + corner exchange");

@@ -43,6 +43,7 @@ class CZ:
         lib.cz_get_residual.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_double, C.POINTER(C.c_double)]
         lib.cz_add_field.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_double]
         lib.cz_set_eps.argtypes = [C.c_void_p, C.c_double]
+        lib.cz_set_neumann.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         lib.cz_set_itr_max.argtypes = [C.c_void_p, C.c_int]
         self.device = int(device)
         if lib.czhip_init(int(device)) != 0:
@@ -197,6 +198,16 @@ class CZ:
         if self.lib.cz_set_eps(self.h, float(eps)) != 1:
             raise ValueError(f"set_eps({eps}): refused")
 
+    def set_neumann(self, faces):
+        """zero-flux (Neumann) faces for pcg: six flags in the order X-, X+, Y-, Y+, Z-, Z+ of the global box, at least one of them zero (a
+        Dirichlet face); after setup, collective with the same mask on every rank.  The face layers of the field there hold the mirror of the
+        first inner layer from now on (cz_set_neumann of include/cz_hip.h)"""
+        f = [1 if v else 0 for v in faces]
+        if len(f) != 6:
+            raise ValueError(f"set_neumann: six flags (X-, X+, Y-, Y+, Z-, Z+), not {len(f)}")
+        if self.lib.cz_set_neumann(self.h, (C.c_int * 6)(*f)) != 1:
+            raise ValueError(f"set_neumann({f}): refused (see stderr)")
+
     def set_itr_max(self, n: int):
         if self.lib.cz_set_itr_max(self.h, int(n)) != 1:
             raise ValueError(f"set_itr_max({n}): refused")
@@ -215,7 +226,7 @@ class CZ:
     def info(self) -> dict:
         """what a (multi-GPU) run decided (cz_info of include/cz_hip.h)"""
         keys = ("ranks", "fused_pass", "shell_slabs", "overlap", "lagged_reduce", "rccl_ranks", "comm_cus", "pass_kind", "exchange_depth", "buffers", "bicg_fused", "rb4_passes",
-                "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother", "field_form")
+                "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother", "field_form", "neumann")
         return {k: self.lib.cz_info(self.h, i) for i, k in enumerate(keys)}
 
     def config_in_force(self) -> dict:

@@ -21,9 +21,10 @@ def scale_of(sumsq: float, npts: int) -> float:
 
 
 class Refined:
-    def __init__(self, gsz, inner=("pcg", 1000, 1.2, "mgrb"), division=None, device=-1):
+    def __init__(self, gsz, inner=("pcg", 1000, 1.2, "mgrb"), division=None, device=-1, neumann=None):
         """gsz: the global box; inner: the FP32 solver as on the command line (solver, ItrMax, coefficient[, preconditioner]); division: as on the
-        command line (every rank of a decomposed run makes its own Refined after joining both libraries' communicators)"""
+        command line (every rank of a decomposed run makes its own Refined after joining both libraries' communicators); neumann: the six
+        flags of CZ.set_neumann, set on both libraries (the inner solver must then be pcg)"""
         import torch  # (only here: the package imports without it)
         self.torch = torch
         div = list(division) if division else []
@@ -33,6 +34,9 @@ class Refined:
             raise RuntimeError("Refined: the FP64 set-up failed")
         if self.lo.setup(list(gsz) + list(inner) + div) != 1:
             raise RuntimeError(f"Refined: the FP32 set-up of {inner} failed")
+        if neumann is not None:
+            self.hi.set_neumann(neumann)
+            self.lo.set_neumann(neumann)
         self.shape = tuple(self.hi.local()["size"])
         if tuple(self.lo.local()["size"]) != self.shape:
             raise RuntimeError("Refined: the two libraries cut the domain differently")

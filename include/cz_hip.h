@@ -382,6 +382,17 @@ int czhip_mg_rb_async(CZ_REAL* x, const CZ_REAL* b, const int* sz, const int* id
 int czhip_mg_tail_rb_async(CZ_REAL* x, const CZ_REAL* b, const int* sz, const int* idx, int g, int level, const int* n0, CZ_REAL omg);
 cz_mg* czhip_mg_create_rb(const int* sz, const int* idx, int g, const CZ_REAL* cf);
 int czhip_mg_kind(const cz_mg* h);
+/* Zero-flux (Neumann) faces.  faces[6]: X-, X+, Y-, Y+, Z-, Z+, non-zero = Neumann.
+ * czhip_mirror_faces_async: on every flagged face that is a physical face of the brick (idx starts at 2 / ends at size - 1 in that direction,
+ *   the inner-range convention of a brick; a rank-internal face is never touched) the face layer becomes the mirror of the first inner
+ *   layer, p(1, j, k) = p(2, j, k) resp. p(size, j, k) = p(size-1, j, k), j and k over idx; edges, corners and every other cell keep their
+ *   bytes.  One launch (label bc_mirror).  With that layer the kernels' own statement is the zero-flux operator at the cells next to it.
+ * czhip_mg_set_neumann: the hierarchy's cycles from now on take these faces as zero-flux faces: level 0 runs single sweeps / colour sweeps with
+ *   the mirror before each one that reads its input, levels >= 1 take D = Wx cx + Wy cy + Wz cz, c = 2 less one per Neumann face the point
+ *   lies on (the correction is zero outside the box, the absent link needs nothing else).  All zero: the cycle of czhip_mg_create, bit for
+ *   bit.  Either returns 1, or 0 when refused (a NULL pointer; all six faces). */
+int czhip_mirror_faces_async(CZ_REAL* p, const int* sz, const int* idx, int g, const int* faces);
+int czhip_mg_set_neumann(cz_mg* h, const int* faces);
 
 /* Convergence bookkeeping on the device (cz_Poisson.cpp:67-77): res = sqrt(res_dev[0]*res_normal);
  * hist_dev[itr] = res; if (res < eps && !*flag) { *flag = 1; conv_itr_dev[0] = itr; }.  No-op when
@@ -451,6 +462,18 @@ int cz_get_field(cz_handle*, CZ_REAL* dst, const long long* stride, int on_devic
  * a scale that is not finite and positive (as given and as CZ_REAL), a handle set up with a _maf solver (its operator is not the unit one). */
 int cz_get_residual(cz_handle*, void* dst, int dst_real_bytes, const long long* stride, int on_device, void* done_stream, double scale, double* sumsq);
 int cz_add_field(cz_handle*, const void* src, int src_real_bytes, const long long* stride, int on_device, void* ready_stream, double scale);
+/* Zero-flux (Neumann) faces for pcg: faces[6], order X-, X+, Y-, Y+, Z-, Z+ of the GLOBAL box (the order of nID), non-zero =
+ * the face is a zero-flux face, zero = a Dirichlet face as before; at least one face must stay Dirichlet.  Called after cz_setup; collective,
+ * with the same mask on every rank.  On a Neumann face the face layer of the field is not data but the mirror of the first inner layer
+ * (p(1, j, k) = p(2, j, k), p(size, j, k) = p(size-1, j, k) over the cells every sweep updates), which makes the stated system
+ * `sum of neighbours - 6 p = b` the zero-flux operator (5 neighbours, -5 p) at the cells next to it; a non-zero flux folds into b.  On return
+ * of every call that writes P (this one, cz_set_field, cz_add_field, cz_solve) those layers hold the mirror: values passed there are
+ * ignored, cz_get_field returns the mirror, cz_get_residual mirrors before its pass.  Returns 1, or 0 with one line on stderr and nothing
+ * changed: before cz_setup, all six faces, a _maf handle.  Accepted on a handle of any other solver, but with a non-zero mask cz_solve,
+ * cz_sweeps and cz_evaluate of a solver other than pcg (none | jacobi | mg | mgrb) return 0 with one line and leave P alone.  All zero: the
+ * Dirichlet problem again (the face layers keep their last values).  cz_setup (and with it cz_evaluate, once it has accepted the solver)
+ * clears the mask: a set-up starts with Dirichlet faces. */
+int cz_set_neumann(cz_handle*, const int* faces);
 int cz_set_eps(cz_handle*, double eps);
 int cz_set_itr_max(cz_handle*, int n);
 int cz_sweeps(cz_handle*, int n);              /* bench leg: n more iterations of the selected stationary solver with the
@@ -477,7 +500,8 @@ double cz_last_solve_seconds(const cz_handle*);
  * of the last PCG solve with mg; 17 the gather level G of a decomposed pcg ... mg (levels >= G run on every rank from an all-gathered copy;
  * 0 on a single domain or where level 0 is the coarsest); 18 halo exchanges and all-gathers of the last V-cycle of a decomposed pcg ... mg;
  * 19 the smoother of the multigrid preconditioner (0 none, 1 relaxed Jacobi: mg, 2 symmetric red-black: mgrb; 15 and 16 count for both);
- * 20 the kernel form of the last cz_set_rhs / cz_set_field / cz_get_field (1 k rows, 2 tile transpose, 3 generic; CZ_FIELD_FORM=3 forces 3). */
+ * 20 the kernel form of the last cz_set_rhs / cz_set_field / cz_get_field (1 k rows, 2 tile transpose, 3 generic; CZ_FIELD_FORM=3 forces 3);
+ * 21 the mask of cz_set_neumann, bit f = face f of X-, X+, Y-, Y+, Z-, Z+ (0: none). */
 int cz_info(const cz_handle*, int what);
 /* The driver's and its communicator's own copies of their switches, as name=value, one per line: overlap, lag_reduce, comm_cus (as asked for;
  * 0 on a single domain), comm_cus_reserved (in force after set-up), bicg_fuse, bicg_devsc, bicg_alias, cg_fuse, mg_tail, mg_gather, mgrb_zero4,
