@@ -50,7 +50,7 @@ inline const CzVarDef* cz_var_defs() {
       {"CZ_BICG_FUSE", "1", "BiCGSTAB: the vector updates that make a preconditioner solve's right-hand side are made by its first pass"},
       {"CZ_BICG_DEVSC", "1", "BiCGSTAB: alpha and omega made on the device behind their dot products (one host wait per iteration)"},
       {"CZ_BICG_ALIAS", "1", "BiCGSTAB without a preconditioner: the solves read p and s themselves instead of cleared-and-copied p_, s_"},
-      {"CZ_CG_FUSE", "1", "PCG: x, r and r.r in one pass (cg_update_k); single domain: the direction update made inside the SpMV pass (0 = unfused)"},
+      {"CZ_CG_FUSE", "1", "PCG: x, r and r.r in one pass (cg_update_k); single domain: the direction update made inside the SpMV pass (0 = unfused); under a Neumann mask only the update, and in a closed box (cz_set_closed_box) not even that: its update is always cg_update_k's closed form"},
       {"CZ_MG_TAIL", "1", "PCG with mg: the coarse levels that fit one workgroup's LDS in one launch (mg_tail_k; 0 = level by level, same bits)"},
       {"CZ_MG_GATHER", "32768", "PCG with mg, decomposed runs: the first coarse level of at most this many global points is all-gathered and run on every rank (same bits for any value)"},
       {"CZ_MGRB_ZERO4", "1", "PCG with mgrb: level 0's two iterations from zero as one two-iteration pass (rb4_k) over a cleared array where that pass takes the box (0 = the from-zero pass and a one-iteration pass; same bits)"},

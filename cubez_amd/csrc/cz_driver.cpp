@@ -52,11 +52,11 @@ constexpr int POLL_SLOTS = 4;
 
 CZ::CZ() {
   czhip_init(-1);
-  HIP_CHECK(hipMalloc(&d_res, 16 * sizeof(double)));
-  HIP_CHECK(hipMemset(d_res, 0, 16 * sizeof(double)));
+  HIP_CHECK(hipMalloc(&d_res, 24 * sizeof(double)));
+  HIP_CHECK(hipMemset(d_res, 0, 24 * sizeof(double)));
   HIP_CHECK(hipMalloc(&d_flag, (2 + 2 * POLL_SLOTS) * sizeof(int)));
   HIP_CHECK(hipMemset(d_flag, 0, (2 + 2 * POLL_SLOTS) * sizeof(int)));
-  HIP_CHECK(hipHostMalloc(&h_scal, 16 * sizeof(double), hipHostMallocDefault));
+  HIP_CHECK(hipHostMalloc(&h_scal, 24 * sizeof(double), hipHostMallocDefault));
   HIP_CHECK(hipHostMalloc(&h_flag, 2 * POLL_SLOTS * sizeof(int), hipHostMallocDefault));
   cfg = CzConfig::from_env();  // the environment as this driver was created in (cz_config.h); nothing below asks it again
   overlap = cfg.num(CZV_OVERLAP, overlap);
@@ -215,6 +215,9 @@ int CZ::Setup(int argc, char** argv) {
   // a set-up starts with Dirichlet faces: the hierarchy it builds knows no mask (cz_set_neumann comes after cz_setup)
   std::fill(neumann, neumann + 6, 0);
   neumann_mask = 0;
+  closed_box = 0;
+  closed_m[0] = closed_m[1] = closed_m[2] = 0.0;
+  closed_m0_on_device = false;
 
   comm_world(&myRank, &numProc);  // rank/size from the launcher environment (replaces MPI_Comm_rank/size, :44-50)
 
@@ -277,6 +280,7 @@ int CZ::Setup(int argc, char** argv) {
   plan_overlap();
   if (!Comm_SUM_1(&sum_r)) return 0;
   res_normal = 1.0 / (double)sum_r;
+  g_npts = (double)sum_r;
 
   // :239-288 (only the arrays the hot path touches)
   RHS = czhip_alloc_s3d(size);
@@ -1379,6 +1383,9 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   double* const d_pq = d_res + 3;                 // (the unfused SpMV writes q.q to d_res[4])
   double* const d_rho = pc ? d_res + 2 : d_rr;    // none: rho is the r.r of the previous update
   REAL_TYPE* const z = pc ? cg_z : cg_r;
+  // the closed box: sc[4] the lagged mean of the residual, sc[5] / sc[6] the means of steps 1 and 3 as cz_closed_mean reports them
+  const bool closed = closed_box != 0;
+  double* const d_cl = d_res + 20;                // (project's two sums)
   res = 0.0;
   cg_fused = 0;
   mg_cycles = 0;
@@ -1386,12 +1393,23 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   mirror(X);
   calc_rk_async(cg_r, X, B, size, innerFidx, gc, cf);
   flop += 14.0 * n;
+  if (closed) {
+    // step 1: the initial residual into the range of the operator; the pass that writes r' returns sum r' (the first lagged mean, sc[4])
+    // and sum r'^2 (none: the one r.r that no update made)
+    if (!project(cg_r, sc + 4, sc + 5) || !Comm_SUM_dev(d_cl, 2)) return 0;
+    mean_scalar_async(d_cl, g_npts, sc + 4, nullptr);
+    flop += 4.0 * n;
+  }
   if (!Comm_S(cg_r)) return 0;
   REAL_TYPE rho = (REAL_TYPE)0;
   if (!pc) {  // the one r.r that no update made
-    dot1_async(cg_r, size, innerFidx, gc, d_rr);
-    flop += 2.0 * n;
-    if (!Comm_SUM_dev(d_rr, 1)) return 0;
+    if (closed) {
+      HIP_CHECK(hipMemcpyAsync(d_rr, d_cl + 1, sizeof(double), hipMemcpyDeviceToDevice, st));
+    } else {
+      dot1_async(cg_r, size, innerFidx, gc, d_rr);
+      flop += 2.0 * n;
+      if (!Comm_SUM_dev(d_rr, 1)) return 0;
+    }
     HIP_CHECK(hipMemcpyAsync(h_scal + 5, d_rr, sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     rho = (REAL_TYPE)h_scal[5];
@@ -1448,7 +1466,10 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
     if (!Comm_SUM_dev(d_pq, 1)) return 0;
     cg_scalar_async(1, d_pq, 0, sc);  // alpha = rho / p.q
     REAL_TYPE* const p = cg_p[cur];
-    if (fuse) {
+    if (closed) {
+      // r = ((-alpha) q + r) - sc[4], sum r^2 and sum r side by side: one all-reduce, then the mean the next update removes
+      czhip_cg_update_closed_async(X, cg_r, p, cg_q, sc, size, innerFidx, gc, d_rr);
+    } else if (fuse) {
       czhip_cg_update_async(X, cg_r, p, cg_q, sc, size, innerFidx, gc, d_rr);
     } else {
       triad_async(X, p, X, (REAL_TYPE)0, size, innerFidx, gc, sc);
@@ -1456,7 +1477,8 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
       dot1_async(cg_r, size, innerFidx, gc, d_rr);
     }
     flop += 6.0 * n;
-    if (!Comm_SUM_dev(d_rr, 1)) return 0;
+    if (!Comm_SUM_dev(d_rr, closed ? 2 : 1)) return 0;
+    if (closed) mean_scalar_async(d_rr + 1, g_npts, sc + 4, nullptr);
     // the one wait of the iteration: r.r (and this iteration's rho)
     HIP_CHECK(hipMemcpyAsync(h_scal + 2, d_res + 2, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
@@ -1476,6 +1498,15 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
     if (!pc) rho = rr;
   }
   if (itr > ItrMax) itr = ItrMax;
+  if (closed) {
+    // step 3: the answer of zero mean (the sums read owned cells only; the exchange below carries the shifted values into the ghost layers)
+    if (!project(X, sc + 6, nullptr)) return 0;
+    flop += 3.0 * n;
+    HIP_CHECK(hipMemcpyAsync(h_scal + 16, sc + 5, 2 * sizeof(REAL_TYPE), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    const REAL_TYPE* hm = reinterpret_cast<const REAL_TYPE*>(h_scal + 16);
+    closed_m[1] = (double)hm[0], closed_m[2] = (double)hm[1];
+  }
   if (!Comm_S(X)) return 0;  // (the ghost layers of the result, as PBiCGSTAB leaves them)
   mirror(X);
   return itr;
@@ -1488,27 +1519,68 @@ void CZ::mirror(REAL_TYPE* X) {
   if (!czhip_mirror_faces_async(X, size, innerFidx, GUIDE, neumann)) cz_fatal(1, "czhip: the mirror of the Neumann faces was refused\n");
 }
 
-int CZ::SetNeumann(const int* faces) {
+int CZ::set_mask(const int* faces, int closed, const char* who) {
   auto refuse = [&](const char* why) {
-    fprintf(stderr, "cz_set_neumann: %s\n", why);
+    fprintf(stderr, "%s: %s\n", who, why);
     return 0;
   };
   if (!set_up) return refuse("no problem is set up (cz_setup first)");
   if (!faces) return refuse("NULL pointer");
   int nm = 0;
   for (int f = 0; f < 6; f++) nm |= faces[f] ? 1 << f : 0;
-  if (nm == 63) return refuse("at least one face must stay a Dirichlet face (the all-Neumann problem is singular)");
+  if (nm == 63 && !closed)
+    return refuse("at least one face must stay a Dirichlet face (the all-Neumann problem is singular: cz_set_closed_box keeps it solvable)");
   if (SW_maf) return refuse("the handle's operator is a MAF one, not the unit-coefficient operator");
   if ((mg && !czhip_mg_set_neumann(mg, faces)) || (mgd && !mgd_set_neumann(mgd, faces))) return refuse("the multigrid hierarchy refused the mask");
   for (int f = 0; f < 6; f++) neumann[f] = faces[f] ? 1 : 0;
   neumann_mask = nm;
+  closed_box = closed;
   // the work vectors whose face layers carried the mirrors of an earlier mask: zeros again, as the unmasked passes read them
   for (REAL_TYPE* a : {cg_z, cg_p[0], cg_p[1]})
     if (a) HIP_CHECK(hipMemsetAsync(a, 0, padded_cells() * sizeof(REAL_TYPE), stream()));
+  if (closed && !project_rhs()) return 0;
   mirror(P);
   wrk_shell_tag = 0;
   czhip_sync();
   return 1;
+}
+
+int CZ::SetNeumann(const int* faces) { return set_mask(faces, 0, "cz_set_neumann"); }
+
+// The closed box: all six faces zero-flux, the right-hand side kept compatible, pcg's residual kept in the range of the
+// operator and its answer of zero mean.  on = 0: the Dirichlet problem again (the right-hand side stays projected)
+int CZ::SetClosedBox(int on) {
+  const int faces[6] = {on ? 1 : 0, on ? 1 : 0, on ? 1 : 0, on ? 1 : 0, on ? 1 : 0, on ? 1 : 0};
+  return set_mask(faces, on ? 1 : 0, "cz_set_closed_box");
+}
+
+// A <- A - m over the inner box, m = (REAL)(sum A / npts) over the GLOBAL inner box: a pass that sums, one all-reduce, the mean on the device
+// (*m_dev, *keep_dev), a pass that subtracts and leaves this rank's sum A' and sum A'^2 in d_res[20..21] (the caller all-reduces what it uses)
+bool CZ::project(REAL_TYPE* A, REAL_TYPE* m_dev, REAL_TYPE* keep_dev) {
+  double* const d_cl = d_res + 20;
+  if (!czhip_shift_sums_async(A, nullptr, size, innerFidx, GUIDE, d_cl) || !Comm_SUM_dev(d_cl, 1)) return false;
+  mean_scalar_async(d_cl, g_npts, m_dev, keep_dev);
+  return czhip_shift_sums_async(A, m_dev, size, innerFidx, GUIDE, d_cl) != 0;
+}
+
+// (no host wait here: cz_set_rhs from a device array stays an event hand-over; the mean stays in sc[7] until cz_closed_mean asks for it)
+bool CZ::project_rhs() {
+  REAL_TYPE* const sc = reinterpret_cast<REAL_TYPE*>(d_res + 12);
+  if (!project(RHS, sc + 7, nullptr) || !Comm_S2(RHS)) return false;
+  closed_m0_on_device = true;
+  return true;
+}
+
+double CZ::ClosedMean(int which) {
+  if (which < 0 || which > 2) return std::nan("");
+  if (which == 0 && closed_m0_on_device) {
+    const REAL_TYPE* const sc = reinterpret_cast<const REAL_TYPE*>(d_res + 12);
+    HIP_CHECK(hipMemcpyAsync(h_scal + 18, sc + 7, sizeof(REAL_TYPE), hipMemcpyDeviceToHost, stream()));
+    HIP_CHECK(hipStreamSynchronize(stream()));
+    closed_m[0] = (double)*reinterpret_cast<const REAL_TYPE*>(h_scal + 18);
+    closed_m0_on_device = false;
+  }
+  return closed_m[which];
 }
 
 void CZ::Field(REAL_TYPE* host) const {
@@ -1606,7 +1678,11 @@ int CZ::FieldIO(int which, void* a, int abytes, const long long* stride, int on_
   if (!last_field_form) return refuse("no kernel form takes these strides");
   if (!to_user) {
     // the ghost layers as Setup fills them; WRK's copy of P's shell is stale
-    if (!Comm_S2(arr)) return 0;
+    if (which == 0 && op == FIO_IMPORT && closed_box) {  // (the closed box keeps the right-hand side compatible; its exchange included)
+      if (!project_rhs()) return 0;
+    } else if (!Comm_S2(arr)) {
+      return 0;
+    }
     if (which == 1) {  // (Neumann faces: what the caller passed there is not data)
       mirror(P);
       wrk_shell_tag = 0;
@@ -1881,6 +1957,8 @@ int cz_add_field(cz_handle* h, const void* src, int src_real_bytes, const long l
   return h ? h->cz.FieldIO(1, const_cast<void*>(src), src_real_bytes, stride, on_device, ready_stream, CZ::FIO_ADD, scale, nullptr, "cz_add_field") : 0;
 }
 int cz_set_neumann(cz_handle* h, const int* faces) { return h ? h->cz.SetNeumann(faces) : 0; }
+int cz_set_closed_box(cz_handle* h, int on) { return h ? h->cz.SetClosedBox(on) : 0; }
+double cz_closed_mean(cz_handle* h, int which) { return h ? h->cz.ClosedMean(which) : std::nan(""); }
 int cz_set_eps(cz_handle* h, double eps) {
   if (!h || !h->cz.set_up || !(eps > 0.0)) {
     fprintf(stderr, "cz_set_eps: %s\n", h && h->cz.set_up ? "the tolerance must be positive" : "no problem is set up (cz_setup first)");
@@ -1931,6 +2009,7 @@ int cz_info(const cz_handle* h, int what) {
     case 9: return c.last_plan.buffers;
     case 20: return c.last_field_form;
     case 21: return c.neumann_mask;
+    case 22: return c.closed_box;
     default: return -1;
   }
 }

@@ -83,6 +83,10 @@ class CZ {
   int last_lag = 0;              // the last stationary solve ran its all-reduce + test one pass behind (cz_info)
   int neumann[6] = {0, 0, 0, 0, 0, 0};  // zero-flux (Neumann) physical faces of the global box, X-, X+, Y-, Y+, Z-, Z+ (cz_set_neumann)
   int neumann_mask = 0;          // ... as bits (cz_info 21); non-zero: P's face layers there hold the mirror of the first inner layer
+  int closed_box = 0;            // the closed box (cz_set_closed_box, cz_info 22): mask 63 and the three projections of pcg
+  double closed_m[3] = {0, 0, 0};  // the means last removed: right-hand side, initial residual, answer (cz_closed_mean)
+  bool closed_m0_on_device = false;  // closed_m[0] is still sc[7] of d_res (cz_set_rhs does not wait for it; ClosedMean fetches)
+  double g_npts = 0.0;           // cells of the GLOBAL inner box (1 / res_normal)
   int field_form = 0;            // CZ_FIELD_FORM: 3 = the generic import / export kernel whatever the strides
   int last_field_form = 0;       // the kernel form of the last import / export (cz_info 20: 1 k rows, 2 tile transpose, 3 generic)
   hipEvent_t ev_io = nullptr;    // the hand-over between the caller's stream and the compute stream
@@ -139,6 +143,11 @@ class CZ {
   int FieldIO(int which, void* a, int abytes, const long long* stride, int on_device, void* user_stream, int op, double scale, double* sumsq,
               const char* who);
   int SetNeumann(const int* faces);  // cz_set_neumann: 1, or 0 with one line on stderr and nothing changed
+  int SetClosedBox(int on);          // cz_set_closed_box: likewise
+  int set_mask(const int* faces, int closed, const char* who);  // what the two share: refusals, the hierarchy, the work vectors, P's mirror
+  bool project(REAL_TYPE* A, REAL_TYPE* m_dev, REAL_TYPE* keep_dev);  // A <- A - mean(A) over the global inner box; d_res[20..21] = this rank's sum A', sum A'^2
+  double ClosedMean(int which);      // cz_closed_mean
+  bool project_rhs();                // ... of RHS, ghost layers included; closed_m[0]
   void mirror(REAL_TYPE* X);         // the Neumann face layers of X from its first inner layers (nothing without a mask)
   void WriteProfile(FILE* fp) const;                                             // cz_Evaluate.cpp:506-545
   bool WriteSph(const char* fname, const REAL_TYPE* padded_host_field) const;  // cz_utility.f90:17-47

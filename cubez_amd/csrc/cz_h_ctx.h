@@ -82,10 +82,10 @@ struct Ctx {
 thread_local Ctx ctx;  // one context per host thread (= per rank; LOCAL transport runs ranks as threads)
 
 enum { LBL_JACOBI = 0, LBL_RBSOR, LBL_AX, LBL_RK, LBL_REDUCE, LBL_EWISE, LBL_DOT, LBL_JACOBI2, LBL_RBSOR2, LBL_PCR, LBL_SHELL, LBL_PSOR, LBL_RBSOR4, LBL_JACOBI3, LBL_MG_RESTRICT, LBL_MG_SMOOTH,
-       LBL_MG_PROLONG, LBL_MG_TAIL, LBL_MG_RB, LBL_FIELD, LBL_BC_MIRROR, LBL_COUNT };
+       LBL_MG_PROLONG, LBL_MG_TAIL, LBL_MG_RB, LBL_FIELD, LBL_BC_MIRROR, LBL_SHIFT_SUMS, LBL_CG_CLOSED, LBL_COUNT };
 static_assert(LBL_COUNT <= 24, "Ctx::t_acc / t_cnt hold 24 labels");
 const char* const kLabelNames[LBL_COUNT] = {"jacobi", "rbsor", "calc_ax", "calc_rk", "reduce", "ewise", "dot", "jacobi2", "rbsor2", "pcr_rb", "pair_shell", "psor", "rbsor4", "jacobi3",
-                                            "mg_restrict", "mg_smooth", "mg_prolong", "mg_tail", "mg_rb", "field_io", "bc_mirror"};
+                                            "mg_restrict", "mg_smooth", "mg_prolong", "mg_tail", "mg_rb", "field_io", "bc_mirror", "shift_sums", "cg_update_closed"};
 
 struct ScopedTimer {
   bool on;

@@ -273,12 +273,13 @@ cz_mg* czhip_mg_create_rb(const int* sz, const int* idx, int g, const CZ_REAL* c
 
 int czhip_mg_levels(const cz_mg* h) { return h ? h->nlev : 0; }
 
-// zero-flux (Neumann) faces for the hierarchy's cycles from now on (faces[6]: X-, X+, Y-, Y+, Z-, Z+; all zero: none); 0 = refused (all six)
+// zero-flux (Neumann) faces for the hierarchy's cycles from now on (faces[6]: X-, X+, Y-, Y+, Z-, Z+; all zero: none); 0 = refused (NULL).
+// All six are accepted: D = Wx cx + Wy cy + Wz cz vanishes only at a point that is first and last in all three directions, and the coarsest
+// level keeps at least 3 points along its longest direction
 int czhip_mg_set_neumann(cz_mg* h, const int* faces) {
   if (!h || !faces) return 0;
   int nm = 0;
   for (int f = 0; f < 6; f++) nm |= faces[f] ? 1 << f : 0;
-  if (nm == 63) return 0;
   h->nm = nm;
   for (int l = h->first; l < h->nlev; l++) h->lev[l].nm = nm;
   if (h->fine_tmp) {  // (its face layers may hold the mirrors of an earlier mask: zeros again, as the unmasked passes read them)

@@ -77,6 +77,7 @@ void bicg_scalar_async(int step, const double* dots_dev, CZ_REAL rho, CZ_REAL* s
 // PCG's rho / beta (step 0, from the dot in dot_dev[0]; first: no beta) and alpha (step 1, from p.Ap in dot_dev[0]) made on the device:
 // sc_dev[0..3] = alpha, -alpha, beta, rho (cg_scal_k)
 void cg_scalar_async(int step, const double* dot_dev, int first, CZ_REAL* sc_dev);
+void mean_scalar_async(const double* sum_dev, double npts, CZ_REAL* m_dev, CZ_REAL* keep_dev);  // *m_dev = (REAL)(sum_dev[0] / npts) (closed box)
 // czhip_jacobi2_from_zero_made_async with the coefficient a of the made right-hand side read from the device (a_dev, may be null)
 int pass_from_zero_made(const CZ_REAL* u_shape, CZ_REAL* w, CZ_REAL* b_out, int op, const CZ_REAL* x, const CZ_REAL* y, const CZ_REAL* z, CZ_REAL a,
                         const CZ_REAL* a_dev, CZ_REAL bb, const int* sz, const int* idx, const int* idx1, int g, const CZ_REAL* cf, CZ_REAL omg,

@@ -288,14 +288,17 @@ triad_dots_k(REAL* Z, const REAL* X, const REAL* Y, const REAL* W, REAL a, EGeom
 
 // PCG's update (beyond the reference): x = alpha*p + x, r = (-alpha)*q + r (blas_triad twice) and dst[0] = sum r*r, one pass over the four
 // arrays.  alpha and -alpha come from the device (g.pa / g.pb, made by cg_scal_k); same structure and launch shape as triad_dots_k.
-template <int V>
+// CLOSED (the closed box): r = ((-alpha)*q + r) - m, m = g.pa[4] the mean of the residual as the update before left it
+// (mean_scal_k), and dst[1] = sum r of the values written, through a second row of partials; false: the code from before there was a closed box.
+template <int V, bool CLOSED>
 __global__ void __launch_bounds__(256)
 cg_update_k(REAL* X, REAL* Rr, const REAL* Pd, const REAL* Q, EGeom g, int nplanes, double* partials, double* dst, unsigned* counter) {
   __shared__ double wsum[4];
   __shared__ int last_flag;
   const long long f = g.F0 + (long long)blockIdx.x * 256 + threadIdx.x;
   const REAL a = *g.pa, na = *g.pb;
-  double acc = 0.0;
+  const REAL m = CLOSED ? g.pa[4] : (REAL)0;
+  double acc = 0.0, accs = 0.0;
   if (f < g.Fend) {
     const int kv = (int)(f % g.R);
     unsigned mk = 0;
@@ -314,8 +317,12 @@ cg_update_k(REAL* X, REAL* Rr, const REAL* Pd, const REAL* Q, EGeom g, int nplan
         for (int cc = 0; cc < V; cc++) {
           xo.v[cc] = a * p.v[cc] + x.v[cc];
           ro.v[cc] = na * q.v[cc] + r.v[cc];
+          if (CLOSED) ro.v[cc] = ro.v[cc] - m;
           const REAL rr = ro.v[cc] * ro.v[cc];
-          if (mk & (1u << cc)) acc += (double)rr;
+          if (mk & (1u << cc)) {
+            acc += (double)rr;
+            if (CLOSED) accs += (double)ro.v[cc];
+          }
         }
         if (mk == (1u << V) - 1) {
           stve<V>(X, pe, xo);
@@ -329,23 +336,121 @@ cg_update_k(REAL* X, REAL* Rr, const REAL* Pd, const REAL* Q, EGeom g, int nplan
     }
   }
   const double s = block_sum<256>(acc, wsum);
+  double s2 = 0.0;
+  if (CLOSED) {
+    __syncthreads();
+    s2 = block_sum<256>(accs, wsum);
+  }
   const int nblk = gridDim.x * gridDim.y;
   const int me = blockIdx.y * gridDim.x + blockIdx.x;
   if (threadIdx.x == 0) {
     __hip_atomic_store(&partials[me], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (CLOSED) __hip_atomic_store(&partials[nblk + me], s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     last_flag = arrive_and_test_last(counter, nblk);
   }
   __syncthreads();
   if (last_flag) {
-    double x = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 256) x += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    double x = 0.0, x2 = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += 256) {
+      x += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (CLOSED) x2 += __hip_atomic_load(&partials[nblk + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     __syncthreads();
     const double tot = block_sum<256>(x, wsum);
+    double tot2 = 0.0;
+    if (CLOSED) {
+      __syncthreads();
+      tot2 = block_sum<256>(x2, wsum);
+    }
     if (threadIdx.x == 0) {
       dst[0] = tot;
+      if (CLOSED) dst[1] = tot2;
       *counter = 0u;
     }
   }
+}
+
+// The closed box: a <- a - *m over the inner box (SHIFT; false: a is only read, m is not), with dst[0] = sum a' and
+// dst[1] = sum a'^2 of the values a holds afterwards -- the squares as REAL products widened, like every dot here.  It projects the
+// right-hand side, the initial residual and the answer of a closed-box solve.  Row split, vector width, edge masks, offsets and the
+// last-workgroup finalisation are those of cg_update_k / triad_dots_k.
+template <int V, bool SHIFT>
+__global__ void __launch_bounds__(256)
+shift_sums_k(REAL* A, const REAL* mp, EGeom g, int nplanes, double* partials, double* dst, unsigned* counter) {
+  __shared__ double wsum[4];
+  __shared__ int last_flag;
+  const long long f = g.F0 + (long long)blockIdx.x * 256 + threadIdx.x;
+  const REAL m = SHIFT ? *mp : (REAL)0;
+  double acc1 = 0.0, acc2 = 0.0;
+  if (f < g.Fend) {
+    const int kv = (int)(f % g.R);
+    unsigned mk = 0;
+#pragma unroll
+    for (int cc = 0; cc < V; cc++) {
+      const int kk = kv * V + cc;
+      if (kk >= g.kk0 && kk <= g.kk1) mk |= 1u << cc;
+    }
+    if (mk != 0) {
+      const long long eo = egeom_eo<V>(g, f);
+      for (int pl = blockIdx.y; pl < nplanes; pl += gridDim.y) {
+        const long long pe = (long long)(g.jj0 + pl) * g.PSE + eo;
+        Vec<V> o = ldve<V>(A, pe);
+#pragma unroll
+        for (int cc = 0; cc < V; cc++) {
+          if (SHIFT) o.v[cc] = o.v[cc] - m;
+          const REAL aa = o.v[cc] * o.v[cc];
+          if (mk & (1u << cc)) {
+            acc1 += (double)o.v[cc];
+            acc2 += (double)aa;
+          }
+        }
+        if (SHIFT) {
+          if (mk == (1u << V) - 1) {
+            stve<V>(A, pe, o);
+          } else {
+#pragma unroll
+            for (int cc = 0; cc < V; cc++)
+              if (mk & (1u << cc)) A[pe + cc] = o.v[cc];
+          }
+        }
+      }
+    }
+  }
+  const double s1 = block_sum<256>(acc1, wsum);
+  __syncthreads();
+  const double s2 = block_sum<256>(acc2, wsum);
+  const int nblk = gridDim.x * gridDim.y;
+  const int me = blockIdx.y * gridDim.x + blockIdx.x;
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(&partials[me], s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&partials[nblk + me], s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last_flag = arrive_and_test_last(counter, nblk);
+  }
+  __syncthreads();
+  if (last_flag) {
+    double x1 = 0.0, x2 = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += 256) {
+      x1 += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      x2 += __hip_atomic_load(&partials[nblk + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    const double t1 = block_sum<256>(x1, wsum);
+    __syncthreads();
+    const double t2 = block_sum<256>(x2, wsum);
+    if (threadIdx.x == 0) {
+      dst[0] = t1;
+      dst[1] = t2;
+      *counter = 0u;
+    }
+  }
+}
+
+// the mean of a closed-box projection on the device: double division, then the one rounding to REAL; keep (optional) receives a copy that
+// no later launch overwrites (cz_closed_mean reads it after the solve)
+__global__ void mean_scal_k(const double* __restrict__ sum, double npts, REAL* __restrict__ m, REAL* __restrict__ keep) {
+  const REAL v = (REAL)(sum[0] / npts);
+  *m = v;
+  if (keep) *keep = v;
 }
 
 // PCG's scalars on the device, with the host's operations (REAL division of REAL-rounded double sums), like bicg_scal_k.

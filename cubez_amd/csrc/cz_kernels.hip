@@ -1455,34 +1455,79 @@ void cg_scalar_async(int step, const double* dot_dev, int first, REAL* sc_dev) {
 }
 }  // namespace czhip_internal
 
-extern "C" {
-void czhip_cg_update_async(CZ_REAL* x, CZ_REAL* r, const CZ_REAL* p, const CZ_REAL* q, const CZ_REAL* alpha_dev, const int* sz, const int* idx, int g,
-                           double* dots_dev) {
+namespace {
+// the launch shape of triad_dots_async; CLOSED: cg_update_k's closed-box form (sc[4] the mean, dots_dev[1] the sum of r)
+template <bool CLOSED>
+void cg_update_launch(REAL* x, REAL* r, const REAL* p, const REAL* q, const REAL* alpha_dev, const int* sz, const int* idx, int g, double* dots_dev) {
   ensure_init();
   const Box b = make_box(sz, idx, g);
   if (b.empty) {
-    HIP_CHECK(hipMemsetAsync(dots_dev, 0, sizeof(double), ctx.stream));
+    HIP_CHECK(hipMemsetAsync(dots_dev, 0, (CLOSED ? 2 : 1) * sizeof(double), ctx.stream));
     return;
   }
   const int nplanes = b.jj1 - b.jj0 + 1;
-  ScopedTimer tm(LBL_EWISE);
-  // the launch shape of triad_dots_async
+  ScopedTimer tm(CLOSED ? LBL_CG_CLOSED : LBL_EWISE);
   if (rows_ok(b, {x, r, p, q})) {
     EGeom e = make_egeom<VW>(b);
     e.pa = alpha_dev, e.pb = alpha_dev + 1;
     const unsigned gx = (unsigned)((e.Fend - e.F0 + 255) / 256);
     const unsigned gy = (unsigned)std::max(1, std::min(nplanes, (int)(4096 / gx)));
-    ensure_partials((size_t)gx * gy);
-    hipLaunchKernelGGL((cg_update_k<VW>), dim3(gx, gy), dim3(256), 0, ctx.stream, x, r, p, q, e, nplanes, ctx.partials, dots_dev, ctx.counter);
+    ensure_partials((size_t)(CLOSED ? 2 : 1) * gx * gy);
+    hipLaunchKernelGGL((cg_update_k<VW, CLOSED>), dim3(gx, gy), dim3(256), 0, ctx.stream, x, r, p, q, e, nplanes, ctx.partials, dots_dev, ctx.counter);
   } else {
     EGeom e = make_egeom<1>(b);
     e.pa = alpha_dev, e.pb = alpha_dev + 1;
     const unsigned gx = (unsigned)((e.Fend - e.F0 + 255) / 256);
     const unsigned gy = (unsigned)std::max(1, std::min(nplanes, (int)(4096 / gx)));
-    ensure_partials((size_t)gx * gy);
-    hipLaunchKernelGGL((cg_update_k<1>), dim3(gx, gy), dim3(256), 0, ctx.stream, x, r, p, q, e, nplanes, ctx.partials, dots_dev, ctx.counter);
+    ensure_partials((size_t)(CLOSED ? 2 : 1) * gx * gy);
+    hipLaunchKernelGGL((cg_update_k<1, CLOSED>), dim3(gx, gy), dim3(256), 0, ctx.stream, x, r, p, q, e, nplanes, ctx.partials, dots_dev, ctx.counter);
   }
   HIP_CHECK(hipGetLastError());
+}
+
+template <int V, bool SHIFT>
+void shift_sums_inst(REAL* a, const REAL* m_dev, const Box& b, double* sums_dev) {
+  const int nplanes = b.jj1 - b.jj0 + 1;
+  const EGeom e = make_egeom<V>(b);
+  const unsigned gx = (unsigned)((e.Fend - e.F0 + 255) / 256);
+  const unsigned gy = (unsigned)std::max(1, std::min(nplanes, (int)(4096 / gx)));
+  ensure_partials((size_t)2 * gx * gy);
+  hipLaunchKernelGGL((shift_sums_k<V, SHIFT>), dim3(gx, gy), dim3(256), 0, ctx.stream, a, m_dev, e, nplanes, ctx.partials, sums_dev, ctx.counter);
+}
+}  // namespace
+
+namespace czhip_internal {
+// *m_dev = (REAL)(sum_dev[0] / npts), and *keep_dev too where given (mean_scal_k)
+void mean_scalar_async(const double* sum_dev, double npts, REAL* m_dev, REAL* keep_dev) {
+  hipLaunchKernelGGL(mean_scal_k, dim3(1), dim3(1), 0, ctx.stream, sum_dev, npts, m_dev, keep_dev);
+  HIP_CHECK(hipGetLastError());
+}
+}  // namespace czhip_internal
+
+extern "C" {
+void czhip_cg_update_async(CZ_REAL* x, CZ_REAL* r, const CZ_REAL* p, const CZ_REAL* q, const CZ_REAL* alpha_dev, const int* sz, const int* idx, int g,
+                           double* dots_dev) {
+  cg_update_launch<false>(x, r, p, q, alpha_dev, sz, idx, g, dots_dev);
+}
+// the closed-box form: r = ((-alpha) q + r) - sc_dev[4]; dots_dev[0] = sum r^2, dots_dev[1] = sum r (sc_dev: five REALs)
+void czhip_cg_update_closed_async(CZ_REAL* x, CZ_REAL* r, const CZ_REAL* p, const CZ_REAL* q, const CZ_REAL* sc_dev, const int* sz, const int* idx, int g,
+                                  double* dots_dev) {
+  cg_update_launch<true>(x, r, p, q, sc_dev, sz, idx, g, dots_dev);
+}
+// a <- a - *m_dev over the inner box (m_dev NULL: a is only read), sums_dev[0] = sum a', sums_dev[1] = sum a'^2 (shift_sums_k); 0 = refused
+int czhip_shift_sums_async(CZ_REAL* a, const CZ_REAL* m_dev, const int* sz, const int* idx, int g, double* sums_dev) {
+  ensure_init();
+  if (!a || !sz || !idx || !sums_dev) return 0;
+  const Box b = make_box(sz, idx, g);
+  if (b.empty) {
+    HIP_CHECK(hipMemsetAsync(sums_dev, 0, 2 * sizeof(double), ctx.stream));
+    return 1;
+  }
+  ScopedTimer tm(LBL_SHIFT_SUMS);
+  if (rows_ok(b, {a})) m_dev ? shift_sums_inst<VW, true>(a, m_dev, b, sums_dev) : shift_sums_inst<VW, false>(a, m_dev, b, sums_dev);
+  else m_dev ? shift_sums_inst<1, true>(a, m_dev, b, sums_dev) : shift_sums_inst<1, false>(a, m_dev, b, sums_dev);
+  HIP_CHECK(hipGetLastError());
+  return 1;
 }
 
 void czhip_cg_dir_ax_async(CZ_REAL* p_new, CZ_REAL* q, const CZ_REAL* z, const CZ_REAL* p_old, const CZ_REAL* beta_dev, const int* sz, const int* idx,

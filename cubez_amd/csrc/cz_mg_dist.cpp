@@ -169,7 +169,7 @@ int mgd_set_neumann(MgDist* h, const int* faces) {
   if (!h || !faces) return 0;
   int nm = 0;
   for (int f = 0; f < 6; f++) nm |= faces[f] ? 1 << f : 0;
-  if (nm == 63 || (h->g && !czhip_mg_set_neumann(h->g, faces))) return 0;
+  if (h->g && !czhip_mg_set_neumann(h->g, faces)) return 0;
   for (int f = 0; f < 6; f++) h->faces[f] = faces[f] ? 1 : 0;
   h->masked = nm != 0;
   for (int l = 0; l < MG_MAXLEV; l++) h->lev[l].nm = nm;

@@ -44,6 +44,9 @@ class CZ:
         lib.cz_add_field.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_double]
         lib.cz_set_eps.argtypes = [C.c_void_p, C.c_double]
         lib.cz_set_neumann.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        lib.cz_set_closed_box.argtypes = [C.c_void_p, C.c_int]
+        lib.cz_closed_mean.argtypes = [C.c_void_p, C.c_int]
+        lib.cz_closed_mean.restype = C.c_double
         lib.cz_set_itr_max.argtypes = [C.c_void_p, C.c_int]
         self.device = int(device)
         if lib.czhip_init(int(device)) != 0:
@@ -208,6 +211,19 @@ class CZ:
         if self.lib.cz_set_neumann(self.h, (C.c_int * 6)(*f)) != 1:
             raise ValueError(f"set_neumann({f}): refused (see stderr)")
 
+    def set_closed_box(self, on=True):
+        """the closed box for pcg: all six faces zero-flux; the right-hand side in the handle (and every later set_rhs) loses its mean, the
+        solve keeps its residual in the range of the operator and returns a field of zero mean; after setup, collective with the same value
+        on every rank.  on=False: Dirichlet faces again, the right-hand side stays projected (cz_set_closed_box of include/cz_hip.h,
+        DESIGN.md §5.14)"""
+        if self.lib.cz_set_closed_box(self.h, 1 if on else 0) != 1:
+            raise ValueError(f"set_closed_box({bool(on)}): refused (see stderr)")
+
+    def closed_mean(self, which: int) -> float:
+        """the mean last removed in closed-box mode: 0 from the right-hand side, 1 from the initial residual of the last solve, 2 from its
+        answer (NaN for another `which`)"""
+        return float(self.lib.cz_closed_mean(self.h, int(which)))
+
     def set_itr_max(self, n: int):
         if self.lib.cz_set_itr_max(self.h, int(n)) != 1:
             raise ValueError(f"set_itr_max({n}): refused")
@@ -226,7 +242,7 @@ class CZ:
     def info(self) -> dict:
         """what a (multi-GPU) run decided (cz_info of include/cz_hip.h)"""
         keys = ("ranks", "fused_pass", "shell_slabs", "overlap", "lagged_reduce", "rccl_ranks", "comm_cus", "pass_kind", "exchange_depth", "buffers", "bicg_fused", "rb4_passes",
-                "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother", "field_form", "neumann")
+                "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother", "field_form", "neumann", "closed")
         return {k: self.lib.cz_info(self.h, i) for i, k in enumerate(keys)}
 
     def config_in_force(self) -> dict:

@@ -21,10 +21,13 @@ def scale_of(sumsq: float, npts: int) -> float:
 
 
 class Refined:
-    def __init__(self, gsz, inner=("pcg", 1000, 1.2, "mgrb"), division=None, device=-1, neumann=None):
+    def __init__(self, gsz, inner=("pcg", 1000, 1.2, "mgrb"), division=None, device=-1, neumann=None, closed=False):
         """gsz: the global box; inner: the FP32 solver as on the command line (solver, ItrMax, coefficient[, preconditioner]); division: as on the
         command line (every rank of a decomposed run makes its own Refined after joining both libraries' communicators); neumann: the six
-        flags of CZ.set_neumann, set on both libraries (the inner solver must then be pcg)"""
+        flags of CZ.set_neumann, set on both libraries (the inner solver must then be pcg); closed: CZ.set_closed_box on both (all six faces
+        zero-flux, right-hand sides projected, answers of zero mean; not together with neumann)"""
+        if closed and neumann is not None:
+            raise ValueError("Refined: closed=True and neumann= exclude each other (the closed box is all six faces)")
         import torch  # (only here: the package imports without it)
         self.torch = torch
         div = list(division) if division else []
@@ -37,6 +40,9 @@ class Refined:
         if neumann is not None:
             self.hi.set_neumann(neumann)
             self.lo.set_neumann(neumann)
+        if closed:
+            self.hi.set_closed_box(True)
+            self.lo.set_closed_box(True)
         self.shape = tuple(self.hi.local()["size"])
         if tuple(self.lo.local()["size"]) != self.shape:
             raise RuntimeError("Refined: the two libraries cut the domain differently")

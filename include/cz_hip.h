@@ -390,9 +390,19 @@ int czhip_mg_kind(const cz_mg* h);
  * czhip_mg_set_neumann: the hierarchy's cycles from now on take these faces as zero-flux faces: level 0 runs single sweeps / colour sweeps with
  *   the mirror before each one that reads its input, levels >= 1 take D = Wx cx + Wy cy + Wz cz, c = 2 less one per Neumann face the point
  *   lies on (the correction is zero outside the box, the absent link needs nothing else).  All zero: the cycle of czhip_mg_create, bit for
- *   bit.  Either returns 1, or 0 when refused (a NULL pointer; all six faces). */
+ *   bit.  Either returns 1, or 0 when refused (a NULL pointer). */
 int czhip_mirror_faces_async(CZ_REAL* p, const int* sz, const int* idx, int g, const int* faces);
 int czhip_mg_set_neumann(cz_mg* h, const int* faces);
+/* The closed box (all six faces zero-flux): the projections onto the zero-mean fields and PCG's update with one folded in.
+ * czhip_shift_sums_async: a <- a - *m_dev over the inner box (one REAL subtraction per cell), then sums_dev[0] = sum a', sums_dev[1] = sum a'^2
+ *   of the values a holds afterwards (REAL products accumulated in double, as czhip_cg_update_async forms r.r).  m_dev NULL: a is only read,
+ *   nothing is stored.  Cells outside the inner box keep their bytes.  One launch (label shift_sums); 1, or 0 when refused (a NULL pointer).
+ * czhip_cg_update_closed_async: czhip_cg_update_async with r = ((-alpha)*q + r) - sc_dev[4] (sc_dev: alpha, -alpha, -, -, m) and
+ *   dots_dev[0] = r.r, dots_dev[1] = sum r of the written values (label cg_update_closed).
+ * In czhip_mg_set_neumann all six faces are accepted: D = Wx cx + Wy cy + Wz cz stays positive. */
+int czhip_shift_sums_async(CZ_REAL* a, const CZ_REAL* m_dev, const int* sz, const int* idx, int g, double* sums_dev);
+void czhip_cg_update_closed_async(CZ_REAL* x, CZ_REAL* r, const CZ_REAL* p, const CZ_REAL* q, const CZ_REAL* sc_dev, const int* sz, const int* idx, int g,
+                                  double* dots_dev);
 
 /* Convergence bookkeeping on the device (cz_Poisson.cpp:67-77): res = sqrt(res_dev[0]*res_normal);
  * hist_dev[itr] = res; if (res < eps && !*flag) { *flag = 1; conv_itr_dev[0] = itr; }.  No-op when
@@ -474,6 +484,24 @@ int cz_add_field(cz_handle*, const void* src, int src_real_bytes, const long lon
  * Dirichlet problem again (the face layers keep their last values).  cz_setup (and with it cz_evaluate, once it has accepted the solver)
  * clears the mask: a set-up starts with Dirichlet faces. */
 int cz_set_neumann(cz_handle*, const int* faces);
+/* The closed box for pcg: all six faces zero-flux.  The operator is then singular (its null space: the constants), so the
+ * mode keeps the right-hand side compatible, the residual in the range of the operator and the answer of zero mean:
+ *   on = 1 (after cz_setup, not a _maf handle): the six faces become Neumann faces (cz_info 21 reports 63, cz_info 22 reports 1), the
+ *     hierarchy learns the mask, the right-hand side the handle holds loses its mean over the global inner box -- S = sum b in double, one
+ *     all-reduce in a decomposed run, m = (REAL)(S / npts), b <- b - m in REAL -- and so does every right-hand side a later cz_set_rhs
+ *     brings; P is mirrored.  cz_solve (pcg with none | jacobi | mg | mgrb) removes the mean of the initial residual, removes in every
+ *     update the mean the residual had after the update before (rounding drift: A p has zero sum), and returns a field of zero mean over
+ *     the inner box with the mirrors in place -- the same field whichever preconditioner ran, up to the tolerance.
+ *   on = 0: mask 0, mode off, the work vectors cleared as cz_set_neumann does.  The right-hand side is NOT restored: it stays projected.
+ * Collective, the same value on every rank.  Returns 1, or 0 with one line on stderr and nothing changed: before cz_setup, a _maf handle,
+ * the hierarchy's refusal.  Solvers other than pcg are refused while the mode is on, as under cz_set_neumann; an accepted cz_set_neumann
+ * leaves the mode (its own refusal of six flags stands: a caller who has not met compatibility is pointed here); cz_setup clears it.
+ * cz_closed_mean: the mean last removed, as a double holding the REAL -- which = 0 from the right-hand side, 1 from the initial residual
+ * of the last solve, 2 from the answer of the last solve; NaN for another `which`, 0.0 where nothing was removed since cz_setup.  The
+ * projection of a right-hand side adds no host wait to cz_set_rhs: its mean stays on the device until cz_closed_mean(h, 0) asks for it,
+ * and that call waits for the compute stream. */
+int cz_set_closed_box(cz_handle*, int on);
+double cz_closed_mean(cz_handle*, int which);
 int cz_set_eps(cz_handle*, double eps);
 int cz_set_itr_max(cz_handle*, int n);
 int cz_sweeps(cz_handle*, int n);              /* bench leg: n more iterations of the selected stationary solver with the
@@ -501,7 +529,8 @@ double cz_last_solve_seconds(const cz_handle*);
  * 0 on a single domain or where level 0 is the coarsest); 18 halo exchanges and all-gathers of the last V-cycle of a decomposed pcg ... mg;
  * 19 the smoother of the multigrid preconditioner (0 none, 1 relaxed Jacobi: mg, 2 symmetric red-black: mgrb; 15 and 16 count for both);
  * 20 the kernel form of the last cz_set_rhs / cz_set_field / cz_get_field (1 k rows, 2 tile transpose, 3 generic; CZ_FIELD_FORM=3 forces 3);
- * 21 the mask of cz_set_neumann, bit f = face f of X-, X+, Y-, Y+, Z-, Z+ (0: none). */
+ * 21 the mask of cz_set_neumann, bit f = face f of X-, X+, Y-, Y+, Z-, Z+ (0: none; 63: the closed box);
+ * 22 the closed-box mode of cz_set_closed_box (0 | 1). */
 int cz_info(const cz_handle*, int what);
 /* The driver's and its communicator's own copies of their switches, as name=value, one per line: overlap, lag_reduce, comm_cus (as asked for;
  * 0 on a single domain), comm_cus_reserved (in force after set-up), bicg_fuse, bicg_devsc, bicg_alias, cg_fuse, mg_tail, mg_gather, mgrb_zero4,
