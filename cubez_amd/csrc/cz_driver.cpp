@@ -216,6 +216,8 @@ int CZ::Setup(int argc, char** argv) {
   std::fill(neumann, neumann + 6, 0);
   neumann_mask = 0;
   closed_box = 0;
+  periodic[0] = periodic[1] = periodic[2] = 0;
+  periodic_mask = 0;
   closed_m[0] = closed_m[1] = closed_m[2] = 0.0;
   closed_m0_on_device = false;
 
@@ -384,8 +386,9 @@ int CZ::Setup(int argc, char** argv) {
 
 // Zero-flux faces are built for pcg (none | jacobi | mg | mgrb) alone: every other loop would sweep with Dirichlet faces
 bool CZ::neumann_refused(const char* who, int s_type) const {
-  if (!neumann_mask || s_type == LS_PCG) return false;
-  fprintf(stderr, "%s: Neumann faces are set (cz_set_neumann) and the solver is not pcg\n", who);
+  if ((!neumann_mask && !periodic_mask) || s_type == LS_PCG) return false;
+  if (neumann_mask) fprintf(stderr, "%s: Neumann faces are set (cz_set_neumann) and the solver is not pcg\n", who);
+  else fprintf(stderr, "%s: periodic directions are set (cz_set_periodic) and the solver is not pcg\n", who);
   return true;
 }
 
@@ -420,7 +423,7 @@ int CZ::Solve() {
 }
 
 int CZ::Evaluate(int argc, char** argv) {
-  if (neumann_mask && argc > 4) {
+  if ((neumann_mask || periodic_mask) && argc > 4) {
     const cz_solvers::Row* named = cz_solvers::find(argv[4], cz_solvers::SOLVER);
     if (neumann_refused("cz_evaluate", named ? named->id : LS_NONE)) return 0;
   }
@@ -1377,7 +1380,8 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   const bool pc = pc_type == LS_JACOBI || pc_type == LS_MG || pc_type == LS_MGRB;
   const bool fuse = cfg.on(CZV_CG_FUSE, true);
   // the direction pass reads z's and p's shells as zeros: single domain only, and no Neumann face (whose layer of p is the mirror)
-  const bool fuse_dir = fuse && numProc == 1 && !neumann_mask;
+  // (nor a periodic direction, whose layer is the wrap)
+  const bool fuse_dir = fuse && numProc == 1 && !neumann_mask && !periodic_mask;
   REAL_TYPE* const sc = reinterpret_cast<REAL_TYPE*>(d_res + 12);  // alpha, -alpha, beta, rho (cg_scal_k)
   double* const d_rr = d_res + 5;
   double* const d_pq = d_res + 3;                 // (the unfused SpMV writes q.q to d_res[4])
@@ -1426,7 +1430,7 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
       if (mg || mgd) {
         if (mg ? !czhip_mg_apply_async(mg, cg_z, cg_r, ac1) : !mgd_apply(mgd, cg_z, cg_r, ac1)) return 0;  // z = V_0(r)
         mg_cycles++;
-      } else if (neumann_mask) {
+      } else if (neumann_mask || periodic_mask) {
         // the 8 relaxed sweeps from zero as single sweeps between cg_z and cg_p[1] (free: the direction is not fused), the exchange and the
         // mirror before every sweep that reads its input
         HIP_CHECK(hipMemsetAsync(cg_z, 0, nbytes, st));
@@ -1514,9 +1518,53 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
 
 // ------------------------------------------------------------------------------------------------------------
 // Zero-flux (Neumann) faces.  The mask is global and the same on every rank; a brick mirrors the faces that are physical on it
+// Periodic directions are never cut, so both their faces are physical on every brick: there the one fill launch wraps, and
+// mirrors the Neumann faces of the other directions with it
 void CZ::mirror(REAL_TYPE* X) {
+  if (periodic_mask) {
+    int kinds[6];
+    for (int f = 0; f < 6; f++) kinds[f] = periodic[f >> 1] ? 2 : neumann[f];
+    if (!czhip_fill_faces_async(X, size, innerFidx, GUIDE, kinds)) cz_fatal(1, "czhip: the fill of the periodic and Neumann faces was refused\n");
+    return;
+  }
   if (!neumann_mask) return;
   if (!czhip_mirror_faces_async(X, size, innerFidx, GUIDE, neumann)) cz_fatal(1, "czhip: the mirror of the Neumann faces was refused\n");
+}
+
+// The one rule of solvability, for the three setters on the combined state: with the closed mode off, some face of a direction that is not
+// periodic must be a Dirichlet face (else the operator is singular).  nullptr: solvable; else the line
+const char* CZ::unsolvable(int nm, int per, int closed) {
+  if (closed) return nullptr;
+  for (int d = 0; d < 3; d++)
+    if (!((per >> d) & 1) && ((nm >> (2 * d)) & 3) != 3) return nullptr;
+  if (!per) return "at least one face must stay a Dirichlet face (the all-Neumann problem is singular: cz_set_closed_box keeps it solvable)";
+  return "no Dirichlet face is left in a direction that is not periodic (the problem is singular: cz_set_closed_box keeps it solvable)";
+}
+
+int CZ::SetPeriodic(const int* dirs) {
+  auto refuse = [&](const char* why) {
+    fprintf(stderr, "cz_set_periodic: %s\n", why);
+    return 0;
+  };
+  if (!set_up) return refuse("no problem is set up (cz_setup first)");
+  if (!dirs) return refuse("NULL pointer");
+  const int per = (dirs[0] ? 1 : 0) | (dirs[1] ? 2 : 0) | (dirs[2] ? 4 : 0);
+  if (SW_maf) return refuse("the handle's operator is a MAF one, not the unit-coefficient operator");
+  for (int d = 0; d < 3; d++) {
+    if (dirs[d] && G_size[d] < 4) return refuse("a periodic direction needs two inner points at least");
+    if (dirs[d] && G_div[d] > 1) return refuse("a periodic direction must not be cut by the decomposition");
+  }
+  if (const char* why = unsolvable(neumann_mask, per, closed_box)) return refuse(why);
+  if ((mg && !czhip_mg_set_periodic(mg, dirs)) || (mgd && !mgd_set_periodic(mgd, dirs))) return refuse("the multigrid hierarchy refused the directions");
+  for (int d = 0; d < 3; d++) periodic[d] = dirs[d] ? 1 : 0;
+  periodic_mask = per;
+  // the work vectors whose face layers carried the wraps and mirrors of the state before: zeros again, as the unmasked passes read them
+  for (REAL_TYPE* a : {cg_z, cg_p[0], cg_p[1]})
+    if (a) HIP_CHECK(hipMemsetAsync(a, 0, padded_cells() * sizeof(REAL_TYPE), stream()));
+  mirror(P);
+  wrk_shell_tag = 0;
+  czhip_sync();
+  return 1;
 }
 
 int CZ::set_mask(const int* faces, int closed, const char* who) {
@@ -1528,8 +1576,7 @@ int CZ::set_mask(const int* faces, int closed, const char* who) {
   if (!faces) return refuse("NULL pointer");
   int nm = 0;
   for (int f = 0; f < 6; f++) nm |= faces[f] ? 1 << f : 0;
-  if (nm == 63 && !closed)
-    return refuse("at least one face must stay a Dirichlet face (the all-Neumann problem is singular: cz_set_closed_box keeps it solvable)");
+  if (const char* why = unsolvable(nm, periodic_mask, closed)) return refuse(why);
   if (SW_maf) return refuse("the handle's operator is a MAF one, not the unit-coefficient operator");
   if ((mg && !czhip_mg_set_neumann(mg, faces)) || (mgd && !mgd_set_neumann(mgd, faces))) return refuse("the multigrid hierarchy refused the mask");
   for (int f = 0; f < 6; f++) neumann[f] = faces[f] ? 1 : 0;
@@ -1958,6 +2005,10 @@ int cz_add_field(cz_handle* h, const void* src, int src_real_bytes, const long l
 }
 int cz_set_neumann(cz_handle* h, const int* faces) { return h ? h->cz.SetNeumann(faces) : 0; }
 int cz_set_closed_box(cz_handle* h, int on) { return h ? h->cz.SetClosedBox(on) : 0; }
+int cz_set_periodic(cz_handle* h, const int* dirs) {
+  if (!h) fprintf(stderr, "cz_set_periodic: NULL handle\n");
+  return h ? h->cz.SetPeriodic(dirs) : 0;
+}
 double cz_closed_mean(cz_handle* h, int which) { return h ? h->cz.ClosedMean(which) : std::nan(""); }
 int cz_set_eps(cz_handle* h, double eps) {
   if (!h || !h->cz.set_up || !(eps > 0.0)) {
@@ -2010,6 +2061,7 @@ int cz_info(const cz_handle* h, int what) {
     case 20: return c.last_field_form;
     case 21: return c.neumann_mask;
     case 22: return c.closed_box;
+    case 23: return c.periodic_mask;
     default: return -1;
   }
 }

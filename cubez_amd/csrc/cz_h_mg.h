@@ -43,7 +43,8 @@ MgdLevel mg_array_level(const int* sz, const int* idx, int g, int level, const i
 
 // the LDS layout of the levels from fine (level l) down to the coarsest: one zero shell per array, b, x, t per level (rb: b and x, the
 // red-black iterations run in place)
-bool mg_tail_plan(MgTail& T, const MgLev& fine, REAL omg, bool rb = false) {
+// (bc: level `fine`'s value of MgdLevel::nm, wrap bits included -- every level of the tail takes its own from it, mg_level_bc; -1: fine.nm)
+bool mg_tail_plan(MgTail& T, const MgLev& fine, REAL omg, bool rb = false, int bc = -1) {
   T = MgTail();
   T.gl = fine, T.omg = omg;
   const int n[3] = {fine.ni, fine.nj, fine.nk};
@@ -53,6 +54,7 @@ bool mg_tail_plan(MgTail& T, const MgLev& fine, REAL omg, bool rb = false) {
   for (int m = 0; m < T.nlev; m++) {
     MgLev& s = T.s[m] = fine;
     s.ni = dims[m][0], s.nj = dims[m][1], s.nk = dims[m][2], s.l = fine.l + m;
+    s.nm = czhip_internal::mg_level_bc((bc < 0 ? fine.nm : bc) & 63, bc < 0 ? 0 : bc >> 6, dims[m]);
     s.nip = s.ni + 2, s.nkp = s.nk + 2, s.i0 = s.j0 = s.k0 = 1;
     T.len[m] = (s.ni + 2) * (s.nj + 2) * (s.nk + 2);
     T.off[m] = T.total;
@@ -63,17 +65,23 @@ bool mg_tail_plan(MgTail& T, const MgLev& fine, REAL omg, bool rb = false) {
 }
 
 // (NM: the level kernels' instantiation for a level with Neumann faces, chosen here from the level's mask -- cz_k_mg.h, mg_weights)
-template <bool RB, bool NM>
+// (PER: some level of the tail wraps a periodic direction, DESIGN.md §5.15.  A level of one point in such a direction carries mask bits that
+// the finer levels do not, so both flags are taken over every level of the tail; without a periodic direction that is T.gl.nm)
+template <bool RB, bool NM, bool PER>
 void mg_tail_launch(REAL* x, const REAL* b, const MgTail& T) {
   ScopedTimer tm(LBL_MG_TAIL);
   const int bytes = T.total * (int)sizeof(REAL);
-  if (bytes > 64 * 1024) allow_dynamic_lds(&mg_tail_k<RB, NM>, 160 * 1024);
-  hipLaunchKernelGGL((mg_tail_k<RB, NM>), dim3(1), dim3(MG_TAIL_THREADS), bytes, ctx.stream, x, b, T);
+  if (bytes > 64 * 1024) allow_dynamic_lds(&mg_tail_k<RB, NM, PER>, 160 * 1024);
+  hipLaunchKernelGGL((mg_tail_k<RB, NM, PER>), dim3(1), dim3(MG_TAIL_THREADS), bytes, ctx.stream, x, b, T);
   HIP_CHECK(hipGetLastError());
 }
 void mg_tail_launch(REAL* x, const REAL* b, const MgTail& T, bool rb) {
-  if (T.gl.nm) rb ? mg_tail_launch<true, true>(x, b, T) : mg_tail_launch<false, true>(x, b, T);
-  else rb ? mg_tail_launch<true, false>(x, b, T) : mg_tail_launch<false, false>(x, b, T);
+  int any = 0;
+  for (int m = 0; m < T.nlev; m++) any |= T.s[m].nm;
+  if (any >> 6) {  // (one instantiation per smoother: a mask of zero gives the unmasked bits)
+    rb ? mg_tail_launch<true, true, true>(x, b, T) : mg_tail_launch<false, true, true>(x, b, T);
+  } else if (any & 63) rb ? mg_tail_launch<true, true, false>(x, b, T) : mg_tail_launch<false, true, false>(x, b, T);
+  else rb ? mg_tail_launch<true, false, false>(x, b, T) : mg_tail_launch<false, false, false>(x, b, T);
 }
 
 dim3 mg_grid(const MgLev& L) { return dim3((unsigned)((L.nk + 63) / 64), (unsigned)((L.ni + 3) / 4), (unsigned)L.nj); }
@@ -272,6 +280,28 @@ cz_mg* czhip_mg_create(const int* sz, const int* idx, int g, const CZ_REAL* cf) 
 cz_mg* czhip_mg_create_rb(const int* sz, const int* idx, int g, const CZ_REAL* cf) { return mg_create_public(sz, idx, g, cf, true); }
 
 int czhip_mg_levels(const cz_mg* h) { return h ? h->nlev : 0; }
+}  // extern "C"
+
+namespace {
+// every level's mask from the state as set (mg_level_bc; without a periodic direction: the Neumann flags at every level, as before there were
+// any).  The arrays whose ghost layers carried the mirrors or wraps of an earlier state are zeros again, as the unmasked passes read them
+void mg_relevel(cz_mg* h) {
+  int wraps = h->per;
+  for (int l = h->first; l < h->nlev; l++) wraps |= h->lev[l].nm >> 6;
+  for (int l = h->first; l < h->nlev; l++) h->lev[l].nm = czhip_internal::mg_level_bc(h->nm_set, h->per, h->lev[l].gn);
+  const int gn0[3] = {h->lev[h->first].n0[0], h->lev[h->first].n0[1], h->lev[h->first].n0[2]};
+  h->nm = czhip_internal::mg_level_bc(h->nm_set, h->per, gn0);
+  if (h->fine_tmp) {
+    const int* sz = h->lev[0].sz;
+    HIP_CHECK(hipMemsetAsync(h->fine_tmp, 0, (size_t)(sz[0] + 4) * (sz[1] + 4) * (sz[2] + 4) * sizeof(REAL), ctx.stream));
+  }
+  for (int l = std::max(h->first, 1); wraps && l < h->nlev; l++)  // (levels >= 1 have ghost layers other than zero only under a wrap)
+    for (REAL* a : {h->x[l], h->t[l]})
+      if (a) HIP_CHECK(hipMemsetAsync(a, 0, (size_t)(h->lev[l].sz[0] + 4) * (h->lev[l].sz[1] + 4) * (h->lev[l].sz[2] + 4) * sizeof(REAL), ctx.stream));
+}
+}  // namespace
+
+extern "C" {
 
 // zero-flux (Neumann) faces for the hierarchy's cycles from now on (faces[6]: X-, X+, Y-, Y+, Z-, Z+; all zero: none); 0 = refused (NULL).
 // All six are accepted: D = Wx cx + Wy cy + Wz cz vanishes only at a point that is first and last in all three directions, and the coarsest
@@ -280,12 +310,17 @@ int czhip_mg_set_neumann(cz_mg* h, const int* faces) {
   if (!h || !faces) return 0;
   int nm = 0;
   for (int f = 0; f < 6; f++) nm |= faces[f] ? 1 << f : 0;
-  h->nm = nm;
-  for (int l = h->first; l < h->nlev; l++) h->lev[l].nm = nm;
-  if (h->fine_tmp) {  // (its face layers may hold the mirrors of an earlier mask: zeros again, as the unmasked passes read them)
-    const int* sz = h->lev[0].sz;
-    HIP_CHECK(hipMemsetAsync(h->fine_tmp, 0, (size_t)(sz[0] + 4) * (sz[1] + 4) * (sz[2] + 4) * sizeof(REAL), ctx.stream));
-  }
+  h->nm_set = nm;
+  mg_relevel(h);
+  return 1;
+}
+
+// periodic directions for the hierarchy's cycles from now on (dirs[3]: X, Y, Z; all zero: none); 0 = refused (NULL).  The Neumann
+// flags of a periodic direction are ignored while it is periodic
+int czhip_mg_set_periodic(cz_mg* h, const int* dirs) {
+  if (!h || !dirs) return 0;
+  h->per = (dirs[0] ? 1 : 0) | (dirs[1] ? 2 : 0) | (dirs[2] ? 4 : 0);
+  mg_relevel(h);
   return 1;
 }
 int czhip_mg_kind(const cz_mg* h) { return h ? 1 + h->rb : 0; }
@@ -304,10 +339,22 @@ void czhip_mg_destroy(cz_mg* h) {
 
 namespace {
 // the Neumann face layers of a level-0 array from its first inner layers
+// (with a periodic direction: the one fill launch that wraps and mirrors)
 void mg_mirror(cz_mg* h, REAL* x) {
   int faces[6];
-  for (int f = 0; f < 6; f++) faces[f] = (h->nm >> f) & 1;
-  if (!czhip_mirror_faces_async(x, h->lev[0].sz, h->lev[0].idx, MG_GUIDE, faces)) cz_fatal(1, "czhip: V-cycle: the mirror of the Neumann faces was refused\n");
+  for (int f = 0; f < 6; f++) faces[f] = (h->nm >> (6 + (f >> 1))) & 1 ? 2 : (h->nm >> f) & 1;
+  if (h->nm >> 6 ? !czhip_fill_faces_async(x, h->lev[0].sz, h->lev[0].idx, MG_GUIDE, faces)
+                 : !czhip_mirror_faces_async(x, h->lev[0].sz, h->lev[0].idx, MG_GUIDE, faces))
+    cz_fatal(1, "czhip: V-cycle: the mirror of the Neumann faces was refused\n");
+}
+// the wrap of a level >= 1 array's ghost layers in the level's periodic directions (nothing without one): before every kernel that reads
+// the array's neighbours.  The masked diagonal needs no mirror there
+bool mg_wraps(const cz_mg* h, int l) { return (h->lev[l].nm >> 6) != 0; }
+void mg_wrap(cz_mg* h, int l, REAL* x) {
+  const int w = h->lev[l].nm >> 6;
+  if (!w) return;
+  const int kinds[6] = {w & 1 ? 2 : 0, w & 1 ? 2 : 0, w & 2 ? 2 : 0, w & 2 ? 2 : 0, w & 4 ? 2 : 0, w & 4 ? 2 : 0};
+  if (!czhip_fill_faces_async(x, h->lev[l].sz, h->lev[l].idx, MG_GUIDE, kinds)) cz_fatal(1, "czhip: V-cycle: the wrap of a periodic level was refused\n");
 }
 
 // level 0's pairs of sweeps with the unit coefficients, u -> w (u = nullptr: from zero): the fused pass, or where it is not taken two single
@@ -347,7 +394,7 @@ struct MgOps {
     MgDLev D;
     MgTail T;
     mg_lev(D, h->lev[l]);
-    mg_tail_plan(T, D.L, omg, h->rb);
+    mg_tail_plan(T, D.L, omg, h->rb, h->lev[l].nm);
     mg_tail_launch(h->x[l], h->b[l], T, h->rb);
     return true;
   }
@@ -394,7 +441,20 @@ struct MgOps {
   void rb_pair(int l, bool zero, bool post) {
     if (l == 0) return fine_rb_pair(zero, post);
     const int c0 = post ? 1 : 0;
-    for (int s = 0; s < 4; s++) must(czhip_internal::mg_rb_async(h->x[l], h->b[l], h->lev[l], omg, (c0 + s) & 1, zero && s < 2 ? s + 1 : 0));
+    // (a periodic level: a wrap after every colour sweep serves the next one, and the first one after the prolongation.  On an odd periodic
+    // extent the seam points share a colour and the ghost holds the value from before the sweep; from zero that value is a zero, so the
+    // array is cleared and swept as an iterate -- the bits of the literal zeros)
+    const bool w = mg_wraps(h, l);
+    if (w && zero) {
+      const int* sz = h->lev[l].sz;
+      HIP_CHECK(hipMemsetAsync(h->x[l], 0, (size_t)(sz[0] + 4) * (sz[1] + 4) * (sz[2] + 4) * sizeof(REAL), ctx.stream));
+    } else if (w) {
+      mg_wrap(h, l, h->x[l]);
+    }
+    for (int s = 0; s < 4; s++) {
+      must(czhip_internal::mg_rb_async(h->x[l], h->b[l], h->lev[l], omg, (c0 + s) & 1, zero && s < 2 && !w ? s + 1 : 0));
+      mg_wrap(h, l, h->x[l]);
+    }
   }
   // level 0's iterate must end in z: how many times the walk moves it
   int fine_moves() const {
@@ -409,11 +469,14 @@ struct MgOps {
       std::swap(x0, o0);
       return;
     }
+    if (!zero) mg_wrap(h, l, h->x[l]);
     must(czhip_internal::mg_smooth_async(zero ? nullptr : h->x[l], h->t[l], h->b[l], h->lev[l], omg));
+    mg_wrap(h, l, h->t[l]);
     must(czhip_internal::mg_smooth_async(h->t[l], h->x[l], h->b[l], h->lev[l], omg));
   }
   void restrict_down(int l) {
     if (l == 0 && h->nm && !h->rb) mirror(x0);  // (mgrb: mirrored after its last colour sweep)
+    if (l && !h->rb) mg_wrap(h, l, h->x[l]);
     must(czhip_internal::mg_restrict_async(h->b[l + 1], h->lev[l + 1], x(l), l ? h->b[l] : r, nullptr, h->lev[l]));
   }
   void prolong_up(int l) {

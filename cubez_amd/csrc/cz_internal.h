@@ -150,7 +150,21 @@ struct MgdLevel {
   int n0[3], o[3], gn[3];
   int dense;
   int nm;  // zero-flux (Neumann) faces of the global box, bit f = X-, X+, Y-, Y+, Z-, Z+: the diagonal of levels >= 1
+           // bits 6 .. 8: the level's ghost layers of direction X, Y, Z hold the periodic wrap (mg_level_bc)
 };
+// One level's value of MgdLevel::nm from the state that was set (nm: the six Neumann flags, per: bit d = direction d is periodic) and the
+// level's global points gn.  In a periodic direction the Neumann flags are ignored; a level of two or more points there wraps (bit 6 + d),
+// a level of one point has no link in that direction -- the point's neighbours are itself -- and takes both mask bits (c = 0) and no wrap.
+// per = 0: nm itself, at every level
+inline int mg_level_bc(int nm, int per, const int* gn) {
+  int v = 0;
+  for (int d = 0; d < 3; d++) {
+    if (!((per >> d) & 1)) v |= nm & (3 << (2 * d));
+    else if (gn[d] < 2) v |= 3 << (2 * d);
+    else v |= 64 << d;
+  }
+  return v;
+}
 // the launches of the level kernels; 0 = refused, nothing launched
 int mg_smooth_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const MgdLevel& L, CZ_REAL omg);  // u = nullptr: from zero
 // rt (nullptr where F is a whole level): the residual of the children on the + neighbours, from mgd_resface_async and its exchange
@@ -180,6 +194,8 @@ struct cz_mg {
   int tail_from = 0;            // first level run by mg_tail_k (nlev: none)
   int rb = 0;                   // the smoother: 0 relaxed Jacobi (mg), 1 symmetric red-black (mgrb; t stays unallocated)
   int nm = 0;                   // zero-flux (Neumann) faces, bit f of the six (czhip_mg_set_neumann): level 0 mirrors, levels >= 1 take the masked diagonal
+                                // (with a periodic direction: level 0's value of mg_level_bc, wrap bits included)
+  int nm_set = 0, per = 0;      // the state as set: the six Neumann flags, the periodic directions (bit d; czhip_mg_set_periodic)
   int zero4 = 0;                // mgrb, level 0: the two iterations from zero as one two-iteration pass over a cleared array (CZ_MGRB_ZERO4)
 };
 

@@ -522,6 +522,47 @@ __global__ void __launch_bounds__(256) mirror_faces_k(REAL* p, MirrorFaces m) {
   }
 }
 
+// Periodic directions: mirror_faces_k's shape with the source layer as a parameter.  Entry q fills layer dst[q] of direction
+// dir[q] from layer src[q], both over the inner box of the other two directions: a mirror takes the first inner layer next to the face, a wrap
+// the last inner layer for the - face (p(1) = p(size-1)) and the first one for the + face (p(size) = p(2)).  Every source is an inner layer and
+// every destination a face layer, so the entries of one launch do not read what another writes.  A Z entry touches one element per k-row; a Z
+// wrap is ONE entry whose thread serves both faces of its row (dst2 / src2 >= 0), so that a short row's two accesses share its cache lines.
+struct FillFaces {
+  int nkp, nip;
+  int ii0, ii1, jj0, jj1, kk0, kk1;  // the inner box (inclusive)
+  int n, dir[6], dst[6], src[6];     // the entries: padded 0-based layer indices
+  int dst2, src2;                    // the second face of a Z wrap entry (-1: none)
+};
+__global__ void __launch_bounds__(256) fill_faces_k(REAL* p, FillFaces m) {
+  const int q = blockIdx.y, d = m.dir[q];
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const long long si = m.nkp, sj = (long long)m.nkp * m.nip;
+  if (d == 0) {  // row = j
+    const int jj = m.jj0 + row;
+    if (jj > m.jj1) return;
+    const long long src = jj * sj + m.src[q] * si, dst = jj * sj + m.dst[q] * si;
+    for (int kk = m.kk0 + lane; kk <= m.kk1; kk += 64) p[dst + kk] = p[src + kk];
+  } else if (d == 1) {  // row = i
+    const int ii = m.ii0 + row;
+    if (ii > m.ii1) return;
+    const long long src = m.src[q] * sj + ii * si, dst = m.dst[q] * sj + ii * si;
+    for (int kk = m.kk0 + lane; kk <= m.kk1; kk += 64) p[dst + kk] = p[src + kk];
+  } else {  // row = j, lanes along i
+    const int jj = m.jj0 + row;
+    if (jj > m.jj1) return;
+    const long long at = jj * sj;
+    for (int ii = m.ii0 + lane; ii <= m.ii1; ii += 64) {
+      REAL* const r = p + at + ii * si;
+      const REAL a = r[m.src[q]];
+      if (m.dst2 >= 0) {
+        const REAL b = r[m.src2];
+        r[m.dst2] = b;
+      }
+      r[m.dst[q]] = a;
+    }
+  }
+}
+
 // copy every element OUTSIDE the inner box (guide cells, Dirichlet faces) from src to dst: one wave per k-row.
 // Used to give the ping-pong partner buffer of a Jacobi solve the same boundary data as the solution array.
 __global__ void __launch_bounds__(256)

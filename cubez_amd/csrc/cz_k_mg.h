@@ -22,6 +22,7 @@ struct MgLev {
   int l;               // level
   int n0i, n0j, n0k;   // level-0 points per direction (the extents E)
   int nm;              // zero-flux (Neumann) physical faces of the box, bit f = face X-, X+, Y-, Y+, Z-, Z+; level 0: always 0
+                       // (the LDS levels of the tail also carry bits 6 .. 8: the level wraps direction X, Y, Z -- mg_tail_wrap)
 };
 
 // global index of a level array's local point (0, 0, 0): zero on a single domain, the brick's first owned point of the level in the
@@ -249,33 +250,67 @@ __device__ __forceinline__ void mg_each_colour(const MgLev& L, int c, F f) {
   }
 }
 
+// Periodic directions in the tail: the wrap of array a of level L into its own one-cell shell, a(-1) = a(n - 1) and a(n) = a(0)
+// in every direction whose wrap bit (6 + d of L.nm) is set, over the level's points of the other two directions (edges stay zero: no kernel
+// reads them).  A workgroup loop over the seam faces; the caller's threads are in step before it, and it ends with them in step
+__device__ __forceinline__ void mg_tail_wrap(const MgLev& L, REAL* a) {
+  const int per = L.nm >> 6;
+  if (!per) return;
+  if (per & 1)
+    for (int q = threadIdx.x; q < L.nj * L.nk; q += blockDim.x) {
+      const int K = q % L.nk, J = q / L.nk;
+      a[mg_at(L, -1, J, K)] = a[mg_at(L, L.ni - 1, J, K)];
+      a[mg_at(L, L.ni, J, K)] = a[mg_at(L, 0, J, K)];
+    }
+  if (per & 2)
+    for (int q = threadIdx.x; q < L.ni * L.nk; q += blockDim.x) {
+      const int K = q % L.nk, I = q / L.nk;
+      a[mg_at(L, I, -1, K)] = a[mg_at(L, I, L.nj - 1, K)];
+      a[mg_at(L, I, L.nj, K)] = a[mg_at(L, I, 0, K)];
+    }
+  if (per & 4)
+    for (int q = threadIdx.x; q < L.ni * L.nj; q += blockDim.x) {
+      const int I = q % L.ni, J = q / L.ni;
+      a[mg_at(L, I, J, -1)] = a[mg_at(L, I, J, L.nk - 1)];
+      a[mg_at(L, I, J, L.nk)] = a[mg_at(L, I, J, 0)];
+    }
+  __syncthreads();
+}
+
 // x <- two smoothing iterations of the level (zero: from zero); RB: red-black in place, backward (colours 1, 0) where post; else relaxed
-// Jacobi through t.  Ends with the workgroup in step
-template <bool RB, bool NM>
+// Jacobi through t.  Ends with the workgroup in step.  PER: a wrap follows every sweep and colour sweep (x is wrapped on return; on an odd
+// periodic extent the seam points share a colour and the shell holds the value from before the sweep -- from zero that is the cleared LDS)
+template <bool RB, bool NM, bool PER>
 __device__ __forceinline__ void mg_tail_pair(const MgLev& L, const REAL* b, REAL* x, REAL* t, bool zero, bool post, REAL omg) {
   if (RB) {
     const int c0 = post ? 1 : 0;
     if (zero) {
       mg_each_colour(L, c0, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<1, NM>(x, b, L, I, J, K, omg); });
       __syncthreads();
+      if (PER) mg_tail_wrap(L, x);
       mg_each_colour(L, 1 - c0, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<2, NM>(x, b, L, I, J, K, omg); });
       __syncthreads();
+      if (PER) mg_tail_wrap(L, x);
     }
     for (int s = zero ? 2 : 0; s < 4; s++) {
       mg_each_colour(L, (c0 + s) & 1, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<0, NM>(x, b, L, I, J, K, omg); });
       __syncthreads();
+      if (PER) mg_tail_wrap(L, x);
     }
     return;
   }
   if (zero) mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<NM, true>(t, b, L, I, J, K, omg); });
   else mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<NM, false>(x, b, L, I, J, K, omg); });
   __syncthreads();
+  if (PER) mg_tail_wrap(L, t);
   mg_each(L, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_sweep_pt<NM, false>(t, b, L, I, J, K, omg); });
   __syncthreads();
+  if (PER) mg_tail_wrap(L, x);
 }
 
-// RB: the cycle of pcg ... mgrb (its levels keep b and x only: T.len[m] apart, no t)
-template <bool RB, bool NM>
+// RB: the cycle of pcg ... mgrb (its levels keep b and x only: T.len[m] apart, no t).  PER: some level of the tail wraps (T.s[m].nm bits 6 .. 8;
+// without it, the code from before there were periodic directions)
+template <bool RB, bool NM, bool PER>
 __global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ xg, const REAL* __restrict__ bg, MgTail T) {
   extern __shared__ __align__(16) unsigned char mg_lds_raw[];
   REAL* const lds = reinterpret_cast<REAL*>(mg_lds_raw);
@@ -291,7 +326,7 @@ __global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ 
   for (int m = 0; m + 1 < T.nlev; m++) {
     const MgLev& L = T.s[m];
     REAL *b = lds + T.off[m], *x = b + T.len[m], *t = x + T.len[m];
-    mg_tail_pair<RB, NM>(L, b, x, t, true, false, omg);
+    mg_tail_pair<RB, NM, PER>(L, b, x, t, true, false, omg);
     const MgLev& Cl = T.s[m + 1];
     REAL* bc = lds + T.off[m + 1];
     mg_each(Cl, [&](int I, int J, int K) { bc[mg_at(Cl, I, J, K)] = mg_restrict_pt<NM>(x, b, L, I, J, K); });
@@ -300,7 +335,7 @@ __global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ 
   {  // the coarsest level: four pairs from zero, the last two post (mg_walk's order)
     const int m = T.nlev - 1;
     REAL *b = lds + T.off[m], *x = b + T.len[m], *t = x + T.len[m];
-    for (int s = 0; s < 4; s++) mg_tail_pair<RB, NM>(T.s[m], b, x, t, s == 0, s >= 2, omg);
+    for (int s = 0; s < 4; s++) mg_tail_pair<RB, NM, PER>(T.s[m], b, x, t, s == 0, s >= 2, omg);
   }
   // up: x += R(alpha x_c(parent)) in place, post-smoothing pair
   for (int m = T.nlev - 2; m >= 0; m--) {
@@ -313,7 +348,8 @@ __global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ 
       x[p] = mg_prolong_pt(x, xc, L, Cl, I, J, K);
     });
     __syncthreads();
-    mg_tail_pair<RB, NM>(L, b, x, t, false, true, omg);
+    if (PER) mg_tail_wrap(L, x);
+    mg_tail_pair<RB, NM, PER>(L, b, x, t, false, true, omg);
   }
   {
     const REAL* x0 = lds + T.off[0] + T.len[0];

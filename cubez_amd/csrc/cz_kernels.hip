@@ -1440,6 +1440,47 @@ int czhip_mirror_faces_async(CZ_REAL* p, const int* sz, const int* idx, int g, c
   HIP_CHECK(hipGetLastError());
   return 1;
 }
+
+// every face layer listed in kinds[6] (X-, X+, Y-, Y+, Z-, Z+: 0 leave, 1 mirror, 2 wrap) in one launch (fill_faces_k).  A mirror
+// on a face that is not physical on the brick is skipped, as czhip_mirror_faces_async skips it; a wrap needs both faces of its direction to be
+// kind 2 and both to be physical on the brick (the direction is not cut).  0 = refused, nothing launched
+int czhip_fill_faces_async(CZ_REAL* p, const int* sz, const int* idx, int g, const int* kinds) {
+  ensure_init();
+  if (!p || !sz || !idx || !kinds) return 0;
+  for (int d = 0; d < 3; d++) {
+    const int a = kinds[2 * d], b = kinds[2 * d + 1];
+    if (a < 0 || a > 2 || b < 0 || b > 2 || ((a == 2) != (b == 2))) return 0;
+    if (a == 2 && (idx[2 * d] != 2 || idx[2 * d + 1] != sz[d] - 1)) return 0;
+  }
+  const Box b = make_box(sz, idx, g);
+  if (b.empty) return 1;
+  FillFaces m;
+  m.nkp = b.nkp, m.nip = b.nip, m.ii0 = b.ii0, m.ii1 = b.ii1, m.jj0 = b.jj0, m.jj1 = b.jj1, m.kk0 = b.kk0, m.kk1 = b.kk1, m.n = 0;
+  m.dst2 = m.src2 = -1;
+  const int lo[3] = {b.ii0, b.jj0, b.kk0}, hi[3] = {b.ii1, b.jj1, b.kk1};
+  int rows = 0;
+  auto entry = [&](int d, int dst, int src) {
+    m.dir[m.n] = d, m.dst[m.n] = dst, m.src[m.n] = src;
+    m.n++;
+    rows = std::max(rows, d == 1 ? b.ii1 - b.ii0 + 1 : b.jj1 - b.jj0 + 1);
+  };
+  for (int d = 0; d < 3; d++) {
+    if (kinds[2 * d] == 2) {
+      entry(d, lo[d] - 1, hi[d]);
+      if (d == 2) m.dst2 = hi[d] + 1, m.src2 = lo[d];
+      else entry(d, hi[d] + 1, lo[d]);
+      continue;
+    }
+    if (kinds[2 * d] == 1 && idx[2 * d] == 2) entry(d, lo[d] - 1, lo[d]);
+    if (kinds[2 * d + 1] == 1 && idx[2 * d + 1] == sz[d] - 1) entry(d, hi[d] + 1, hi[d]);
+  }
+  for (int q = m.n; q < 6; q++) m.dir[q] = 0, m.dst[q] = m.src[q] = lo[0];
+  if (!m.n) return 1;
+  ScopedTimer tm(LBL_BC_MIRROR);
+  hipLaunchKernelGGL(fill_faces_k, dim3((unsigned)((rows + 3) / 4), (unsigned)m.n), dim3(256), 0, ctx.stream, p, m);
+  HIP_CHECK(hipGetLastError());
+  return 1;
+}
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------------------

@@ -40,6 +40,7 @@ struct MgDist {
   int exchanges = 0;               // halo exchanges + all-gathers of the last cycle
   int faces[6] = {0, 0, 0, 0, 0, 0};  // zero-flux (Neumann) faces of the global box (mgd_set_neumann)
   bool masked = false;
+  int nm = 0, per = 0;             // the state as set: the six flags as bits, the periodic directions (bit d; mgd_set_periodic)
 };
 
 namespace {
@@ -56,6 +57,21 @@ bool brick_range(const CZ& cz, int rank, int h[3], int m[3], int nid[6]) {
 
 void fatal_if(bool bad, const char* what) {
   if (bad) cz_fatal(1, "czhip: distributed V-cycle: %s failed\n", what);
+}
+
+size_t padded(const MgdLevel& L) { return (size_t)(L.sz[0] + 2 * GUIDE) * (L.sz[1] + 2 * GUIDE) * (L.sz[2] + 2 * GUIDE); }
+
+// every distributed level's and the gathered block's mask from the state as set (mg_level_bc: without a periodic direction the six flags at
+// every level); the arrays whose ghost layers carried an earlier state's mirrors or wraps are zeros again
+void mgd_relevel(MgDist* h) {
+  int wraps = h->per;
+  for (int l = 0; l < std::max(h->G, 1); l++) wraps |= h->lev[l].nm >> 6;
+  for (int l = 0; l < MG_MAXLEV; l++) h->lev[l].nm = l < std::max(h->G, 1) ? mg_level_bc(h->nm, h->per, h->lev[l].gn) : h->nm;
+  h->blk.nm = h->G > 0 ? mg_level_bc(h->nm, h->per, h->blk.gn) : h->nm;
+  HIP_CHECK(hipMemsetAsync(h->tmp0, 0, padded(h->lev[0]) * sizeof(REAL_TYPE), stream()));
+  for (int l = 1; wraps && l < h->G; l++)
+    for (REAL_TYPE* a : {h->x[l], h->t[l]})
+      if (a) HIP_CHECK(hipMemsetAsync(a, 0, padded(h->lev[l]) * sizeof(REAL_TYPE), stream()));
 }
 }  // namespace
 
@@ -172,10 +188,18 @@ int mgd_set_neumann(MgDist* h, const int* faces) {
   if (h->g && !czhip_mg_set_neumann(h->g, faces)) return 0;
   for (int f = 0; f < 6; f++) h->faces[f] = faces[f] ? 1 : 0;
   h->masked = nm != 0;
-  for (int l = 0; l < MG_MAXLEV; l++) h->lev[l].nm = nm;
-  h->blk.nm = nm;
-  const MgdLevel& F = h->lev[0];
-  HIP_CHECK(hipMemsetAsync(h->tmp0, 0, (size_t)(F.sz[0] + 2 * GUIDE) * (F.sz[1] + 2 * GUIDE) * (F.sz[2] + 2 * GUIDE) * sizeof(REAL_TYPE), stream()));
+  h->nm = nm;
+  mgd_relevel(h);
+  return 1;
+}
+
+// the periodic directions, the same on every rank and none of them cut by the decomposition (the driver checks): every brick then holds both
+// faces of such a direction at every level, and the wrap is the single domain's fill beside the exchange
+int mgd_set_periodic(MgDist* h, const int* dirs) {
+  if (!h || !dirs) return 0;
+  if (h->g && !czhip_mg_set_periodic(h->g, dirs)) return 0;
+  h->per = (dirs[0] ? 1 : 0) | (dirs[1] ? 2 : 0) | (dirs[2] ? 4 : 0);
+  mgd_relevel(h);
   return 1;
 }
 
@@ -198,7 +222,13 @@ struct MgdOps {
   void halo(int l, REAL_TYPE* X) {
     fatal_if(!comm_halo(h->comm[l], X, nullptr, stream()), "face exchange");
     h->exchanges++;
-    if (l == 0 && h->masked) fatal_if(!czhip_mirror_faces_async(X, h->lev[0].sz, h->lev[0].idx, GUIDE, h->faces), "mirror of the Neumann faces");
+    if (h->lev[l].nm >> 6) {  // (periodic directions: the one fill that wraps and, at level 0, mirrors -- DESIGN.md §5.15)
+      int kinds[6];
+      for (int f = 0; f < 6; f++) kinds[f] = (h->lev[l].nm >> (6 + (f >> 1))) & 1 ? 2 : l == 0 ? (h->lev[0].nm >> f) & 1 : 0;
+      fatal_if(!czhip_fill_faces_async(X, h->lev[l].sz, h->lev[l].idx, GUIDE, kinds), "fill of the periodic and Neumann faces");
+    } else if (l == 0 && h->masked) {
+      fatal_if(!czhip_mirror_faces_async(X, h->lev[0].sz, h->lev[0].idx, GUIDE, h->faces), "mirror of the Neumann faces");
+    }
   }
   void halo_full(int l, REAL_TYPE* X) {
     fatal_if(!comm_halo_full(h->comm[l], X, stream()), "face + edge + corner exchange");

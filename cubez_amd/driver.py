@@ -45,6 +45,7 @@ class CZ:
         lib.cz_set_eps.argtypes = [C.c_void_p, C.c_double]
         lib.cz_set_neumann.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         lib.cz_set_closed_box.argtypes = [C.c_void_p, C.c_int]
+        lib.cz_set_periodic.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         lib.cz_closed_mean.argtypes = [C.c_void_p, C.c_int]
         lib.cz_closed_mean.restype = C.c_double
         lib.cz_set_itr_max.argtypes = [C.c_void_p, C.c_int]
@@ -219,6 +220,17 @@ class CZ:
         if self.lib.cz_set_closed_box(self.h, 1 if on else 0) != 1:
             raise ValueError(f"set_closed_box({bool(on)}): refused (see stderr)")
 
+    def set_periodic(self, dirs):
+        """periodic directions for pcg: three flags in the order X, Y, Z of the global box; after setup, collective with the same flags on every
+        rank.  The two face layers of the field in such a direction hold the wrap from now on, and its Neumann flags are ignored.  With the
+        closed box off, some face of a direction that is not periodic must stay a Dirichlet face: set_closed_box() first for the channel
+        (1, 0, 1) and the triply periodic box (1, 1, 1) (cz_set_periodic of include/cz_hip.h)"""
+        d = [1 if v else 0 for v in dirs]
+        if len(d) != 3:
+            raise ValueError(f"set_periodic: three flags (X, Y, Z), not {len(d)}")
+        if self.lib.cz_set_periodic(self.h, (C.c_int * 3)(*d)) != 1:
+            raise ValueError(f"set_periodic({d}): refused (see stderr)")
+
     def closed_mean(self, which: int) -> float:
         """the mean last removed in closed-box mode: 0 from the right-hand side, 1 from the initial residual of the last solve, 2 from its
         answer (NaN for another `which`)"""
@@ -242,7 +254,7 @@ class CZ:
     def info(self) -> dict:
         """what a (multi-GPU) run decided (cz_info of include/cz_hip.h)"""
         keys = ("ranks", "fused_pass", "shell_slabs", "overlap", "lagged_reduce", "rccl_ranks", "comm_cus", "pass_kind", "exchange_depth", "buffers", "bicg_fused", "rb4_passes",
-                "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother", "field_form", "neumann", "closed")
+                "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother", "field_form", "neumann", "closed", "periodic")
         return {k: self.lib.cz_info(self.h, i) for i, k in enumerate(keys)}
 
     def config_in_force(self) -> dict:

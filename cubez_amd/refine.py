@@ -21,11 +21,12 @@ def scale_of(sumsq: float, npts: int) -> float:
 
 
 class Refined:
-    def __init__(self, gsz, inner=("pcg", 1000, 1.2, "mgrb"), division=None, device=-1, neumann=None, closed=False):
+    def __init__(self, gsz, inner=("pcg", 1000, 1.2, "mgrb"), division=None, device=-1, neumann=None, closed=False, periodic=None):
         """gsz: the global box; inner: the FP32 solver as on the command line (solver, ItrMax, coefficient[, preconditioner]); division: as on the
         command line (every rank of a decomposed run makes its own Refined after joining both libraries' communicators); neumann: the six
         flags of CZ.set_neumann, set on both libraries (the inner solver must then be pcg); closed: CZ.set_closed_box on both (all six faces
-        zero-flux, right-hand sides projected, answers of zero mean; not together with neumann)"""
+        zero-flux, right-hand sides projected, answers of zero mean; not together with neumann); periodic: the three flags of CZ.set_periodic (X, Y, Z), set on both after neumann= or
+        closed=, with either of which it combines (closed=True with (1, 0, 1) is the channel, with (1, 1, 1) the triply periodic box)"""
         if closed and neumann is not None:
             raise ValueError("Refined: closed=True and neumann= exclude each other (the closed box is all six faces)")
         import torch  # (only here: the package imports without it)
@@ -43,6 +44,9 @@ class Refined:
         if closed:
             self.hi.set_closed_box(True)
             self.lo.set_closed_box(True)
+        if periodic is not None:
+            self.hi.set_periodic(periodic)
+            self.lo.set_periodic(periodic)
         self.shape = tuple(self.hi.local()["size"])
         if tuple(self.lo.local()["size"]) != self.shape:
             raise RuntimeError("Refined: the two libraries cut the domain differently")

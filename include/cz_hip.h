@@ -393,6 +393,19 @@ int czhip_mg_kind(const cz_mg* h);
  *   bit.  Either returns 1, or 0 when refused (a NULL pointer). */
 int czhip_mirror_faces_async(CZ_REAL* p, const int* sz, const int* idx, int g, const int* faces);
 int czhip_mg_set_neumann(cz_mg* h, const int* faces);
+/* Periodic directions.
+ * czhip_fill_faces_async: kinds[6], order X-, X+, Y-, Y+, Z-, Z+: 0 leave the face layer, 1 the mirror of czhip_mirror_faces_async (skipped on a
+ *   face that is not physical on the brick), 2 the wrap, p(1, j, k) = p(size-1, j, k) and p(size, j, k) = p(2, j, k), j and k over idx.  A
+ *   wrap needs both faces of its direction to be 2 and both to be physical on the brick.  One launch for every face listed (label bc_mirror);
+ *   edges, corners and every other cell keep their bytes.  It serves the level arrays of a hierarchy as well (S3D arrays, sz / idx / g).
+ * czhip_mg_set_periodic: dirs[3], X, Y, Z, non-zero = periodic.  The hierarchy's cycles from now on wrap those directions: at level 0 the
+ *   fill stands where the mirror stands (and does the mirrors too), at levels >= 1 the ghost layers are wrapped before every kernel that reads
+ *   the iterate's neighbours, which carries the ordinary link Wx = Ey Ez across the seam; a level of ONE point in a periodic direction has no
+ *   link there (both mask bits, c = 0, ghost layers zero).  The Neumann flags of a periodic direction are ignored.  All zero: the cycle
+ *   of before, bit for bit.  Either returns 1, or 0 when refused (a NULL pointer; a kind other than 0, 1, 2; half a wrap; a wrap on a face
+ *   that is not physical). */
+int czhip_fill_faces_async(CZ_REAL* p, const int* sz, const int* idx, int g, const int* kinds);
+int czhip_mg_set_periodic(cz_mg* h, const int* dirs);
 /* The closed box (all six faces zero-flux): the projections onto the zero-mean fields and PCG's update with one folded in.
  * czhip_shift_sums_async: a <- a - *m_dev over the inner box (one REAL subtraction per cell), then sums_dev[0] = sum a', sums_dev[1] = sum a'^2
  *   of the values a holds afterwards (REAL products accumulated in double, as czhip_cg_update_async forms r.r).  m_dev NULL: a is only read,
@@ -502,6 +515,20 @@ int cz_set_neumann(cz_handle*, const int* faces);
  * and that call waits for the compute stream. */
 int cz_set_closed_box(cz_handle*, int on);
 double cz_closed_mean(cz_handle*, int which);
+/* Periodic directions for pcg: dirs[3], order X, Y, Z of the GLOBAL box, non-zero = periodic.  Called after cz_setup;
+ * collective, with the same flags on every rank.  In a periodic direction the two face layers of the field are not data but the wrap,
+ * p(1, j, k) = p(size-1, j, k) and p(size, j, k) = p(2, j, k) over the cells every sweep updates, which makes the stated system
+ * `sum of neighbours - 6 p = b` the periodic operator.  On return of every call that writes P (this one, cz_set_neumann, cz_set_closed_box,
+ * cz_set_field, cz_add_field, cz_solve) those layers hold the wrap: values passed there are ignored, cz_get_field returns the wrap,
+ * cz_get_residual fills before its pass.  The flags are a state of their own beside the mask of cz_set_neumann and the closed mode:
+ * cz_setup clears them, the other two setters leave them alone, and in a periodic direction the Neumann flags are ignored (cz_info 21 keeps
+ * reporting them).  All three setters apply one rule to the combined state: with the closed mode off, some face of a direction that is not
+ * periodic must be a Dirichlet face.  cz_set_closed_box(h, 1) then cz_set_periodic(h, {1,0,1}) is the channel, with {1,1,1} the triply
+ * periodic box; {1,0,0} alone is periodic X with Dirichlet Y and Z.  Returns 1, or 0 with one line on stderr and nothing changed: before
+ * cz_setup, NULL, a _maf handle, a periodic direction of fewer than two inner points (G_size < 4) or one that the decomposition cuts
+ * (G_div > 1), the rule above.  With a flag set, cz_solve, cz_sweeps and cz_evaluate of a solver other than pcg (none | jacobi | mg | mgrb)
+ * return 0 with one line and leave P alone. */
+int cz_set_periodic(cz_handle*, const int* dirs);
 int cz_set_eps(cz_handle*, double eps);
 int cz_set_itr_max(cz_handle*, int n);
 int cz_sweeps(cz_handle*, int n);              /* bench leg: n more iterations of the selected stationary solver with the
@@ -530,7 +557,7 @@ double cz_last_solve_seconds(const cz_handle*);
  * 19 the smoother of the multigrid preconditioner (0 none, 1 relaxed Jacobi: mg, 2 symmetric red-black: mgrb; 15 and 16 count for both);
  * 20 the kernel form of the last cz_set_rhs / cz_set_field / cz_get_field (1 k rows, 2 tile transpose, 3 generic; CZ_FIELD_FORM=3 forces 3);
  * 21 the mask of cz_set_neumann, bit f = face f of X-, X+, Y-, Y+, Z-, Z+ (0: none; 63: the closed box);
- * 22 the closed-box mode of cz_set_closed_box (0 | 1). */
+ * 22 the closed-box mode of cz_set_closed_box (0 | 1); 23 the periodic directions of cz_set_periodic, bit d = X, Y, Z (0: none). */
 int cz_info(const cz_handle*, int what);
 /* The driver's and its communicator's own copies of their switches, as name=value, one per line: overlap, lag_reduce, comm_cus (as asked for;
  * 0 on a single domain), comm_cus_reserved (in force after set-up), bicg_fuse, bicg_devsc, bicg_alias, cg_fuse, mg_tail, mg_gather, mgrb_zero4,
