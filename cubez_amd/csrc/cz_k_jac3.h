@@ -89,8 +89,22 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
     };
 
     // One plane step q.  uc = u(q+1) and b1 = b(q) were requested one step ago; un / bn receive this step's requests.
-    auto step = [&](const int q, Vec<V>& uc, Vec<V>& un, Vec<V>& b1, Vec<V>& bn) __attribute__((always_inline)) {
-      {
+    // Two forms.  The general one clamps every requested plane, tests it for the array's last plane and gates every stage by its plane.  The
+    // INNER one is for the steps on which none of that acts -- q - 2 >= ja and q <= jb, so all three stages work on planes of the chunk, and
+    // q + 2 <= jlast - 1, so no request is clamped or touches the last plane: the plane addresses are pointers carried from step to step
+    // (uN = u(q+1), bN = b(q+1), wN = w(q-2)), the masks are `inbox` and `own` as they stand.  Same loads from the same addresses, same
+    // masks => the same bits; what goes is the scalar work per request (clamps, a 64-bit product, the last-plane test and its selects on the
+    // load offsets) and per stage (plane gates): 5-6 % of the kernel at 512^3, profiles/r19/jac3_step_instructions.txt.
+    const char* uN = Ub;
+    const char* bN = Bb;
+    char* wN = Wb;
+    auto step = [&](auto inner, const int q, Vec<V>& uc, Vec<V>& un, Vec<V>& b1, Vec<V>& bn) __attribute__((always_inline)) {
+      constexpr bool INNER = decltype(inner)::value;
+      if constexpr (INNER) {
+        hx = ld16<V>(uN, h.bo);
+        un = ld16<V>(uN + PB, bo);
+        bn = ld16<V>(bN, bo);
+      } else {
         const int qu = rv.pl(q + 2 <= jb + 3 ? q + 2 : jb + 3), qb = rv.pl(q + 1 <= jb + 2 ? q + 1 : jb + 2);
         hx = ld16<V>(Ub + (size_t)rv.pl(q + 1) * PB, rv.lim(h.bo, rv.pl(q + 1)));
         un = ld16<V>(Ub + (size_t)qu * PB, rv.lim(bo, qu));
@@ -98,8 +112,8 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
       }
       // planes of the three stages; masks: inside the inner box a stage updates, inside the chunk the owner counts the residual
       const int p1 = q, p2 = q - 1, p3 = q - 2;
-      auto upd = [&](int p) -> unsigned { return (p >= g.jj0 && p <= g.jj1) ? inbox : 0u; };
-      auto cnt = [&](int p) -> unsigned { return (p >= ja && p <= jb) ? own : 0u; };
+      auto upd = [&](int p) -> unsigned { return (INNER || (p >= g.jj0 && p <= g.jj1)) ? inbox : 0u; };
+      auto cnt = [&](int p) -> unsigned { return (INNER || (p >= ja && p <= jb)) ? own : 0u; };
       const Vec<V>* cU = ldsU + (size_t)(p1 & 1) * LU + R;  // u(p1) in E2 coordinates (index x)
       const Vec<V>* pU = ldsU + (size_t)((p1 - 1) & 1) * LU + R;
       Vec<V>* F1 = ldsF;
@@ -111,9 +125,9 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
       if (wave2) v2 = stage(F1 + (size_t)(p2 & 1) * LV, F1 + (size_t)((p2 - 1) & 1) * LV, v1, bq1, upd(p2), cnt(p2), acc2);
       // ---- stage 3: f3(p3) = the output, owned vectors of the chunk's planes.  Whole waves: the k neighbours travel by lane shifts, and the
       // lane next to the first owned vector of a window holds a halo vector -- it owns nothing but must take part.
-      if (p3 >= ja && wave3) {
+      if ((INNER || p3 >= ja) && wave3) {
         const Vec<V> o = stage(F2 + (size_t)(p3 & 1) * LV, F2 + (size_t)((p3 - 1) & 1) * LV, v2, bq2, own, own, acc3);
-        store_owned<V>(Wb + (size_t)p3 * PB, bo, own, o);
+        store_owned<V>(INNER ? wN : Wb + (size_t)p3 * PB, bo, own, o);
       }
       // ---- publish: f1(p1), f2(p2) and the next u centre plane u(q+1) with its outer rows
       F1[(size_t)(p1 & 1) * LV + x] = v1;
@@ -122,15 +136,36 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
       nU[R + x] = uc;
       if (h.has) nU[h.hl] = hx;
       bq2 = bq1, bq1 = b1;  // (b1 is complete: stage 1 used it)
+      if constexpr (INNER) uN += PB, bN += PB, wN += PB;
       __syncthreads();
     };
     // (stage s first matters at plane ja - (3 - s), which it reaches at step ja - 2 + (s - 1): every field buffer a valid point reads was
     // written by a step of this loop)
-    for (int q = q0;; q += 2) {
-      step(q, uA, uB, bA, bB);
-      if (q + 1 > jb + 2) break;
-      step(q + 1, uB, uA, bB, bA);
-      if (q + 2 > jb + 2) break;
+    // The march, steps q0 = ja - 2 .. jb + 2, in three parts:
+    //   phase 0   q0 .. ja + 1: the four steps that fill the pipeline, general form.  Always four (ja <= jb, so ja + 1 < jb + 2): two A/B pairs,
+    //             so uA / bA hold the pending requests again when it ends, at q = ja + 2
+    //   inner     q = ja + 2 .. qi in A/B pairs, while a whole pair fits (q + 1 <= qi); none for chunks of fewer than four planes
+    //   phase 1   from where the inner steps stopped to jb + 2, general form: at least jb + 1 and jb + 2, one more where an odd inner step
+    //             was left over, two more where the chunk ends at the array's last inner plane (jb = jlast - 2, qi = jb - 1)
+    // The general loop is ONE copy in the code, run once per phase (nounroll: two copies would cost code size for nothing).
+    const int qi = jb < g.jlast - 3 ? jb : g.jlast - 3;  // the last step that may take the inner form: q <= jb and q + 2 <= jlast - 1
+    int q = q0;
+#pragma nounroll
+    for (int phase = 0; phase < 2; phase++) {
+      const int qg = phase == 0 ? ja + 1 : jb + 2;
+      for (;;) {
+        step(std::false_type{}, q, uA, uB, bA, bB);
+        if (++q > qg) break;
+        step(std::false_type{}, q, uB, uA, bB, bA);
+        if (++q > qg) break;
+      }
+      if (phase == 0) {  // (q = ja + 2: an even number of steps lies behind, uA / bA hold the requests again)
+        uN = Ub + (size_t)(q + 1) * PB, bN = Bb + (size_t)(q + 1) * PB, wN = Wb + (size_t)(q - 2) * PB;  // (q - 2 = ja: inside the array)
+        for (; q + 1 <= qi; q += 2) {
+          step(std::true_type{}, q, uA, uB, bA, bB);
+          step(std::true_type{}, q + 1, uB, uA, bB, bA);
+        }
+      }
     }
   }
 
