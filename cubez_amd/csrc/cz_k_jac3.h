@@ -11,10 +11,43 @@
 //     LDS         u: 2 x (LV + 2R), f1, f2: 2 x LV each (by plane parity; the j-1 operand of a vector is read by the thread that wrote it)
 //     k windows   KT vectors + hv halo vectors per side; three stages reach 3 elements beyond a window: hv = 1 (FP32), 2 (FP64)
 //     planes      stage s at step q works on plane q - s + 1: f1(q) from u(q-1..q+1), f2(q-1) from f1, f3(q-2) -> W
+//     in flight   step q requests u(q+2) and b(q+1) of its own vector first of all, and -- only the waves that hold a thread of the outer
+//                 rows, after stage 1 -- the outer rows of u(q+2).  Nothing in step q waits for them: all three are first used in step
+//                 q+1, behind barrier q (u(q+2) as the j+1 operand and b(q+1) in stage 1; the outer rows are written to LDS after stage 1,
+//                 into the outer slots [0, R) and [LV + R, LV + 2R) of the buffer of u(q+2).  That buffer is step q+1's `prv` buffer, read
+//                 at [R, R + LV) only; its outer slots were last read in step q and are next read in step q+2).  The prologue primes the
+//                 outer rows of two planes.  The store of W(q-2) is younger than the requests of step q: the wait for b(q+1) in step q+1
+//                 retires it as well (gfx9 counts loads and stores in one counter, in order).  profiles/r20/jac3_requests_in_flight.txt
 // Per point: relax_vec<V, UNIT> with the hoisted IEEE division (or its checked shorter form, MED), the operations of jacobi2p_k on the same
 // values => the same bits as three single sweeps.  The three residuals (sum dp^2 of sweeps n+1, n+2, n+3) are produced and finalised in the kernel; if the first or the second
 // converges, the driver re-runs one sweep or one pair from the untouched input (out of place, like the pair).
 // ------------------------------------------------------------------------------------------------------------
+
+// The three helpers below are empty asm statements that pin what the compiler makes of the inner step (scalar-base requests, no wait on a
+// step's requests before its barrier).  They change no value.  What they achieve depends on the compiler: the listing of the inner loop in
+// profiles/r20/jac3_requests_in_flight.txt (loads, vmcnt waits, barriers, registers) is the contract to compare against after a change of
+// the toolchain; tests cannot see it.
+// A plane pointer the compiler must take as it stands: global memory, in a scalar register pair.
+template <class T>
+__device__ __forceinline__ T* uniform_global(T* p) {
+  auto g = (__attribute__((address_space(1))) T*)p;
+  asm("" : "+s"(g));
+  return (T*)g;
+}
+
+// ... and the 32-bit lane offset that goes with it, widened where it is used and not once in front of the loop.
+__device__ __forceinline__ unsigned lane_offset(unsigned o) {
+  asm("" : "+v"(o));
+  return o;
+}
+
+// A value that has to be complete at this place of the code: what is computed from it comes after, what it is computed from before.
+template <int V>
+__device__ __forceinline__ void complete_here(Vec<V>& x) {
+  static_assert(V == 2 || V == 4, "one constraint per component");
+  if constexpr (V == 4) asm volatile("" : "+v"(x.v[0]), "+v"(x.v[1]), "+v"(x.v[2]), "+v"(x.v[3]));
+  else asm volatile("" : "+v"(x.v[0]), "+v"(x.v[1]));
+}
 
 // MED = 1 (FP32): the division with one correction step (mediumdiv, cz_k_fastdiv.h), taken only for a divisor that passed the exhaustive
 // comparison with `n / d` on this context (jac3_medium, cz_h_launch.h)
@@ -45,25 +78,31 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
     const RowView<V> rv = row_view<V>(g, it);
     const int x = t;  // this thread's vector: index in E2
     const long long f = e2_0 + x;
-    const unsigned bo = rv.off_of(f);
+    unsigned bo = rv.off_of(f);  // (not const: the inner steps pass it through `lane_offset`)
     const VecMask mk = vec_mask<V>(g, it, f);
     const unsigned inbox = mk.rows ? mk.bits : 0u;                                                     // components inside the inner box (every stage updates only those)
     const unsigned own = (x >= 2 * R && x < LV - 2 * R && mk.rows && mk.kown) ? mk.bits : 0u;  // ... of a vector this workgroup owns (stores, residual counts)
     // wave-uniform: does this wave hold a vector of E1 (stage 2) / an owned vector (stage 3)?
     const bool wave2 = __builtin_amdgcn_ballot_w64(x >= R && x < LV - R) != 0ull;
     const bool wave3 = __builtin_amdgcn_ballot_w64(own != 0) != 0ull;
-    const OuterRow h = outer_row<V, TB>(rv, LV, it.fb - 3 * (long long)R, f);  // the outer rows of E3
+    OuterRow h = outer_row<V, TB>(rv, LV, it.fb - 3 * (long long)R, f);  // the outer rows of E3
+    const bool waveh = __builtin_amdgcn_ballot_w64(h.has) != 0ull;                // wave-uniform: does this wave stage a vector of them?
     const char* Ub = reinterpret_cast<const char*>(U);
     const char* Bb = reinterpret_cast<const char*>(B);
     char* Wb = reinterpret_cast<char*>(W);
 
-    // ---- prologue: the first step is q0 = ja - 2 (stage 1 on plane ja - 2): LDS u(q0 - 1) own, u(q0) on E3; in flight u(q0 + 1), b(q0)
+    // ---- prologue: the first step is q0 = ja - 2 (stage 1 on plane ja - 2): LDS u(q0 - 1) own, u(q0) on E3; in flight u(q0 + 1) with its
+    // outer rows (hx), b(q0)
     const int q0 = ja - 2;
-    Vec<V> uA, uB, bA, bB, hx;
+    Vec<V> uA, uB, bA, bB, hx = zerov<V>();
     {
       const Vec<V> t2 = ld16<V>(Ub + (size_t)rv.pl(q0 - 1) * PB, rv.lim(bo, rv.pl(q0 - 1)));
       const Vec<V> t1 = ld16<V>(Ub + (size_t)rv.pl(q0) * PB, rv.lim(bo, rv.pl(q0)));
-      const Vec<V> h1 = ld16<V>(Ub + (size_t)rv.pl(q0) * PB, rv.lim(h.bo, rv.pl(q0)));
+      Vec<V> h1 = zerov<V>();
+      if (waveh) {
+        h1 = ld16<V>(Ub + (size_t)rv.pl(q0) * PB, rv.lim(h.bo, rv.pl(q0)));
+        hx = ld16<V>(Ub + (size_t)rv.pl(q0 + 1) * PB, rv.lim(h.bo, rv.pl(q0 + 1)));
+      }
       uA = ld16<V>(Ub + (size_t)rv.pl(q0 + 1) * PB, rv.lim(bo, rv.pl(q0 + 1)));
       bA = ld16<V>(Bb + (size_t)rv.pl(q0) * PB, rv.lim(bo, rv.pl(q0)));
       ldsU[(size_t)((q0 - 1) & 1) * LU + R + x] = t2;
@@ -88,28 +127,32 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
       return relax_vec<V, UNIT>(pc, im, ip, pm, nxt, kl, kr, bb, c, dv, msk, cnt, acc);
     };
 
-    // One plane step q.  uc = u(q+1) and b1 = b(q) were requested one step ago; un / bn receive this step's requests.
+    // One plane step q.  uc = u(q+1), its outer rows hx and b1 = b(q) were requested one step ago; un / bn / hx receive this step's requests
+    // (u(q+2), b(q+1), the outer rows of u(q+2)).  b2 = b(q-1), b3 = b(q-2): the right-hand sides of stages 2 and 3.
     // Two forms.  The general one clamps every requested plane, tests it for the array's last plane and gates every stage by its plane.  The
     // INNER one is for the steps on which none of that acts -- q - 2 >= ja and q <= jb, so all three stages work on planes of the chunk, and
     // q + 2 <= jlast - 1, so no request is clamped or touches the last plane: the plane addresses are pointers carried from step to step
-    // (uN = u(q+1), bN = b(q+1), wN = w(q-2)), the masks are `inbox` and `own` as they stand.  Same loads from the same addresses, same
+    // (uN = u(q+2), bN = b(q+1), wN = w(q-2)), the masks are `inbox` and `own` as they stand.  Same loads from the same addresses, same
     // masks => the same bits; what goes is the scalar work per request (clamps, a 64-bit product, the last-plane test and its selects on the
     // load offsets) and per stage (plane gates): 5-6 % of the kernel at 512^3, profiles/r19/jac3_step_instructions.txt.
     const char* uN = Ub;
     const char* bN = Bb;
     char* wN = Wb;
-    auto step = [&](auto inner, const int q, Vec<V>& uc, Vec<V>& un, Vec<V>& b1, Vec<V>& bn) __attribute__((always_inline)) {
+    auto step = [&](auto inner, const int q, Vec<V>& uc, Vec<V>& un, Vec<V>& b1, Vec<V>& bn, Vec<V>& b2, Vec<V>& b3) __attribute__((always_inline)) {
       constexpr bool INNER = decltype(inner)::value;
+      const char *up, *bp;  // the planes u(q+2) and b(q+1) of this step's requests, and the lane offsets into them
+      unsigned uo, bo1, ho;
       if constexpr (INNER) {
-        hx = ld16<V>(uN, h.bo);
-        un = ld16<V>(uN + PB, bo);
-        bn = ld16<V>(bN, bo);
+        uN = uniform_global(uN), bN = uniform_global(bN), wN = uniform_global(wN);
+        bo = lane_offset(bo), h.bo = lane_offset(h.bo);
+        up = uN, bp = bN, uo = bo, bo1 = bo, ho = h.bo;
       } else {
         const int qu = rv.pl(q + 2 <= jb + 3 ? q + 2 : jb + 3), qb = rv.pl(q + 1 <= jb + 2 ? q + 1 : jb + 2);
-        hx = ld16<V>(Ub + (size_t)rv.pl(q + 1) * PB, rv.lim(h.bo, rv.pl(q + 1)));
-        un = ld16<V>(Ub + (size_t)qu * PB, rv.lim(bo, qu));
-        bn = ld16<V>(Bb + (size_t)qb * PB, rv.lim(bo, qb));
+        up = Ub + (size_t)qu * PB, bp = Bb + (size_t)qb * PB;
+        uo = rv.lim(bo, qu), bo1 = rv.lim(bo, qb), ho = rv.lim(h.bo, qu);
       }
+      un = ld16<V>(up, uo);
+      bn = ld16<V>(bp, bo1);
       // planes of the three stages; masks: inside the inner box a stage updates, inside the chunk the owner counts the residual
       const int p1 = q, p2 = q - 1, p3 = q - 2;
       auto upd = [&](int p) -> unsigned { return (INNER || (p >= g.jj0 && p <= g.jj1)) ? inbox : 0u; };
@@ -119,23 +162,29 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
       Vec<V>* F1 = ldsF;
       Vec<V>* F2 = ldsF + (size_t)2 * LV;
       // ---- stage 1: f1(p1) on every vector of E2
-      const Vec<V> v1 = stage(cU, pU, uc, b1, upd(p1), cnt(p1), acc1);
+      Vec<V> v1 = stage(cU, pU, uc, b1, upd(p1), cnt(p1), acc1);
+      complete_here<V>(v1);
+      // ---- the outer rows of u(q+1), requested one step ago (they landed with uc): into the buffer of u(q+1), this step's `prv` buffer, which
+      // is read at [R, R + LV) only; then the request of those of u(q+2)
+      if (waveh) {
+        if (h.has) ldsU[(size_t)((p1 + 1) & 1) * LU + h.hl] = hx;
+        hx = ld16<V>(up, ho);
+      }
       // ---- stage 2: f2(p2) from f1(p2 - 1) [LDS], f1(p2) [LDS], f1(p1) [v1]
       Vec<V> v2 = v1;  // (a wave outside E1 publishes a value no valid point reads)
-      if (wave2) v2 = stage(F1 + (size_t)(p2 & 1) * LV, F1 + (size_t)((p2 - 1) & 1) * LV, v1, bq1, upd(p2), cnt(p2), acc2);
+      if (wave2) v2 = stage(F1 + (size_t)(p2 & 1) * LV, F1 + (size_t)((p2 - 1) & 1) * LV, v1, b2, upd(p2), cnt(p2), acc2);
       // ---- stage 3: f3(p3) = the output, owned vectors of the chunk's planes.  Whole waves: the k neighbours travel by lane shifts, and the
       // lane next to the first owned vector of a window holds a halo vector -- it owns nothing but must take part.
       if ((INNER || p3 >= ja) && wave3) {
-        const Vec<V> o = stage(F2 + (size_t)(p3 & 1) * LV, F2 + (size_t)((p3 - 1) & 1) * LV, v2, bq2, own, own, acc3);
+        const Vec<V> o = stage(F2 + (size_t)(p3 & 1) * LV, F2 + (size_t)((p3 - 1) & 1) * LV, v2, b3, own, own, acc3);
         store_owned<V>(INNER ? wN : Wb + (size_t)p3 * PB, bo, own, o);
       }
-      // ---- publish: f1(p1), f2(p2) and the next u centre plane u(q+1) with its outer rows
+      // ---- publish: f1(p1), f2(p2) and the next u centre plane u(q+1) (its outer rows were written behind stage 1)
       F1[(size_t)(p1 & 1) * LV + x] = v1;
       F2[(size_t)(p2 & 1) * LV + x] = v2;
       Vec<V>* nU = ldsU + (size_t)((p1 + 1) & 1) * LU;
       nU[R + x] = uc;
-      if (h.has) nU[h.hl] = hx;
-      bq2 = bq1, bq1 = b1;  // (b1 is complete: stage 1 used it)
+      if constexpr (!INNER) b3 = b2, b2 = b1;  // (b1 is complete: stage 1 used it; the inner steps rotate the four sets by name)
       if constexpr (INNER) uN += PB, bN += PB, wN += PB;
       __syncthreads();
     };
@@ -144,9 +193,14 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
     // The march, steps q0 = ja - 2 .. jb + 2, in three parts:
     //   phase 0   q0 .. ja + 1: the four steps that fill the pipeline, general form.  Always four (ja <= jb, so ja + 1 < jb + 2): two A/B pairs,
     //             so uA / bA hold the pending requests again when it ends, at q = ja + 2
-    //   inner     q = ja + 2 .. qi in A/B pairs, while a whole pair fits (q + 1 <= qi); none for chunks of fewer than four planes
-    //   phase 1   from where the inner steps stopped to jb + 2, general form: at least jb + 1 and jb + 2, one more where an odd inner step
-    //             was left over, two more where the chunk ends at the array's last inner plane (jb = jlast - 2, qi = jb - 1)
+    //   inner     q = ja + 2 .. qi in groups of four, while a whole group fits (q + 3 <= qi); none for chunks of fewer than six planes.  Four,
+    //             because b lives for three steps (stages 1, 2, 3) plus the step that requests it: the four register sets bA, bB, bq1, bq2
+    //             rotate BY NAME and are back in place after four steps, the two u sets after every two.  (In A/B pairs the b sets rotated
+    //             by copies, which the compiler put at the loop head, in front of a wait for everything outstanding.)
+    //   phase 1   from where the inner steps stopped to jb + 2, general form (it rotates b by copies): at least jb + 1 and jb + 2, and in front
+    //             of them the steps up to jb that no whole group of four took -- up to three.  Where the chunk ends at the array's last inner
+    //             plane (jb = jlast - 2) the inner form ends one step earlier, qi = jlast - 3 = jb - 1: step jb requests the array's last
+    //             plane and takes the general form in any case, and the up to three left-over steps lie in front of it
     // The general loop is ONE copy in the code, run once per phase (nounroll: two copies would cost code size for nothing).
     const int qi = jb < g.jlast - 3 ? jb : g.jlast - 3;  // the last step that may take the inner form: q <= jb and q + 2 <= jlast - 1
     int q = q0;
@@ -154,16 +208,18 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
     for (int phase = 0; phase < 2; phase++) {
       const int qg = phase == 0 ? ja + 1 : jb + 2;
       for (;;) {
-        step(std::false_type{}, q, uA, uB, bA, bB);
+        step(std::false_type{}, q, uA, uB, bA, bB, bq1, bq2);
         if (++q > qg) break;
-        step(std::false_type{}, q, uB, uA, bB, bA);
+        step(std::false_type{}, q, uB, uA, bB, bA, bq1, bq2);
         if (++q > qg) break;
       }
-      if (phase == 0) {  // (q = ja + 2: an even number of steps lies behind, uA / bA hold the requests again)
-        uN = Ub + (size_t)(q + 1) * PB, bN = Bb + (size_t)(q + 1) * PB, wN = Wb + (size_t)(q - 2) * PB;  // (q - 2 = ja: inside the array)
-        for (; q + 1 <= qi; q += 2) {
-          step(std::true_type{}, q, uA, uB, bA, bB);
-          step(std::true_type{}, q + 1, uB, uA, bB, bA);
+      if (phase == 0) {  // (q = ja + 2: an even number of steps lies behind, uA / bA hold the requests again, bq1 / bq2 = b(q-1), b(q-2))
+        uN = Ub + (size_t)(q + 2) * PB, bN = Bb + (size_t)(q + 1) * PB, wN = Wb + (size_t)(q - 2) * PB;  // (q - 2 = ja: inside the array)
+        for (; q + 3 <= qi; q += 4) {
+          step(std::true_type{}, q, uA, uB, bA, bB, bq1, bq2);
+          step(std::true_type{}, q + 1, uB, uA, bB, bq2, bA, bq1);
+          step(std::true_type{}, q + 2, uA, uB, bq2, bq1, bB, bA);
+          step(std::true_type{}, q + 3, uB, uA, bq1, bA, bq2, bB);
         }
       }
     }
