@@ -54,7 +54,7 @@ inline const CzVarDef* cz_var_defs() {
       {"CZ_MG_TAIL", "1", "PCG with mg: the coarse levels that fit one workgroup's LDS in one launch (mg_tail_k; 0 = level by level, same bits)"},
       {"CZ_MG_GATHER", "32768", "PCG with mg, decomposed runs: the first coarse level of at most this many global points is all-gathered and run on every rank (same bits for any value)"},
       {"CZ_MGRB_ZERO4", "1", "PCG with mgrb: level 0's two iterations from zero as one two-iteration pass (rb4_k) over a cleared array where that pass takes the box (0 = the from-zero pass and a one-iteration pass; same bits)"},
-      {"CZ_FIELD_FORM", "0", "cz_set_rhs / cz_set_field / cz_get_field: 0 = the kernel form the strides allow (k rows, tile transpose, generic), 3 = always the generic form (same bytes)"},
+      {"CZ_FIELD_FORM", "0", "cz_set_rhs / cz_set_field / cz_get_field and the residual, correction and projection entries: 0 = the kernel form the strides allow (k rows, tile transpose, generic), 3 = always the generic form (same bytes)"},
       {"CZ_SPH", "0", "write p_%05d.sph / e_%05d.sph like the reference's -D_aurora_=1 build (cz_utility.f90:17-47)"},
       {"CZ_PROFILE", "1", "cz command line: write profiling.txt (cz_Evaluate.cpp:506-545)"},
       {"CZ_TEST_SKEW", "", "test aid \"rank,milliseconds\": that rank sleeps before every look at the convergence flag"},

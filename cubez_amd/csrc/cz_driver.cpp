@@ -1634,6 +1634,81 @@ void CZ::Field(REAL_TYPE* host) const {
   czhip_d2h(host, P, padded_cells() * sizeof(REAL_TYPE));
 }
 
+// What FieldIO and ProjectIO share.  field_check: NULL, alignment, strides; *span = the elements the strides cover.  nullptr, or the refusal's line
+const char* CZ::field_check(const void* a, int abytes, const long long* stride, long long* span) const {
+  if (!a || !stride) return "NULL pointer";
+  if (reinterpret_cast<uintptr_t>(a) & (uintptr_t)(abytes - 1)) return "the array is not aligned to its element size";
+  for (int d = 0; d < 3; d++)
+    if (stride[d] < 1) return "strides must be positive (elements)";
+  *span = 1;
+  for (int d = 0; d < 3; d++) *span += (long long)(size[d] - 1) * stride[d];
+  return nullptr;
+}
+// two cells of a destination must not share an element.  Accepted: ordered by stride, every stride is at least the span of the
+// directions below it (dense arrays in any order of the directions, and slices of them); directions of one cell do not count
+const char* CZ::field_distinct(const long long* stride) const {
+  int o[3] = {0, 1, 2};
+  std::sort(o, o + 3, [&](int x, int y) { return stride[x] < stride[y]; });
+  long long below = 1;  // span of the directions already passed
+  for (int n = 0; n < 3; n++) {
+    const int d = o[n];
+    if (size[d] == 1) continue;
+    if (stride[d] < below) return "two cells of the destination share an element under these strides";
+    below += (long long)(size[d] - 1) * stride[d];
+  }
+  return nullptr;
+}
+const char* CZ::field_on_device(const void* a) const {
+  hipPointerAttribute_t at;
+  int cur = -1;
+  HIP_CHECK(hipGetDevice(&cur));
+  if (hipPointerGetAttributes(&at, a) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != cur) {
+    (void)hipGetLastError();
+    return "not a pointer to memory of the handle's device";
+  }
+  return nullptr;
+}
+// the compute stream waits for what the caller's stream holds (NULL: nothing to wait for)
+void CZ::field_wait_for(void* user_stream) {
+  if (!user_stream) return;
+  if (!ev_io) HIP_CHECK(hipEventCreateWithFlags(&ev_io, hipEventDisableTiming));
+  HIP_CHECK(hipEventRecord(ev_io, (hipStream_t)user_stream));
+  HIP_CHECK(hipStreamWaitEvent(stream(), ev_io, 0));
+}
+// the caller's stream waits for the compute stream; NULL, or host_waits (a host value is due on return): the host waits for the compute stream
+void CZ::field_hand_back(void* user_stream, bool host_waits) {
+  if (user_stream) {
+    HIP_CHECK(hipEventRecord(ev_io, stream()));
+    HIP_CHECK(hipStreamWaitEvent((hipStream_t)user_stream, ev_io, 0));
+  }
+  if (!user_stream || host_waits) HIP_CHECK(hipStreamSynchronize(stream()));
+}
+// the device buffer host arrays go through, of `bytes` at least
+void* CZ::field_stage(size_t bytes) {
+  if (bytes > io_stage_cap) {
+    if (io_stage) {
+      HIP_CHECK(hipStreamSynchronize(stream()));
+      HIP_CHECK(hipFree(io_stage));
+    }
+    HIP_CHECK(hipMalloc(&io_stage, bytes));
+    io_stage_cap = bytes;
+  }
+  return io_stage;
+}
+// the brick's cells and nothing else from a copy `tmp` of the span into the caller's array, the direction of the smallest stride innermost
+void CZ::field_copy_cells(void* a, const void* tmp, int abytes, const long long* stride) const {
+  int o[3] = {0, 1, 2};
+  std::sort(o, o + 3, [&](int x, int y) { return stride[x] > stride[y]; });
+  const long long s0 = stride[o[0]], s1 = stride[o[1]], s2 = stride[o[2]];
+  unsigned char* out = static_cast<unsigned char*>(a);
+  const unsigned char* in = static_cast<const unsigned char*>(tmp);
+  for (int x = 0; x < size[o[0]]; x++)
+    for (int y = 0; y < size[o[1]]; y++) {
+      const long long base = x * s0 + y * s1;
+      for (int z = 0; z < size[o[2]]; z++) memcpy(out + (size_t)(base + z * s2) * abytes, in + (size_t)(base + z * s2) * abytes, (size_t)abytes);
+    }
+}
+
 // The caller's problem: import into RHS / P, export of P (cz_set_rhs, cz_set_field, cz_get_field), and the two operations of
 // mixed-precision refinement, the residual of P out and a correction into P (cz_get_residual, cz_add_field), whose caller's
 // side holds float or double (abytes).  Device arrays are handed
@@ -1659,54 +1734,20 @@ int CZ::FieldIO(int which, void* a, int abytes, const long long* stride, int on_
     if (!none && abytes != 4 && abytes != 8) return refuse("the element size must be 4 or 8 bytes");
   }
   long long span = 1;
-  if (!none) {
-    if (!a || !stride) return refuse("NULL pointer");
-    if (reinterpret_cast<uintptr_t>(a) & (uintptr_t)(abytes - 1)) return refuse("the array is not aligned to its element size");
-    for (int d = 0; d < 3; d++)
-      if (stride[d] < 1) return refuse("strides must be positive (elements)");
-    for (int d = 0; d < 3; d++) span += (long long)(size[d] - 1) * stride[d];
-  }
-  if (to_user && !none) {
-    // two cells of a destination must not share an element.  Accepted: ordered by stride, every stride is at least the span of the
-    // directions below it (dense arrays in any order of the directions, and slices of them); directions of one cell do not count
-    int o[3] = {0, 1, 2};
-    std::sort(o, o + 3, [&](int x, int y) { return stride[x] < stride[y]; });
-    long long below = 1;  // span of the directions already passed
-    for (int n = 0; n < 3; n++) {
-      const int d = o[n];
-      if (size[d] == 1) continue;
-      if (stride[d] < below) return refuse("two cells of the destination share an element under these strides");
-      below += (long long)(size[d] - 1) * stride[d];
-    }
-  }
+  if (!none)
+    if (const char* why = field_check(a, abytes, stride, &span)) return refuse(why);
+  if (to_user && !none)
+    if (const char* why = field_distinct(stride)) return refuse(why);
   hipStream_t st = stream();
   REAL_TYPE* arr = which == 0 ? RHS : P;
   void* dev = a;
   const size_t span_bytes = (size_t)span * (size_t)abytes;
   if (none) {
   } else if (on_device) {
-    hipPointerAttribute_t at;
-    int cur = -1;
-    HIP_CHECK(hipGetDevice(&cur));
-    if (hipPointerGetAttributes(&at, a) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != cur) {
-      (void)hipGetLastError();
-      return refuse("not a pointer to memory of the handle's device");
-    }
-    if (user_stream) {
-      if (!ev_io) HIP_CHECK(hipEventCreateWithFlags(&ev_io, hipEventDisableTiming));
-      HIP_CHECK(hipEventRecord(ev_io, (hipStream_t)user_stream));
-      HIP_CHECK(hipStreamWaitEvent(st, ev_io, 0));
-    }
+    if (const char* why = field_on_device(a)) return refuse(why);
+    field_wait_for(user_stream);
   } else {
-    if (span_bytes > io_stage_cap) {
-      if (io_stage) {
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipFree(io_stage));
-      }
-      HIP_CHECK(hipMalloc(&io_stage, span_bytes));
-      io_stage_cap = span_bytes;
-    }
-    dev = io_stage;
+    dev = field_stage(span_bytes);
     // (an export fills the brick's cells of the device span only; the host copies exactly those cells below -- the other elements of the
     // caller's span are not the library's to touch: they may be another rank's cells of one shared array)
     if (!to_user) HIP_CHECK(hipMemcpyAsync(dev, a, span_bytes, hipMemcpyHostToDevice, st));
@@ -1748,25 +1789,81 @@ int CZ::FieldIO(int which, void* a, int abytes, const long long* stride, int on_
       HIP_CHECK(hipMemcpyAsync(tmp.data(), dev, span_bytes, hipMemcpyDeviceToHost, st));
     }
     HIP_CHECK(hipStreamSynchronize(st));
-    if (to_user) {  // the brick's cells and nothing else, the direction of the smallest stride innermost
-      int o[3] = {0, 1, 2};
-      std::sort(o, o + 3, [&](int x, int y) { return stride[x] > stride[y]; });
-      const long long s0 = stride[o[0]], s1 = stride[o[1]], s2 = stride[o[2]];
-      unsigned char* out = static_cast<unsigned char*>(a);
-      for (int x = 0; x < size[o[0]]; x++)
-        for (int y = 0; y < size[o[1]]; y++) {
-          const long long base = x * s0 + y * s1;
-          for (int z = 0; z < size[o[2]]; z++) memcpy(out + (size_t)(base + z * s2) * abytes, tmp.data() + (size_t)(base + z * s2) * abytes, (size_t)abytes);
-        }
-    }
-  } else if (user_stream) {
-    HIP_CHECK(hipEventRecord(ev_io, st));
-    HIP_CHECK(hipStreamWaitEvent((hipStream_t)user_stream, ev_io, 0));
-    if (op == FIO_RESIDUAL) HIP_CHECK(hipStreamSynchronize(st));  // (the one wait: the sum is a host value on return)
+    if (to_user) field_copy_cells(a, tmp.data(), abytes, stride);
   } else {
-    HIP_CHECK(hipStreamSynchronize(st));
+    field_hand_back(user_stream, op == FIO_RESIDUAL);  // (the one wait with a stream: the sum is a host value on return)
   }
   if (op == FIO_RESIDUAL) *sumsq = h_scal[10];
+  return 1;
+}
+
+// The projection step on a staggered velocity (cz_set_rhs_div, cz_sub_grad): vel = the three components, bricks of REAL_TYPE
+// with one stride triple.  PRJ_DIV: RHS = div vel scale, then what cz_set_rhs does after its import; *sumsq (may be NULL) = sum div^2.
+// PRJ_GRAD: vel = vel - grad P scale in place, P's face layers re-made first.  Checks, hand-over and staging are FieldIO's; every refusal
+// comes before the first launch.
+int CZ::ProjectIO(int op, REAL_TYPE* const* vel, const long long* stride, int on_device, void* user_stream, double scale, double* sumsq, const char* who) {
+  auto refuse = [&](const char* why) {
+    fprintf(stderr, "%s: %s\n", who, why);
+    return 0;
+  };
+  const int abytes = (int)sizeof(REAL_TYPE);
+  if (!set_up) return refuse("no problem is set up (cz_setup first)");
+  if (SW_maf) return refuse("the handle's operator is a MAF one, not the unit-coefficient operator");
+  if (numProc > 1)
+    return refuse("a decomposed run: faces between bricks need an exchange of one velocity layer, which is the follow-up (single domain only)");
+  const REAL_TYPE rs = (REAL_TYPE)scale;
+  if (!(scale > 0.0) || !std::isfinite(scale) || !(rs > (REAL_TYPE)0) || !std::isfinite(rs)) return refuse("the scale must be finite and positive");
+  long long span = 1;
+  for (int c = 0; c < 3; c++)
+    if (const char* why = field_check(vel[c], abytes, stride, &span)) return refuse(why);
+  if (op == PRJ_GRAD) {
+    if (const char* why = field_distinct(stride)) return refuse(why);
+    if (vel[0] == vel[1] || vel[0] == vel[2] || vel[1] == vel[2]) return refuse("two components of the velocity are the same array");
+  }
+  if (on_device)
+    for (int c = 0; c < 3; c++)
+      if (const char* why = field_on_device(vel[c])) return refuse(why);
+  hipStream_t st = stream();
+  const size_t span_bytes = (size_t)span * (size_t)abytes;
+  REAL_TYPE* dev[3] = {vel[0], vel[1], vel[2]};
+  if (on_device) {
+    field_wait_for(user_stream);
+  } else {
+    unsigned char* stage = static_cast<unsigned char*>(field_stage(3 * span_bytes));
+    for (int c = 0; c < 3; c++) {
+      dev[c] = reinterpret_cast<REAL_TYPE*>(stage + (size_t)c * span_bytes);
+      HIP_CHECK(hipMemcpyAsync(dev[c], vel[c], span_bytes, hipMemcpyHostToDevice, st));
+    }
+  }
+  const int form = field_form == 3 ? 3 : 0;
+  if (op == PRJ_DIV) {
+    last_field_form = field_div_async(RHS, dev[0], dev[1], dev[2], size, GUIDE, stride, periodic_mask, scale, form, d_res + 10);
+  } else {
+    mirror(P);
+    last_field_form = field_grad_async(dev[0], dev[1], dev[2], P, size, GUIDE, stride, periodic_mask, scale, form);
+  }
+  if (!last_field_form) return refuse("no kernel form takes these strides");
+  if (op == PRJ_DIV) {
+    if (closed_box) {  // (as cz_set_rhs: the closed box keeps the right-hand side compatible)
+      if (!project_rhs()) return 0;
+    } else if (!Comm_S2(RHS)) {
+      return 0;
+    }
+    if (sumsq) HIP_CHECK(hipMemcpyAsync(h_scal + 10, d_res + 10, sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  if (!on_device) {
+    std::vector<unsigned char> tmp;
+    if (op == PRJ_GRAD) {
+      tmp.resize(3 * span_bytes);
+      HIP_CHECK(hipMemcpyAsync(tmp.data(), dev[0], 3 * span_bytes, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (op == PRJ_GRAD)
+      for (int c = 0; c < 3; c++) field_copy_cells(vel[c], tmp.data() + (size_t)c * span_bytes, abytes, stride);
+  } else {
+    field_hand_back(user_stream, op == PRJ_DIV && sumsq);  // (a sum asked for is a host value on return; without one no host wait)
+  }
+  if (op == PRJ_DIV && sumsq) *sumsq = h_scal[10];
   return 1;
 }
 
@@ -2002,6 +2099,15 @@ int cz_get_residual(cz_handle* h, void* dst, int dst_real_bytes, const long long
 }
 int cz_add_field(cz_handle* h, const void* src, int src_real_bytes, const long long* stride, int on_device, void* ready_stream, double scale) {
   return h ? h->cz.FieldIO(1, const_cast<void*>(src), src_real_bytes, stride, on_device, ready_stream, CZ::FIO_ADD, scale, nullptr, "cz_add_field") : 0;
+}
+int cz_set_rhs_div(cz_handle* h, const CZ_REAL* u, const CZ_REAL* v, const CZ_REAL* w, const long long* stride, int on_device, void* ready_stream, double scale,
+                   double* sumsq) {
+  CZ_REAL* const vel[3] = {const_cast<CZ_REAL*>(u), const_cast<CZ_REAL*>(v), const_cast<CZ_REAL*>(w)};
+  return h ? h->cz.ProjectIO(CZ::PRJ_DIV, vel, stride, on_device, ready_stream, scale, sumsq, "cz_set_rhs_div") : 0;
+}
+int cz_sub_grad(cz_handle* h, CZ_REAL* u, CZ_REAL* v, CZ_REAL* w, const long long* stride, int on_device, void* stream, double scale) {
+  CZ_REAL* const vel[3] = {u, v, w};
+  return h ? h->cz.ProjectIO(CZ::PRJ_GRAD, vel, stride, on_device, stream, scale, nullptr, "cz_sub_grad") : 0;
 }
 int cz_set_neumann(cz_handle* h, const int* faces) { return h ? h->cz.SetNeumann(faces) : 0; }
 int cz_set_closed_box(cz_handle* h, int on) { return h ? h->cz.SetClosedBox(on) : 0; }

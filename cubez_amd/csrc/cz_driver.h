@@ -144,6 +144,18 @@ class CZ {
   enum { FIO_IMPORT = 0, FIO_EXPORT = 1, FIO_RESIDUAL = 2, FIO_ADD = 3 };
   int FieldIO(int which, void* a, int abytes, const long long* stride, int on_device, void* user_stream, int op, double scale, double* sumsq,
               const char* who);
+  // the projection step on a staggered velocity (cz_set_rhs_div, cz_sub_grad): vel[3] = u, v, w, bricks with one stride triple.
+  // PRJ_DIV: RHS = div vel scale, *sumsq (may be NULL) = sum div^2; PRJ_GRAD: vel = vel - grad P scale in place.  Single domain.
+  enum { PRJ_DIV = 0, PRJ_GRAD = 1 };
+  int ProjectIO(int op, REAL_TYPE* const* vel, const long long* stride, int on_device, void* user_stream, double scale, double* sumsq, const char* who);
+  // what the two share: the checks (nullptr, or the refusal's line), the event hand-over, the staging of host arrays
+  const char* field_check(const void* a, int abytes, const long long* stride, long long* span) const;
+  const char* field_distinct(const long long* stride) const;
+  const char* field_on_device(const void* a) const;
+  void field_wait_for(void* user_stream);
+  void field_hand_back(void* user_stream, bool host_waits);
+  void* field_stage(size_t bytes);
+  void field_copy_cells(void* a, const void* tmp, int abytes, const long long* stride) const;
   int SetNeumann(const int* faces);  // cz_set_neumann: 1, or 0 with one line on stderr and nothing changed
   int SetClosedBox(int on);          // cz_set_closed_box: likewise
   int SetPeriodic(const int* dirs);  // cz_set_periodic: likewise

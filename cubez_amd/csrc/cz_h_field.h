@@ -134,3 +134,48 @@ int field_add_async(REAL* p, const void* user, int user_bytes, const int* sz, co
   if (user_bytes == 4) return field_add_launch<float>(p, static_cast<const float*>(user), idx, fg, (REAL)scale, form);
   return field_add_launch<double>(p, static_cast<const double*>(user), idx, fg, (REAL)scale, form);
 }
+
+// The projection step (cz_k_project.h).  u, v, w: the staggered velocity, three bricks with one stride triple; per: the
+// periodic directions (bit d).  form: 0 = the row form where s2 == 1, else the generic one; 3 = generic.  Returns the form taken, 0 = refused.
+// field_div_async: rhs = div (REAL)scale at the inner cells, 0 at the brick's other cells, sumsq_dev[0] = sum div^2 of the unscaled div.
+static int proj_form_of(const FieldGeom& fg, int form, int slots) {
+  if (form != 0 && form != 3) return 0;
+  return (form == 0 && fg.s2 == 1 && (long long)fg.ni * slots <= 0x7ff00000LL) ? 1 : 3;
+}
+int field_div_async(REAL* rhs, const REAL* u, const REAL* v, const REAL* w, const int* sz, int g, const long long* stride, int per, double scale, int form,
+                    double* sumsq_dev) {
+  ensure_init();
+  FieldGeom fg;
+  if (!rhs || !u || !v || !w || !sumsq_dev || !field_geom(fg, sz, g, stride)) return 0;
+  const int slots = (fg.nk + 2 * VW - 2) / VW;
+  const int take = proj_form_of(fg, form, slots);
+  if (!take) return 0;
+  // about 4096 workgroups in all, each walking its share of a plane: every workgroup ends with one ticket on one counter, and a workgroup per
+  // 256 runs (132 096 of them at 512^3) spent three quarters of the kernel's time queueing there (profiles/r19/project.txt)
+  const unsigned gy = (unsigned)std::min(fg.nj, 65535);
+  const long long need = (take == 1 ? (long long)fg.ni * slots + 255 : (long long)fg.ni * fg.nk + 255) / 256;
+  const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>(need, 4096 / gy));
+  ensure_partials((size_t)gx * gy);
+  ScopedTimer tm(LBL_FIELD);
+  if (take == 1) hipLaunchKernelGGL((div_row_k<VW>), dim3(gx, gy), dim3(256), 0, ctx.stream, rhs, u, v, w, fg, per, (REAL)scale, slots, ctx.partials, sumsq_dev, ctx.counter);
+  else hipLaunchKernelGGL(div_any_k, dim3(gx, gy), dim3(256), 0, ctx.stream, rhs, u, v, w, fg, per, (REAL)scale, ctx.partials, sumsq_dev, ctx.counter);
+  HIP_CHECK(hipGetLastError());
+  return take;
+}
+// field_grad_async: u(i) = u(i) - (p(i + 1) - p(i)) (REAL)scale on the faces 0 .. n - 2 at inner tangential cells, v and w likewise; p's face
+// layers as the caller left them; face 0 of a periodic direction = face n - 2
+int field_grad_async(REAL* u, REAL* v, REAL* w, const REAL* p, const int* sz, int g, const long long* stride, int per, double scale, int form) {
+  ensure_init();
+  FieldGeom fg;
+  if (!p || !u || !v || !w || !field_geom(fg, sz, g, stride)) return 0;
+  const int slots = (fg.nk + 2 * VW - 2) / VW;
+  const int take = proj_form_of(fg, form, slots);
+  if (!take) return 0;
+  const unsigned gy = (unsigned)std::min(fg.nj, 65535);
+  const unsigned gx = (unsigned)std::min<long long>((take == 1 ? (long long)fg.ni * slots + 255 : (long long)fg.ni * fg.nk + 255) / 256, 4096);
+  ScopedTimer tm(LBL_FIELD);
+  if (take == 1) hipLaunchKernelGGL((grad_row_k<VW>), dim3(gx, gy), dim3(256), 0, ctx.stream, u, v, w, p, fg, per, (REAL)scale, slots);
+  else hipLaunchKernelGGL(grad_any_k, dim3(gx, gy), dim3(256), 0, ctx.stream, u, v, w, p, fg, per, (REAL)scale);
+  HIP_CHECK(hipGetLastError());
+  return take;
+}

@@ -138,6 +138,13 @@ int field_copy_async(CZ_REAL* arr, CZ_REAL* user, const int* sz, int g, const lo
 int field_residual_async(const CZ_REAL* p, const CZ_REAL* rhs, CZ_REAL* wrk, void* user, int user_bytes, const int* sz, const int* idx, int g,
                          const long long* stride, const CZ_REAL* cf, double scale, int form, double* sumsq_dev);
 int field_add_async(CZ_REAL* p, const void* user, int user_bytes, const int* sz, const int* idx, int g, const long long* stride, double scale, int form);
+// cz_set_rhs_div / cz_sub_grad (cz_k_project.h, cz_h_field.h): u, v, w are the staggered velocity, three bricks with one stride
+// triple; per: the periodic directions (bit d).  field_div_async: rhs = div (REAL)scale at the inner cells, 0 at the brick's other cells,
+// sumsq_dev[0] = sum div^2 (unscaled).  field_grad_async: u(i) -= (p(i + 1) - p(i)) (REAL)scale on the faces 0 .. n - 2, v and w likewise.
+// form: 0 = the row form where stride[2] == 1, else the generic one; 3 = generic.  Return the form taken (1 | 3), 0 = refused.
+int field_div_async(CZ_REAL* rhs, const CZ_REAL* u, const CZ_REAL* v, const CZ_REAL* w, const int* sz, int g, const long long* stride, int per,
+                    double scale, int form, double* sumsq_dev);
+int field_grad_async(CZ_REAL* u, CZ_REAL* v, CZ_REAL* w, const CZ_REAL* p, const int* sz, int g, const long long* stride, int per, double scale, int form);
 void bc_async(const int* sz, int g, CZ_REAL* p, CZ_REAL dh, const CZ_REAL* org, const int* nID, int ioff = 0, int joff = 0);
 
 // ---- the multigrid V-cycle of pcg ... mg (cz_h_mg.h, and cz_mg_dist.cpp for decomposed runs)

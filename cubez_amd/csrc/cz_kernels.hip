@@ -53,6 +53,7 @@ namespace {
 #include "cz_k_mg.h"
 #include "cz_k_field.h"
 #include "cz_k_resid.h"
+#include "cz_k_project.h"
 #include "cz_h_ctx.h"
 #include "cz_h_launch.h"
 

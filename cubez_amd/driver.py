@@ -42,6 +42,8 @@ class CZ:
             getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_int, C.c_void_p]
         lib.cz_get_residual.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_double, C.POINTER(C.c_double)]
         lib.cz_add_field.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_double]
+        lib.cz_set_rhs_div.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_double, C.POINTER(C.c_double)]
+        lib.cz_sub_grad.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_double]
         lib.cz_set_eps.argtypes = [C.c_void_p, C.c_double]
         lib.cz_set_neumann.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         lib.cz_set_closed_box.argtypes = [C.c_void_p, C.c_int]
@@ -193,6 +195,45 @@ class CZ:
         if self.lib.cz_add_field(self.h, C.c_void_p(ptr), self._itemsize(a), (C.c_longlong * 3)(*strides), on_dev,
                                  C.c_void_p(stream) if stream else None, float(scale)) != 1:
             raise RuntimeError("add_field: refused (see stderr)")
+
+    # -- the projection step on a staggered velocity (cz_set_rhs_div / cz_sub_grad of include/cz_hip.h): u, v, w of the brick's
+    # shape, u[i, j, k] the normal velocity on the face between cells i and i + 1 (the last entry along its own direction is never touched),
+    # v and w the same along j and k; three arrays of equal strides (three tensors of one layout, or vel[..., 0], vel[..., 1], vel[..., 2])
+    def _velocity(self, u, v, w, what):
+        parts = [self._brick(a, f"{what}: {n}") for a, n in zip((u, v, w), "uvw")]
+        ptr0, strides, on_dev, stream, ts = parts[0]
+        if any(q[1] != strides for q in parts[1:]):
+            raise ValueError(f"{what}: the three components must have equal strides, not {[q[1] for q in parts]}")
+        if any(q[2] != on_dev for q in parts[1:]):
+            raise ValueError(f"{what}: the three components must be all numpy arrays or all device tensors")
+        if on_dev and stream is None:
+            ts.synchronize()
+        return [C.c_void_p(q[0]) for q in parts], (C.c_longlong * 3)(*strides), on_dev, C.c_void_p(stream) if stream else None
+
+    def set_rhs_div(self, u, v, w, scale=1.0, want_norm=True):
+        """the right-hand side b = (discrete divergence of the staggered velocity) * scale at the inner cells, 0 elsewhere, and what set_rhs does
+        after its import; returns the sum of div^2 (unscaled, in double) over the inner cells, or None with want_norm=False (then device
+        tensors are handed over on torch's current stream without a host wait).  Single domain"""
+        ptrs, strides, on_dev, stream = self._velocity(u, v, w, "set_rhs_div")
+        ss = C.c_double(0.0)
+        if self.lib.cz_set_rhs_div(self.h, *ptrs, strides, on_dev, stream, float(scale), C.byref(ss) if want_norm else None) != 1:
+            raise RuntimeError("set_rhs_div: refused (see stderr)")
+        return ss.value if want_norm else None
+
+    def sub_grad(self, u, v, w, scale=1.0):
+        """u[i, j, k] -= (p[i + 1, j, k] - p[i, j, k]) * scale on the faces at inner j, k, in place (p: the field in the handle, its face layers
+        the mirror / the wrap / the Dirichlet values); v and w the same along j and k.  Single domain"""
+        ptrs, strides, on_dev, stream = self._velocity(u, v, w, "sub_grad")
+        if self.lib.cz_sub_grad(self.h, *ptrs, strides, on_dev, stream, float(scale)) != 1:
+            raise RuntimeError("sub_grad: refused (see stderr)")
+
+    def project(self, u, v, w):
+        """the projection step: set_rhs_div, solve, sub_grad at scale 1 (a uniform scale cancels between the two: A p = s div u and
+        u -= grad p / s); returns (iterations, sum of div^2 before).  Afterwards the divergence of (u, v, w) is the residual of the solve"""
+        ss = self.set_rhs_div(u, v, w)
+        itr = self.solve()
+        self.sub_grad(u, v, w)
+        return itr, ss
 
     @staticmethod
     def _itemsize(a):

@@ -485,6 +485,36 @@ int cz_get_field(cz_handle*, CZ_REAL* dst, const long long* stride, int on_devic
  * a scale that is not finite and positive (as given and as CZ_REAL), a handle set up with a _maf solver (its operator is not the unit one). */
 int cz_get_residual(cz_handle*, void* dst, int dst_real_bytes, const long long* stride, int on_device, void* done_stream, double scale, double* sumsq);
 int cz_add_field(cz_handle*, const void* src, int src_real_bytes, const long long* stride, int on_device, void* ready_stream, double scale);
+/* The projection step on a staggered velocity: the discrete divergence of a velocity straight into the right-hand side, and
+ * the gradient of the field subtracted from the velocity in place.  Single domain only.  With the handle's solver in between,
+ *   cz_set_rhs_div(h, u, v, w, ...);  cz_solve(h);  cz_sub_grad(h, u, v, w, ...);          (both at the same scale)
+ * leaves a velocity whose discrete divergence is the residual of the solve: div(u - grad p) = div u - (sum of neighbours - 6 p), exactly,
+ * with the face layers of cz_set_neumann (the mirror) and cz_set_periodic (the wrap) as they are.
+ * The grid: the brick's cells are 1 .. n_d (n_d = size[d]), the inner cells 2 .. n_d - 1.  u, v, w are three arrays of the brick's shape that
+ * share ONE stride triple, laid out and handed over as for cz_set_field (three tensors of equal layout, or the three components of one
+ * vel[..., 3]).  u(i, j, k) is the normal velocity on the face between cells i and i + 1 in X, i = 1 .. n_0 - 1; entry i = n_0 is never read
+ * or written; v and w are the same along j and k.  In a periodic direction cell 1 is cell n - 1 and cell n is cell 2, so face 1 is an alias
+ * of face n - 1: on input face 1 is ignored and face n - 1 read in its place, on output face 1 receives the value of face n - 1.  Nothing
+ * else depends on the boundary state: on a zero-flux face the wall-normal velocity u(1) or u(n - 1) is the caller's datum (0 for a wall, the
+ * inflow for an inflow plane), enters the divergence like any face, and is left alone by the gradient because the mirror makes
+ * p(2) - p(1) = 0; on a Dirichlet face p(1) is the given value and the face is corrected like any other.
+ *   cz_set_rhs_div  at every inner cell, each operation rounded once in CZ_REAL:  dx = u(i) - u(i-1), dy = v(j) - v(j-1), dz = w(k) - w(k-1),
+ *     d = (dx + dy) + dz, RHS = d * (CZ_REAL)scale; the brick's other cells of RHS get 0.  Afterwards exactly what cz_set_rhs does after its
+ *     import (in closed-box mode the mean is removed and cz_closed_mean(h, 0) reports it).  *sumsq (a host pointer, written on return) = the
+ *     sum of d^2 of the unscaled d over the inner cells, every square and the sum in double, the same bits from run to run.  sumsq = NULL:
+ *     no sum is reported, and with a device array and a stream the call is a pure event hand-over without a host wait.
+ *   cz_sub_grad     u(i, j, k) = u(i, j, k) - (p(i+1, j, k) - p(i, j, k)) * (CZ_REAL)scale for i = 1 .. n_0 - 1 and inner j, k -- one subtraction,
+ *     one multiplication and one subtraction, each rounded once -- v and w the same along their directions; p is the field in the handle, its
+ *     face layers re-made first as cz_get_residual does.  Faces whose tangential index lies on a boundary layer, and entry n, are not
+ *     written; of a host array no element outside the brick is written.  In a periodic direction face 1 is written with the value of face n - 1.
+ * Return 1, or 0 with one line on stderr and nothing changed: before cz_setup, a NULL array or stride, a stride < 1, an array that is not
+ * aligned to CZ_REAL, a pointer that is not on the handle's device, a scale that is not finite and positive (as given and as CZ_REAL), a
+ * handle set up with a _maf solver, a decomposed run (faces between bricks need an exchange of one velocity layer: the follow-up); for
+ * cz_sub_grad also strides under which two cells of one component share an element (the rule of cz_get_field) and two components given the
+ * same pointer.  Accepted on a handle of any other solver; cz_solve keeps its own rules about masks and flags. */
+int cz_set_rhs_div(cz_handle*, const CZ_REAL* u, const CZ_REAL* v, const CZ_REAL* w, const long long* stride, int on_device, void* ready_stream,
+                   double scale, double* sumsq);
+int cz_sub_grad(cz_handle*, CZ_REAL* u, CZ_REAL* v, CZ_REAL* w, const long long* stride, int on_device, void* stream, double scale);
 /* Zero-flux (Neumann) faces for pcg: faces[6], order X-, X+, Y-, Y+, Z-, Z+ of the GLOBAL box (the order of nID), non-zero =
  * the face is a zero-flux face, zero = a Dirichlet face as before; at least one face must stay Dirichlet.  Called after cz_setup; collective,
  * with the same mask on every rank.  On a Neumann face the face layer of the field is not data but the mirror of the first inner layer
@@ -555,7 +585,8 @@ double cz_last_solve_seconds(const cz_handle*);
  * of the last PCG solve with mg; 17 the gather level G of a decomposed pcg ... mg (levels >= G run on every rank from an all-gathered copy;
  * 0 on a single domain or where level 0 is the coarsest); 18 halo exchanges and all-gathers of the last V-cycle of a decomposed pcg ... mg;
  * 19 the smoother of the multigrid preconditioner (0 none, 1 relaxed Jacobi: mg, 2 symmetric red-black: mgrb; 15 and 16 count for both);
- * 20 the kernel form of the last cz_set_rhs / cz_set_field / cz_get_field (1 k rows, 2 tile transpose, 3 generic; CZ_FIELD_FORM=3 forces 3);
+ * 20 the kernel form of the last cz_set_rhs / cz_set_field / cz_get_field / cz_get_residual / cz_add_field / cz_set_rhs_div / cz_sub_grad (1 k rows,
+ * 2 tile transpose, 3 generic; CZ_FIELD_FORM=3 forces 3; the last two have no transpose form);
  * 21 the mask of cz_set_neumann, bit f = face f of X-, X+, Y-, Y+, Z-, Z+ (0: none; 63: the closed box);
  * 22 the closed-box mode of cz_set_closed_box (0 | 1); 23 the periodic directions of cz_set_periodic, bit d = X, Y, Z (0: none). */
 int cz_info(const cz_handle*, int what);
