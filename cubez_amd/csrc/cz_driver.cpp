@@ -220,6 +220,7 @@ int CZ::Setup(int argc, char** argv) {
   periodic_mask = 0;
   closed_m[0] = closed_m[1] = closed_m[2] = 0.0;
   closed_m0_on_device = false;
+  solve_plan = PassPlan();
 
   comm_world(&myRank, &numProc);  // rank/size from the launcher environment (replaces MPI_Comm_rank/size, :44-50)
 
@@ -401,6 +402,7 @@ int CZ::Solve() {
   history.clear();
   sweeps_done = 0;
   line_error = false;
+  solve_plan = PassPlan();  // (cz_info 7-9 describe this solve: a solve that plans no pass -- pcg under a mask -- reports a fresh handle's values)
   if (profile) czhip_timing(1);  // restart the section timers (the reference's PM.start/stop around the kernels)
   czhip_sync();
   const double t0 = now_s();
@@ -480,6 +482,7 @@ int CZ::Sweeps(int n) {
   eps = -1.0;
   double res = 0.0, flop = 0.0;
   history.clear();
+  solve_plan = PassPlan();
   run(ls_type, res, P, RHS, n, flop);
   eps = keep;
   sweeps_done += n;
@@ -688,6 +691,7 @@ CZ::PassPlan CZ::plan_pass(REAL_TYPE* X, REAL_TYPE* B, int s_type, int itr_max, 
     plan_printed = true;
   }
   last_plan = p;
+  solve_plan = p;
   return p;
 }
 
@@ -2161,9 +2165,9 @@ int cz_info(const cz_handle* h, int what) {
     case 19: return c.mg ? czhip_mg_kind(c.mg) : c.mgd ? 1 : 0;
     case 5: return comm_transport_ranks(c.comm);
     case 6: return c.comm_cus;
-    case 7: return c.last_plan.kind;
-    case 8: return c.last_plan.depth;
-    case 9: return c.last_plan.buffers;
+    case 7: return c.solve_plan.kind;
+    case 8: return c.solve_plan.depth;
+    case 9: return c.solve_plan.buffers;
     case 20: return c.last_field_form;
     case 21: return c.neumann_mask;
     case 22: return c.closed_box;

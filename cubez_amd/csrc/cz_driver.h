@@ -113,7 +113,8 @@ class CZ {
     int maf = 0, rb = 0;
     int comm_cus = 0;
   };
-  PassPlan last_plan;
+  PassPlan last_plan;            // the last plan made (the debug line prints a plan when it differs from this one)
+  PassPlan solve_plan;           // the plan of the stationary sweeps of the current / last cz_solve or cz_sweeps (cz_info 7-9); a fresh one where it ran none
   bool plan_printed = false;
   int comm_cus = 0;              // CUs per XCD the sweeps leave to the exchange stream (CZ_COMM_CUS; 0 in single-domain runs)
   int n_shell = 0;               // shell boxes (cells within two layers of a rank-internal face), 1-based index ranges

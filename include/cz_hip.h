@@ -574,8 +574,9 @@ void cz_set_quiet(cz_handle*, int quiet);     /* suppress stdout / history file 
 double cz_last_solve_seconds(const cz_handle*);
 /* What a (multi-GPU) run decided: what = 0 ranks, 1 every brick takes the fused pass, 2 shell slabs of this brick, 3 overlapped exchange,
  * 4 the last stationary solve ran its residual all-reduce + test one pass behind, 5 ranks of the RCCL communicator (ncclCommCount; 0 = LOCAL
- * test transport or single process), 6 CUs per XCD the sweeps leave to the exchange stream (CZ_COMM_CUS); the plan of the last stationary
- * solve: 7 kind of pass (0 single sweeps, 1 fused pass over the whole box, 2 fused pass as shell slabs + interior with the exchange
+ * test transport or single process), 6 CUs per XCD the sweeps leave to the exchange stream (CZ_COMM_CUS); the plan of the stationary sweeps
+ * of the last cz_solve / cz_sweeps (the preconditioner's, for a Krylov solver; 0, 1, 2 as after cz_setup where that call planned none, as pcg
+ * does under a mask or a periodic flag): 7 kind of pass (0 single sweeps, 1 fused pass over the whole box, 2 fused pass as shell slabs + interior with the exchange
  * overlapped), 8 ghost layers exchanged per pass, 9 rotating field buffers; 10 vector updates of the last BiCGSTAB solve that were made inside
  * the first pair of the preconditioner solve they feed (czhip_jacobi2_from_zero_made_async); 11 passes of the last red-black SOR solve that made
  * two iterations each (czhip_rbsor4_async); 12 converged iterations of the last Jacobi or red-black SOR solve that were the first of a fused pass
