@@ -402,6 +402,9 @@ int CZ::Solve() {
   history.clear();
   sweeps_done = 0;
   line_error = false;
+  pcg_void_start = 0;
+  result_itr = 0;
+  result_res = 0.0;  // (a solve that returns 0 reports no iteration and no residual, not those of the solve before)
   solve_plan = PassPlan();  // (cz_info 7-9 describe this solve: a solve that plans no pass -- pcg under a mask -- reports a fresh handle's values)
   if (profile) czhip_timing(1);  // restart the section timers (the reference's PM.start/stop around the kernels)
   czhip_sync();
@@ -1373,6 +1376,10 @@ int CZ::PBiCGSTAB(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop, int s_t
 //   r = b - A x;  for itr = 1 .. ItrMax:  z = M^-1 r;  rho = r.z;  p = z (itr 1) | z + beta p, beta = rho / rho_old;  q = A p;
 //   alpha = rho / p.q;  x = alpha p + x;  r = (-alpha) q + r;  res = sqrt(r.r * res_normal)
 // Every scalar is made on the device (cg_scal_k) from REAL-rounded double sums, so the host waits once per iteration, for r.r and rho.
+// Breakdown: |rho| < FLT_MIN (absolute, in both precisions) ends the solve with itr = 0 BEFORE the iteration's update of x and r.  none:
+// the host holds rho before the first launch.  jacobi | mg | mgrb: the host reads rho at the iteration's one wait, after the update pass was
+// launched, so that pass carries the test itself (cg_update_guarded_async: it stores nothing under the threshold); the unfused update
+// (CZ_CG_FUSE=0) waits for rho before its triads instead.  pcg_void_start (cz_info 24): the breakdown came at iteration 1 -- x is the caller's.
 // CZ_CG_FUSE (default on): x, r and r.r in one pass (czhip_cg_update_async); in a single-domain run also the direction update inside the
 // SpMV pass (czhip_cg_dir_ax_async, ping-pong between cg_p[0] and cg_p[1]).  Off, and for the direction in decomposed runs: the update,
 // Comm_S(p), then the SpMV with its dot folded in.
@@ -1397,6 +1404,7 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   res = 0.0;
   cg_fused = 0;
   mg_cycles = 0;
+  pcg_void_start = 0;
 
   mirror(X);
   calc_rk_async(cg_r, X, B, size, innerFidx, gc, cf);
@@ -1426,6 +1434,7 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   int itr;
   for (itr = 1; itr <= ItrMax; itr++) {
     if (!pc && fabs(rho) < FLT_MIN) {  // breakdown (as PBiCGSTAB)
+      pcg_void_start = itr == 1;
       itr = 0;
       break;
     }
@@ -1476,10 +1485,19 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
     REAL_TYPE* const p = cg_p[cur];
     if (closed) {
       // r = ((-alpha) q + r) - sc[4], sum r^2 and sum r side by side: one all-reduce, then the mean the next update removes
-      czhip_cg_update_closed_async(X, cg_r, p, cg_q, sc, size, innerFidx, gc, d_rr);
+      cg_update_guarded_async(true, X, cg_r, p, cg_q, sc, size, innerFidx, gc, d_rr);
     } else if (fuse) {
-      czhip_cg_update_async(X, cg_r, p, cg_q, sc, size, innerFidx, gc, d_rr);
+      cg_update_guarded_async(false, X, cg_r, p, cg_q, sc, size, innerFidx, gc, d_rr);
     } else {
+      if (pc) {  // the triads carry no test of their own: the host learns rho before them
+        HIP_CHECK(hipMemcpyAsync(h_scal + 2, d_rho, sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (fabs((REAL_TYPE)h_scal[2]) < FLT_MIN) {
+          pcg_void_start = itr == 1;
+          itr = 0;
+          break;
+        }
+      }
       triad_async(X, p, X, (REAL_TYPE)0, size, innerFidx, gc, sc);
       triad_async(cg_r, cg_q, cg_r, (REAL_TYPE)0, size, innerFidx, gc, sc + 1);
       dot1_async(cg_r, size, innerFidx, gc, d_rr);
@@ -1493,7 +1511,8 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
     const REAL_TYPE rr = (REAL_TYPE)h_scal[5];
     if (pc) {
       rho = (REAL_TYPE)h_scal[2];
-      if (fabs(rho) < FLT_MIN) {  // (found after the iteration's launches: the iterate is void, like any failed solve)
+      if (fabs(rho) < FLT_MIN) {  // (found after the iteration's launches, whose update pass stored nothing: x is that of the iteration before)
+        pcg_void_start = itr == 1;
         itr = 0;
         break;
       }
@@ -2172,6 +2191,7 @@ int cz_info(const cz_handle* h, int what) {
     case 21: return c.neumann_mask;
     case 22: return c.closed_box;
     case 23: return c.periodic_mask;
+    case 24: return c.pcg_void_start;
     default: return -1;
   }
 }

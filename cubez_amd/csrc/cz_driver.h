@@ -77,6 +77,7 @@ class CZ {
   int jac3_passes = 0;           // three-sweep Jacobi passes (jac3_k) of the last JACOBI solve (cz_info 14)
   int exact_reruns = 0;          // converged first iterations of a fused pass re-run alone from the pass's input, last JACOBI / RBSOR solve (cz_info 12)
   int mg_cycles = 0;             // V-cycles of the last PCG solve with mg (cz_info 16)
+  int pcg_void_start = 0;        // the last solve was a PCG that stopped at a breakdown (|rho| < FLT_MIN) before any update of P: P is the caller's (cz_info 24)
   int cg_fused = 0;              // iterations of the last PCG solve whose direction update was made inside the SpMV pass (cz_info 13)
   int bicg_fused = 0;            // vector updates of the last BiCGSTAB solve that were made inside the first pair of a preconditioner solve (cz_info 10)
   bool in_precond = false;       // inside Preconditioner: an unchecked solve does not drain the queue (the caller's next launch follows in stream order)

@@ -78,6 +78,10 @@ void bicg_scalar_async(int step, const double* dots_dev, CZ_REAL rho, CZ_REAL* s
 // sc_dev[0..3] = alpha, -alpha, beta, rho (cg_scal_k)
 void cg_scalar_async(int step, const double* dot_dev, int first, CZ_REAL* sc_dev);
 void mean_scalar_async(const double* sum_dev, double npts, CZ_REAL* m_dev, CZ_REAL* keep_dev);  // *m_dev = (REAL)(sum_dev[0] / npts) (closed box)
+// PCG's update pass (czhip_cg_update_async; closed: czhip_cg_update_closed_async) guarded by rho = sc_dev[3]: under the breakdown threshold
+// (|rho| < FLT_MIN) x and r keep their bytes and the sums are 0
+void cg_update_guarded_async(bool closed, CZ_REAL* x, CZ_REAL* r, const CZ_REAL* p, const CZ_REAL* q, const CZ_REAL* sc_dev, const int* sz, const int* idx,
+                             int g, double* dots_dev);
 // czhip_jacobi2_from_zero_made_async with the coefficient a of the made right-hand side read from the device (a_dev, may be null)
 int pass_from_zero_made(const CZ_REAL* u_shape, CZ_REAL* w, CZ_REAL* b_out, int op, const CZ_REAL* x, const CZ_REAL* y, const CZ_REAL* z, CZ_REAL a,
                         const CZ_REAL* a_dev, CZ_REAL bb, const int* sz, const int* idx, const int* idx1, int g, const CZ_REAL* cf, CZ_REAL omg,

@@ -68,6 +68,8 @@ struct EGeom {
   // where set they replace the by-value arguments a / b of ewise_k and triad_dots_k -- the host need not read the dot products back first
   const REAL* pa = nullptr;
   const REAL* pb = nullptr;
+  // PCG's breakdown guard (cg_update_k): where set and |*pg| < FLT_MIN (rho, cg_scal_k's sc[3]) the launch stores nothing and its sums are 0
+  const REAL* pg = nullptr;
 };
 // element offset of vector f of the row view inside a plane in memory
 template <int V>
@@ -290,6 +292,8 @@ triad_dots_k(REAL* Z, const REAL* X, const REAL* Y, const REAL* W, REAL a, EGeom
 // arrays.  alpha and -alpha come from the device (g.pa / g.pb, made by cg_scal_k); same structure and launch shape as triad_dots_k.
 // CLOSED (the closed box): r = ((-alpha)*q + r) - m, m = g.pa[4] the mean of the residual as the update before left it
 // (mean_scal_k), and dst[1] = sum r of the values written, through a second row of partials; false: the code from before there was a closed box.
+// g.pg (CZ::PCG sets it to rho): a rho under the breakdown threshold makes alpha = rho / p.q meaningless (0 / 0 from an exact start), and the
+// host learns rho only after this launch -- so the launch itself leaves x and r alone there, every thread alike, and returns sums of 0.
 template <int V, bool CLOSED>
 __global__ void __launch_bounds__(256)
 cg_update_k(REAL* X, REAL* Rr, const REAL* Pd, const REAL* Q, EGeom g, int nplanes, double* partials, double* dst, unsigned* counter) {
@@ -298,8 +302,9 @@ cg_update_k(REAL* X, REAL* Rr, const REAL* Pd, const REAL* Q, EGeom g, int nplan
   const long long f = g.F0 + (long long)blockIdx.x * 256 + threadIdx.x;
   const REAL a = *g.pa, na = *g.pb;
   const REAL m = CLOSED ? g.pa[4] : (REAL)0;
+  const bool live = !(g.pg && fabs(*g.pg) < (REAL)FLT_MIN);  // (the host's test, CZ::PCG)
   double acc = 0.0, accs = 0.0;
-  if (f < g.Fend) {
+  if (live && f < g.Fend) {
     const int kv = (int)(f % g.R);
     unsigned mk = 0;
 #pragma unroll

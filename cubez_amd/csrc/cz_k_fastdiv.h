@@ -6,7 +6,8 @@
 //     num_s = div_scale(n, d, n)   q = refinement of num_s * r1 against den_s, div_fmas, div_fixup
 // (AMDGPU LowerFDIV32 / LowerFDIV64) -- 11 instructions for FP32, one of them the quarter-rate v_rcp_f32; about 40 % of the vector
 // instructions of a sweep.  den_s takes only two numeric values for a divisor of ordinary magnitude: d itself, or d * 2^64 (FP32; 2^128
-// in FP64) when the numerator is tiny or the quotient close to overflow (and NaN for a zero numerator, where div_fixup supplies the
+// in FP64) when the quotient is close to overflow, exponent(n) - exponent(d) >= 96 (768); a tiny numerator or a subnormal quotient scales
+// num_s alone (measured: profiles/r21/div_scale_classes.txt; and NaN for a zero numerator, where div_fixup supplies the
 // result).  So the reciprocal refinement is done ONCE per thread for both values with the very same instructions, and a point only
 // selects between the two: bit-identical to `n / d` by construction, 3 instructions (FP32; 5 in FP64) and the transcendental cheaper.
 // czhip_selftest_fastdiv (tests/test_gpu_kernels.py) compares the result with `n / d` for all 2^32 float numerators (2^32 sampled double

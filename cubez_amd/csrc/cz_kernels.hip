@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1498,9 +1499,10 @@ void cg_scalar_async(int step, const double* dot_dev, int first, REAL* sc_dev) {
 }  // namespace czhip_internal
 
 namespace {
-// the launch shape of triad_dots_async; CLOSED: cg_update_k's closed-box form (sc[4] the mean, dots_dev[1] the sum of r)
+// the launch shape of triad_dots_async; CLOSED: cg_update_k's closed-box form (sc[4] the mean, dots_dev[1] the sum of r); guard_dev: EGeom::pg
 template <bool CLOSED>
-void cg_update_launch(REAL* x, REAL* r, const REAL* p, const REAL* q, const REAL* alpha_dev, const int* sz, const int* idx, int g, double* dots_dev) {
+void cg_update_launch(REAL* x, REAL* r, const REAL* p, const REAL* q, const REAL* alpha_dev, const int* sz, const int* idx, int g, double* dots_dev,
+                      const REAL* guard_dev = nullptr) {
   ensure_init();
   const Box b = make_box(sz, idx, g);
   if (b.empty) {
@@ -1511,14 +1513,14 @@ void cg_update_launch(REAL* x, REAL* r, const REAL* p, const REAL* q, const REAL
   ScopedTimer tm(CLOSED ? LBL_CG_CLOSED : LBL_EWISE);
   if (rows_ok(b, {x, r, p, q})) {
     EGeom e = make_egeom<VW>(b);
-    e.pa = alpha_dev, e.pb = alpha_dev + 1;
+    e.pa = alpha_dev, e.pb = alpha_dev + 1, e.pg = guard_dev;
     const unsigned gx = (unsigned)((e.Fend - e.F0 + 255) / 256);
     const unsigned gy = (unsigned)std::max(1, std::min(nplanes, (int)(4096 / gx)));
     ensure_partials((size_t)(CLOSED ? 2 : 1) * gx * gy);
     hipLaunchKernelGGL((cg_update_k<VW, CLOSED>), dim3(gx, gy), dim3(256), 0, ctx.stream, x, r, p, q, e, nplanes, ctx.partials, dots_dev, ctx.counter);
   } else {
     EGeom e = make_egeom<1>(b);
-    e.pa = alpha_dev, e.pb = alpha_dev + 1;
+    e.pa = alpha_dev, e.pb = alpha_dev + 1, e.pg = guard_dev;
     const unsigned gx = (unsigned)((e.Fend - e.F0 + 255) / 256);
     const unsigned gy = (unsigned)std::max(1, std::min(nplanes, (int)(4096 / gx)));
     ensure_partials((size_t)(CLOSED ? 2 : 1) * gx * gy);
@@ -1543,6 +1545,13 @@ namespace czhip_internal {
 void mean_scalar_async(const double* sum_dev, double npts, REAL* m_dev, REAL* keep_dev) {
   hipLaunchKernelGGL(mean_scal_k, dim3(1), dim3(1), 0, ctx.stream, sum_dev, npts, m_dev, keep_dev);
   HIP_CHECK(hipGetLastError());
+}
+// CZ::PCG's update from cg_scal_k's scalars sc_dev[0..3] (closed: [4] the mean too): czhip_cg_update_async / czhip_cg_update_closed_async that
+// store nothing and return sums of 0 where |rho| = |sc_dev[3]| < FLT_MIN (the breakdown the host finds at the iteration's one wait)
+void cg_update_guarded_async(bool closed, REAL* x, REAL* r, const REAL* p, const REAL* q, const REAL* sc_dev, const int* sz, const int* idx, int g,
+                             double* dots_dev) {
+  if (closed) cg_update_launch<true>(x, r, p, q, sc_dev, sz, idx, g, dots_dev, sc_dev + 3);
+  else cg_update_launch<false>(x, r, p, q, sc_dev, sz, idx, g, dots_dev, sc_dev + 3);
 }
 }  // namespace czhip_internal
 

@@ -229,7 +229,12 @@ class CZ:
 
     def project(self, u, v, w):
         """the projection step: set_rhs_div, solve, sub_grad at scale 1 (a uniform scale cancels between the two: A p = s div u and
-        u -= grad p / s); returns (iterations, sum of div^2 before).  Afterwards the divergence of (u, v, w) is the residual of the solve"""
+        u -= grad p / s); returns (iterations, sum of div^2 before).  Afterwards the divergence of (u, v, w) is the residual of the solve.
+        (0, 0.0) means nothing was to be projected: the velocity was discretely divergence-free already (a fluid at rest) and the solve
+        stopped before it touched the field (info()["void_start"] == 1).  sub_grad is called whatever the iteration count: it subtracts the
+        gradient of whatever field the handle holds -- after a solve that stopped at a breakdown that is the field from before the
+        breakdown (the caller's own at iteration 1), never a half-made iterate.  0 iterations with a non-zero sum: a divergence below the
+        solver's absolute threshold (void_start 1), or an error"""
         ss = self.set_rhs_div(u, v, w)
         itr = self.solve()
         self.sub_grad(u, v, w)
@@ -295,7 +300,7 @@ class CZ:
     def info(self) -> dict:
         """what a (multi-GPU) run decided (cz_info of include/cz_hip.h)"""
         keys = ("ranks", "fused_pass", "shell_slabs", "overlap", "lagged_reduce", "rccl_ranks", "comm_cus", "pass_kind", "exchange_depth", "buffers", "bicg_fused", "rb4_passes",
-                "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother", "field_form", "neumann", "closed", "periodic")
+                "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother", "field_form", "neumann", "closed", "periodic", "void_start")
         return {k: self.lib.cz_info(self.h, i) for i, k in enumerate(keys)}
 
     def config_in_force(self) -> dict:

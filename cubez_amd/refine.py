@@ -67,7 +67,8 @@ class Refined:
 
     def solve(self, tol=1e-10, max_outer=20, inner_eps=INNER_EPS) -> int:
         """refine until |b - A p| <= tol |b - A p0|; returns the outer steps taken, 0 where max_outer steps did not reach it.
-        history: [(outer step, |r| / |r0| after it, inner iterations of it)].  Collective in a decomposed run."""
+        history: [(outer step, |r| / |r0| after it, inner iterations of it)].  Collective in a decomposed run.
+        A start whose residual is exactly zero returns 0 too, with an empty history and the field untouched: there was nothing to refine."""
         torch, hi, lo, r32 = self.torch, self.hi, self.lo, self.r32
         self.history = []
         _, ss0 = hi.get_residual()

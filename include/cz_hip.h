@@ -437,7 +437,8 @@ int cz_evaluate(cz_handle*, int argc, char** argv);
 /* Split form used by bench.py / tests: setup (parse + allocate + boundary conditions), then solve. */
 int cz_setup(cz_handle*, int argc, char** argv);
 int cz_solve(cz_handle*);                      /* runs the selected solver to ItrMax / eps; returns Iter (0 = error).  Repeatable: every call
-                                                  starts from the current P with the history and the counters of cz_info a fresh set-up leaves */
+                                                  starts from the current P with the history and the counters of cz_info a fresh set-up leaves.
+                                                  A Krylov breakdown returns 0 too; pcg breaks down before it updates P (cz_info 24) */
 /* A caller's own problem (INTEGRATION.md "Level 3").  After cz_setup (sizes, solver, ItrMax, coefficient, preconditioner,
  * division as on the command line) the built-in test case in P and RHS is replaced by the caller's:
  *   cz_set_rhs    the right-hand side b,
@@ -589,7 +590,10 @@ double cz_last_solve_seconds(const cz_handle*);
  * 20 the kernel form of the last cz_set_rhs / cz_set_field / cz_get_field / cz_get_residual / cz_add_field / cz_set_rhs_div / cz_sub_grad (1 k rows,
  * 2 tile transpose, 3 generic; CZ_FIELD_FORM=3 forces 3; the last two have no transpose form);
  * 21 the mask of cz_set_neumann, bit f = face f of X-, X+, Y-, Y+, Z-, Z+ (0: none; 63: the closed box);
- * 22 the closed-box mode of cz_set_closed_box (0 | 1); 23 the periodic directions of cz_set_periodic, bit d = X, Y, Z (0: none). */
+ * 22 the closed-box mode of cz_set_closed_box (0 | 1); 23 the periodic directions of cz_set_periodic, bit d = X, Y, Z (0: none);
+ * 24 the last cz_solve was a pcg that stopped at a breakdown (|rho| < FLT_MIN, absolute in both precisions) before any update: cz_solve
+ * returned 0, P holds the caller's bytes (in the closed box: less its mean), cz_result_iter, cz_result_res and the history are 0 / empty --
+ * the start was the answer already, or the problem is scaled below the threshold (1); anything else, a refusal or an error included (0). */
 int cz_info(const cz_handle*, int what);
 /* The driver's and its communicator's own copies of their switches, as name=value, one per line: overlap, lag_reduce, comm_cus (as asked for;
  * 0 on a single domain), comm_cus_reserved (in force after set-up), bicg_fuse, bicg_devsc, bicg_alias, cg_fuse, mg_tail, mg_gather, mgrb_zero4,

@@ -4,10 +4,16 @@ partial vectors at every alignment of the box edge inside a component pair, and 
 cases a step with wave masks in scalar registers or packed FP32 operations has to pass; both were built, measured and not kept:
 profiles/r19/jac3_step_instructions.txt).  Every case goes through czhip_jacobi3_async against three oracle sweeps: fields bit for bit, the
 input untouched, the three residual sums to 1e-11; every listed form must be taken by the launcher."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from oracle import cz_oracle as O
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from special_operands import special  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -107,19 +113,9 @@ def test_box_edge_at_every_place_of_a_component_pair(nkp, prec, unit):
             _check_forms(h, p, b, sz, idx, cf, want, res, [(5, 0), (0, 0)])
 
 
-# ---- 3. values on which a packed FP32 operation, or a flushing one, would round unlike the single IEEE operation
-def _special(rng, shape):
-    """per element one of: 0, -0, the smallest subnormal, a random subnormal, a value in [2^-120, 2^-100], an ordinary value; random signs"""
-    kind = rng.integers(0, 6, shape)
-    sub = rng.integers(1, 1 << 23, shape).astype(np.uint32).view(np.float32)
-    tiny = np.ldexp(rng.uniform(1.0, 2.0, shape), rng.integers(-120, -100, shape)).astype(np.float32)  # exponents -120 .. -101
-    mag = np.select([kind <= 1, kind == 2, kind == 3, kind == 4], [np.float32(0), np.float32(2.0 ** -149), sub, tiny],
-                    rng.uniform(0.0, 1.0, shape).astype(np.float32)).astype(np.float32)
-    x = np.copysign(mag, rng.choice(np.array([-1.0, 1.0], dtype=np.float32), shape)).astype(np.float32)
-    assert np.isfinite(x).all()
-    return x
-
-
+# ---- 3. values on which a packed FP32 operation, or a flushing one, would round unlike the single IEEE operation (the family `special` of
+# tests/special_operands.py: it reaches the division's special branch in the first of the three stages; tests/test_gpu_special_operands.py has
+# the families that reach it in every stage)
 def test_update_on_zeros_subnormals_and_tiny_values():
     from cubez_amd import CzHip
     ni, nj, nk = 12, 10, 60
@@ -128,7 +124,7 @@ def test_update_on_zeros_subnormals_and_tiny_values():
     rng = np.random.default_rng(20190)
     cf = np.array([1, 1, 1, 1, 1, 1, 6], dtype=np.float32)
     shape = (nj + 4, ni + 4, nk + 4)
-    p, b = _special(rng, shape), _special(rng, shape)
+    p, b = special(rng, shape), special(rng, shape)
     for x in (p, b):  # every class is present
         assert (x == 0).any() and np.signbit(x[x == 0]).any() and (np.abs(x) == np.float32(2.0 ** -149)).any()
         assert ((np.abs(x) > 0) & (np.abs(x) < np.float32(2.0 ** -126))).any() and ((np.abs(x) >= 2.0 ** -120) & (np.abs(x) <= 2.0 ** -100)).any()
