@@ -213,11 +213,8 @@ int CZ::Setup(int argc, char** argv) {
   if (argc != 7 && argc != 8 && argc != 10 && argc != 11) return 0;  // main.cpp:19
 
   // a set-up starts with Dirichlet faces: the hierarchy it builds knows no mask (cz_set_neumann comes after cz_setup)
-  std::fill(neumann, neumann + 6, 0);
-  neumann_mask = 0;
+  bc = CzBc();
   closed_box = 0;
-  periodic[0] = periodic[1] = periodic[2] = 0;
-  periodic_mask = 0;
   closed_m[0] = closed_m[1] = closed_m[2] = 0.0;
   closed_m0_on_device = false;
   solve_plan = PassPlan();
@@ -387,8 +384,8 @@ int CZ::Setup(int argc, char** argv) {
 
 // Zero-flux faces are built for pcg (none | jacobi | mg | mgrb) alone: every other loop would sweep with Dirichlet faces
 bool CZ::neumann_refused(const char* who, int s_type) const {
-  if ((!neumann_mask && !periodic_mask) || s_type == LS_PCG) return false;
-  if (neumann_mask) fprintf(stderr, "%s: Neumann faces are set (cz_set_neumann) and the solver is not pcg\n", who);
+  if (!bc.any() || s_type == LS_PCG) return false;
+  if (bc.nm) fprintf(stderr, "%s: Neumann faces are set (cz_set_neumann) and the solver is not pcg\n", who);
   else fprintf(stderr, "%s: periodic directions are set (cz_set_periodic) and the solver is not pcg\n", who);
   return true;
 }
@@ -428,7 +425,7 @@ int CZ::Solve() {
 }
 
 int CZ::Evaluate(int argc, char** argv) {
-  if ((neumann_mask || periodic_mask) && argc > 4) {
+  if (bc.any() && argc > 4) {
     const cz_solvers::Row* named = cz_solvers::find(argv[4], cz_solvers::SOLVER);
     if (neumann_refused("cz_evaluate", named ? named->id : LS_NONE)) return 0;
   }
@@ -1392,7 +1389,7 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   const bool fuse = cfg.on(CZV_CG_FUSE, true);
   // the direction pass reads z's and p's shells as zeros: single domain only, and no Neumann face (whose layer of p is the mirror)
   // (nor a periodic direction, whose layer is the wrap)
-  const bool fuse_dir = fuse && numProc == 1 && !neumann_mask && !periodic_mask;
+  const bool fuse_dir = fuse && numProc == 1 && !bc.any();
   REAL_TYPE* const sc = reinterpret_cast<REAL_TYPE*>(d_res + 12);  // alpha, -alpha, beta, rho (cg_scal_k)
   double* const d_rr = d_res + 5;
   double* const d_pq = d_res + 3;                 // (the unfused SpMV writes q.q to d_res[4])
@@ -1443,7 +1440,7 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
       if (mg || mgd) {
         if (mg ? !czhip_mg_apply_async(mg, cg_z, cg_r, ac1) : !mgd_apply(mgd, cg_z, cg_r, ac1)) return 0;  // z = V_0(r)
         mg_cycles++;
-      } else if (neumann_mask || periodic_mask) {
+      } else if (bc.any()) {
         // the 8 relaxed sweeps from zero as single sweeps between cg_z and cg_p[1] (free: the direction is not fused), the exchange and the
         // mirror before every sweep that reads its input
         HIP_CHECK(hipMemsetAsync(cg_z, 0, nbytes, st));
@@ -1544,84 +1541,72 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
 // Periodic directions are never cut, so both their faces are physical on every brick: there the one fill launch wraps, and
 // mirrors the Neumann faces of the other directions with it
 void CZ::mirror(REAL_TYPE* X) {
-  if (periodic_mask) {
-    int kinds[6];
-    for (int f = 0; f < 6; f++) kinds[f] = periodic[f >> 1] ? 2 : neumann[f];
-    if (!czhip_fill_faces_async(X, size, innerFidx, GUIDE, kinds)) cz_fatal(1, "czhip: the fill of the periodic and Neumann faces was refused\n");
-    return;
-  }
-  if (!neumann_mask) return;
-  if (!czhip_mirror_faces_async(X, size, innerFidx, GUIDE, neumann)) cz_fatal(1, "czhip: the mirror of the Neumann faces was refused\n");
+  const int gn[3] = {G_size[0] - 2, G_size[1] - 2, G_size[2] - 2};
+  if (!fill_bc_async(X, size, innerFidx, GUIDE, mg_level_bc(bc, gn), true)) cz_fatal(1, "czhip: the fill of the periodic and Neumann faces was refused\n");
 }
 
 // The one rule of solvability, for the three setters on the combined state: with the closed mode off, some face of a direction that is not
 // periodic must be a Dirichlet face (else the operator is singular).  nullptr: solvable; else the line
-const char* CZ::unsolvable(int nm, int per, int closed) {
+const char* CZ::unsolvable(CzBc next, int closed) {
   if (closed) return nullptr;
   for (int d = 0; d < 3; d++)
-    if (!((per >> d) & 1) && ((nm >> (2 * d)) & 3) != 3) return nullptr;
-  if (!per) return "at least one face must stay a Dirichlet face (the all-Neumann problem is singular: cz_set_closed_box keeps it solvable)";
+    if (!((next.per >> d) & 1) && ((next.nm >> (2 * d)) & 3) != 3) return nullptr;
+  if (!next.per) return "at least one face must stay a Dirichlet face (the all-Neumann problem is singular: cz_set_closed_box keeps it solvable)";
   return "no Dirichlet face is left in a direction that is not periodic (the problem is singular: cz_set_closed_box keeps it solvable)";
 }
 
-int CZ::SetPeriodic(const int* dirs) {
-  auto refuse = [&](const char* why) {
-    fprintf(stderr, "cz_set_periodic: %s\n", why);
-    return 0;
-  };
-  if (!set_up) return refuse("no problem is set up (cz_setup first)");
-  if (!dirs) return refuse("NULL pointer");
-  const int per = (dirs[0] ? 1 : 0) | (dirs[1] ? 2 : 0) | (dirs[2] ? 4 : 0);
-  if (SW_maf) return refuse("the handle's operator is a MAF one, not the unit-coefficient operator");
-  for (int d = 0; d < 3; d++) {
-    if (dirs[d] && G_size[d] < 4) return refuse("a periodic direction needs two inner points at least");
-    if (dirs[d] && G_div[d] > 1) return refuse("a periodic direction must not be cut by the decomposition");
-  }
-  if (const char* why = unsolvable(neumann_mask, per, closed_box)) return refuse(why);
-  if ((mg && !czhip_mg_set_periodic(mg, dirs)) || (mgd && !mgd_set_periodic(mgd, dirs))) return refuse("the multigrid hierarchy refused the directions");
-  for (int d = 0; d < 3; d++) periodic[d] = dirs[d] ? 1 : 0;
-  periodic_mask = per;
+const char* CZ::bc_unready(const void* arg) const {
+  if (!set_up) return "no problem is set up (cz_setup first)";
+  if (!arg) return "NULL pointer";
+  if (SW_maf) return "the handle's operator is a MAF one, not the unit-coefficient operator";
+  return nullptr;
+}
+static int bc_refuse(const char* who, const char* why) {
+  fprintf(stderr, "%s: %s\n", who, why);
+  return 0;
+}
+
+// The next state of the handle, from any of the three setters (`who`, after bc_unready and its own checks): refused with one line and nothing
+// changed, or taken by the hierarchy and the driver.  closed: the closed mode from now on; project: cz_set_closed_box(1) alone projects the
+// right-hand side here, inside the one synchronisation
+int CZ::set_bc(CzBc next, int closed, bool project, const char* who) {
+  if (const char* why = unsolvable(next, closed)) return bc_refuse(who, why);
+  if (mg) mg_set_bc(mg, next);
+  if (mgd) mgd_set_bc(mgd, next);
+  bc = next;
+  closed_box = closed;
   // the work vectors whose face layers carried the wraps and mirrors of the state before: zeros again, as the unmasked passes read them
   for (REAL_TYPE* a : {cg_z, cg_p[0], cg_p[1]})
     if (a) HIP_CHECK(hipMemsetAsync(a, 0, padded_cells() * sizeof(REAL_TYPE), stream()));
+  if (project && !project_rhs()) return 0;
   mirror(P);
   wrk_shell_tag = 0;
   czhip_sync();
   return 1;
 }
 
-int CZ::set_mask(const int* faces, int closed, const char* who) {
-  auto refuse = [&](const char* why) {
-    fprintf(stderr, "%s: %s\n", who, why);
-    return 0;
-  };
-  if (!set_up) return refuse("no problem is set up (cz_setup first)");
-  if (!faces) return refuse("NULL pointer");
-  int nm = 0;
-  for (int f = 0; f < 6; f++) nm |= faces[f] ? 1 << f : 0;
-  if (const char* why = unsolvable(nm, periodic_mask, closed)) return refuse(why);
-  if (SW_maf) return refuse("the handle's operator is a MAF one, not the unit-coefficient operator");
-  if ((mg && !czhip_mg_set_neumann(mg, faces)) || (mgd && !mgd_set_neumann(mgd, faces))) return refuse("the multigrid hierarchy refused the mask");
-  for (int f = 0; f < 6; f++) neumann[f] = faces[f] ? 1 : 0;
-  neumann_mask = nm;
-  closed_box = closed;
-  // the work vectors whose face layers carried the mirrors of an earlier mask: zeros again, as the unmasked passes read them
-  for (REAL_TYPE* a : {cg_z, cg_p[0], cg_p[1]})
-    if (a) HIP_CHECK(hipMemsetAsync(a, 0, padded_cells() * sizeof(REAL_TYPE), stream()));
-  if (closed && !project_rhs()) return 0;
-  mirror(P);
-  wrk_shell_tag = 0;
-  czhip_sync();
-  return 1;
+int CZ::SetPeriodic(const int* dirs) {
+  const char* const who = "cz_set_periodic";
+  const char* why = bc_unready(dirs);
+  for (int d = 0; !why && d < 3; d++) {
+    if (dirs[d] && G_size[d] < 4) why = "a periodic direction needs two inner points at least";
+    else if (dirs[d] && G_div[d] > 1) why = "a periodic direction must not be cut by the decomposition";
+  }
+  return why ? bc_refuse(who, why) : set_bc(bc.with_dirs(dirs), closed_box, false, who);
 }
 
-int CZ::SetNeumann(const int* faces) { return set_mask(faces, 0, "cz_set_neumann"); }
+int CZ::SetNeumann(const int* faces) {
+  const char* const who = "cz_set_neumann";
+  const char* const why = bc_unready(faces);
+  return why ? bc_refuse(who, why) : set_bc(bc.with_faces(faces), 0, false, who);
+}
 
 // The closed box: all six faces zero-flux, the right-hand side kept compatible, pcg's residual kept in the range of the
 // operator and its answer of zero mean.  on = 0: the Dirichlet problem again (the right-hand side stays projected)
 int CZ::SetClosedBox(int on) {
-  const int faces[6] = {on ? 1 : 0, on ? 1 : 0, on ? 1 : 0, on ? 1 : 0, on ? 1 : 0, on ? 1 : 0};
-  return set_mask(faces, on ? 1 : 0, "cz_set_closed_box");
+  const char* const who = "cz_set_closed_box";
+  const char* const why = bc_unready(this);
+  return why ? bc_refuse(who, why) : set_bc(CzBc(on ? 63 : 0, bc.per), on ? 1 : 0, on != 0, who);
 }
 
 // A <- A - m over the inner box, m = (REAL)(sum A / npts) over the GLOBAL inner box: a pass that sums, one all-reduce, the mean on the device
@@ -1860,10 +1845,10 @@ int CZ::ProjectIO(int op, REAL_TYPE* const* vel, const long long* stride, int on
   }
   const int form = field_form == 3 ? 3 : 0;
   if (op == PRJ_DIV) {
-    last_field_form = field_div_async(RHS, dev[0], dev[1], dev[2], size, GUIDE, stride, periodic_mask, scale, form, d_res + 10);
+    last_field_form = field_div_async(RHS, dev[0], dev[1], dev[2], size, GUIDE, stride, bc.per, scale, form, d_res + 10);
   } else {
     mirror(P);
-    last_field_form = field_grad_async(dev[0], dev[1], dev[2], P, size, GUIDE, stride, periodic_mask, scale, form);
+    last_field_form = field_grad_async(dev[0], dev[1], dev[2], P, size, GUIDE, stride, bc.per, scale, form);
   }
   if (!last_field_form) return refuse("no kernel form takes these strides");
   if (op == PRJ_DIV) {
@@ -2188,9 +2173,9 @@ int cz_info(const cz_handle* h, int what) {
     case 8: return c.solve_plan.depth;
     case 9: return c.solve_plan.buffers;
     case 20: return c.last_field_form;
-    case 21: return c.neumann_mask;
+    case 21: return c.bc.nm;
     case 22: return c.closed_box;
-    case 23: return c.periodic_mask;
+    case 23: return c.bc.per;
     case 24: return c.pcg_void_start;
     default: return -1;
   }

@@ -82,10 +82,10 @@ class CZ {
   int bicg_fused = 0;            // vector updates of the last BiCGSTAB solve that were made inside the first pair of a preconditioner solve (cz_info 10)
   bool in_precond = false;       // inside Preconditioner: an unchecked solve does not drain the queue (the caller's next launch follows in stream order)
   int last_lag = 0;              // the last stationary solve ran its all-reduce + test one pass behind (cz_info)
-  int neumann[6] = {0, 0, 0, 0, 0, 0};  // zero-flux (Neumann) physical faces of the global box, X-, X+, Y-, Y+, Z-, Z+ (cz_set_neumann)
-  int neumann_mask = 0;          // ... as bits (cz_info 21); non-zero: P's face layers there hold the mirror of the first inner layer
-  int periodic[3] = {0, 0, 0};   // periodic directions X, Y, Z of the global box (cz_set_periodic): a state of its own beside the mask
-  int periodic_mask = 0;         // ... as bits (cz_info 23); there P's two face layers hold the wrap and the Neumann flags are ignored
+  CzBc bc;                       // the boundary faces of the global box as set (cz_bc.h; set_bc).  nm (cz_info 21): the zero-flux (Neumann) faces of
+                                 // cz_set_neumann, DESIGN.md §5.13 -- P's face layers there hold the mirror of the first inner layer.  per (cz_info 23):
+                                 // the periodic directions of cz_set_periodic, DESIGN.md §5.15 -- there P's two face layers hold the wrap and the
+                                 // Neumann flags are ignored
   int closed_box = 0;            // the closed box (cz_set_closed_box, cz_info 22): mask 63 and the three projections of pcg
   double closed_m[3] = {0, 0, 0};  // the means last removed: right-hand side, initial residual, answer (cz_closed_mean)
   bool closed_m0_on_device = false;  // closed_m[0] is still sc[7] of d_res (cz_set_rhs does not wait for it; ClosedMean fetches)
@@ -161,12 +161,13 @@ class CZ {
   int SetNeumann(const int* faces);  // cz_set_neumann: 1, or 0 with one line on stderr and nothing changed
   int SetClosedBox(int on);          // cz_set_closed_box: likewise
   int SetPeriodic(const int* dirs);  // cz_set_periodic: likewise
-  static const char* unsolvable(int nm, int per, int closed);  // the setters' one rule on the combined state: nullptr, or the line of the refusal
-  int set_mask(const int* faces, int closed, const char* who);  // what the two share: refusals, the hierarchy, the work vectors, P's mirror
+  static const char* unsolvable(CzBc next, int closed);  // the setters' one rule on the combined state: nullptr, or the line of the refusal
+  const char* bc_unready(const void* arg) const;         // what every setter refuses before it reads its argument: nullptr, or the line
+  int set_bc(CzBc next, int closed, bool project, const char* who);  // the one way to a new state: the rule, the hierarchy, the store, the work vectors, P's face layers
   bool project(REAL_TYPE* A, REAL_TYPE* m_dev, REAL_TYPE* keep_dev);  // A <- A - mean(A) over the global inner box; d_res[20..21] = this rank's sum A', sum A'^2
   double ClosedMean(int which);      // cz_closed_mean
   bool project_rhs();                // ... of RHS, ghost layers included; closed_m[0]
-  void mirror(REAL_TYPE* X);         // the Neumann face layers of X from its first inner layers (nothing without a mask)
+  void mirror(REAL_TYPE* X);         // X's face layers of the state: mirrors on the Neumann faces, wraps in the periodic directions (nothing without either)
   void WriteProfile(FILE* fp) const;                                             // cz_Evaluate.cpp:506-545
   bool WriteSph(const char* fname, const REAL_TYPE* padded_host_field) const;  // cz_utility.f90:17-47
   void Exact(std::vector<REAL_TYPE>& e) const;                                   // cz_utility.f90:52-82
@@ -255,8 +256,7 @@ class CZ {
 MgDist* mgd_create(const CZ& cz, CommCtx* comm0, int gather_points, bool tail);
 void mgd_destroy(MgDist*);
 int mgd_apply(MgDist*, REAL_TYPE* z, const REAL_TYPE* r, REAL_TYPE omg);  // z = V_0(r) on this rank's brick, collective
-int mgd_set_periodic(MgDist*, const int* dirs3);  // the periodic directions, uncut, on every rank; 0 = refused
-int mgd_set_neumann(MgDist*, const int* faces6);  // the global mask of zero-flux faces, on every rank; 0 = refused
+void mgd_set_bc(MgDist*, CzBc bc);  // the state of the global box, on every rank; periodic directions uncut
 int mgd_levels(const MgDist*);
 int mgd_gather_level(const MgDist*);
 int mgd_exchanges(const MgDist*);  // halo exchanges + all-gathers of the last cycle

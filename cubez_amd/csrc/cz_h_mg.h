@@ -4,6 +4,17 @@
 using czhip_internal::MgdLevel;
 
 namespace {
+// f(std::bool_constant...) for the flags given: the launches below name a kernel's instantiation once, with the flags as template arguments
+template <class F>
+void with_flags(F&& f) {
+  f();
+}
+template <class F, class... Rest>
+void with_flags(F&& f, bool flag, Rest... rest) {
+  if (flag) with_flags([&](auto... c) { f(std::true_type(), c...); }, rest...);
+  else with_flags([&](auto... c) { f(std::false_type(), c...); }, rest...);
+}
+
 // the device description of a level from the host one; false if it does not describe level M.level of a grid of M.n0 points
 bool mg_lev(MgDLev& D, const MgdLevel& M) {
   MgLev& L = D.L;
@@ -94,11 +105,8 @@ int mg_smooth_async(const REAL* u, REAL* w, const REAL* b, const MgdLevel& M, RE
   if (!w || !b || u == w || !mg_lev(D, M) || M.dense) return 0;
   if (mg_none(D)) return 1;
   ScopedTimer tm(LBL_MG_SMOOTH);
-  if (D.L.nm) {
-    if (u) hipLaunchKernelGGL((mg_smooth_k<false, true>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, u, w, b, D, omg);
-    else hipLaunchKernelGGL((mg_smooth_k<true, true>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, w, w, b, D, omg);
-  } else if (u) hipLaunchKernelGGL((mg_smooth_k<false, false>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, u, w, b, D, omg);
-  else hipLaunchKernelGGL((mg_smooth_k<true, false>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, w, w, b, D, omg);
+  with_flags([&](auto ZERO, auto NM) { hipLaunchKernelGGL((mg_smooth_k<ZERO(), NM()>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, u ? u : w, w, b, D, omg); },
+             !u, D.L.nm != 0);
   HIP_CHECK(hipGetLastError());
   return 1;
 }
@@ -110,13 +118,11 @@ int mg_rb_async(REAL* x, const REAL* b, const MgdLevel& M, REAL omg, int colour,
   if (mg_none(D)) return 1;
   ScopedTimer tm(LBL_MG_RB);
   const dim3 grid((unsigned)(((D.L.nk + 1) / 2 + 63) / 64), (unsigned)((D.L.ni + 3) / 4), (unsigned)D.L.nj);
-  if (D.L.nm) {
-    if (zero == 0) hipLaunchKernelGGL((mg_rb_k<0, true>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
-    else if (zero == 1) hipLaunchKernelGGL((mg_rb_k<1, true>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
-    else hipLaunchKernelGGL((mg_rb_k<2, true>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
-  } else if (zero == 0) hipLaunchKernelGGL((mg_rb_k<0, false>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
-  else if (zero == 1) hipLaunchKernelGGL((mg_rb_k<1, false>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
-  else hipLaunchKernelGGL((mg_rb_k<2, false>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
+  with_flags([&](auto NM) {
+    if (zero == 0) hipLaunchKernelGGL((mg_rb_k<0, NM()>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
+    else if (zero == 1) hipLaunchKernelGGL((mg_rb_k<1, NM()>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
+    else hipLaunchKernelGGL((mg_rb_k<2, NM()>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
+  }, D.L.nm != 0);
   HIP_CHECK(hipGetLastError());
   return 1;
 }
@@ -130,8 +136,7 @@ int mgd_resface_async(REAL* rt, const REAL* x, const REAL* b, const MgdLevel& M,
     if (!minus[d]) continue;
     const int fast = d == 2 ? D.L.ni : D.L.nk, slow = d == 0 ? D.L.nj : d == 1 ? D.L.ni : D.L.nj;
     const dim3 grid((unsigned)((fast + 63) / 64), (unsigned)slow);
-    if (D.L.nm) hipLaunchKernelGGL(mgd_resface_k<true>, grid, dim3(64), 0, ctx.stream, rt, x, b, D, d, minus[0], minus[1]);
-    else hipLaunchKernelGGL(mgd_resface_k<false>, grid, dim3(64), 0, ctx.stream, rt, x, b, D, d, minus[0], minus[1]);
+    with_flags([&](auto NM) { hipLaunchKernelGGL(mgd_resface_k<NM()>, grid, dim3(64), 0, ctx.stream, rt, x, b, D, d, minus[0], minus[1]); }, D.L.nm != 0);
     HIP_CHECK(hipGetLastError());
   }
   return 1;
@@ -144,11 +149,8 @@ int mg_restrict_async(REAL* bc, const MgdLevel& MC, const REAL* x, const REAL* b
   if (mg_none(C)) return 1;
   ScopedTimer tm(LBL_MG_RESTRICT);
   // (the children's residual takes the FINE level's weights: its mask)
-  if (F.L.nm) {
-    if (rt) hipLaunchKernelGGL((mg_restrict_k<true, true>), mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C);
-    else hipLaunchKernelGGL((mg_restrict_k<false, true>), mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C);
-  } else if (rt) hipLaunchKernelGGL((mg_restrict_k<true, false>), mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C);
-  else hipLaunchKernelGGL((mg_restrict_k<false, false>), mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C);
+  with_flags([&](auto RT, auto NM) { hipLaunchKernelGGL((mg_restrict_k<RT(), NM()>), mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C); },
+             rt != nullptr, F.L.nm != 0);
   HIP_CHECK(hipGetLastError());
   return 1;
 }
@@ -282,15 +284,14 @@ cz_mg* czhip_mg_create_rb(const int* sz, const int* idx, int g, const CZ_REAL* c
 int czhip_mg_levels(const cz_mg* h) { return h ? h->nlev : 0; }
 }  // extern "C"
 
-namespace {
-// every level's mask from the state as set (mg_level_bc; without a periodic direction: the Neumann flags at every level, as before there were
+namespace czhip_internal {
+// every level's word from the state (mg_level_bc; without a periodic direction: the Neumann flags at every level, as before there were
 // any).  The arrays whose ghost layers carried the mirrors or wraps of an earlier state are zeros again, as the unmasked passes read them
-void mg_relevel(cz_mg* h) {
-  int wraps = h->per;
+void mg_set_bc(cz_mg* h, CzBc bc) {
+  int wraps = bc.per;
   for (int l = h->first; l < h->nlev; l++) wraps |= h->lev[l].nm >> 6;
-  for (int l = h->first; l < h->nlev; l++) h->lev[l].nm = czhip_internal::mg_level_bc(h->nm_set, h->per, h->lev[l].gn);
-  const int gn0[3] = {h->lev[h->first].n0[0], h->lev[h->first].n0[1], h->lev[h->first].n0[2]};
-  h->nm = czhip_internal::mg_level_bc(h->nm_set, h->per, gn0);
+  h->bc = bc;
+  for (int l = h->first; l < h->nlev; l++) h->lev[l].nm = mg_level_bc(bc, h->lev[l].gn);
   if (h->fine_tmp) {
     const int* sz = h->lev[0].sz;
     HIP_CHECK(hipMemsetAsync(h->fine_tmp, 0, (size_t)(sz[0] + 4) * (sz[1] + 4) * (sz[2] + 4) * sizeof(REAL), ctx.stream));
@@ -299,7 +300,7 @@ void mg_relevel(cz_mg* h) {
     for (REAL* a : {h->x[l], h->t[l]})
       if (a) HIP_CHECK(hipMemsetAsync(a, 0, (size_t)(h->lev[l].sz[0] + 4) * (h->lev[l].sz[1] + 4) * (h->lev[l].sz[2] + 4) * sizeof(REAL), ctx.stream));
 }
-}  // namespace
+}  // namespace czhip_internal
 
 extern "C" {
 
@@ -308,10 +309,7 @@ extern "C" {
 // level keeps at least 3 points along its longest direction
 int czhip_mg_set_neumann(cz_mg* h, const int* faces) {
   if (!h || !faces) return 0;
-  int nm = 0;
-  for (int f = 0; f < 6; f++) nm |= faces[f] ? 1 << f : 0;
-  h->nm_set = nm;
-  mg_relevel(h);
+  czhip_internal::mg_set_bc(h, h->bc.with_faces(faces));
   return 1;
 }
 
@@ -319,8 +317,7 @@ int czhip_mg_set_neumann(cz_mg* h, const int* faces) {
 // flags of a periodic direction are ignored while it is periodic
 int czhip_mg_set_periodic(cz_mg* h, const int* dirs) {
   if (!h || !dirs) return 0;
-  h->per = (dirs[0] ? 1 : 0) | (dirs[1] ? 2 : 0) | (dirs[2] ? 4 : 0);
-  mg_relevel(h);
+  czhip_internal::mg_set_bc(h, h->bc.with_dirs(dirs));
   return 1;
 }
 int czhip_mg_kind(const cz_mg* h) { return h ? 1 + h->rb : 0; }
@@ -338,23 +335,16 @@ void czhip_mg_destroy(cz_mg* h) {
 }  // extern "C"
 
 namespace {
-// the Neumann face layers of a level-0 array from its first inner layers
-// (with a periodic direction: the one fill launch that wraps and mirrors)
+// the face layers of a level-0 array: the mirror of the first inner layer on its Neumann faces, the wrap in its periodic
+// directions, in one launch
 void mg_mirror(cz_mg* h, REAL* x) {
-  int faces[6];
-  for (int f = 0; f < 6; f++) faces[f] = (h->nm >> (6 + (f >> 1))) & 1 ? 2 : (h->nm >> f) & 1;
-  if (h->nm >> 6 ? !czhip_fill_faces_async(x, h->lev[0].sz, h->lev[0].idx, MG_GUIDE, faces)
-                 : !czhip_mirror_faces_async(x, h->lev[0].sz, h->lev[0].idx, MG_GUIDE, faces))
-    cz_fatal(1, "czhip: V-cycle: the mirror of the Neumann faces was refused\n");
+  if (!czhip_internal::fill_bc_async(x, h->lev[0].sz, h->lev[0].idx, MG_GUIDE, h->lev[0].nm, true)) cz_fatal(1, "czhip: V-cycle: the mirror of the Neumann faces was refused\n");
 }
 // the wrap of a level >= 1 array's ghost layers in the level's periodic directions (nothing without one): before every kernel that reads
 // the array's neighbours.  The masked diagonal needs no mirror there
 bool mg_wraps(const cz_mg* h, int l) { return (h->lev[l].nm >> 6) != 0; }
 void mg_wrap(cz_mg* h, int l, REAL* x) {
-  const int w = h->lev[l].nm >> 6;
-  if (!w) return;
-  const int kinds[6] = {w & 1 ? 2 : 0, w & 1 ? 2 : 0, w & 2 ? 2 : 0, w & 2 ? 2 : 0, w & 4 ? 2 : 0, w & 4 ? 2 : 0};
-  if (!czhip_fill_faces_async(x, h->lev[l].sz, h->lev[l].idx, MG_GUIDE, kinds)) cz_fatal(1, "czhip: V-cycle: the wrap of a periodic level was refused\n");
+  if (!czhip_internal::fill_bc_async(x, h->lev[l].sz, h->lev[l].idx, MG_GUIDE, h->lev[l].nm, false)) cz_fatal(1, "czhip: V-cycle: the wrap of a periodic level was refused\n");
 }
 
 // level 0's pairs of sweeps with the unit coefficients, u -> w (u = nullptr: from zero): the fused pass, or where it is not taken two single
@@ -364,18 +354,18 @@ void mg_fine_pair(cz_mg* h, REAL* u, REAL* w, REAL* o, const REAL* b, REAL omg) 
   const int* sz = h->lev[0].sz;
   const int* idx = h->lev[0].idx;
   REAL cf[7] = {1, 1, 1, 1, 1, 1, 6};
-  if (!h->nm && (u ? czhip_jacobi2_async(u, w, b, sz, idx, nullptr, MG_GUIDE, cf, omg, h->res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr)
+  if (!h->lev[0].nm && (u ? czhip_jacobi2_async(u, w, b, sz, idx, nullptr, MG_GUIDE, cf, omg, h->res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr)
                    : czhip_jacobi2_from_zero_async(w, w, b, sz, idx, nullptr, MG_GUIDE, cf, omg, h->res)))
     return;
   const size_t nbytes = (size_t)(sz[0] + 4) * (sz[1] + 4) * (sz[2] + 4) * sizeof(REAL);
   if (!u) {
     HIP_CHECK(hipMemsetAsync(o, 0, nbytes, ctx.stream));
     u = o;
-  } else if (h->nm) {
+  } else if (h->lev[0].nm) {
     mg_mirror(h, u);
   }
   czhip_jacobi_async(u, w, b, sz, idx, MG_GUIDE, cf, omg, h->res, 0, nullptr);
-  if (h->nm) mg_mirror(h, w);
+  if (h->lev[0].nm) mg_mirror(h, w);
   czhip_jacobi_async(w, o, b, sz, idx, MG_GUIDE, cf, omg, h->res, 0, nullptr);
   HIP_CHECK(hipMemcpyAsync(w, o, nbytes, hipMemcpyDeviceToDevice, ctx.stream));
 }
@@ -408,7 +398,7 @@ struct MgOps {
     const int* sz = h->lev[0].sz;
     const int* idx = h->lev[0].idx;
     const REAL cf[7] = {1, 1, 1, 1, 1, 1, 6};
-    if (h->nm) return 0;  // (Neumann faces: the colour sweeps in place, a mirror after each)
+    if (h->lev[0].nm) return 0;  // (Neumann faces: the colour sweeps in place, a mirror after each)
     if ((!zero || h->zero4) && czhip_rbsor4_async(x0, o0, r, sz, idx, MG_GUIDE, cf, 0, omg, h->res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 1)) return 1;
     return czhip_internal::pair_probe(x0, o0, r, sz, idx, idx, MG_GUIDE, (REAL)6, 0) ? 2 : 0;
   }
@@ -431,10 +421,10 @@ struct MgOps {
     } else {
       // (Neumann faces: the ghost of a cell is read by that cell alone, so one mirror after every colour sweep serves the next one; the
       // prolongation moved the iterate to an array whose face layers are stale)
-      if (h->nm && !zero) mirror(x0);
+      if (h->lev[0].nm && !zero) mirror(x0);
       for (int s = 0; s < 4; s++) {
         czhip_rbsor_async(x0, r, sz, idx, MG_GUIDE, cf, ofst, s & 1, omg, h->res, 0, nullptr);
-        if (h->nm) mirror(x0);
+        if (h->lev[0].nm) mirror(x0);
       }
     }
   }
@@ -475,7 +465,7 @@ struct MgOps {
     must(czhip_internal::mg_smooth_async(h->t[l], h->x[l], h->b[l], h->lev[l], omg));
   }
   void restrict_down(int l) {
-    if (l == 0 && h->nm && !h->rb) mirror(x0);  // (mgrb: mirrored after its last colour sweep)
+    if (l == 0 && h->lev[0].nm && !h->rb) mirror(x0);  // (mgrb: mirrored after its last colour sweep)
     if (l && !h->rb) mg_wrap(h, l, h->x[l]);
     must(czhip_internal::mg_restrict_async(h->b[l + 1], h->lev[l + 1], x(l), l ? h->b[l] : r, nullptr, h->lev[l]));
   }

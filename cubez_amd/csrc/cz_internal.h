@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "cz_bc.h"
 #include "cz_hip.h"
 #include "cz_mg_cycle.h"
 
@@ -150,6 +151,9 @@ int field_div_async(CZ_REAL* rhs, const CZ_REAL* u, const CZ_REAL* v, const CZ_R
                     double scale, int form, double* sumsq_dev);
 int field_grad_async(CZ_REAL* u, CZ_REAL* v, CZ_REAL* w, const CZ_REAL* p, const int* sz, int g, const long long* stride, int per, double scale, int form);
 void bc_async(const int* sz, int g, CZ_REAL* p, CZ_REAL dh, const CZ_REAL* org, const int* nID, int ioff = 0, int joff = 0);
+// the face layers of an array of a level with packed word `word` (cz_bc.h: bc_kinds, czhip_fill_faces_async): one launch, none where the
+// word leaves nothing to fill; 0 = refused
+int fill_bc_async(CZ_REAL* p, const int* sz, const int* idx, int g, int word, bool mirrors);
 
 // ---- the multigrid V-cycle of pcg ... mg (cz_h_mg.h, and cz_mg_dist.cpp for decomposed runs)
 // What one domain holds of level `level` of a grid of n0 level-0 points: an array of guide g (sz / idx as a fine brick's: inner 1 .. size on
@@ -163,19 +167,6 @@ struct MgdLevel {
   int nm;  // zero-flux (Neumann) faces of the global box, bit f = X-, X+, Y-, Y+, Z-, Z+: the diagonal of levels >= 1
            // bits 6 .. 8: the level's ghost layers of direction X, Y, Z hold the periodic wrap (mg_level_bc)
 };
-// One level's value of MgdLevel::nm from the state that was set (nm: the six Neumann flags, per: bit d = direction d is periodic) and the
-// level's global points gn.  In a periodic direction the Neumann flags are ignored; a level of two or more points there wraps (bit 6 + d),
-// a level of one point has no link in that direction -- the point's neighbours are itself -- and takes both mask bits (c = 0) and no wrap.
-// per = 0: nm itself, at every level
-inline int mg_level_bc(int nm, int per, const int* gn) {
-  int v = 0;
-  for (int d = 0; d < 3; d++) {
-    if (!((per >> d) & 1)) v |= nm & (3 << (2 * d));
-    else if (gn[d] < 2) v |= 3 << (2 * d);
-    else v |= 64 << d;
-  }
-  return v;
-}
 // the launches of the level kernels; 0 = refused, nothing launched
 int mg_smooth_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const MgdLevel& L, CZ_REAL omg);  // u = nullptr: from zero
 // rt (nullptr where F is a whole level): the residual of the children on the + neighbours, from mgd_resface_async and its exchange
@@ -193,6 +184,9 @@ int mgd_unpack_async(CZ_REAL* X, const MgdLevel& G, const CZ_REAL* blk, const in
 // a single domain only).  nullptr: no such level
 cz_mg* mg_create(const int* n0, int l0, bool tail, const int* sz0 = nullptr, const int* idx0 = nullptr, bool rb = false);
 int mg_cycle_async(cz_mg* h, CZ_REAL omg);  // x[first] = V_first(b[first]) of a hierarchy with first >= 1 (0: refused)
+// the boundary state of the hierarchy's cycles from now on: every level's word, and zeros again in the arrays whose ghost layers carried the
+// state before (what czhip_mg_set_neumann and czhip_mg_set_periodic come to, each with its half of the state replaced)
+void mg_set_bc(cz_mg* h, CzBc bc);
 }  // namespace czhip_internal
 
 // the handle of the public C-ABI: levels first .. nlev-1 of a hierarchy of nlev levels
@@ -204,9 +198,8 @@ struct cz_mg {
   double* res = nullptr;        // the sums the level-0 sweeps write (unused)
   int tail_from = 0;            // first level run by mg_tail_k (nlev: none)
   int rb = 0;                   // the smoother: 0 relaxed Jacobi (mg), 1 symmetric red-black (mgrb; t stays unallocated)
-  int nm = 0;                   // zero-flux (Neumann) faces, bit f of the six (czhip_mg_set_neumann): level 0 mirrors, levels >= 1 take the masked diagonal
-                                // (with a periodic direction: level 0's value of mg_level_bc, wrap bits included)
-  int nm_set = 0, per = 0;      // the state as set: the six Neumann flags, the periodic directions (bit d; czhip_mg_set_periodic)
+  CzBc bc;                      // the state as set (mg_set_bc): lev[l].nm is level l's word of it.  Level 0 mirrors its Neumann faces, levels >= 1
+                                // take the masked diagonal; a periodic direction wraps at every level
   int zero4 = 0;                // mgrb, level 0: the two iterations from zero as one two-iteration pass over a cleared array (CZ_MGRB_ZERO4)
 };
 

@@ -1418,34 +1418,11 @@ void bc_async(const int* sz, int g, REAL* p, REAL dh, const REAL* org, const int
 }  // namespace czhip_internal
 
 extern "C" {
-// the mirror of the first inner layer into the face layer of every face flagged in faces[6] that is a physical face of the brick (idx starts at 2
-// / ends at size - 1 there: the inner-range convention of a brick), in one launch (mirror_faces_k); 0 = refused, nothing launched
-int czhip_mirror_faces_async(CZ_REAL* p, const int* sz, const int* idx, int g, const int* faces) {
-  ensure_init();
-  if (!p || !sz || !idx || !faces) return 0;
-  const Box b = make_box(sz, idx, g);
-  if (b.empty) return 1;
-  MirrorFaces m;
-  m.nkp = b.nkp, m.nip = b.nip, m.ii0 = b.ii0, m.ii1 = b.ii1, m.jj0 = b.jj0, m.jj1 = b.jj1, m.kk0 = b.kk0, m.kk1 = b.kk1, m.n = 0;
-  int rows = 0;
-  for (int f = 0; f < 6; f++) {
-    const int d = f >> 1;
-    const bool physical = (f & 1) ? idx[2 * d + 1] == sz[d] - 1 : idx[2 * d] == 2;
-    if (!faces[f] || !physical) continue;
-    m.face[m.n++] = f;
-    rows = std::max(rows, d == 1 ? b.ii1 - b.ii0 + 1 : b.jj1 - b.jj0 + 1);
-  }
-  for (int q = m.n; q < 6; q++) m.face[q] = 0;
-  if (!m.n) return 1;
-  ScopedTimer tm(LBL_BC_MIRROR);
-  hipLaunchKernelGGL(mirror_faces_k, dim3((unsigned)((rows + 3) / 4), (unsigned)m.n), dim3(256), 0, ctx.stream, p, m);
-  HIP_CHECK(hipGetLastError());
-  return 1;
-}
-
-// every face layer listed in kinds[6] (X-, X+, Y-, Y+, Z-, Z+: 0 leave, 1 mirror, 2 wrap) in one launch (fill_faces_k).  A mirror
-// on a face that is not physical on the brick is skipped, as czhip_mirror_faces_async skips it; a wrap needs both faces of its direction to be
-// kind 2 and both to be physical on the brick (the direction is not cut).  0 = refused, nothing launched
+// every face layer listed in kinds[6] (X-, X+, Y-, Y+, Z-, Z+: 0 leave, 1 mirror, 2 wrap) in one launch (fill_faces_k; without a wrap
+// mirror_faces_k, which makes the same stores).  A
+// mirror is made on a physical face of the brick only (idx starts at 2 / ends at size - 1 there: the inner-range convention of a brick) and
+// skipped elsewhere; a wrap needs both faces of its direction to be kind 2 and both to be physical on the brick (the direction is not cut).
+// 0 = refused, nothing launched
 int czhip_fill_faces_async(CZ_REAL* p, const int* sz, const int* idx, int g, const int* kinds) {
   ensure_init();
   if (!p || !sz || !idx || !kinds) return 0;
@@ -1479,11 +1456,37 @@ int czhip_fill_faces_async(CZ_REAL* p, const int* sz, const int* idx, int g, con
   for (int q = m.n; q < 6; q++) m.dir[q] = 0, m.dst[q] = m.src[q] = lo[0];
   if (!m.n) return 1;
   ScopedTimer tm(LBL_BC_MIRROR);
-  hipLaunchKernelGGL(fill_faces_k, dim3((unsigned)((rows + 3) / 4), (unsigned)m.n), dim3(256), 0, ctx.stream, p, m);
+  const dim3 grid((unsigned)((rows + 3) / 4), (unsigned)m.n);
+  if (kinds[0] == 2 || kinds[2] == 2 || kinds[4] == 2) {
+    hipLaunchKernelGGL(fill_faces_k, grid, dim3(256), 0, ctx.stream, p, m);
+  } else {
+    // no wrap: every entry is a mirror, and mirror_faces_k makes the same stores from the face's number alone; per launch it measured 1 - 3 %
+    // (0.3 - 0.6 us at 512^3) under the fill of the same faces, more than the run-to-run spread (profiles/r22/one_boundary_state.txt)
+    MirrorFaces f;
+    f.nkp = m.nkp, f.nip = m.nip, f.ii0 = m.ii0, f.ii1 = m.ii1, f.jj0 = m.jj0, f.jj1 = m.jj1, f.kk0 = m.kk0, f.kk1 = m.kk1, f.n = m.n;
+    for (int q = 0; q < 6; q++) f.face[q] = q < m.n ? 2 * m.dir[q] + (m.dst[q] > m.src[q] ? 1 : 0) : 0;
+    hipLaunchKernelGGL(mirror_faces_k, grid, dim3(256), 0, ctx.stream, p, f);
+  }
   HIP_CHECK(hipGetLastError());
   return 1;
 }
+
+// the mirrors alone: the fill with kind 1 on every flagged face (any non-zero flag) and kind 0 on the others
+int czhip_mirror_faces_async(CZ_REAL* p, const int* sz, const int* idx, int g, const int* faces) {
+  if (!faces) return 0;
+  int kinds[6];
+  for (int f = 0; f < 6; f++) kinds[f] = faces[f] ? 1 : 0;
+  return czhip_fill_faces_async(p, sz, idx, g, kinds);
+}
 }  // extern "C"
+
+namespace czhip_internal {
+int fill_bc_async(REAL* p, const int* sz, const int* idx, int g, int word, bool mirrors) {
+  int kinds[6];
+  bc_kinds(kinds, word, mirrors);
+  return czhip_fill_faces_async(p, sz, idx, g, kinds);
+}
+}  // namespace czhip_internal
 
 // ------------------------------------------------------------------------------------------------------------
 // PCG (beyond the reference; CZ::PCG, DESIGN.md "PCG"): the update pass, the direction + SpMV pass and the scalars

@@ -26,7 +26,7 @@ using namespace czhip_internal;
 struct MgDist {
   int nlev = 0, G = 0, nproc = 1;
   int n0[3] = {0, 0, 0};
-  MgdLevel lev[MG_MAXLEV];         // distributed levels 0 .. G-1 (level 0: the driver's arrays)
+  MgdLevel lev[MG_MAXLEV];         // distributed levels 0 .. G-1 (level 0: the driver's arrays); nm: the level's word of the state (mgd_set_bc)
   MgdLevel blk;                    // this brick's owned block of level G (dense: the all-gather's send buffer)
   cz_mg* g = nullptr;              // levels G .. coarsest: a single-domain hierarchy on every rank
   CommCtx* comm[MG_MAXLEV] = {};   // level 0: the driver's; 1 .. G-1 own ones
@@ -38,9 +38,6 @@ struct MgDist {
   std::vector<int> bo, bc;         // every rank's level-G block: global offset and points, 3 per rank
   double* res = nullptr;           // the sums the level-0 sweeps write (unused)
   int exchanges = 0;               // halo exchanges + all-gathers of the last cycle
-  int faces[6] = {0, 0, 0, 0, 0, 0};  // zero-flux (Neumann) faces of the global box (mgd_set_neumann)
-  bool masked = false;
-  int nm = 0, per = 0;             // the state as set: the six flags as bits, the periodic directions (bit d; mgd_set_periodic)
 };
 
 namespace {
@@ -61,19 +58,24 @@ void fatal_if(bool bad, const char* what) {
 
 size_t padded(const MgdLevel& L) { return (size_t)(L.sz[0] + 2 * GUIDE) * (L.sz[1] + 2 * GUIDE) * (L.sz[2] + 2 * GUIDE); }
 
-// every distributed level's and the gathered block's mask from the state as set (mg_level_bc: without a periodic direction the six flags at
+}  // namespace
+
+// The state of the global box, the same on every rank; its periodic directions are not cut by the decomposition (the driver checks), so every
+// brick holds both faces of such a direction at every level and the wrap is the single domain's fill beside the exchange.  Every distributed
+// level, the gathered block and the hierarchy of the gathered levels learn it (mg_level_bc: without a periodic direction the six flags at
 // every level); the arrays whose ghost layers carried an earlier state's mirrors or wraps are zeros again
-void mgd_relevel(MgDist* h) {
-  int wraps = h->per;
-  for (int l = 0; l < std::max(h->G, 1); l++) wraps |= h->lev[l].nm >> 6;
-  for (int l = 0; l < MG_MAXLEV; l++) h->lev[l].nm = l < std::max(h->G, 1) ? mg_level_bc(h->nm, h->per, h->lev[l].gn) : h->nm;
-  h->blk.nm = h->G > 0 ? mg_level_bc(h->nm, h->per, h->blk.gn) : h->nm;
+void mgd_set_bc(MgDist* h, CzBc bc) {
+  if (h->g) mg_set_bc(h->g, bc);
+  const int dist = std::max(h->G, 1);
+  int wraps = bc.per;
+  for (int l = 0; l < dist; l++) wraps |= h->lev[l].nm >> 6;
+  for (int l = 0; l < dist; l++) h->lev[l].nm = mg_level_bc(bc, h->lev[l].gn);
+  h->blk.nm = mg_level_bc(bc, h->blk.gn);  // (G = 0: there is no block)
   HIP_CHECK(hipMemsetAsync(h->tmp0, 0, padded(h->lev[0]) * sizeof(REAL_TYPE), stream()));
   for (int l = 1; wraps && l < h->G; l++)
     for (REAL_TYPE* a : {h->x[l], h->t[l]})
       if (a) HIP_CHECK(hipMemsetAsync(a, 0, padded(h->lev[l]) * sizeof(REAL_TYPE), stream()));
 }
-}  // namespace
 
 MgDist* mgd_create(const CZ& cz, CommCtx* comm0, int gather_points, bool tail) {
   if (cz.numProc < 2 || !comm0) return nullptr;
@@ -180,29 +182,6 @@ void mgd_destroy(MgDist* h) {
   delete h;
 }
 
-// the global mask, the same on every rank: every distributed level, the gathered block and the hierarchy of the gathered levels learn it
-int mgd_set_neumann(MgDist* h, const int* faces) {
-  if (!h || !faces) return 0;
-  int nm = 0;
-  for (int f = 0; f < 6; f++) nm |= faces[f] ? 1 << f : 0;
-  if (h->g && !czhip_mg_set_neumann(h->g, faces)) return 0;
-  for (int f = 0; f < 6; f++) h->faces[f] = faces[f] ? 1 : 0;
-  h->masked = nm != 0;
-  h->nm = nm;
-  mgd_relevel(h);
-  return 1;
-}
-
-// the periodic directions, the same on every rank and none of them cut by the decomposition (the driver checks): every brick then holds both
-// faces of such a direction at every level, and the wrap is the single domain's fill beside the exchange
-int mgd_set_periodic(MgDist* h, const int* dirs) {
-  if (!h || !dirs) return 0;
-  if (h->g && !czhip_mg_set_periodic(h->g, dirs)) return 0;
-  h->per = (dirs[0] ? 1 : 0) | (dirs[1] ? 2 : 0) | (dirs[2] ? 4 : 0);
-  mgd_relevel(h);
-  return 1;
-}
-
 int mgd_levels(const MgDist* h) { return h ? h->nlev : 0; }
 int mgd_gather_level(const MgDist* h) { return h ? h->G : 0; }
 int mgd_exchanges(const MgDist* h) { return h ? h->exchanges : 0; }
@@ -218,17 +197,12 @@ struct MgdOps {
 
   REAL_TYPE* x(int l) { return l ? h->x[l] : x0; }
   const REAL_TYPE* b(int l) { return l ? h->b[l] : r; }
-  // (level 0 with Neumann faces: the mirror of the brick's physical faces stands beside the exchange; it is not one)
+  // (the fill of the brick's physical faces stands beside the exchange; it is not one: level 0 mirrors its Neumann faces, every level wraps
+  // its periodic directions -- DESIGN.md §5.13, §5.15)
   void halo(int l, REAL_TYPE* X) {
     fatal_if(!comm_halo(h->comm[l], X, nullptr, stream()), "face exchange");
     h->exchanges++;
-    if (h->lev[l].nm >> 6) {  // (periodic directions: the one fill that wraps and, at level 0, mirrors -- DESIGN.md §5.15)
-      int kinds[6];
-      for (int f = 0; f < 6; f++) kinds[f] = (h->lev[l].nm >> (6 + (f >> 1))) & 1 ? 2 : l == 0 ? (h->lev[0].nm >> f) & 1 : 0;
-      fatal_if(!czhip_fill_faces_async(X, h->lev[l].sz, h->lev[l].idx, GUIDE, kinds), "fill of the periodic and Neumann faces");
-    } else if (l == 0 && h->masked) {
-      fatal_if(!czhip_mirror_faces_async(X, h->lev[0].sz, h->lev[0].idx, GUIDE, h->faces), "mirror of the Neumann faces");
-    }
+    fatal_if(!fill_bc_async(X, h->lev[l].sz, h->lev[l].idx, GUIDE, h->lev[l].nm, l == 0), "fill of the periodic and Neumann faces");
   }
   void halo_full(int l, REAL_TYPE* X) {
     fatal_if(!comm_halo_full(h->comm[l], X, stream()), "face + edge + corner exchange");

@@ -383,7 +383,8 @@ int czhip_mg_tail_rb_async(CZ_REAL* x, const CZ_REAL* b, const int* sz, const in
 cz_mg* czhip_mg_create_rb(const int* sz, const int* idx, int g, const CZ_REAL* cf);
 int czhip_mg_kind(const cz_mg* h);
 /* Zero-flux (Neumann) faces.  faces[6]: X-, X+, Y-, Y+, Z-, Z+, non-zero = Neumann.
- * czhip_mirror_faces_async: on every flagged face that is a physical face of the brick (idx starts at 2 / ends at size - 1 in that direction,
+ * czhip_mirror_faces_async: czhip_fill_faces_async (below) with kind 1 on every face whose flag is non-zero and kind 0 on the others; no flag
+ *   means a wrap, none is refused.  On every flagged face that is a physical face of the brick (idx starts at 2 / ends at size - 1 in that direction,
  *   the inner-range convention of a brick; a rank-internal face is never touched) the face layer becomes the mirror of the first inner
  *   layer, p(1, j, k) = p(2, j, k) resp. p(size, j, k) = p(size-1, j, k), j and k over idx; edges, corners and every other cell keep their
  *   bytes.  One launch (label bc_mirror).  With that layer the kernels' own statement is the zero-flux operator at the cells next to it.
@@ -394,7 +395,7 @@ int czhip_mg_kind(const cz_mg* h);
 int czhip_mirror_faces_async(CZ_REAL* p, const int* sz, const int* idx, int g, const int* faces);
 int czhip_mg_set_neumann(cz_mg* h, const int* faces);
 /* Periodic directions.
- * czhip_fill_faces_async: kinds[6], order X-, X+, Y-, Y+, Z-, Z+: 0 leave the face layer, 1 the mirror of czhip_mirror_faces_async (skipped on a
+ * czhip_fill_faces_async: kinds[6], order X-, X+, Y-, Y+, Z-, Z+: 0 leave the face layer, 1 the mirror described at czhip_mirror_faces_async (skipped on a
  *   face that is not physical on the brick), 2 the wrap, p(1, j, k) = p(size-1, j, k) and p(size, j, k) = p(2, j, k), j and k over idx.  A
  *   wrap needs both faces of its direction to be 2 and both to be physical on the brick.  One launch for every face listed (label bc_mirror);
  *   edges, corners and every other cell keep their bytes.  It serves the level arrays of a hierarchy as well (S3D arrays, sz / idx / g).
