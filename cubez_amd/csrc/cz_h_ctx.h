@@ -24,6 +24,7 @@ struct Tuning {
   int jac3 = 1, jac3_kwin = 0, jac3_tj = 0;       // three Jacobi sweeps per pass (jac3_k) in single-domain runs: 0 off, 1 above the size gate, 2 also
                                                   // below it; vectors per k window / planes per chunk (0: the launcher's rule); CZHIP_JAC3
   int jac3_medium = 1;                            // jac3_k FP32: the checked shorter division (mediumdiv) for divisors that passed (CZHIP_JAC3_MEDIUM)
+  int jac3_gate = 1;                              // jac3_k: the gated form of its division -- huge numerators tested per vector, not per point -- for divisors that passed (czhip_set_jac3_gate)
   int unit_coef = 1;                              // the kernels' form for coefficients that are all exactly 1 (offdiag_sum<UNIT>; CZHIP_UNIT_COEF)
   int t2_pre = 1;                                 // two-stage pass on small grids: every operand of a chunk requested before its first step (jacobi2p_k<PRE>; CZHIP_T2_PRE)
   int t2_map = 1;                                 // multi-stage passes: equal shares of (segment, chunk) items per XCD where bands would idle, and row bands of
@@ -69,6 +70,7 @@ struct Ctx {
   struct PairMap { int* dev = nullptr; long long nblk = 0; };
   std::map<long long, PairMap> pair_maps;        // workgroup id -> (segment, chunk) tables of the two-stage pass, key nwin << 48 | nsegw << 24 | nchunk
   std::map<unsigned long long, bool> medium_div;  // divisor bits -> did mediumdiv give the bits of n / d for every numerator (jac3_medium)
+  std::map<unsigned long long, bool> gated_div[2];  // ... did the gated tail of the hoisted [0] / medium [1] form for every numerator that is not huge (jac3_gated)
   std::set<const void*> lds_allowed;             // kernels whose dynamic LDS limit is raised on this context's device (allow_dynamic_lds)
   int num_cu = 256;
   int cu_reserved = 0;          // CUs per XCD the sweeps leave to the exchange stream (decomposed runs; reserve_comm_cus): the launch geometry counts them out

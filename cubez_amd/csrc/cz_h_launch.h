@@ -431,19 +431,21 @@ bool launch_rb4(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box&
   return true;
 }
 
-// numerators (of 2^32; see fastdiv_check_k) whose quotient by d in division form FORM (0 hoisted, 1 short, 2 medium) differs from `n / d`
+// numerators (of 2^32; see fastdiv_check_k) whose quotient by d in division form FORM (0 hoisted, 1 short, 2 medium, 3 / 4 the gated tail of the
+// hoisted / medium form) differs from `n / d`; *compared = how many were compared (all of them but for the gated tails, which skip the huge ones)
 template <int FORM>
-long long div_check_count(REAL d) {
-  unsigned long long* bad = nullptr;
-  HIP_CHECK(hipMalloc(&bad, sizeof(*bad)));
-  HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(*bad), ctx.stream));
-  hipLaunchKernelGGL(fastdiv_check_k<FORM>, dim3(4096), dim3(256), 0, ctx.stream, d, bad);
+long long div_check_count(REAL d, long long* compared = nullptr) {
+  unsigned long long* out = nullptr;
+  HIP_CHECK(hipMalloc(&out, 2 * sizeof(*out)));
+  HIP_CHECK(hipMemsetAsync(out, 0, 2 * sizeof(*out), ctx.stream));
+  hipLaunchKernelGGL(fastdiv_check_k<FORM>, dim3(4096), dim3(256), 0, ctx.stream, d, out);
   HIP_CHECK(hipGetLastError());
-  unsigned long long h = 0;
-  HIP_CHECK(hipMemcpyAsync(&h, bad, sizeof(h), hipMemcpyDeviceToHost, ctx.stream));
+  unsigned long long h[2] = {0, 0};
+  HIP_CHECK(hipMemcpyAsync(h, out, sizeof(h), hipMemcpyDeviceToHost, ctx.stream));
   HIP_CHECK(hipStreamSynchronize(ctx.stream));
-  HIP_CHECK(hipFree(bad));
-  return (long long)h;
+  HIP_CHECK(hipFree(out));
+  if (compared) *compared = (long long)h[1];
+  return (long long)h[0];
 }
 // Does jac3_k divide by d with mediumdiv (cz_k_fastdiv.h: 8 instructions against 10)?  FP32 only, ctx.tune.jac3_medium.  Only a divisor whose
 // quotients agree with `n / d` in every bit for all 2^32 numerators: the comparison runs once per context and divisor (a few ms, synchronous),
@@ -458,6 +460,26 @@ inline bool jac3_medium(REAL d) {
     if constexpr (sizeof(REAL) == 4) bad = div_check_count<2>(d);
     it = ctx.medium_div.emplace(key, bad == 0).first;
   }
+  return it->second;
+}
+
+// the gated tail of the form jac3_k takes (medium: FP32 only) against `n / d`
+inline long long gated_check(REAL d, bool med, long long* compared) {
+  if constexpr (sizeof(REAL) == 4) {
+    if (med) return div_check_count<4>(d, compared);
+  }
+  return div_check_count<3>(d, compared);
+}
+// Does jac3_k divide by d in the gated form (GatedDiv, cz_k_pass.h) of the division it takes, medium or hoisted?  ctx.tune.jac3_gate, and only
+// a divisor whose gated tail agreed with `n / d` in every bit for all numerators below the threshold (FP32: all 2^32 floats; FP64: the 2^32
+// sampled doubles the hoisted form rests on): once per context, divisor and form, synchronous, at the first launch that needs it.
+inline bool jac3_gated(REAL d, bool med) {
+  if (!ctx.tune.jac3_gate || !fastdiv_ok(d)) return false;
+  unsigned long long key = 0;
+  memcpy(&key, &d, sizeof(REAL));
+  auto& verdicts = ctx.gated_div[med ? 1 : 0];
+  auto it = verdicts.find(key);
+  if (it == verdicts.end()) it = verdicts.emplace(key, gated_check(d, med, nullptr) == 0).first;
   return it->second;
 }
 
@@ -488,11 +510,19 @@ bool launch_jac3(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box
   if (probe) return true;
   fin.single = 0;
   const bool unit = ctx.tune.unit_coef && coef_is_unit(c);
-  if (!jac3_medium(c.dd)) {
-    launch_pass(!unit ? &jac3_k<VW, TB, 0, 0> : &jac3_k<VW, TB, 1, 0>, LBL_JACOBI3, p, U, B, W, c, skip, fin);  // (UNIT = 0 named first: it keeps its place in the code object)
-  } else {
-    if constexpr (sizeof(REAL) == 4) launch_pass(!unit ? &jac3_k<VW, TB, 0, 1> : &jac3_k<VW, TB, 1, 1>, LBL_JACOBI3, p, U, B, W, c, skip, fin);
+  const bool med = jac3_medium(c.dd), gate = jac3_gated(c.dd, med);
+  // (the ungated instantiations are named first, UNIT = 0 before UNIT = 1: they keep their place in the code object)
+  auto kernel = !unit ? &jac3_k<VW, TB, 0, 0> : &jac3_k<VW, TB, 1, 0>;
+  if constexpr (sizeof(REAL) == 4) {
+    if (med) kernel = !unit ? &jac3_k<VW, TB, 0, 1> : &jac3_k<VW, TB, 1, 1>;
   }
+  if (gate) {
+    kernel = !unit ? &jac3_k<VW, TB, 0, 0, 1> : &jac3_k<VW, TB, 1, 0, 1>;
+    if constexpr (sizeof(REAL) == 4) {
+      if (med) kernel = !unit ? &jac3_k<VW, TB, 0, 1, 1> : &jac3_k<VW, TB, 1, 1, 1>;
+    }
+  }
+  launch_pass(kernel, LBL_JACOBI3, p, U, B, W, c, skip, fin);
   return true;
 }
 

@@ -51,7 +51,11 @@ __device__ __forceinline__ void complete_here(Vec<V>& x) {
 
 // MED = 1 (FP32): the division with one correction step (mediumdiv, cz_k_fastdiv.h), taken only for a divisor that passed the exhaustive
 // comparison with `n / d` on this context (jac3_medium, cz_h_launch.h)
-template <int V, int TB, int UNIT, int MED>
+// GATE = 1: that division (medium or hoisted, by MED) in its gated form (GatedDiv, cz_k_pass.h): whether a numerator is huge is tested once per
+// vector and wave instead of at every point.  Taken only for a divisor that passed its comparison on this context (jac3_gated, cz_h_launch.h).
+// What the compiler has to make of it -- the tail without den_s a block of its own in the inner step -- is part of the listing in
+// profiles/r23/jac3_gated_division.txt.
+template <int V, int TB, int UNIT, int MED, int GATE = 0>
 __global__ void __launch_bounds__(TB, 1)
 jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict__ W, Coef c, Geom2 g, double* partials,
        const int* __restrict__ skip, Fin2 fin) {
@@ -70,7 +74,7 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
   const int ja = it.ja, jb = it.jb;
 
   double acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-  const typename std::conditional<MED != 0, MediumDiv, HoistedDiv>::type dv{fastdiv_init(c.dd)};
+  const typename std::conditional<GATE != 0, GatedDiv<MED>, typename std::conditional<MED != 0, MediumDiv, HoistedDiv>::type>::type dv{fastdiv_init(c.dd)};
 
   if (it.work) {
     const long long e2_0 = it.fb - 2 * (long long)R;  // first vector of E2

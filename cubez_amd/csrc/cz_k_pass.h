@@ -115,6 +115,36 @@ struct MediumDiv {
   __device__ __forceinline__ REAL operator()(REAL n) const { return mediumdiv(n, f); }
 };
 
+// The medium (MED = 1) or hoisted (MED = 0) form, GATED (cz_k_fastdiv.h): one test per vector and wave whether any numerator is huge, and
+// where none is -- every wave of a real field -- the tail without den_s, compare and select.  A policy with a vector-level entry: relax_vec
+// hands it the V numerators of a vector at once.  Only for divisors that passed fastdiv_check_k<3 | 4> on this context (jac3_gated, cz_h_launch.h).
+__device__ __forceinline__ float uniform_real(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); }
+__device__ __forceinline__ double uniform_real(double x) {
+  const unsigned long long b = __builtin_bit_cast(unsigned long long, x);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+template <int MED>
+struct GatedDiv {
+  FastDiv<REAL> f;
+  REAL T;  // f.T, the same in every lane (a scalar register)
+  __device__ __forceinline__ explicit GatedDiv(const FastDiv<REAL>& f_) : f(f_), T(uniform_real(f_.T)) {}
+  template <int V>
+  __device__ __forceinline__ void vec(const REAL (&n)[V], REAL (&q)[V]) const {
+    if (__builtin_expect(gated_none_huge<V>(n, T), 1)) {  // (expected: the gated tail is the fall-through path)
+#pragma unroll
+      for (int cc = 0; cc < V; cc++) q[cc] = gated_tail<MED>(n[cc], f);
+    } else {
+#pragma unroll
+      for (int cc = 0; cc < V; cc++) q[cc] = general_tail<MED>(n[cc], f);
+    }
+  }
+};
+template <class DIV>
+struct has_vec_entry : std::false_type {};
+template <int MED>
+struct has_vec_entry<GatedDiv<MED>> : std::true_type {};
+
 template <int V, int UNIT = 0, class DIV>
 __device__ __forceinline__ Vec<V> relax_vec(const Vec<V>& pc, const Vec<V>& im, const Vec<V>& ip, const Vec<V>& pm,
                                             const Vec<V>& pn, REAL kl, REAL kr, const Vec<V>& bb, const Coef& c, const DIV& dv,
@@ -123,13 +153,30 @@ __device__ __forceinline__ Vec<V> relax_vec(const Vec<V>& pc, const Vec<V>& im, 
 #if defined(CZ_P2_RES_GROUP)  // tools/pair_lab A/B only: the vector's dp^2 summed in REAL, one conversion and one double add per vector
   REAL grp = (REAL)0;
 #endif
+  constexpr bool BY_VECTOR = has_vec_entry<DIV>::value;  // the policy divides the V numerators of the vector at once
+  REAL nv[V], qv[V];
+  if constexpr (BY_VECTOR) {
+#pragma unroll
+    for (int cc = 0; cc < V; cc++) {
+      const REAL km1 = (cc == 0) ? kl : pc.v[cc > 0 ? cc - 1 : 0];
+      const REAL kp1 = (cc == V - 1) ? kr : pc.v[cc < V - 1 ? cc + 1 : V - 1];
+      nv[cc] = offdiag_sum<UNIT>(c, ip.v[cc], im.v[cc], pn.v[cc], pm.v[cc], kp1, km1) - bb.v[cc];
+    }
+    dv.template vec<V>(nv, qv);
+  }
 #pragma unroll
   for (int cc = 0; cc < V; cc++) {
     const REAL pp = pc.v[cc];
-    const REAL km1 = (cc == 0) ? kl : pc.v[cc > 0 ? cc - 1 : 0];
-    const REAL kp1 = (cc == V - 1) ? kr : pc.v[cc < V - 1 ? cc + 1 : V - 1];
-    const REAL ss = offdiag_sum<UNIT>(c, ip.v[cc], im.v[cc], pn.v[cc], pm.v[cc], kp1, km1);
-    const REAL dp = (dv(ss - bb.v[cc]) - pp) * c.omg;
+    REAL qd;
+    if constexpr (BY_VECTOR) {
+      qd = qv[cc];
+    } else {
+      const REAL km1 = (cc == 0) ? kl : pc.v[cc > 0 ? cc - 1 : 0];
+      const REAL kp1 = (cc == V - 1) ? kr : pc.v[cc < V - 1 ? cc + 1 : V - 1];
+      const REAL ss = offdiag_sum<UNIT>(c, ip.v[cc], im.v[cc], pn.v[cc], pm.v[cc], kp1, km1);
+      qd = dv(ss - bb.v[cc]);
+    }
+    const REAL dp = (qd - pp) * c.omg;
     const REAL d2 = dp * dp;
     o.v[cc] = (mask & (1u << cc)) ? pp + dp : pp;
 #if defined(CZ_P2_NO_RES)  // tools/pair_lab A/B only: no residual at all (what the accumulation costs at most)

@@ -158,7 +158,7 @@ const char* czhip_tuning_describe(void) {
       {"ready", ctx.ready ? 1 : 0}, {"threads", t.threads}, {"m", t.m}, {"tj", t.tj}, {"pf", t.pf}, {"fuse_fin", t.fuse_fin},
       {"use_t2", t.use_t2}, {"t2_threads", t.t2_threads}, {"t2_mv", t.t2_mv}, {"t2_tj", t.t2_tj}, {"t2_map", t.t2_map},
       {"t2_any_rows", t.t2_any_rows}, {"t2_kwin", t.t2_kwin}, {"t2_pre", t.t2_pre}, {"rb4", t.rb4}, {"rb4_kwin", t.rb4_kwin},
-      {"rb4_tj", t.rb4_tj}, {"jac3", t.jac3}, {"jac3_kwin", t.jac3_kwin}, {"jac3_tj", t.jac3_tj}, {"jac3_medium", t.jac3_medium},
+      {"rb4_tj", t.rb4_tj}, {"jac3", t.jac3}, {"jac3_kwin", t.jac3_kwin}, {"jac3_tj", t.jac3_tj}, {"jac3_medium", t.jac3_medium}, {"jac3_gate", t.jac3_gate},
       {"unit_coef", t.unit_coef}, {"pcr_fast", t.pcr_fast}, {"pcr_variant", t.pcr_variant}, {"pcr_pipe", t.pcr_pipe},
       {"pipe_spin_ticks", t.pipe_spin_ticks}, {"pcr_rows", t.pcr_rows}, {"pcr_q", t.pcr_q}, {"pcr_wg_per_cu", t.pcr_wg_per_cu},
       {"pcr_max_wg", t.pcr_max_wg}, {"pcr_slots", t.pcr_slots}, {"psor_col", t.psor_col}, {"psor_wg_per_cu", t.psor_wg_per_cu},
@@ -540,12 +540,30 @@ int czhip_set_jac3_medium(int enable) {
   return before;
 }
 
+// jac3_k: the gated form of its division on (1) or off (0); negative: keep.  Returns the setting that was in force.  Same bits either way, but
+// for one case: a residual sum over a field that holds NaNs of several payloads is NaN either way, with a payload and sign that may differ
+// (which NaN an addition hands on depends on its operand order, and the two instantiations are compiled apart).
+int czhip_set_jac3_gate(int enable) {
+  ensure_init();
+  const int before = ctx.tune.jac3_gate;
+  if (enable >= 0) ctx.tune.jac3_gate = enable;
+  return before;
+}
+
 // the division jac3_k takes for the divisor d on this context: 1 = mediumdiv, 0 = the hoisted form, -1 = the pass does not take d at all
 // (fastdiv_ok).  Runs the exhaustive check where it is due, as the first launch would.
 int czhip_jac3_division(CZ_REAL d) {
   ensure_init();
   if (!fastdiv_ok(d)) return -1;
   return jac3_medium(d) ? 1 : 0;
+}
+
+// does jac3_k take the gated form of its division for the divisor d on this context now: 1 yes, 0 no (switched off, or the comparison found a
+// difference), -1 = the pass does not take d at all.  Runs the comparison where it is due, as the first launch would.
+int czhip_jac3_gated(CZ_REAL d) {
+  ensure_init();
+  if (!fastdiv_ok(d)) return -1;
+  return jac3_gated(d, jac3_medium(d)) ? 1 : 0;
 }
 
 // rb4_k switches (measurements): enable 0 | 1, vectors per k window, planes per chunk (0: the launcher's rule); negative: keep.
@@ -647,6 +665,16 @@ long long czhip_selftest_mediumdiv(CZ_REAL d) {
   ensure_init();
   if (sizeof(CZ_REAL) != 4 || !fastdiv_ok(d)) return -1;
   return div_check_count<2>(d);
+}
+
+// The comparison jac3_gated decides by, for the form jac3_k takes for d on this context now (medium or hoisted: jac3_medium): numerators that
+// are not huge -- |n| < 2^(exponent(d) + 96), + 768 in FP64; NaNs count as not huge -- whose gated tail differs from `n / d`; *compared = how
+// many were compared.  -1 where the divisor is not eligible.
+long long czhip_selftest_gateddiv(CZ_REAL d, long long* compared) {
+  ensure_init();
+  if (compared) *compared = 0;
+  if (!fastdiv_ok(d)) return -1;
+  return gated_check(d, jac3_medium(d), compared);
 }
 
 // Measurement aid (tools/cu_reserve_cost.py): put the CU reservation of decomposed runs in force on this context by hand; returns what is in force.

@@ -238,6 +238,16 @@ int czhip_set_jac3(int enable, int window, int planes);
  * division for all 2^32 numerators on this context (once per divisor, at the first launch) and agreed in every bit; others keep the hoisted
  * form.  1 = on (default), 0 = off, negative = keep.  Returns the previous setting.  Results do not depend on it. */
 int czhip_set_jac3_medium(int enable);
+/* ... its division in the gated form: whether a numerator is so large that the division scales the divisor (|n| >= 2^(exponent(d) + 96), + 768 in
+ * FP64) is tested once per vector and wave, and where none is the quotient is formed without that case.  Taken for a divisor whose gated
+ * quotients were compared with the IEEE division on this context (once per divisor, at the first launch) and agreed in every bit.  1 = on
+ * (default), 0 = off, negative = keep.  Returns the previous setting.  Results do not depend on it, with one exception: a residual sum over a
+ * field that holds NaNs of several payloads is NaN either way, but its payload and sign may differ (the two forms are compiled apart, and
+ * which NaN an addition hands on depends on its operand order).  Fields keep every bit, NaN payloads included. */
+int czhip_set_jac3_gate(int enable);
+/* ... whether that pass takes the gated form for divisor d on this context now: 1 yes, 0 no, -1 = the pass does not take d (it runs the
+ * comparison where it is due, like the first launch). */
+int czhip_jac3_gated(CZ_REAL d);
 /* ... the division that pass takes for divisor d on this context: 1 = the shorter form, 0 = the hoisted form, -1 = the pass does not take d
  * (it runs the comparison where it is due, like the first launch). */
 int czhip_jac3_division(CZ_REAL d);
@@ -316,7 +326,7 @@ int czhip_set_unit_coef(int enable);
  * NAME (unset; default ...) otherwise; only_set != 0 lists the former only.  The string lives until the next call on the calling thread. */
 const char* czhip_config_describe(int only_set);
 /* What czhip_init and the setters made of the kernel switches: the calling thread's tuning (threads, m, tj, pf, fuse_fin, use_t2, t2_threads,
- * t2_mv, t2_tj, t2_map, t2_any_rows, t2_kwin, t2_pre, rb4, rb4_kwin, rb4_tj, jac3, jac3_kwin, jac3_tj, jac3_medium, unit_coef, pcr_fast,
+ * t2_mv, t2_tj, t2_map, t2_any_rows, t2_kwin, t2_pre, rb4, rb4_kwin, rb4_tj, jac3, jac3_kwin, jac3_tj, jac3_medium, jac3_gate, unit_coef, pcr_fast,
  * pcr_variant, pcr_pipe, pipe_spin_ticks, pcr_rows, pcr_q, pcr_wg_per_cu, pcr_max_wg, pcr_slots, psor_col, psor_wg_per_cu, psor_ahead), num_cu
  * and cu_reserved (the CU reservation of czhip_set_comm_cus), as name=value, one per line.  ready=0: the thread's context has not started,
  * the values are the built-in defaults (the call does not start it).  Read-only; the string lives until the next call on the calling thread. */
@@ -329,6 +339,9 @@ int czhip_set_comm_cus(int k);
 long long czhip_selftest_fastdiv(CZ_REAL d);
 /* the same for the shorter form jac3_k takes where it agrees (FP32; -1 = divisor not eligible, and in FP64, which has no such form) */
 long long czhip_selftest_mediumdiv(CZ_REAL d);
+/* the same for the gated form of the division jac3_k takes for d now: numerators below the threshold (NaNs included) whose quotient differs
+ * (expected 0); *compared = how many were compared; -1 = divisor not eligible */
+long long czhip_selftest_gateddiv(CZ_REAL d, long long* compared);
 
 /* PCG (beyond the reference; DESIGN.md "PCG"), the two passes of its iteration:
  * czhip_cg_update_async: x = alpha*p + x, r = (-alpha)*q + r on the inner box (blas_triad_ twice) and dots_dev[0] = r.r (per-point products in
