@@ -76,6 +76,7 @@ CZ::~CZ() {
   if (d_zc) (void)hipFree(d_zc);
   for (REAL_TYPE* a : arrs)
     if (a) czhip_free(a);
+  coef_clear();
   if (d_hist) (void)hipFree(d_hist);
   (void)hipFree(d_res);
   (void)hipFree(d_flag);
@@ -215,6 +216,7 @@ int CZ::Setup(int argc, char** argv) {
   // a set-up starts with Dirichlet faces: the hierarchy it builds knows no mask (cz_set_neumann comes after cz_setup)
   bc = CzBc();
   closed_box = 0;
+  coef_clear();  // (and with unit coefficients: cz_set_face_coef comes after cz_setup)
   closed_m[0] = closed_m[1] = closed_m[2] = 0.0;
   closed_m0_on_device = false;
   solve_plan = PassPlan();
@@ -384,8 +386,9 @@ int CZ::Setup(int argc, char** argv) {
 
 // Zero-flux faces are built for pcg (none | jacobi | mg | mgrb) alone: every other loop would sweep with Dirichlet faces
 bool CZ::neumann_refused(const char* who, int s_type) const {
-  if (!bc.any() || s_type == LS_PCG) return false;
-  if (bc.nm) fprintf(stderr, "%s: Neumann faces are set (cz_set_neumann) and the solver is not pcg\n", who);
+  if ((!bc.any() && !coef_on()) || s_type == LS_PCG) return false;
+  if (coef_on()) fprintf(stderr, "%s: face coefficients are set (cz_set_face_coef) and the solver is not pcg\n", who);
+  else if (bc.nm) fprintf(stderr, "%s: Neumann faces are set (cz_set_neumann) and the solver is not pcg\n", who);
   else fprintf(stderr, "%s: periodic directions are set (cz_set_periodic) and the solver is not pcg\n", who);
   return true;
 }
@@ -425,7 +428,7 @@ int CZ::Solve() {
 }
 
 int CZ::Evaluate(int argc, char** argv) {
-  if (bc.any() && argc > 4) {
+  if ((bc.any() || coef_on()) && argc > 4) {
     const cz_solvers::Row* named = cz_solvers::find(argv[4], cz_solvers::SOLVER);
     if (neumann_refused("cz_evaluate", named ? named->id : LS_NONE)) return 0;
   }
@@ -1389,7 +1392,10 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   const bool fuse = cfg.on(CZV_CG_FUSE, true);
   // the direction pass reads z's and p's shells as zeros: single domain only, and no Neumann face (whose layer of p is the mirror)
   // (nor a periodic direction, whose layer is the wrap)
-  const bool fuse_dir = fuse && numProc == 1 && !bc.any();
+  // face coefficients: A_beta where the operator is applied (the start and the SpMV, which stays unfused), and the
+  // preconditioner z = s M^-1 (s r) with M^-1 the constant-coefficient one below (cg_q is free for s r at that point)
+  const bool coef = coef_on();
+  const bool fuse_dir = fuse && numProc == 1 && !bc.any() && !coef;
   REAL_TYPE* const sc = reinterpret_cast<REAL_TYPE*>(d_res + 12);  // alpha, -alpha, beta, rho (cg_scal_k)
   double* const d_rr = d_res + 5;
   double* const d_pq = d_res + 3;                 // (the unfused SpMV writes q.q to d_res[4])
@@ -1404,8 +1410,9 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   pcg_void_start = 0;
 
   mirror(X);
-  calc_rk_async(cg_r, X, B, size, innerFidx, gc, cf);
-  flop += 14.0 * n;
+  if (!coef) calc_rk_async(cg_r, X, B, size, innerFidx, gc, cf);
+  else if (!coef_ax_async(1, cg_r, X, B, coef_b[0], coef_b[1], coef_b[2], size, innerFidx, gc, d_res + 10)) return 0;
+  flop += (coef ? 23.0 : 14.0) * n;
   if (closed) {
     // step 1: the initial residual into the range of the operator; the pass that writes r' returns sum r' (the first lagged mean, sc[4])
     // and sum r'^2 (none: the one r.r that no update made)
@@ -1437,8 +1444,13 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
     }
     if (pc) {
       if (!Comm_S(cg_r)) return 0;  // (a decomposed pass reads the right-hand side in its ghost layer)
+      REAL_TYPE* const rin = coef ? cg_q : cg_r;  // what M^-1 is applied to
+      if (coef) {
+        coef_scale_async(cg_q, cg_r, coef_s, size, gc);
+        flop += n;
+      }
       if (mg || mgd) {
-        if (mg ? !czhip_mg_apply_async(mg, cg_z, cg_r, ac1) : !mgd_apply(mgd, cg_z, cg_r, ac1)) return 0;  // z = V_0(r)
+        if (mg ? !czhip_mg_apply_async(mg, cg_z, rin, ac1) : !mgd_apply(mgd, cg_z, rin, ac1)) return 0;  // z = V_0(r)
         mg_cycles++;
       } else if (bc.any()) {
         // the 8 relaxed sweeps from zero as single sweeps between cg_z and cg_p[1] (free: the direction is not fused), the exchange and the
@@ -1450,14 +1462,18 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
             if (!Comm_S(src)) return 0;
             mirror(src);
           }
-          czhip_jacobi_async(src, dst, cg_r, size, innerFidx, gc, cf, ac1, d_res, 0, nullptr);
+          czhip_jacobi_async(src, dst, rin, size, innerFidx, gc, cf, ac1, d_res, 0, nullptr);
           std::swap(src, dst);
         }
         flop += 8 * 18.0 * n;
       } else {
         double fc = 0.0;
-        Preconditioner(cg_z, cg_r, fc, LS_JACOBI);
+        Preconditioner(cg_z, rin, fc, LS_JACOBI);
         flop += fc;
+      }
+      if (coef) {
+        coef_scale_async(cg_z, cg_z, coef_s, size, gc);
+        flop += n;
       }
       dot2_async(cg_r, cg_z, size, innerFidx, gc, d_rho);
       flop += 2.0 * n;
@@ -1473,10 +1489,11 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
       else triad_async(cg_p[cur], cg_p[cur], z, (REAL_TYPE)0, size, innerFidx, gc, sc + 2);  // p = beta p + z
       if (!Comm_S(cg_p[cur])) return 0;
       mirror(cg_p[cur]);
-      calc_ax_dots_async(cg_q, cg_p[cur], cg_p[cur], size, innerFidx, gc, cf, nullptr, d_pq);
+      if (!coef) calc_ax_dots_async(cg_q, cg_p[cur], cg_p[cur], size, innerFidx, gc, cf, nullptr, d_pq);
+      else if (!coef_ax_async(0, cg_q, cg_p[cur], nullptr, coef_b[0], coef_b[1], coef_b[2], size, innerFidx, gc, d_pq)) return 0;
     }
     if (itr > 1) flop += 2.0 * n;
-    flop += 13.0 * n + 2.0 * n;
+    flop += (coef ? 22.0 : 13.0) * n + 2.0 * n;
     if (!Comm_SUM_dev(d_pq, 1)) return 0;
     cg_scalar_async(1, d_pq, 0, sc);  // alpha = rho / p.q
     REAL_TYPE* const p = cg_p[cur];
@@ -1573,6 +1590,9 @@ int CZ::set_bc(CzBc next, int closed, bool project, const char* who) {
   if (const char* why = unsolvable(next, closed)) return bc_refuse(who, why);
   if (mg) mg_set_bc(mg, next);
   if (mgd) mgd_set_bc(mgd, next);
+  // face coefficients: the alias faces and the scaling follow the periodic directions; a face that was ignored and is read now may be bad
+  if (coef_on() && next.per != coef_per && !coef_prepare(next.per))
+    fprintf(stderr, "%s: a face coefficient that the new state reads is not finite and positive: the handle is left without coefficients\n", who);
   bc = next;
   closed_box = closed;
   // the work vectors whose face layers carried the wraps and mirrors of the state before: zeros again, as the unmasked passes read them
@@ -1765,7 +1785,11 @@ int CZ::FieldIO(int which, void* a, int abytes, const long long* stride, int on_
     // (the stencil reads one ghost layer of P; a solve may have left it one exchange behind)
     if (!Comm_S(P)) return 0;
     mirror(P);
-    last_field_form = field_residual_async(P, RHS, WRK, dev, abytes, size, innerFidx, GUIDE, stride, cf, scale, form, d_res + 10);
+    if (coef_on()) {
+      last_field_form = field_residual_coef_async(P, RHS, WRK, dev, abytes, size, innerFidx, GUIDE, stride, coef_b[0], coef_b[1], coef_b[2], scale, form, d_res + 10);
+    } else {
+      last_field_form = field_residual_async(P, RHS, WRK, dev, abytes, size, innerFidx, GUIDE, stride, cf, scale, form, d_res + 10);
+    }
   } else if (op == FIO_ADD) {
     last_field_form = field_add_async(P, dev, abytes, size, innerFidx, GUIDE, stride, scale, form);
   } else {
@@ -1848,7 +1872,8 @@ int CZ::ProjectIO(int op, REAL_TYPE* const* vel, const long long* stride, int on
     last_field_form = field_div_async(RHS, dev[0], dev[1], dev[2], size, GUIDE, stride, bc.per, scale, form, d_res + 10);
   } else {
     mirror(P);
-    last_field_form = field_grad_async(dev[0], dev[1], dev[2], P, size, GUIDE, stride, bc.per, scale, form);
+    if (coef_on()) last_field_form = field_grad_coef_async(dev[0], dev[1], dev[2], P, coef_b[0], coef_b[1], coef_b[2], size, GUIDE, stride, bc.per, scale, form);
+    else last_field_form = field_grad_async(dev[0], dev[1], dev[2], P, size, GUIDE, stride, bc.per, scale, form);
   }
   if (!last_field_form) return refuse("no kernel form takes these strides");
   if (op == PRJ_DIV) {
@@ -1872,6 +1897,99 @@ int CZ::ProjectIO(int op, REAL_TYPE* const* vel, const long long* stride, int on
     field_hand_back(user_stream, op == PRJ_DIV && sumsq);  // (a sum asked for is a host value on return; without one no host wait)
   }
   if (op == PRJ_DIV && sumsq) *sumsq = h_scal[10];
+  return 1;
+}
+
+// Face coefficients for pcg (cz_set_face_coef): b = bx, by, bz, three bricks with one stride triple, laid out and handed over as
+// the velocity of ProjectIO.  They are copied into padded arrays of the handle (the import kernels of cz_set_field), one more pass writes the
+// alias faces of the periodic directions, the scaling s and the count of values that are not finite and positive; the call waits for that
+// count.  All three NULL: the state is cleared.  Every refusal but that of a bad value comes before the first launch and changes nothing; a
+// bad value leaves the handle without coefficients.
+void CZ::coef_clear() {
+  if (!coef_on() && !coef_b[0]) return;
+  HIP_CHECK(hipStreamSynchronize(stream()));
+  for (REAL_TYPE*& a : coef_b) {
+    if (a) czhip_free(a);
+    a = nullptr;
+  }
+  if (coef_s) czhip_free(coef_s);
+  coef_s = nullptr;
+  coef_per = 0;
+}
+
+bool CZ::coef_prepare(int per) {
+  hipStream_t st = stream();
+  unsigned* const d_bad = reinterpret_cast<unsigned*>(d_res + 11);
+  unsigned* const h_bad = reinterpret_cast<unsigned*>(h_scal + 11);
+  HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(unsigned), st));
+  coef_prep_async(coef_b[0], coef_b[1], coef_b[2], coef_s, size, innerFidx, GUIDE, per, coef_per, d_bad);
+  HIP_CHECK(hipMemcpyAsync(h_bad, d_bad, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  coef_per = per;
+  if (*h_bad) coef_clear();
+  return *h_bad == 0u;
+}
+
+int CZ::SetFaceCoef(REAL_TYPE* const* b, const long long* stride, int on_device, void* user_stream) {
+  const char* const who = "cz_set_face_coef";
+  auto refuse = [&](const char* why) {
+    fprintf(stderr, "%s: %s\n", who, why);
+    return 0;
+  };
+  const int abytes = (int)sizeof(REAL_TYPE);
+  if (!set_up) return refuse("no problem is set up (cz_setup first)");
+  if (SW_maf) return refuse("the handle's operator is a MAF one, not the unit-coefficient operator");
+  const int given = (b[0] != nullptr) + (b[1] != nullptr) + (b[2] != nullptr);
+  if (given == 0) {  // back to the unit coefficients: the work vectors as the fused passes read them (set_bc does the same)
+    coef_clear();
+    for (REAL_TYPE* a : {cg_z, cg_p[0], cg_p[1]})
+      if (a) HIP_CHECK(hipMemsetAsync(a, 0, padded_cells() * sizeof(REAL_TYPE), stream()));
+    czhip_sync();
+    return 1;
+  }
+  if (given != 3) return refuse("bx, by, bz: all three arrays, or all three NULL (which clears the coefficients)");
+  if (numProc > 1)
+    return refuse("a decomposed run: the faces in the ghost layers need an exchange of the coefficients, which is the follow-up (single domain only)");
+  long long span = 1;
+  for (int c = 0; c < 3; c++)
+    if (const char* why = field_check(b[c], abytes, stride, &span)) return refuse(why);
+  if (on_device)
+    for (int c = 0; c < 3; c++)
+      if (const char* why = field_on_device(b[c])) return refuse(why);
+  hipStream_t st = stream();
+  const size_t span_bytes = (size_t)span * (size_t)abytes;
+  REAL_TYPE* dev[3] = {b[0], b[1], b[2]};
+  if (on_device) {
+    field_wait_for(user_stream);
+  } else {
+    unsigned char* stage = static_cast<unsigned char*>(field_stage(3 * span_bytes));
+    for (int c = 0; c < 3; c++) {
+      dev[c] = reinterpret_cast<REAL_TYPE*>(stage + (size_t)c * span_bytes);
+      HIP_CHECK(hipMemcpyAsync(dev[c], b[c], span_bytes, hipMemcpyHostToDevice, st));
+    }
+  }
+  for (REAL_TYPE*& a : coef_b)
+    if (!a) a = czhip_alloc_s3d(size);
+  if (!coef_s) coef_s = czhip_alloc_s3d(size);
+  const int form = field_form == 3 ? 3 : 0;
+  int took = 0;
+  for (int c = 0; c < 3; c++) {
+    took = field_copy_async(coef_b[c], dev[c], size, GUIDE, stride, 0, form);
+    if (!took) break;
+  }
+  if (took) last_field_form = took;
+  if (on_device) field_hand_back(user_stream, false);  // (the caller's arrays are free from here on)
+  coef_per = 0;
+  if (!took) {
+    coef_clear();
+    return refuse("no kernel form takes these strides (the handle is left without coefficients)");
+  }
+  if (!coef_prepare(bc.per))  // (the one host wait)
+    return refuse("a coefficient on a face that the operator reads is not finite and positive (the handle is left without coefficients)");
+  // the work vectors whose shells the fused passes read as zeros (the unfused direction leaves mirrors and wraps there): as set_bc
+  for (REAL_TYPE* a : {cg_z, cg_p[0], cg_p[1]})
+    if (a) HIP_CHECK(hipMemsetAsync(a, 0, padded_cells() * sizeof(REAL_TYPE), st));
+  czhip_sync();
   return 1;
 }
 
@@ -2117,6 +2235,10 @@ int cz_sub_grad(cz_handle* h, CZ_REAL* u, CZ_REAL* v, CZ_REAL* w, const long lon
   CZ_REAL* const vel[3] = {u, v, w};
   return h ? h->cz.ProjectIO(CZ::PRJ_GRAD, vel, stride, on_device, stream, scale, nullptr, "cz_sub_grad") : 0;
 }
+int cz_set_face_coef(cz_handle* h, const CZ_REAL* bx, const CZ_REAL* by, const CZ_REAL* bz, const long long* stride, int on_device, void* ready_stream) {
+  CZ_REAL* const b[3] = {const_cast<CZ_REAL*>(bx), const_cast<CZ_REAL*>(by), const_cast<CZ_REAL*>(bz)};
+  return h ? h->cz.SetFaceCoef(b, stride, on_device, ready_stream) : 0;
+}
 int cz_set_neumann(cz_handle* h, const int* faces) { return h ? h->cz.SetNeumann(faces) : 0; }
 int cz_set_closed_box(cz_handle* h, int on) { return h ? h->cz.SetClosedBox(on) : 0; }
 int cz_set_periodic(cz_handle* h, const int* dirs) {
@@ -2177,6 +2299,7 @@ int cz_info(const cz_handle* h, int what) {
     case 22: return c.closed_box;
     case 23: return c.bc.per;
     case 24: return c.pcg_void_start;
+    case 25: return c.coef_on() ? 1 : 0;
     default: return -1;
   }
 }

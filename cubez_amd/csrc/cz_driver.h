@@ -86,6 +86,15 @@ class CZ {
                                  // cz_set_neumann, DESIGN.md §5.13 -- P's face layers there hold the mirror of the first inner layer.  per (cz_info 23):
                                  // the periodic directions of cz_set_periodic, DESIGN.md §5.15 -- there P's two face layers hold the wrap and the
                                  // Neumann flags are ignored
+  // face coefficients (cz_set_face_coef, cz_info 25): padded copies of the caller's bx, by, bz and the scaling s = sqrt(6 / D);
+  // allocated while coefficients are in force, nullptr otherwise -- pcg then applies A_beta where it applies the operator and s M^-1 s where
+  // it preconditions; every other solver is refused
+  REAL_TYPE *coef_b[3] = {nullptr, nullptr, nullptr}, *coef_s = nullptr;
+  bool coef_on() const { return coef_s != nullptr; }
+  int coef_per = 0;              // the periodic directions whose face 0 holds the copy of face n - 2 in coef_b
+  bool coef_prepare(int per);    // the alias faces for `per`, s, and the check (one host wait); false: a bad value, the arrays are freed
+  void coef_clear();             // frees the four arrays (after the compute stream has drained)
+  int SetFaceCoef(REAL_TYPE* const* b, const long long* stride, int on_device, void* user_stream);  // cz_set_face_coef: 1 / 0
   int closed_box = 0;            // the closed box (cz_set_closed_box, cz_info 22): mask 63 and the three projections of pcg
   double closed_m[3] = {0, 0, 0};  // the means last removed: right-hand side, initial residual, answer (cz_closed_mean)
   bool closed_m0_on_device = false;  // closed_m[0] is still sc[7] of d_res (cz_set_rhs does not wait for it; ClosedMean fetches)

@@ -179,3 +179,97 @@ int field_grad_async(REAL* u, REAL* v, REAL* w, const REAL* p, const int* sz, in
   HIP_CHECK(hipGetLastError());
   return take;
 }
+
+// Face coefficients (cz_set_face_coef; cz_k_coef.h).  bx, by, bz, s: padded arrays of the handle.
+// coef_prep_async: after the three imports (per_old 0) or a change of the periodic directions (per_old: those in force before) -- the alias
+// faces of the periodic directions `per`, s = sqrt(6 / D) at the cells of idx and 0 at
+// the brick's other cells, *bad_dev += the faces and cells that are not finite and positive (the caller zeroed it).  Label field_io.
+void coef_prep_async(REAL* bx, REAL* by, REAL* bz, REAL* s, const int* sz, const int* idx, int g, int per, int per_old, unsigned* bad_dev) {
+  ensure_init();
+  static const long long unit[3] = {1, 1, 1};
+  FieldGeom fg;
+  if (!field_geom(fg, sz, g, unit)) return;
+  const unsigned gy = (unsigned)std::min(fg.nj, 65535);
+  const unsigned gx = (unsigned)std::min<long long>(((long long)fg.ni * fg.nk + 255) / 256, 4096);
+  ScopedTimer tm(LBL_FIELD);
+  hipLaunchKernelGGL(coef_prep_k, dim3(gx, gy), dim3(256), 0, ctx.stream, bx, by, bz, s, fg, field_box(idx), per, per_old, bad_dev);
+  HIP_CHECK(hipGetLastError());
+}
+// coef_ax_async: mode 0: q = A p at the cells of idx, out[0] = p.q, out[1] = q.q (the slots of calc_ax_dots_async; label calc_ax); mode 1:
+// q = b - A p there, out[0] = sum r^2, out[1] = 0 (label calc_rk).  q's other cells keep their bytes.  About 4096 workgroups at most, each
+// with one ticket on the one counter (field_div_async's finding).  0 = refused (the row index does not fit), nothing launched.
+int coef_ax_async(int mode, REAL* q, const REAL* p, const REAL* b, const REAL* bx, const REAL* by, const REAL* bz, const int* sz, const int* idx, int g,
+                  double* out) {
+  ensure_init();
+  static const long long unit[3] = {1, 1, 1};
+  FieldGeom fg;
+  if (!q || !p || !bx || !by || !bz || !out || (mode == 1 && !b) || !field_geom(fg, sz, g, unit)) return 0;
+  const FieldBox box = field_box(idx);
+  if (box.hi0 < box.lo0 || box.hi1 < box.lo1 || box.hi2 < box.lo2) {
+    HIP_CHECK(hipMemsetAsync(out, 0, 2 * sizeof(double), ctx.stream));
+    return 1;
+  }
+  const int slots = (fg.nk + 2 * VW - 2) / VW;  // vectors a row can touch, whatever its phase
+  const long long rows = box.hi0 - box.lo0 + 1, planes = box.hi1 - box.lo1 + 1;
+  if (rows * slots > 0x7ff00000LL) return 0;
+  const unsigned gy = (unsigned)std::min<long long>(planes, 4096);
+  const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((rows * slots + 255) / 256, 4096 / gy));
+  ensure_partials((size_t)2 * gx * gy);
+  ScopedTimer tm(mode ? LBL_RK : LBL_AX);
+  if (mode) hipLaunchKernelGGL((ax_coef_k<VW, 1>), dim3(gx, gy), dim3(256), 0, ctx.stream, q, p, b, bx, by, bz, fg, box, slots, ctx.partials, out, ctx.counter);
+  else hipLaunchKernelGGL((ax_coef_k<VW, 0>), dim3(gx, gy), dim3(256), 0, ctx.stream, q, p, b, bx, by, bz, fg, box, slots, ctx.partials, out, ctx.counter);
+  HIP_CHECK(hipGetLastError());
+  return 1;
+}
+// coef_scale_async: out = s in where s is not zero (the cells of the box), 0 at every other cell of the padded array; out may be in.  Label ewise.
+void coef_scale_async(REAL* out, const REAL* in, const REAL* s, const int* sz, int g) {
+  ensure_init();
+  const long long n = (long long)(sz[0] + 2 * g) * (sz[1] + 2 * g) * (sz[2] + 2 * g);
+  const long long nvec = (n + VW - 1) / VW;
+  const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((nvec + 255) / 256, 8192));
+  ScopedTimer tm(LBL_EWISE);
+  hipLaunchKernelGGL((coef_scale_k<VW>), dim3(gx), dim3(256), 0, ctx.stream, out, in, s, nvec, n);
+  HIP_CHECK(hipGetLastError());
+}
+// cz_get_residual under coefficients: r = rhs - A p into wrk (coef_ax_async mode 1, sumsq_dev[0] = sum r^2), then wrk out as (T)(r scale)
+// through the transpose / generic export forms (a k-row destination takes the generic one: the row form of the export is resid_row_k's own
+// pass).  Returns the form taken (norm only: 1), 0 = refused, nothing launched.
+int field_residual_coef_async(const REAL* p, const REAL* rhs, REAL* wrk, void* user, int user_bytes, const int* sz, const int* idx, int g,
+                              const long long* stride, const REAL* bx, const REAL* by, const REAL* bz, double scale, int form, double* sumsq_dev) {
+  ensure_init();
+  static const long long unit[3] = {1, 1, 1};
+  FieldGeom fg;
+  if (!p || !rhs || !wrk || !sumsq_dev || !field_geom(fg, sz, g, user ? stride : unit)) return 0;
+  int take = 1;
+  if (user) {
+    if ((user_bytes != 4 && user_bytes != 8) || (reinterpret_cast<uintptr_t>(user) & (uintptr_t)(user_bytes - 1))) return 0;
+    take = field_form_of(fg, form, true);
+    if (!take) return 0;
+    if (take == 1) take = 3;
+  }
+  if (!coef_ax_async(1, wrk, p, rhs, bx, by, bz, sz, idx, g, sumsq_dev)) return 0;
+  if (!user) return take;
+  const FieldBox box = field_box(idx);
+  ScopedTimer tm(LBL_FIELD);
+  const bool ok = user_bytes == 4 ? field_tr_any_launch<1, float, 1>(take, static_cast<float*>(user), wrk, fg, box, (REAL)scale)
+                                  : field_tr_any_launch<1, double, 1>(take, static_cast<double*>(user), wrk, fg, box, (REAL)scale);
+  HIP_CHECK(hipGetLastError());
+  return ok ? take : 0;
+}
+// field_grad_async's coefficient form: u(i) = u(i) - (bx(i) (p(i + 1) - p(i))) (REAL)scale, v and w likewise
+int field_grad_coef_async(REAL* u, REAL* v, REAL* w, const REAL* p, const REAL* bx, const REAL* by, const REAL* bz, const int* sz, int g,
+                          const long long* stride, int per, double scale, int form) {
+  ensure_init();
+  FieldGeom fg;
+  if (!p || !u || !v || !w || !bx || !by || !bz || !field_geom(fg, sz, g, stride)) return 0;
+  const int slots = (fg.nk + 2 * VW - 2) / VW;
+  const int take = proj_form_of(fg, form, slots);
+  if (!take) return 0;
+  const unsigned gy = (unsigned)std::min(fg.nj, 65535);
+  const unsigned gx = (unsigned)std::min<long long>((take == 1 ? (long long)fg.ni * slots + 255 : (long long)fg.ni * fg.nk + 255) / 256, 4096);
+  ScopedTimer tm(LBL_FIELD);
+  if (take == 1) hipLaunchKernelGGL((grad_coef_row_k<VW>), dim3(gx, gy), dim3(256), 0, ctx.stream, u, v, w, p, bx, by, bz, fg, per, (REAL)scale, slots);
+  else hipLaunchKernelGGL(grad_coef_any_k, dim3(gx, gy), dim3(256), 0, ctx.stream, u, v, w, p, bx, by, bz, fg, per, (REAL)scale);
+  HIP_CHECK(hipGetLastError());
+  return take;
+}

@@ -150,6 +150,20 @@ int field_add_async(CZ_REAL* p, const void* user, int user_bytes, const int* sz,
 int field_div_async(CZ_REAL* rhs, const CZ_REAL* u, const CZ_REAL* v, const CZ_REAL* w, const int* sz, int g, const long long* stride, int per,
                     double scale, int form, double* sumsq_dev);
 int field_grad_async(CZ_REAL* u, CZ_REAL* v, CZ_REAL* w, const CZ_REAL* p, const int* sz, int g, const long long* stride, int per, double scale, int form);
+// cz_set_face_coef (cz_k_coef.h, cz_h_field.h): bx, by, bz, s are padded arrays of the handle, bx at a cell = the coefficient on
+// the face towards the next cell in X.  coef_prep_async: the alias faces of the periodic directions (per_old: those that hold one already), s = sqrt(6 / D) at the cells of idx (0
+// at the brick's other cells), *bad_dev += what is not finite and positive.  coef_ax_async: mode 0 q = A p with out[0] = p.q, out[1] = q.q;
+// mode 1 q = b - A p with out[0] = sum r^2; at the cells of idx; 0 = refused.  coef_scale_async: out = s in at the cells where s is not
+// zero, 0 elsewhere (out may be in).  field_residual_coef_async / field_grad_coef_async: field_residual_async / field_grad_async with the
+// coefficients (the residual goes through wrk and the transpose / generic export: forms 2 | 3).
+void coef_prep_async(CZ_REAL* bx, CZ_REAL* by, CZ_REAL* bz, CZ_REAL* s, const int* sz, const int* idx, int g, int per, int per_old, unsigned* bad_dev);
+int coef_ax_async(int mode, CZ_REAL* q, const CZ_REAL* p, const CZ_REAL* b, const CZ_REAL* bx, const CZ_REAL* by, const CZ_REAL* bz, const int* sz,
+                  const int* idx, int g, double* out);
+void coef_scale_async(CZ_REAL* out, const CZ_REAL* in, const CZ_REAL* s, const int* sz, int g);
+int field_residual_coef_async(const CZ_REAL* p, const CZ_REAL* rhs, CZ_REAL* wrk, void* user, int user_bytes, const int* sz, const int* idx, int g,
+                              const long long* stride, const CZ_REAL* bx, const CZ_REAL* by, const CZ_REAL* bz, double scale, int form, double* sumsq_dev);
+int field_grad_coef_async(CZ_REAL* u, CZ_REAL* v, CZ_REAL* w, const CZ_REAL* p, const CZ_REAL* bx, const CZ_REAL* by, const CZ_REAL* bz, const int* sz, int g,
+                          const long long* stride, int per, double scale, int form);
 void bc_async(const int* sz, int g, CZ_REAL* p, CZ_REAL dh, const CZ_REAL* org, const int* nID, int ioff = 0, int joff = 0);
 // the face layers of an array of a level with packed word `word` (cz_bc.h: bc_kinds, czhip_fill_faces_async): one launch, none where the
 // word leaves nothing to fill; 0 = refused

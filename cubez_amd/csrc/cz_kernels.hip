@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <set>
 #include <string>
@@ -55,6 +56,7 @@ namespace {
 #include "cz_k_field.h"
 #include "cz_k_resid.h"
 #include "cz_k_project.h"
+#include "cz_k_coef.h"
 #include "cz_h_ctx.h"
 #include "cz_h_launch.h"
 

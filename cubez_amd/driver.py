@@ -44,6 +44,7 @@ class CZ:
         lib.cz_add_field.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_double]
         lib.cz_set_rhs_div.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_double, C.POINTER(C.c_double)]
         lib.cz_sub_grad.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_double]
+        lib.cz_set_face_coef.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_longlong), C.c_int, C.c_void_p]
         lib.cz_set_eps.argtypes = [C.c_void_p, C.c_double]
         lib.cz_set_neumann.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         lib.cz_set_closed_box.argtypes = [C.c_void_p, C.c_int]
@@ -240,6 +241,23 @@ class CZ:
         self.sub_grad(u, v, w)
         return itr, ss
 
+    def set_face_coef(self, bx, by=None, bz=None):
+        """face coefficients for pcg: div(beta grad p) = b with beta given on the faces -- bx, by, bz laid out as u, v, w of set_rhs_div
+        (bx[i, j, k] on the face between cells i and i + 1; three numpy arrays or device tensors of equal strides), finite and positive on
+        every face the operator reads.  The values are copied: the arrays are the caller's again on return.  From then on solve (pcg only),
+        get_residual and sub_grad take the variable operator, the preconditioner is the constant one inside a diagonal scaling, and
+        info()["face_coef"] is 1.  set_face_coef(None) goes back to the unit coefficients.  A value that is not finite and positive is
+        refused and leaves the handle WITHOUT coefficients.  Single domain (cz_set_face_coef of include/cz_hip.h)"""
+        if bx is None and by is None and bz is None:
+            if self.lib.cz_set_face_coef(self.h, None, None, None, None, 0, None) != 1:
+                raise RuntimeError("set_face_coef(None): refused (see stderr)")
+            return
+        if bx is None or by is None or bz is None:
+            raise ValueError("set_face_coef: bx, by and bz, or None alone")
+        ptrs, strides, on_dev, stream = self._velocity(bx, by, bz, "set_face_coef")
+        if self.lib.cz_set_face_coef(self.h, *ptrs, strides, on_dev, stream) != 1:
+            raise RuntimeError("set_face_coef: refused (see stderr)")
+
     @staticmethod
     def _itemsize(a):
         return a.itemsize if isinstance(a, np.ndarray) else a.element_size()
@@ -300,7 +318,8 @@ class CZ:
     def info(self) -> dict:
         """what a (multi-GPU) run decided (cz_info of include/cz_hip.h)"""
         keys = ("ranks", "fused_pass", "shell_slabs", "overlap", "lagged_reduce", "rccl_ranks", "comm_cus", "pass_kind", "exchange_depth", "buffers", "bicg_fused", "rb4_passes",
-                "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother", "field_form", "neumann", "closed", "periodic", "void_start")
+                "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother", "field_form", "neumann", "closed", "periodic", "void_start",
+                "face_coef")
         return {k: self.lib.cz_info(self.h, i) for i, k in enumerate(keys)}
 
     def config_in_force(self) -> dict:

@@ -65,6 +65,25 @@ class Refined:
     def get_field(self, out=None):
         return self.hi.get_field(out)
 
+    def set_face_coef(self, bx, by=None, bz=None):
+        """CZ.set_face_coef on both libraries: the FP64 values as given, their FP32 roundings (made by torch) for the inner solver, which then
+        corrects with the operator of the rounded coefficients -- a perturbation of relative size 6e-8 that the outer steps absorb.
+        set_face_coef(None) clears both.  Raises where either library refuses (a refusal of a bad value leaves that library without
+        coefficients: the other one is then cleared too)"""
+        if bx is None and by is None and bz is None:
+            self.hi.set_face_coef(None)
+            self.lo.set_face_coef(None)
+            return
+        torch = self.torch
+        self.hi.set_face_coef(bx, by, bz)
+        try:
+            lo3 = [torch.as_tensor(a).to(device=self.r32.device, dtype=torch.float32).contiguous() for a in (bx, by, bz)]
+            self.lo.set_face_coef(*lo3)
+        except Exception:
+            self.hi.set_face_coef(None)
+            self.lo.set_face_coef(None)
+            raise
+
     def solve(self, tol=1e-10, max_outer=20, inner_eps=INNER_EPS) -> int:
         """refine until |b - A p| <= tol |b - A p0|; returns the outer steps taken, 0 where max_outer steps did not reach it.
         history: [(outer step, |r| / |r0| after it, inner iterations of it)].  Collective in a decomposed run.

@@ -530,6 +530,35 @@ int cz_add_field(cz_handle*, const void* src, int src_real_bytes, const long lon
 int cz_set_rhs_div(cz_handle*, const CZ_REAL* u, const CZ_REAL* v, const CZ_REAL* w, const long long* stride, int on_device, void* ready_stream,
                    double scale, double* sumsq);
 int cz_sub_grad(cz_handle*, CZ_REAL* u, CZ_REAL* v, CZ_REAL* w, const long long* stride, int on_device, void* stream, double scale);
+/* Face coefficients for pcg: the variable-density pressure solve div(beta grad p) = b, beta = dt / rho given on the faces
+ * (constant bx != by != bz: grid spacings that differ by direction).  bx, by, bz are laid out and handed over exactly as u, v, w of
+ * cz_set_rhs_div: three arrays of the brick's shape with ONE stride triple, bx(i, j, k) on the face between cells i and i + 1, i = 1 .. n_0 - 1;
+ * entry n_0 is never read; in a periodic direction face 1 is ignored and face n - 1 read in its place; only faces at inner tangential
+ * indices are read.  The values are copied into padded arrays of the handle (the caller may reuse its arrays at once; with a stream the
+ * hand-over is by events), together with a scaling array s = sqrt(6 / D), D = ((bx+ + bx-) + (by+ + by-)) + (bz+ + bz-) over the six faces a
+ * cell's row reads -- every operation rounded once in CZ_REAL, IEEE division and square root.  While coefficients are in force (cz_info 25):
+ *   the operator is, per direction d, t_d = beta_d(c) (p(c + e_d) - p(c)) - beta_d(c - e_d) (p(c) - p(c - e_d)), A p = (t_x + t_y) + t_z, each
+ *     operation rounded once, p's face layers what the handle's state makes them (Dirichlet value, mirror, wrap): a zero-flux face drops
+ *     out because the mirror makes its difference 0.  With beta = 1 it is the stated system in exact arithmetic (not bit for bit);
+ *   cz_solve (pcg with none | jacobi | mg | mgrb) applies it at the start and once per iteration (the direction is made unfused: cz_info 13
+ *     reports 0); every preconditioner application is z = s M^-1 (s r) with M^-1 the constant-coefficient jacobi / mg / mgrb under the handle's
+ *     boundary state -- symmetric and positive definite, good for smooth coefficients and moderate jumps, slow (but correct) for large
+ *     jumps (DESIGN.md 5.19 has the counts); none stays z = r;
+ *   cz_get_residual returns r = b - A p of that operator (kernel forms 2 and 3 of cz_info 20: the residual goes through a work array);
+ *   cz_sub_grad subtracts (beta_x(i, j, k) (p(i+1) - p(i))) scale from u, likewise v and w, so that div(u - beta grad p) = div u - A p exactly;
+ *   cz_set_rhs_div, cz_add_field and cz_precondition are unchanged (the last applies the constant-coefficient M^-1 without the scaling);
+ *   cz_solve, cz_sweeps and cz_evaluate of a solver other than pcg return 0 with one line and leave P alone.
+ * All three pointers NULL clears the state (the arrays are freed; the handle then runs the code and gives the bytes of a handle that never
+ * had coefficients); cz_setup clears it too.  cz_set_periodic / cz_set_closed_box / cz_set_neumann after this call keep the coefficients:
+ * the alias faces and s follow the periodic directions (face 1's own value is kept for the day its direction stops being periodic).
+ * Return 1, or 0 with one line on stderr and nothing changed: before cz_setup, some but not all pointers NULL, a NULL stride or a stride < 1,
+ * an array that is not aligned to CZ_REAL, a pointer that is not on the handle's device, a _maf handle, a decomposed run (the faces in the
+ * ghost layers need an exchange: the follow-up).  One more refusal is NOT "nothing changed": some face that the operator reads holds a
+ * value that is not finite and positive (or D overflows, or s is not finite and positive).  That is a count made on the device after the
+ * import; the call waits for it (its one host wait), returns 0 with a line and leaves the handle WITHOUT coefficients, also where it had
+ * some before.  The same holds where a later change of the periodic directions makes the operator read a bad face 1: that setter prints
+ * the line, takes the new state and leaves the handle without coefficients (cz_info 25 tells). */
+int cz_set_face_coef(cz_handle*, const CZ_REAL* bx, const CZ_REAL* by, const CZ_REAL* bz, const long long* stride, int on_device, void* ready_stream);
 /* Zero-flux (Neumann) faces for pcg: faces[6], order X-, X+, Y-, Y+, Z-, Z+ of the GLOBAL box (the order of nID), non-zero =
  * the face is a zero-flux face, zero = a Dirichlet face as before; at least one face must stay Dirichlet.  Called after cz_setup; collective,
  * with the same mask on every rank.  On a Neumann face the face layer of the field is not data but the mirror of the first inner layer
@@ -607,7 +636,8 @@ double cz_last_solve_seconds(const cz_handle*);
  * 22 the closed-box mode of cz_set_closed_box (0 | 1); 23 the periodic directions of cz_set_periodic, bit d = X, Y, Z (0: none);
  * 24 the last cz_solve was a pcg that stopped at a breakdown (|rho| < FLT_MIN, absolute in both precisions) before any update: cz_solve
  * returned 0, P holds the caller's bytes (in the closed box: less its mean), cz_result_iter, cz_result_res and the history are 0 / empty --
- * the start was the answer already, or the problem is scaled below the threshold (1); anything else, a refusal or an error included (0). */
+ * the start was the answer already, or the problem is scaled below the threshold (1); anything else, a refusal or an error included (0);
+ * 25 face coefficients are in force (cz_set_face_coef; 0 | 1). */
 int cz_info(const cz_handle*, int what);
 /* The driver's and its communicator's own copies of their switches, as name=value, one per line: overlap, lag_reduce, comm_cus (as asked for;
  * 0 on a single domain), comm_cus_reserved (in force after set-up), bicg_fuse, bicg_devsc, bicg_alias, cg_fuse, mg_tail, mg_gather, mgrb_zero4,
