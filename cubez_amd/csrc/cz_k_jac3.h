@@ -18,15 +18,30 @@
 //                 at [R, R + LV) only; its outer slots were last read in step q and are next read in step q+2).  The prologue primes the
 //                 outer rows of two planes.  The store of W(q-2) is younger than the requests of step q: the wait for b(q+1) in step q+1
 //                 retires it as well (gfx9 counts loads and stores in one counter, in order).  profiles/r20/jac3_requests_in_flight.txt
+//     LDS in flight  a stage is `fetch` (its six LDS reads: centre, j-1, j+1, the plane before, the two k edges) and `relax` (lane shifts and
+//                 relax_vec).  Behind barrier q - 1 a step issues stage 1's six reads and then stage 2's six (f1 of earlier planes: published
+//                 before that barrier), then computes stage 1; behind the outer-row block it issues stage 3's six (f2 of earlier planes) and
+//                 then computes stages 2 and 3.  So the round trip of stage s + 1's operands runs under stage s's arithmetic instead of in
+//                 front of its own.  The ORDER matters: LDS returns in order and lgkmcnt counts in order, so a stage's wait for its last
+//                 operand retires everything issued before that operand.  All six reads of a stage, the edge reads included, therefore
+//                 stand in front of every read of the next (reads_stay_in_order: the compiler put stage 1's edge reads behind stage 2's
+//                 vector reads otherwise), and the fetches are unconditional: behind a wave-uniform `if (wave2)` the compiler counts the
+//                 waits of stage 1 for the path with the fewer reads outstanding, which retires stage 2's reads on the other.  A wave
+//                 that skips stage 2 or 3 thus requests operands it never uses, from addresses no stage that runs would read in its lanes:
+//                 F1 + x +- R for x outside [R, LV - R) and F2 + x +- R for x outside the owned range reach at most R vectors below a
+//                 field buffer -- into the u buffers or f1 -- or R vectors beyond the last one, the padding deep_lds puts behind it (and in
+//                 front of the first u buffer): inside the allocation.  Buffers, parities, the publish and the barrier are unchanged; the
+//                 second set of operands costs 15-16 VGPRs (122-123 FP32, 127-128 FP64, no scratch).  profiles/r25/jac3_operands_ahead.txt
 // Per point: relax_vec<V, UNIT> with the hoisted IEEE division (or its checked shorter form, MED), the operations of jacobi2p_k on the same
 // values => the same bits as three single sweeps.  The three residuals (sum dp^2 of sweeps n+1, n+2, n+3) are produced and finalised in the kernel; if the first or the second
 // converges, the driver re-runs one sweep or one pair from the untouched input (out of place, like the pair).
 // ------------------------------------------------------------------------------------------------------------
 
 // The three helpers below are empty asm statements that pin what the compiler makes of the inner step (scalar-base requests, no wait on a
-// step's requests before its barrier).  They change no value.  What they achieve depends on the compiler: the listing of the inner loop in
-// profiles/r20/jac3_requests_in_flight.txt (loads, vmcnt waits, barriers, registers) is the contract to compare against after a change of
-// the toolchain; tests cannot see it.
+// step's requests before its barrier); reads_stay_in_order further down pins the order of the LDS reads.  They change no value.  What they
+// achieve depends on the compiler: the listing of the inner step in profiles/r25/jac3_operands_ahead.txt (global requests, LDS reads and
+// writes, vmcnt and lgkmcnt waits, gate branches, barriers, registers) is the contract to compare against after a change of the toolchain;
+// tests cannot see it.
 // A plane pointer the compiler must take as it stands: global memory, in a scalar register pair.
 template <class T>
 __device__ __forceinline__ T* uniform_global(T* p) {
@@ -48,6 +63,30 @@ __device__ __forceinline__ void complete_here(Vec<V>& x) {
   if constexpr (V == 4) asm volatile("" : "+v"(x.v[0]), "+v"(x.v[1]), "+v"(x.v[2]), "+v"(x.v[3]));
   else asm volatile("" : "+v"(x.v[0]), "+v"(x.v[1]));
 }
+
+// A stage's six LDS operands between their request and their use.  lds_request is the read alone, lds_whole the constraint of lds_ld
+// (cz_k_pass.h) on the value that came back: together they are lds_ld, apart they let other work stand between the two.
+template <int V>
+struct LdsOperands {
+  typename NatVec<V>::type pc, im, ip, pm;  // centre, j-1 row, j+1 row of the current plane; centre of the plane before
+  REAL elo, ehi;                            // the k neighbours beyond the wave's first and last vector
+};
+template <int V>
+__device__ __forceinline__ typename NatVec<V>::type lds_request(const Vec<V>* p) {
+  return *reinterpret_cast<const typename NatVec<V>::type*>(p);
+}
+template <int V>
+__device__ __forceinline__ Vec<V> lds_whole(typename NatVec<V>::type x) {
+  asm("" : "+v"(x));  // (as in lds_ld: whole, in consecutive registers -- one ds_read_b128)
+  Vec<V> r;
+  __builtin_memcpy(&r, &x, sizeof(r));
+  return r;
+}
+
+// Nothing is scheduled across this place: the LDS reads in front of it are issued before the ones behind it.  LDS returns in order and
+// lgkmcnt counts in order, so a stage's wait for its own last operand retires every read issued before that operand -- it must not be a
+// read of the next stage.
+__device__ __forceinline__ void reads_stay_in_order() { __builtin_amdgcn_sched_barrier(0); }
 
 // MED = 1 (FP32): the division with one correction step (mediumdiv, cz_k_fastdiv.h), taken only for a divisor that passed the exhaustive
 // comparison with `n / d` on this context (jac3_medium, cz_h_launch.h)
@@ -118,16 +157,26 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
 
     // the k neighbours beyond the wave's first and last vector come from LDS (one element each, the same address in all lanes)
     const int x_first = __builtin_amdgcn_readfirstlane(x), x_last = __builtin_amdgcn_readlane(x, 63);
-    auto stage = [&](const Vec<V>* cur, const Vec<V>* prv, const Vec<V>& nxt, const Vec<V>& bb, unsigned msk, unsigned cnt,
+    // A stage in two parts.  `fetch` requests its six LDS operands and uses none of them; `relax` takes them whole (lds_whole) and does
+    // the arithmetic.  What stands between the two in the step is what the round trip hides behind.
+    auto fetch = [&](const Vec<V>* cur, const Vec<V>* prv) __attribute__((always_inline)) -> LdsOperands<V> {
+      LdsOperands<V> o;
+      o.pc = lds_request<V>(cur + x);
+      o.im = lds_request<V>(cur + x - R);
+      o.ip = lds_request<V>(cur + x + R);
+      o.pm = lds_request<V>(prv + x);
+      o.elo = reinterpret_cast<const REAL*>(cur)[(long long)x_first * V - 1];
+      o.ehi = reinterpret_cast<const REAL*>(cur)[(long long)(x_last + 1) * V];
+      return o;
+    };
+    auto relax = [&](const LdsOperands<V>& o, const Vec<V>& nxt, const Vec<V>& bb, unsigned msk, unsigned cnt,
                      double& acc) __attribute__((always_inline)) -> Vec<V> {
-      const Vec<V> pc = lds_ld<V>(cur + x);
-      const Vec<V> im = lds_ld<V>(cur + x - R);
-      const Vec<V> ip = lds_ld<V>(cur + x + R);
-      const Vec<V> pm = lds_ld<V>(prv + x);
-      const REAL elo = reinterpret_cast<const REAL*>(cur)[(long long)x_first * V - 1];
-      const REAL ehi = reinterpret_cast<const REAL*>(cur)[(long long)(x_last + 1) * V];
-      const REAL kl = lane_shr1(elo, pc.v[V - 1]);
-      const REAL kr = lane_shl1(ehi, pc.v[0]);
+      const Vec<V> pc = lds_whole<V>(o.pc);
+      const Vec<V> im = lds_whole<V>(o.im);
+      const Vec<V> ip = lds_whole<V>(o.ip);
+      const Vec<V> pm = lds_whole<V>(o.pm);
+      const REAL kl = lane_shr1(o.elo, pc.v[V - 1]);
+      const REAL kr = lane_shl1(o.ehi, pc.v[0]);
       return relax_vec<V, UNIT>(pc, im, ip, pm, nxt, kl, kr, bb, c, dv, msk, cnt, acc);
     };
 
@@ -165,8 +214,16 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
       const Vec<V>* pU = ldsU + (size_t)((p1 - 1) & 1) * LU + R;
       Vec<V>* F1 = ldsF;
       Vec<V>* F2 = ldsF + (size_t)2 * LV;
+      const bool run3 = (INNER || p3 >= ja) && wave3;
+      // ---- the LDS operands of stage 1 and, behind ALL six of them, those of stage 2 (f1 of earlier planes: published before barrier q - 1)
+      const LdsOperands<V> o1 = fetch(cU, pU);
+      reads_stay_in_order();
+      // Every wave requests them, also one that skips the stage (see "LDS in flight" above): a branch here would merge two counts of
+      // outstanding reads in front of stage 1's waits, and the compiler waits for the smaller one -- which retires these reads.
+      const LdsOperands<V> o2 = fetch(F1 + (size_t)(p2 & 1) * LV, F1 + (size_t)((p2 - 1) & 1) * LV);
+      reads_stay_in_order();
       // ---- stage 1: f1(p1) on every vector of E2
-      Vec<V> v1 = stage(cU, pU, uc, b1, upd(p1), cnt(p1), acc1);
+      Vec<V> v1 = relax(o1, uc, b1, upd(p1), cnt(p1), acc1);
       complete_here<V>(v1);
       // ---- the outer rows of u(q+1), requested one step ago (they landed with uc): into the buffer of u(q+1), this step's `prv` buffer, which
       // is read at [R, R + LV) only; then the request of those of u(q+2)
@@ -174,13 +231,16 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
         if (h.has) ldsU[(size_t)((p1 + 1) & 1) * LU + h.hl] = hx;
         hx = ld16<V>(up, ho);
       }
+      // ---- the LDS operands of stage 3 (f2 of earlier planes), in front of stage 2's arithmetic
+      const LdsOperands<V> o3 = fetch(F2 + (size_t)(p3 & 1) * LV, F2 + (size_t)((p3 - 1) & 1) * LV);
+      reads_stay_in_order();
       // ---- stage 2: f2(p2) from f1(p2 - 1) [LDS], f1(p2) [LDS], f1(p1) [v1]
       Vec<V> v2 = v1;  // (a wave outside E1 publishes a value no valid point reads)
-      if (wave2) v2 = stage(F1 + (size_t)(p2 & 1) * LV, F1 + (size_t)((p2 - 1) & 1) * LV, v1, b2, upd(p2), cnt(p2), acc2);
+      if (wave2) v2 = relax(o2, v1, b2, upd(p2), cnt(p2), acc2);
       // ---- stage 3: f3(p3) = the output, owned vectors of the chunk's planes.  Whole waves: the k neighbours travel by lane shifts, and the
       // lane next to the first owned vector of a window holds a halo vector -- it owns nothing but must take part.
-      if ((INNER || p3 >= ja) && wave3) {
-        const Vec<V> o = stage(F2 + (size_t)(p3 & 1) * LV, F2 + (size_t)((p3 - 1) & 1) * LV, v2, b3, own, own, acc3);
+      if (run3) {
+        const Vec<V> o = relax(o3, v2, b3, own, own, acc3);
         store_owned<V>(INNER ? wN : Wb + (size_t)p3 * PB, bo, own, o);
       }
       // ---- publish: f1(p1), f2(p2) and the next u centre plane u(q+1) (its outer rows were written behind stage 1)
