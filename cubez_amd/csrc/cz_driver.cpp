@@ -892,7 +892,12 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
   // solve; triples while three sweeps remain, then the pair or the single sweep
   const bool jac3 = plan.kind == PassPlan::WHOLE && numProc == 1 && !maf && !in_precond && itr_max >= 3 &&
                     czhip_jacobi3_async(X, WRK, B, size, innerFidx, gc, cf, ac1, d_res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 1) != 0;
-  jac3_passes = 0;
+  // FOUR sweeps per pass (jac4_k) where that pass takes the box as well and the solve is long enough (czhip_jac4_min_sweeps: a solve of
+  // fewer than eight sweeps keeps the triples it had, the passes cz_info 14 reports): quads while four sweeps remain, then the triple,
+  // the pair or the single sweep
+  const bool jac4 = jac3 && itr_max >= czhip_jac4_min_sweeps() &&
+                    czhip_jacobi4_async(X, WRK, B, size, innerFidx, gc, cf, ac1, d_res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 1) != 0;
+  jac3_passes = 0, jac4_passes = 0;
   bool stop = false;
   int itr = 1;
   while (itr <= itr_max && !stop) {
@@ -902,6 +907,13 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
     const bool pass = plan.kind != PassPlan::SINGLE && itr + 1 <= itr_max;
     if (pass && plan.kind == PassPlan::SPLIT) {
       if (!split_pass(L, -1, 2, itr, mpp)) return 0;  // :58 twice, :63 hidden behind the interior, :67-77 for both sweeps
+    } else if (pass && jac4 && itr + 3 <= itr_max && !(plan.zero_start && itr == 1)) {
+      if (!czhip_jacobi4_async(src, dst, B, size, innerFidx, gc, cf, ac1, d_res, res_normal, eps, itr, converge_check ? d_hist : nullptr, d_flag,
+                               d_flag + 1, skip, 0)) {  // :58 + :67-77, four times (d_res[0..3]; the re-runs below write d_res[4..6])
+        cz_fatal(1, "error : the four-sweep pass refused after a successful probe\n");
+      }
+      done = 4;
+      jac4_passes++;
     } else if (pass && jac3 && itr + 2 <= itr_max && !(plan.zero_start && itr == 1)) {
       if (!czhip_jacobi3_async(src, dst, B, size, innerFidx, gc, cf, ac1, d_res, res_normal, eps, itr, converge_check ? d_hist : nullptr, d_flag,
                                d_flag + 1, skip, 0)) {  // :58 + :67-77, three times
@@ -945,7 +957,11 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
     if (converge_check && L.launches.size() % (POLL_EVERY / 2) == 0 && itr <= itr_max) stop = L.poll.stop();
   }
   return fused_end(L, X, itr_max, res, [&](const Launch& l, int k, REAL_TYPE* s, REAL_TYPE* d) {
-    if (k == 1) {  // the second sweep of a three-sweep pass: one pair
+    if (k == 2) {  // the third sweep of a four-sweep pass: one three-sweep pass
+      if (!czhip_jacobi3_async(s, d, B, size, innerFidx, gc, cf, ac1, d_res + 4, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 0)) {
+        cz_fatal(1, "error : the three-sweep pass refused after a successful probe\n");
+      }
+    } else if (k == 1) {  // the second sweep of a three- or four-sweep pass: one pair
       if (!czhip_jacobi2_async(s, d, B, size, innerFidx, idx1, gc, cf, ac1, d_res + 4, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr)) {
         cz_fatal(1, "error : fused pass refused after a successful probe\n");
       }
@@ -2300,6 +2316,7 @@ int cz_info(const cz_handle* h, int what) {
     case 23: return c.bc.per;
     case 24: return c.pcg_void_start;
     case 25: return c.coef_on() ? 1 : 0;
+    case 26: return c.jac4_passes;
     default: return -1;
   }
 }

@@ -74,6 +74,7 @@ class CZ {
   hipEvent_t ev_shell = nullptr, ev_src = nullptr, ev_comm = nullptr, ev_int = nullptr, ev_chk[2] = {nullptr, nullptr};
   bool pairs_ok = true;          // decomposed runs: EVERY brick can run the fused pass (agreed at set-up; the exchange pattern depends on it)
   int rb4_passes = 0;            // two-iteration red-black passes (rb4_k) of the last RBSOR solve (cz_info 11)
+  int jac4_passes = 0;           // four-sweep Jacobi passes (jac4_k) of the last JACOBI solve (cz_info 26)
   int jac3_passes = 0;           // three-sweep Jacobi passes (jac3_k) of the last JACOBI solve (cz_info 14)
   int exact_reruns = 0;          // converged first iterations of a fused pass re-run alone from the pass's input, last JACOBI / RBSOR solve (cz_info 12)
   int mg_cycles = 0;             // V-cycles of the last PCG solve with mg (cz_info 16)

@@ -23,6 +23,8 @@ struct Tuning {
   int rb4 = 1, rb4_kwin = 0, rb4_tj = 0;          // two red-black iterations per pass (rb4_k) in single-domain runs; vectors per k window / planes per chunk (0: the launcher's rule); CZHIP_RB4
   int jac3 = 1, jac3_kwin = 0, jac3_tj = 0;       // three Jacobi sweeps per pass (jac3_k) in single-domain runs: 0 off, 1 above the size gate, 2 also
                                                   // below it; vectors per k window / planes per chunk (0: the launcher's rule); CZHIP_JAC3
+  int jac4 = 1, jac4_kwin = 0, jac4_tj = 0;       // four Jacobi sweeps per pass (jac4_k) where jac3_k is taken: 0 off, 1 above its size gate in solves of eight sweeps or more, 2 no gate (tests);
+                                                  // vectors per k window / planes per chunk (0: the launcher's rule); czhip_set_jac4.  Off whenever jac3 is off
   int jac3_medium = 1;                            // jac3_k FP32: the checked shorter division (mediumdiv) for divisors that passed (CZHIP_JAC3_MEDIUM)
   int jac3_gate = 1;                              // jac3_k: the gated form of its division -- huge numerators tested per vector, not per point -- for divisors that passed (czhip_set_jac3_gate)
   int unit_coef = 1;                              // the kernels' form for coefficients that are all exactly 1 (offdiag_sum<UNIT>; CZHIP_UNIT_COEF)
@@ -83,10 +85,10 @@ struct Ctx {
 };
 thread_local Ctx ctx;  // one context per host thread (= per rank; LOCAL transport runs ranks as threads)
 
-enum { LBL_JACOBI = 0, LBL_RBSOR, LBL_AX, LBL_RK, LBL_REDUCE, LBL_EWISE, LBL_DOT, LBL_JACOBI2, LBL_RBSOR2, LBL_PCR, LBL_SHELL, LBL_PSOR, LBL_RBSOR4, LBL_JACOBI3, LBL_MG_RESTRICT, LBL_MG_SMOOTH,
+enum { LBL_JACOBI = 0, LBL_RBSOR, LBL_AX, LBL_RK, LBL_REDUCE, LBL_EWISE, LBL_DOT, LBL_JACOBI2, LBL_RBSOR2, LBL_PCR, LBL_SHELL, LBL_PSOR, LBL_RBSOR4, LBL_JACOBI3, LBL_JACOBI4, LBL_MG_RESTRICT, LBL_MG_SMOOTH,
        LBL_MG_PROLONG, LBL_MG_TAIL, LBL_MG_RB, LBL_FIELD, LBL_BC_MIRROR, LBL_SHIFT_SUMS, LBL_CG_CLOSED, LBL_COUNT };
 static_assert(LBL_COUNT <= 24, "Ctx::t_acc / t_cnt hold 24 labels");
-const char* const kLabelNames[LBL_COUNT] = {"jacobi", "rbsor", "calc_ax", "calc_rk", "reduce", "ewise", "dot", "jacobi2", "rbsor2", "pcr_rb", "pair_shell", "psor", "rbsor4", "jacobi3",
+const char* const kLabelNames[LBL_COUNT] = {"jacobi", "rbsor", "calc_ax", "calc_rk", "reduce", "ewise", "dot", "jacobi2", "rbsor2", "pcr_rb", "pair_shell", "psor", "rbsor4", "jacobi3", "jacobi4",
                                             "mg_restrict", "mg_smooth", "mg_prolong", "mg_tail", "mg_rb", "field_io", "bc_mirror", "shift_sums", "cg_update_closed"};
 
 struct ScopedTimer {

@@ -526,6 +526,54 @@ bool launch_jac3(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box
   return true;
 }
 
+// FOUR Jacobi sweeps per pass (jac4_k, cz_k_jac4.h): the boxes launch_jac3 takes, under the same gates.  Returns false when the geometry does
+// not suit the kernel or the box lies below the size gate (the caller then runs the three-sweep pass).
+// By measurement (profiles/r26/jac4_four_sweeps_per_pass.txt; FP32, ms per sweep against jac3_k under its own rule):
+//   window   512^3: 26 vectors 0.1156 (1.088 x jac3_k), 20: 0.1164, 32: 0.1157, 43: 0.1292 (0.974 x: S = 754, 18 row segments, two rounds);
+//            384^3: 26: 0.0543 (1.099 x), 32: 0.0545; 1024^3: 26: 0.9671 (1.075 x), 32: 0.9826.  Rule: 26, jac3_k's window.
+//   chunks   512^3: the one-round plan of pair_tj_model with long_chunks (3 chunks of 170 planes, 255 workgroups) 0.1156, chunks of 64: 0.1294,
+//            of 32: 0.1482; 1024^3: the model's choice 0.9671, chunks of 128: 0.9792.  Rule: the model, with extra = 7.5 plane steps per chunk
+//            (six redundant planes and the prologue, rb4_k's figure for the same depth; not swept on its own -- the model's choices above
+//            were the fastest chunk lengths tried at every size).
+//   size     256^3: 0.0210 against 0.0204 (0.97 x); 384^3: 1.105 x; 512^3: 1.088 x; 1024^3: 1.075 x.  Nothing was measured between 256^3 and
+//            384^3, so the gate is jac3_k's (below which the issue allows none): 300^3 inner points.
+inline int jac4_window(int) { return 26; }
+constexpr long long kJac4MinPoints = kJac3MinPoints;
+bool launch_jac4(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box& b, const int* skip, Fin2 fin, bool probe, PassPlan* plan_out = nullptr) {
+  // FP32 only: the FP64 instantiations need 12-16 bytes of scratch per lane at 128 registers, so FP64 keeps jac3_k (profiles/r26)
+  if constexpr (sizeof(REAL) == 4) {
+    constexpr int TB = 1024;
+    if (!ctx.tune.jac4 || !ctx.tune.jac3 || !ctx.tune.fuse_fin || !ctx.tune.use_t2 || !deep_pass_ok(U, B, W, c, b)) return false;
+    const long long npts = (long long)(b.ii1 - b.ii0 + 1) * (b.jj1 - b.jj0 + 1) * (b.kk1 - b.kk0 + 1);
+    if (ctx.tune.jac4 == 1 && (npts < kJac4MinPoints || pair_small_form_fits(b))) return false;  // (jac4 = 2: also there -- tests)
+    PassPlan p;
+    p.TB = TB, p.own = TB, p.halo_rows = 6, p.max_R = TB / 12;  // at least half of the workgroup's vectors must be its own
+    p.hv = 1;                                                   // four stages reach four elements beyond a window: one FP32 vector
+    p.wg_per_cu = 1, p.extra = 7.5;                             // (six redundant planes and a longer prologue per chunk)
+    p.tj = ctx.tune.jac4_tj, p.nres = 4, p.long_chunks = true;
+    const int Rfull = (b.nkp + VW - 1) / VW;
+    const int want = ctx.tune.jac4_kwin > 0 ? ctx.tune.jac4_kwin : jac4_window(Rfull);
+    if (Rfull > want + 2 * p.hv) p.kwin = want;
+    const auto lds_bytes = [](int R, int) { return ((size_t)2 * R + (size_t)2 * (TB + 2 * R) + (size_t)6 * TB) * sizeof(Vec<VW>) + 18 * sizeof(double); };
+    if (!plan_pass(p, b, b, lds_bytes)) return false;
+    if (plan_out) *plan_out = p;
+    if (probe) return true;
+    fin.single = 0;
+    const bool unit = ctx.tune.unit_coef && coef_is_unit(c);
+    const bool med = jac3_medium(c.dd), gate = jac3_gated(c.dd, med);
+    auto kernel = !unit ? &jac4_k<VW, TB, 0, 0> : &jac4_k<VW, TB, 1, 0>;
+    if (med) kernel = !unit ? &jac4_k<VW, TB, 0, 1> : &jac4_k<VW, TB, 1, 1>;
+    if (gate) {
+      kernel = !unit ? &jac4_k<VW, TB, 0, 0, 1> : &jac4_k<VW, TB, 1, 0, 1>;
+      if (med) kernel = !unit ? &jac4_k<VW, TB, 0, 1, 1> : &jac4_k<VW, TB, 1, 1, 1>;
+    }
+    launch_pass(kernel, LBL_JACOBI4, p, U, B, W, c, skip, fin);
+    return true;
+  } else {
+    return false;
+  }
+}
+
 // the shell boxes of a decomposed brick, all in one launch (pair_shell_k); boxes: n x (ist,ied,jst,jed,kst,ked), 1-based
 template <int RB, int MAF = 0>
 void launch_pair_shell(const REAL* U, const REAL* B, REAL* W, const Coef& c, const int* sz, int g, const Box& ba, const int* boxes, int n,

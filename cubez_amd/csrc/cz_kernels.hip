@@ -49,6 +49,7 @@ namespace {
 #include "cz_k_pair2.h"
 #include "cz_k_rb4.h"
 #include "cz_k_jac3.h"
+#include "cz_k_jac4.h"
 #include "cz_k_linesor.h"
 #include "cz_k_psor.h"
 #include "cz_k_blas.h"
@@ -160,7 +161,7 @@ const char* czhip_tuning_describe(void) {
       {"ready", ctx.ready ? 1 : 0}, {"threads", t.threads}, {"m", t.m}, {"tj", t.tj}, {"pf", t.pf}, {"fuse_fin", t.fuse_fin},
       {"use_t2", t.use_t2}, {"t2_threads", t.t2_threads}, {"t2_mv", t.t2_mv}, {"t2_tj", t.t2_tj}, {"t2_map", t.t2_map},
       {"t2_any_rows", t.t2_any_rows}, {"t2_kwin", t.t2_kwin}, {"t2_pre", t.t2_pre}, {"rb4", t.rb4}, {"rb4_kwin", t.rb4_kwin},
-      {"rb4_tj", t.rb4_tj}, {"jac3", t.jac3}, {"jac3_kwin", t.jac3_kwin}, {"jac3_tj", t.jac3_tj}, {"jac3_medium", t.jac3_medium}, {"jac3_gate", t.jac3_gate},
+      {"rb4_tj", t.rb4_tj}, {"jac3", t.jac3}, {"jac3_kwin", t.jac3_kwin}, {"jac3_tj", t.jac3_tj}, {"jac3_medium", t.jac3_medium}, {"jac3_gate", t.jac3_gate}, {"jac4", t.jac4}, {"jac4_kwin", t.jac4_kwin}, {"jac4_tj", t.jac4_tj},
       {"unit_coef", t.unit_coef}, {"pcr_fast", t.pcr_fast}, {"pcr_variant", t.pcr_variant}, {"pcr_pipe", t.pcr_pipe},
       {"pipe_spin_ticks", t.pipe_spin_ticks}, {"pcr_rows", t.pcr_rows}, {"pcr_q", t.pcr_q}, {"pcr_wg_per_cu", t.pcr_wg_per_cu},
       {"pcr_max_wg", t.pcr_max_wg}, {"pcr_slots", t.pcr_slots}, {"psor_col", t.psor_col}, {"psor_wg_per_cu", t.psor_wg_per_cu},
@@ -531,6 +532,51 @@ int czhip_set_jac3(int enable, int window, int planes) {
   if (enable >= 0) ctx.tune.jac3 = enable;
   if (window >= 0) ctx.tune.jac3_kwin = window;
   if (planes >= 0) ctx.tune.jac3_tj = planes;
+  return 0;
+}
+
+// FOUR Jacobi sweeps in one pass over memory, u -> w (jac4_k; single-domain boxes).  As czhip_jacobi3_async with res_dev[0..3]: a converged
+// first, second or third sweep leaves the flag set with conv_itr = itr, itr + 1 or itr + 2, and the caller recomputes one, two or three
+// sweeps from u, which this kernel never modifies.  Returns 1 if launched (or launchable), 0 otherwise (the caller runs the three-sweep pass).
+int czhip_jacobi4_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, int g, const CZ_REAL* cf, CZ_REAL omg,
+                        double* res_dev, double res_normal, double eps, int itr, double* hist_dev, int* flag_dev, int* conv_itr_dev,
+                        const int* skip_flag_dev, int probe) {
+  ensure_init();
+  const Box bx = make_box(sz, idx, g);
+  if (bx.empty || g < 2) return 0;
+  Fin2 fin = fin_check<Fin2>(hist_dev, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev);
+  fin.dst = res_dev;
+  return launch_jac4(u, b, w, make_coef(cf, omg), bx, hist_dev ? flag_dev : skip_flag_dev, fin, probe != 0) ? 1 : 0;
+}
+
+// the geometry launch_jac4 plans for the box under the switches in force: out[0..7] = vectors per row of a workgroup's view (R), own vectors per
+// segment (S), k windows per row, vectors a window owns (whole rows: the row length), row segments per window, planes per chunk, chunks, LDS
+// bytes.  Returns 1 where the pass takes the box (out is then filled), 0 otherwise.
+int czhip_jac4_plan(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, int g, const CZ_REAL* cf, CZ_REAL omg, int* out) {
+  ensure_init();
+  const Box bx = make_box(sz, idx, g);
+  if (bx.empty || g < 2) return 0;
+  PassPlan p;
+  if (!launch_jac4(u, b, w, make_coef(cf, omg), bx, nullptr, Fin2(), true, &p)) return 0;
+  const int vals[8] = {p.g.R, p.g.S, p.g.nwin, p.g.nwin > 1 ? p.g.KT : p.g.R, p.g.nsegw, p.g.TJ, p.nchunk, (int)p.lds};
+  for (int i = 0; i < 8; i++) out[i] = vals[i];
+  return 1;
+}
+
+// the fewest sweeps of a solve (its ItrMax) for which the driver takes four-sweep passes under the switches in force: 8 at jac4 = 1 -- two
+// quads; a shorter solve gains one launch at most and keeps its composition of triples -- and 4 at jac4 = 2 (tests: no gate at all)
+int czhip_jac4_min_sweeps(void) {
+  ensure_init();
+  return ctx.tune.jac4 == 2 ? 4 : 8;
+}
+
+// jac4_k switches: enable 0 | 1 | 2 (2: also below the size gate -- tests), vectors per k window, planes per chunk (0: the launcher's rule);
+// negative: keep.
+int czhip_set_jac4(int enable, int window, int planes) {
+  ensure_init();
+  if (enable >= 0) ctx.tune.jac4 = enable;
+  if (window >= 0) ctx.tune.jac4_kwin = window;
+  if (planes >= 0) ctx.tune.jac4_tj = planes;
   return 0;
 }
 

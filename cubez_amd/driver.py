@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from .lib import GUIDE, LABELS, _pairs, load, tuning_in_force
+from .lib import GUIDE, JAC4_LABEL, LABELS, _pairs, load, tuning_in_force
 
 
 class CZ:
@@ -319,7 +319,7 @@ class CZ:
         """what a (multi-GPU) run decided (cz_info of include/cz_hip.h)"""
         keys = ("ranks", "fused_pass", "shell_slabs", "overlap", "lagged_reduce", "rccl_ranks", "comm_cus", "pass_kind", "exchange_depth", "buffers", "bicg_fused", "rb4_passes",
                 "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother", "field_form", "neumann", "closed", "periodic", "void_start",
-                "face_coef")
+                "face_coef", "jac4_passes")
         return {k: self.lib.cz_info(self.h, i) for i, k in enumerate(keys)}
 
     def config_in_force(self) -> dict:
@@ -348,7 +348,7 @@ class CZ:
 
     def launches(self) -> dict:
         """launches recorded under every label since timing was enabled on the calling thread"""
-        return {k: self.timing_read(k)[0] for k in LABELS}
+        return {k: self.timing_read(k)[0] for k in LABELS + (JAC4_LABEL,)}
 
     def close(self):
         if self.h:

@@ -234,6 +234,24 @@ int czhip_jacobi3_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const in
 /* ... its switches (measurements; negative = keep): 0 off / 1 on above the size gate / 2 on also for small grids (tests), vectors per k window,
  * planes per chunk (0 = chosen per launch).  czhip_set_tuning2 with enable 0 (single sweeps) turns it off as well. */
 int czhip_set_jac3(int enable, int window, int planes);
+/* FOUR relaxed-Jacobi sweeps in ONE pass over memory (FP32; the FP64 library answers 0), u -> w out of place, for the boxes czhip_jacobi3_async
+ * takes: bit-identical to four czhip_jacobi_async sweeps.  res_dev[0..3] = the sums dp^2 of sweeps itr .. itr + 3; check arguments as for
+ * czhip_jacobi3_async (four sweeps in order; a converged first, second or third sweep leaves conv_itr = itr, itr + 1 or itr + 2 and the caller
+ * recomputes that sweep, pair or triple from u).  probe != 0: only says whether the launch would be taken.  Returns 0 when it is not (the
+ * caller then runs czhip_jacobi3_async). */
+int czhip_jacobi4_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, int g, const CZ_REAL* cf, CZ_REAL omg,
+                        double* res_dev, double res_normal, double eps, int itr, double* hist_dev, int* flag_dev, int* conv_itr_dev,
+                        const int* skip_flag_dev, int probe);
+/* ... its switches (negative = keep): 0 off / 1 on above the size gate / 2 on also for small grids (tests), vectors per k window, planes per
+ * chunk (0 = chosen per launch).  Off whenever czhip_set_jac3 is off. */
+int czhip_set_jac4(int enable, int window, int planes);
+/* ... and the fewest sweeps of a solve (its ItrMax) for which the driver takes four-sweep passes: 8 at enable = 1 (two quads; a shorter
+ * solve keeps its three-sweep passes), 4 at enable = 2 */
+int czhip_jac4_min_sweeps(void);
+/* ... and the geometry it plans for a box under the switches in force: out[0..7] = vectors per row of a workgroup's view, own vectors per
+ * segment, k windows per row, vectors a window owns (whole rows: the row length), row segments per window, planes per chunk, chunks, LDS
+ * bytes.  Returns 0 where the pass does not take the box. */
+int czhip_jac4_plan(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, int g, const CZ_REAL* cf, CZ_REAL omg, int* out);
 /* ... FP32: its division by the diagonal with one correction step instead of two, for a divisor whose quotients were compared with the IEEE
  * division for all 2^32 numerators on this context (once per divisor, at the first launch) and agreed in every bit; others keep the hoisted
  * form.  1 = on (default), 0 = off, negative = keep.  Returns the previous setting.  Results do not depend on it. */
@@ -637,7 +655,8 @@ double cz_last_solve_seconds(const cz_handle*);
  * 24 the last cz_solve was a pcg that stopped at a breakdown (|rho| < FLT_MIN, absolute in both precisions) before any update: cz_solve
  * returned 0, P holds the caller's bytes (in the closed box: less its mean), cz_result_iter, cz_result_res and the history are 0 / empty --
  * the start was the answer already, or the problem is scaled below the threshold (1); anything else, a refusal or an error included (0);
- * 25 face coefficients are in force (cz_set_face_coef; 0 | 1). */
+ * 25 face coefficients are in force (cz_set_face_coef; 0 | 1); 26 four-sweep Jacobi passes of the last Jacobi solve (czhip_jacobi4_async;
+ * 14 counts the three-sweep passes beside them). */
 int cz_info(const cz_handle*, int what);
 /* The driver's and its communicator's own copies of their switches, as name=value, one per line: overlap, lag_reduce, comm_cus (as asked for;
  * 0 on a single domain), comm_cus_reserved (in force after set-up), bicg_fuse, bicg_devsc, bicg_alias, cg_fuse, mg_tail, mg_gather, mgrb_zero4,
