@@ -888,15 +888,25 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
   FusedLoop L(*this, plan, B, converge_check);
   if (!fused_begin(L, X, itr_max, x_is_zero, made)) return 0;
   const int* skip = L.skip;
+  // One Jacobi pass of n sweeps s -> d: n = 3, 4 through the deep entries (jac3_k, jac4_k), n = 2 the pair; the sums go to rs[0 .. n-1].
+  // check: with the solve's bookkeeping for iteration it (:58 + :67-77, n times) and its skip flag; else bare, as the probes and re-runs are
+  auto jacobi_pass = [&](int n, REAL_TYPE* s, REAL_TYPE* d, double* rs, bool check, int it, int probe) -> int {
+    const double rn = check ? res_normal : 0.0, ep = check ? eps : 0.0;
+    double* hist = (check && converge_check) ? d_hist : nullptr;
+    int* flag = check ? d_flag : nullptr;
+    int* conv = check ? d_flag + 1 : nullptr;
+    const int* sk = check ? skip : nullptr;
+    if (n == 4) return czhip_jacobi4_async(s, d, B, size, innerFidx, gc, cf, ac1, rs, rn, ep, it, hist, flag, conv, sk, probe);
+    if (n == 3) return czhip_jacobi3_async(s, d, B, size, innerFidx, gc, cf, ac1, rs, rn, ep, it, hist, flag, conv, sk, probe);
+    return czhip_jacobi2_async(s, d, B, size, innerFidx, idx1, gc, cf, ac1, rs, rn, ep, it, hist, flag, conv, sk);
+  };
   // THREE sweeps per pass (jac3_k) where the whole inner box is one launch of one rank with constant coefficients, outside a preconditioner
   // solve; triples while three sweeps remain, then the pair or the single sweep
-  const bool jac3 = plan.kind == PassPlan::WHOLE && numProc == 1 && !maf && !in_precond && itr_max >= 3 &&
-                    czhip_jacobi3_async(X, WRK, B, size, innerFidx, gc, cf, ac1, d_res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 1) != 0;
+  const bool jac3 = plan.kind == PassPlan::WHOLE && numProc == 1 && !maf && !in_precond && itr_max >= 3 && jacobi_pass(3, X, WRK, d_res, false, 0, 1) != 0;
   // FOUR sweeps per pass (jac4_k) where that pass takes the box as well and the solve is long enough (czhip_jac4_min_sweeps: a solve of
   // fewer than eight sweeps keeps the triples it had, the passes cz_info 14 reports): quads while four sweeps remain, then the triple,
   // the pair or the single sweep
-  const bool jac4 = jac3 && itr_max >= czhip_jac4_min_sweeps() &&
-                    czhip_jacobi4_async(X, WRK, B, size, innerFidx, gc, cf, ac1, d_res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 1) != 0;
+  const bool jac4 = jac3 && itr_max >= czhip_jac4_min_sweeps() && jacobi_pass(4, X, WRK, d_res, false, 0, 1) != 0;
   jac3_passes = 0, jac4_passes = 0;
   bool stop = false;
   int itr = 1;
@@ -907,20 +917,12 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
     const bool pass = plan.kind != PassPlan::SINGLE && itr + 1 <= itr_max;
     if (pass && plan.kind == PassPlan::SPLIT) {
       if (!split_pass(L, -1, 2, itr, mpp)) return 0;  // :58 twice, :63 hidden behind the interior, :67-77 for both sweeps
-    } else if (pass && jac4 && itr + 3 <= itr_max && !(plan.zero_start && itr == 1)) {
-      if (!czhip_jacobi4_async(src, dst, B, size, innerFidx, gc, cf, ac1, d_res, res_normal, eps, itr, converge_check ? d_hist : nullptr, d_flag,
-                               d_flag + 1, skip, 0)) {  // :58 + :67-77, four times (d_res[0..3]; the re-runs below write d_res[4..6])
-        cz_fatal(1, "error : the four-sweep pass refused after a successful probe\n");
-      }
-      done = 4;
-      jac4_passes++;
     } else if (pass && jac3 && itr + 2 <= itr_max && !(plan.zero_start && itr == 1)) {
-      if (!czhip_jacobi3_async(src, dst, B, size, innerFidx, gc, cf, ac1, d_res, res_normal, eps, itr, converge_check ? d_hist : nullptr, d_flag,
-                               d_flag + 1, skip, 0)) {  // :58 + :67-77, three times
-        cz_fatal(1, "error : the three-sweep pass refused after a successful probe\n");
+      done = (jac4 && itr + 3 <= itr_max) ? 4 : 3;  // :58 + :67-77, `done` times (d_res[0 .. done-1]; the re-runs below write d_res[4..6])
+      if (!jacobi_pass(done, src, dst, d_res, true, itr, 0)) {
+        cz_fatal(1, "error : the %s-sweep pass refused after a successful probe\n", done == 4 ? "four" : "three");
       }
-      done = 3;
-      jac3_passes++;
+      (done == 4 ? jac4_passes : jac3_passes)++;
     } else if (pass) {  // the whole inner box in one launch
       const bool in_kernel_check = converge_check && numProc == 1;
       int launched;
@@ -957,13 +959,10 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
     if (converge_check && L.launches.size() % (POLL_EVERY / 2) == 0 && itr <= itr_max) stop = L.poll.stop();
   }
   return fused_end(L, X, itr_max, res, [&](const Launch& l, int k, REAL_TYPE* s, REAL_TYPE* d) {
-    if (k == 2) {  // the third sweep of a four-sweep pass: one three-sweep pass
-      if (!czhip_jacobi3_async(s, d, B, size, innerFidx, gc, cf, ac1, d_res + 4, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 0)) {
-        cz_fatal(1, "error : the three-sweep pass refused after a successful probe\n");
-      }
-    } else if (k == 1) {  // the second sweep of a three- or four-sweep pass: one pair
-      if (!czhip_jacobi2_async(s, d, B, size, innerFidx, idx1, gc, cf, ac1, d_res + 4, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr)) {
-        cz_fatal(1, "error : fused pass refused after a successful probe\n");
+    // k + 1 sweeps from the launch's source: a triple, a pair, or one plain sweep
+    if (k >= 1) {
+      if (!jacobi_pass(k + 1, s, d, d_res + 4, false, 0, 0)) {
+        cz_fatal(1, "error : %s refused after a successful probe\n", k == 2 ? "the three-sweep pass" : "fused pass");
       }
     } else if (maf) {  // the first sweep of a fused pass: one plain sweep
       jacobi_maf_async(s, d, B, size, innerFidx, gc, d_xc, d_yc, d_zc, ac1, d_res + 4, nullptr, 0, 0.0, 0.0, 0, nullptr, nullptr, nullptr);

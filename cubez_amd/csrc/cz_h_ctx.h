@@ -3,6 +3,12 @@
 // ------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------
+// The switches of a deep pass (launch_deep, cz_h_launch.h): on = 0 off, 1 above the pass's size gate and where the small preloaded forms of
+// the pair do not fit, 2 also there (measurements and tests); vectors per k window and planes per chunk (0: the launcher's rule)
+struct DeepSwitch {
+  int on = 1, kwin = 0, tj = 0;
+};
+
 struct Tuning {
   int threads = 512, m = 2, tj = 16 /* 0 = auto */, pf = 0;  // best of tools/tune_jacobi.py at 512^3 FP32
   int fuse_fin = 1;
@@ -20,11 +26,10 @@ struct Tuning {
   int t2_threads = 0, t2_mv = 2, t2_tj = 0;  // two-stage pass: threads per workgroup and planes per chunk, 0 = chosen per launch by
                                               // the balance model (pair_tj_model, cz_h_launch.h); CZHIP_T2=enable,threads,2,tj fixes them
   int t2_kwin = -1;                               // two-stage pass: vectors per k window; -1 = chosen per launch, 0 = whole rows where they fit (CZHIP_T2_KWIN)
-  int rb4 = 1, rb4_kwin = 0, rb4_tj = 0;          // two red-black iterations per pass (rb4_k) in single-domain runs; vectors per k window / planes per chunk (0: the launcher's rule); CZHIP_RB4
-  int jac3 = 1, jac3_kwin = 0, jac3_tj = 0;       // three Jacobi sweeps per pass (jac3_k) in single-domain runs: 0 off, 1 above the size gate, 2 also
-                                                  // below it; vectors per k window / planes per chunk (0: the launcher's rule); CZHIP_JAC3
-  int jac4 = 1, jac4_kwin = 0, jac4_tj = 0;       // four Jacobi sweeps per pass (jac4_k) where jac3_k is taken: 0 off, 1 above its size gate in solves of eight sweeps or more, 2 no gate (tests);
-                                                  // vectors per k window / planes per chunk (0: the launcher's rule); czhip_set_jac4.  Off whenever jac3 is off
+  DeepSwitch rb4;                                 // two red-black iterations per pass (rb4_k) in single-domain runs; CZHIP_RB4
+  DeepSwitch jac3;                                // three Jacobi sweeps per pass (jac3_k) in single-domain runs; CZHIP_JAC3
+  DeepSwitch jac4;                                // four Jacobi sweeps per pass (jac4_k) where jac3_k is taken: on = 1 only in solves of eight sweeps or more;
+                                                  // czhip_set_jac4.  Off whenever jac3 is off
   int jac3_medium = 1;                            // jac3_k FP32: the checked shorter division (mediumdiv) for divisors that passed (CZHIP_JAC3_MEDIUM)
   int jac3_gate = 1;                              // jac3_k: the gated form of its division -- huge numerators tested per vector, not per point -- for divisors that passed (czhip_set_jac3_gate)
   int unit_coef = 1;                              // the kernels' form for coefficients that are all exactly 1 (offdiag_sum<UNIT>; CZHIP_UNIT_COEF)

@@ -199,7 +199,7 @@ inline bool coef_is_unit(const Coef& c) {
   return c.c1 == (REAL)1 && c.c2 == (REAL)1 && c.c3 == (REAL)1 && c.c4 == (REAL)1 && c.c5 == (REAL)1 && c.c6 == (REAL)1;
 }
 
-// A multi-stage pass (jacobi2p_k, rb4_k, jac3_k, all on Geom2): what its launcher chooses, and what plan_pass makes of it
+// A multi-stage pass (jacobi2p_k, rb4_k, jac3_k, jac4_k, all on Geom2): what its launcher chooses, and what plan_pass makes of it
 struct PassPlan {
   int TB = 0;             // threads per workgroup
   int own = 0;            // vectors a workgroup holds; S = own - halo_rows * R of them are its own
@@ -384,52 +384,11 @@ bool launch_jacobi2(const REAL* U, const REAL* B, REAL* W, const Coef& c, const 
   return launch_jacobi2_inst<1024, 2, RB, 0>(U, B, W, c, b, ba, tu.t2_tj, skip, fin, par, probe, nullptr);
 }
 
-// rb4_k, jac3_k: arrays of any REAL alignment, a dd that takes the hoisted division, and two layers between the box and the array's i, j edges
-inline bool deep_pass_ok(const REAL* U, const REAL* B, const REAL* W, const Coef& c, const Box& b) {
-  return rows_ok(b, {U, B, W}) && fastdiv_ok(c.dd) && b.ii0 >= 2 && b.jj0 >= 2 && b.ii1 <= b.nip - 3 && b.jj1 <= b.njp - 3;
-}
-
-// TWO red-black iterations per pass (rb4_k, cz_k_rb4.h): single-domain boxes, constant coefficients.  Returns false when the geometry does not suit
-// the kernel (the caller then runs two fused iterations, jacobi2p_k<RB = 1>).  The k axis is cut into windows of about kRb4Win vectors whatever
-// the row length: the six halo rows of a segment must stay a small share of the 1 024 vectors a workgroup holds.
-// Window length by measurement (profiles/r04/rb4_two_iterations_per_pass.txt; 128^3 .. 1024^3): FP32 rows up to 50 vectors whole (128^3, 192^3:
-// 1.12 x / 1.25 x the one-iteration pass), rows of 65 / 97 vectors in windows of 22 / 25 (1.14 x / 1.28 x; windows of 33 give 1.02 x / 1.09 x), rows of
-// 129 / 257 in windows of 43 (1.15-1.19 x; 26 and 33 give 1.10 x); FP64 anything from 20 to 33 (1.25-1.32 x).
-inline int rb4_window(int Rfull) { return VW == 4 ? (Rfull < 115 ? 26 : 48) : 28; }
-constexpr int kRb4Win = 48;
-// do the 256-thread preloaded forms of the one-iteration pass (launch_jacobi2: small grids) take this box?  Where they do they beat rb4_k
-// (32^3 .. 80^3: rb4_k 0.67-0.85 x; from 96^3 on, where they no longer fit, 1.00-1.16 x: profiles/r04/rb4_two_iterations_per_pass.txt)
-inline bool pair_small_form_fits(const Box& b) {
-  if (!ctx.tune.t2_pre || ctx.tune.t2_tj != 0 || ctx.tune.t2_threads == 1024) return false;
-  const int R = (b.nkp + VW - 1) / VW;
-  if (4 * R >= 256) return false;
-  const long long S = 256 - 2 * R, nf = (long long)(b.ii1 - b.ii0 + 1) * R, nseg = (nf + S - 1) / S;
-  const int nplanes = b.jj1 - b.jj0 + 1;
-  const long long slots = (long long)std::max(1, ctx.num_cu / 8 - ctx.cu_reserved) * 8;
-  return nseg * ((nplanes + 1) / 2) <= slots || nseg * ((nplanes + 3) / 4) <= slots;
-}
-bool launch_rb4(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box& b, const int* skip, Fin2 fin, int par, bool probe) {
-  constexpr int TB = 1024;
-  if (!ctx.tune.rb4 || !ctx.tune.fuse_fin || !deep_pass_ok(U, B, W, c, b)) return false;
-  if (ctx.tune.rb4 == 1 && pair_small_form_fits(b)) return false;  // (rb4 = 2: also there -- measurements and tests)
-  PassPlan p;
-  p.TB = TB, p.own = TB, p.halo_rows = 6, p.max_R = TB / 8;  // at least a quarter of the workgroup's vectors must be its own
-  p.hv = VW == 4 ? 1 : 2;                                    // four stages reach three elements beyond a window
-  p.wg_per_cu = 1, p.extra = 7.5;                            // (six redundant planes and a longer prologue per chunk)
-  p.tj = ctx.tune.rb4_tj, p.par = par;
-  const int Rfull = (b.nkp + VW - 1) / VW;
-  const int want = ctx.tune.rb4_kwin > 0 ? ctx.tune.rb4_kwin : rb4_window(Rfull);
-  if (Rfull > (ctx.tune.rb4_kwin > 0 ? want : kRb4Win) + 2 * p.hv) p.kwin = want;
-  const auto lds_bytes = [](int R, int) { return ((size_t)2 * R + (size_t)2 * (TB + 2 * R) + (size_t)6 * TB) * sizeof(Vec<VW>) + 18 * sizeof(double); };
-  if (!plan_pass(p, b, b, lds_bytes)) return false;
-  if (probe) return true;
-  fin.single = 0;
-  // (unit coefficients: rb4_k is an arithmetic kernel -- vector ALU 93 % busy -- and the six multiplications are a fifth of a point's
-  // instructions: 6-7 % at 512^3 FP32, profiles/r04/unit_coefficients.txt)
-  const bool unit = ctx.tune.unit_coef && coef_is_unit(c);
-  launch_pass(!unit ? &rb4_k<VW, TB, 0> : &rb4_k<VW, TB, 1>, LBL_RBSOR4, p, U, B, W, c, skip, fin);  // (UNIT = 0 named first: it keeps its place in the code object)
-  return true;
-}
+// rb4_k's two forms (launch_deep).  Named here, ahead of the division checks and UNIT = 0 first: the kernels keep their place in the code object.
+// (unit coefficients: rb4_k is an arithmetic kernel -- vector ALU 93 % busy -- and the six multiplications are a fifth of a point's
+// instructions: 6-7 % at 512^3 FP32, profiles/r04/unit_coefficients.txt)
+constexpr int kDeepTB = 1024;
+inline auto rb4_form(bool unit) { return !unit ? &rb4_k<VW, kDeepTB, 0> : &rb4_k<VW, kDeepTB, 1>; }
 
 // numerators (of 2^32; see fastdiv_check_k) whose quotient by d in division form FORM (0 hoisted, 1 short, 2 medium, 3 / 4 the gated tail of the
 // hoisted / medium form) differs from `n / d`; *compared = how many were compared (all of them but for the gated tails, which skip the huge ones)
@@ -483,96 +442,126 @@ inline bool jac3_gated(REAL d, bool med) {
   return it->second;
 }
 
-// THREE Jacobi sweeps per pass (jac3_k, cz_k_jac3.h): single-domain boxes, constant coefficients.  Returns false when the geometry does not suit
-// the kernel or the box lies below the size gate (the caller then runs the two-sweep pass).  The k axis is cut into windows of about
-// jac3_window() vectors: the four halo rows of a segment must stay a small share of the 1 024 vectors a workgroup holds.
-// By measurement (profiles/r06/jac3_three_sweeps_per_pass.txt), per sweep against the pair: FP32 windows of 26 vectors 1.09 x at 512^3 (43: 1.01 x,
-// 20: 0.98 x), 1.11 x at 384^3, 1.07 x at 1024^3, 1.01 x at 256^3; FP64 512^3 windows of 36 1.22 x (28: 1.19 x, 20: 1.11 x).
-// Re-swept with the shorter FP32 division (profiles/r08/jac3_fetch_split_and_medium_division.txt): no window or gate beats these beyond noise.
+// ------------------------------------------------------------------------------------------------------------
+// The DEEP passes -- rb4_k (two red-black iterations), jac3_k, jac4_k (three, four Jacobi sweeps) per pass over memory: single-domain boxes,
+// constant coefficients, 1 024 threads with one vector each (deep_lds, cz_k_pass.h).  One launcher (launch_deep); what differs between the
+// passes is a row of kDeepPass, and the measurements that justify a row's constants stand above it.
+// do the 256-thread preloaded forms of the one-iteration pass (launch_jacobi2: small grids) take this box?  Where they do they beat rb4_k
+// (32^3 .. 80^3: rb4_k 0.67-0.85 x; from 96^3 on, where they no longer fit, 1.00-1.16 x: profiles/r04/rb4_two_iterations_per_pass.txt)
+inline bool pair_small_form_fits(const Box& b) {
+  if (!ctx.tune.t2_pre || ctx.tune.t2_tj != 0 || ctx.tune.t2_threads == 1024) return false;
+  const int R = (b.nkp + VW - 1) / VW;
+  if (4 * R >= 256) return false;
+  const long long S = 256 - 2 * R, nf = (long long)(b.ii1 - b.ii0 + 1) * R, nseg = (nf + S - 1) / S;
+  const int nplanes = b.jj1 - b.jj0 + 1;
+  const long long slots = (long long)std::max(1, ctx.num_cu / 8 - ctx.cu_reserved) * 8;
+  return nseg * ((nplanes + 1) / 2) <= slots || nseg * ((nplanes + 3) / 4) <= slots;
+}
+inline int rb4_window(int Rfull) { return VW == 4 ? (Rfull < 115 ? 26 : 48) : 28; }
 inline int jac3_window(int) { return VW == 4 ? 26 : 36; }
-// size gate of ctx.tune.jac3 = 1: inner points of the box (256^3: no gain worth the switch; 384^3: 1.11 x)
+inline int jac4_window(int) { return 26; }
+constexpr int kRb4Win = 48;
+// size gate of jac3 = 1: inner points of the box (256^3: no gain worth the switch; 384^3: 1.11 x)
 constexpr long long kJac3MinPoints = 300LL * 300 * 300;
-bool launch_jac3(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box& b, const int* skip, Fin2 fin, bool probe) {
-  constexpr int TB = 1024;
-  if (!ctx.tune.jac3 || !ctx.tune.fuse_fin || !ctx.tune.use_t2 || !deep_pass_ok(U, B, W, c, b)) return false;
+constexpr long long kJac4MinPoints = kJac3MinPoints;
+
+enum DeepKind { DEEP_RB4 = 0, DEEP_JAC3 = 1, DEEP_JAC4 = 2 };
+struct DeepPass {
+  int label;                  // timing label
+  int halo_rows;              // 2 (D - 1) for a pass of D stages: S = TB - halo_rows * R vectors of a workgroup are its own
+  int max_R;                  // longest row of a workgroup's view: the halo rows must stay a small share of its 1 024 vectors
+  int hv;                     // halo vectors on either side of a k window: D stages reach D - 1 (red-black: 3) elements beyond it
+  double extra;               // plane steps a chunk costs beyond its own: the redundant planes and the prologue (pair_tj_model)
+  int nres;                   // residual sums per workgroup
+  bool long_chunks;           // pair_tj_model may take chunks of more than 128 planes where the launch is then one round
+  int (*window)(int Rfull);   // vectors per k window where the switch forces none
+  int whole_rows;             // ... and rows up to this many vectors (and the halo) then stay whole; 0: up to the window itself
+  long long min_points;       // size gate of switch = 1: inner points of the box
+  bool needs_t2;              // only where the driver may fuse Jacobi sweeps at all (use_t2)
+  bool fp64;                  // built for FP64 as well
+  DeepSwitch Tuning::*sw;     // its switches
+  DeepSwitch Tuning::*needs;  // the pass that has to be switched on as well (or null)
+};
+const DeepPass kDeepPass[3] = {
+    // rb4_k (cz_k_rb4.h); refused: the caller runs two fused iterations, jacobi2p_k<RB = 1>.  The k axis is cut into windows of about kRb4Win
+    // vectors whatever the row length: the six halo rows of a segment must stay a small share of the 1 024 vectors a workgroup holds (max_R:
+    // at least a quarter of them must be its own).  extra: six redundant planes and a longer prologue per chunk.
+    // Window length by measurement (profiles/r04/rb4_two_iterations_per_pass.txt; 128^3 .. 1024^3): FP32 rows up to 50 vectors whole (128^3,
+    // 192^3: 1.12 x / 1.25 x the one-iteration pass), rows of 65 / 97 vectors in windows of 22 / 25 (1.14 x / 1.28 x; windows of 33 give 1.02 x /
+    // 1.09 x), rows of 129 / 257 in windows of 43 (1.15-1.19 x; 26 and 33 give 1.10 x); FP64 anything from 20 to 33 (1.25-1.32 x).
+    {LBL_RBSOR4, 6, kDeepTB / 8, VW == 4 ? 1 : 2, 7.5, 2, false, rb4_window, kRb4Win, 0, false, true, &Tuning::rb4, nullptr},
+    // jac3_k (cz_k_jac3.h); refused, or below the size gate: the caller runs the two-sweep pass.  Four halo rows (max_R: at least half of the
+    // workgroup's vectors must be its own); extra: four redundant planes and a longer prologue per chunk.
+    // By measurement (profiles/r06/jac3_three_sweeps_per_pass.txt), per sweep against the pair: FP32 windows of 26 vectors 1.09 x at 512^3 (43:
+    // 1.01 x, 20: 0.98 x), 1.11 x at 384^3, 1.07 x at 1024^3, 1.01 x at 256^3; FP64 512^3 windows of 36 1.22 x (28: 1.19 x, 20: 1.11 x).
+    // Re-swept with the shorter FP32 division (profiles/r08/jac3_fetch_split_and_medium_division.txt): no window or gate beats these beyond noise.
+    {LBL_JACOBI3, 4, kDeepTB / 8, VW == 4 ? 1 : 2, 5.5, 3, true, jac3_window, 0, kJac3MinPoints, true, true, &Tuning::jac3, nullptr},
+    // jac4_k (cz_k_jac4.h): the boxes jac3_k takes, under the same gates; refused: the caller runs the three-sweep pass.  FP32 only: the FP64
+    // instantiations need 12-16 bytes of scratch per lane at 128 registers, so FP64 keeps jac3_k (profiles/r26).  Six halo rows (max_R: at
+    // least half of the vectors its own); four stages reach four elements beyond a window: one FP32 vector.
+    // By measurement (profiles/r26/jac4_four_sweeps_per_pass.txt; FP32, ms per sweep against jac3_k under its own rule):
+    //   window   512^3: 26 vectors 0.1156 (1.088 x jac3_k), 20: 0.1164, 32: 0.1157, 43: 0.1292 (0.974 x: S = 754, 18 row segments, two rounds);
+    //            384^3: 26: 0.0543 (1.099 x), 32: 0.0545; 1024^3: 26: 0.9671 (1.075 x), 32: 0.9826.  Rule: 26, jac3_k's window.
+    //   chunks   512^3: the one-round plan of pair_tj_model with long_chunks (3 chunks of 170 planes, 255 workgroups) 0.1156, chunks of 64: 0.1294,
+    //            of 32: 0.1482; 1024^3: the model's choice 0.9671, chunks of 128: 0.9792.  Rule: the model, with extra = 7.5 plane steps per chunk
+    //            (six redundant planes and the prologue, rb4_k's figure for the same depth; not swept on its own -- the model's choices above
+    //            were the fastest chunk lengths tried at every size).
+    //   size     256^3: 0.0210 against 0.0204 (0.97 x); 384^3: 1.105 x; 512^3: 1.088 x; 1024^3: 1.075 x.  Nothing was measured between 256^3 and
+    //            384^3, so the gate is jac3_k's (below which the issue allows none): 300^3 inner points.
+    {LBL_JACOBI4, 6, kDeepTB / 12, 1, 7.5, 4, true, jac4_window, 0, kJac4MinPoints, true, false, &Tuning::jac4, &Tuning::jac3},
+};
+
+// The eight forms of a Jacobi kernel K by unit coefficients, division (MED: FP32 only) and its gated form.  The ungated instantiations are
+// named first, UNIT = 0 before UNIT = 1: they keep their place in the code object.
+#define CZ_JAC_FORMS(K)                                                                \
+  kernel = !unit ? &K<VW, TB, 0, 0> : &K<VW, TB, 1, 0>;                                \
+  if constexpr (sizeof(REAL) == 4) {                                                   \
+    if (med) kernel = !unit ? &K<VW, TB, 0, 1> : &K<VW, TB, 1, 1>;                     \
+  }                                                                                    \
+  if (gate) {                                                                          \
+    kernel = !unit ? &K<VW, TB, 0, 0, 1> : &K<VW, TB, 1, 0, 1>;                        \
+    if constexpr (sizeof(REAL) == 4) {                                                 \
+      if (med) kernel = !unit ? &K<VW, TB, 0, 1, 1> : &K<VW, TB, 1, 1, 1>;             \
+    }                                                                                  \
+  }
+
+// Plans and launches the deep pass `kind` u -> w over the box b (par: the colour parity of rb4_k).  Returns false where the pass is switched
+// off, the box lies below its gates or the geometry does not suit the kernel.  probe: plan only; plan_out receives the plan.
+bool launch_deep(DeepKind kind, const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box& b, const int* skip, Fin2 fin, int par, bool probe,
+                 PassPlan* plan_out = nullptr) {
+  constexpr int TB = kDeepTB;
+  const DeepPass& d = kDeepPass[kind];
+  const Tuning& tu = ctx.tune;
+  const DeepSwitch& sw = tu.*d.sw;
+  if ((sizeof(REAL) == 8 && !d.fp64) || !sw.on || (d.needs && !(tu.*d.needs).on) || !tu.fuse_fin || (d.needs_t2 && !tu.use_t2)) return false;
+  // arrays of any REAL alignment, a dd that takes the hoisted division, and two layers between the box and the array's i, j edges
+  if (!rows_ok(b, {U, B, W}) || !fastdiv_ok(c.dd) || b.ii0 < 2 || b.jj0 < 2 || b.ii1 > b.nip - 3 || b.jj1 > b.njp - 3) return false;
   const long long npts = (long long)(b.ii1 - b.ii0 + 1) * (b.jj1 - b.jj0 + 1) * (b.kk1 - b.kk0 + 1);
-  if (ctx.tune.jac3 == 1 && (npts < kJac3MinPoints || pair_small_form_fits(b))) return false;  // (jac3 = 2: also there -- tests)
+  if (sw.on == 1 && (npts < d.min_points || pair_small_form_fits(b))) return false;  // (2: also there -- measurements and tests)
   PassPlan p;
-  p.TB = TB, p.own = TB, p.halo_rows = 4, p.max_R = TB / 8;  // at least half of the workgroup's vectors must be its own
-  p.hv = VW == 4 ? 1 : 2;                                    // three stages reach three elements beyond a window
-  p.wg_per_cu = 1, p.extra = 5.5;                            // (four redundant planes and a longer prologue per chunk)
-  p.tj = ctx.tune.jac3_tj, p.nres = 3, p.long_chunks = true;
+  p.TB = TB, p.own = TB, p.halo_rows = d.halo_rows, p.max_R = d.max_R, p.hv = d.hv;
+  p.wg_per_cu = 1, p.extra = d.extra, p.tj = sw.tj, p.nres = d.nres, p.long_chunks = d.long_chunks, p.par = par;
   const int Rfull = (b.nkp + VW - 1) / VW;
-  const int want = ctx.tune.jac3_kwin > 0 ? ctx.tune.jac3_kwin : jac3_window(Rfull);
-  if (Rfull > want + 2 * p.hv) p.kwin = want;
-  const auto lds_bytes = [](int R, int) { return ((size_t)2 * R + (size_t)2 * (TB + 2 * R) + (size_t)4 * TB) * sizeof(Vec<VW>) + 18 * sizeof(double); };
-  if (!plan_pass(p, b, b, lds_bytes)) return false;
+  const int want = sw.kwin > 0 ? sw.kwin : d.window(Rfull);
+  if (Rfull > ((sw.kwin > 0 || !d.whole_rows) ? want : d.whole_rows) + 2 * p.hv) p.kwin = want;
+  const int depth = d.halo_rows / 2 + 1;
+  if (!plan_pass(p, b, b, [depth](int R, int) { return deep_lds_bytes<VW>(TB, depth, R); })) return false;
+  if (plan_out) *plan_out = p;
   if (probe) return true;
   fin.single = 0;
-  const bool unit = ctx.tune.unit_coef && coef_is_unit(c);
-  const bool med = jac3_medium(c.dd), gate = jac3_gated(c.dd, med);
-  // (the ungated instantiations are named first, UNIT = 0 before UNIT = 1: they keep their place in the code object)
-  auto kernel = !unit ? &jac3_k<VW, TB, 0, 0> : &jac3_k<VW, TB, 1, 0>;
-  if constexpr (sizeof(REAL) == 4) {
-    if (med) kernel = !unit ? &jac3_k<VW, TB, 0, 1> : &jac3_k<VW, TB, 1, 1>;
-  }
-  if (gate) {
-    kernel = !unit ? &jac3_k<VW, TB, 0, 0, 1> : &jac3_k<VW, TB, 1, 0, 1>;
+  const bool unit = tu.unit_coef && coef_is_unit(c);
+  auto kernel = rb4_form(unit);
+  if (kind != DEEP_RB4) {
+    const bool med = jac3_medium(c.dd), gate = jac3_gated(c.dd, med);
+    CZ_JAC_FORMS(jac3_k)
     if constexpr (sizeof(REAL) == 4) {
-      if (med) kernel = !unit ? &jac3_k<VW, TB, 0, 1, 1> : &jac3_k<VW, TB, 1, 1, 1>;
+      if (kind == DEEP_JAC4) { CZ_JAC_FORMS(jac4_k) }
     }
   }
-  launch_pass(kernel, LBL_JACOBI3, p, U, B, W, c, skip, fin);
+  launch_pass(kernel, d.label, p, U, B, W, c, skip, fin);
   return true;
 }
-
-// FOUR Jacobi sweeps per pass (jac4_k, cz_k_jac4.h): the boxes launch_jac3 takes, under the same gates.  Returns false when the geometry does
-// not suit the kernel or the box lies below the size gate (the caller then runs the three-sweep pass).
-// By measurement (profiles/r26/jac4_four_sweeps_per_pass.txt; FP32, ms per sweep against jac3_k under its own rule):
-//   window   512^3: 26 vectors 0.1156 (1.088 x jac3_k), 20: 0.1164, 32: 0.1157, 43: 0.1292 (0.974 x: S = 754, 18 row segments, two rounds);
-//            384^3: 26: 0.0543 (1.099 x), 32: 0.0545; 1024^3: 26: 0.9671 (1.075 x), 32: 0.9826.  Rule: 26, jac3_k's window.
-//   chunks   512^3: the one-round plan of pair_tj_model with long_chunks (3 chunks of 170 planes, 255 workgroups) 0.1156, chunks of 64: 0.1294,
-//            of 32: 0.1482; 1024^3: the model's choice 0.9671, chunks of 128: 0.9792.  Rule: the model, with extra = 7.5 plane steps per chunk
-//            (six redundant planes and the prologue, rb4_k's figure for the same depth; not swept on its own -- the model's choices above
-//            were the fastest chunk lengths tried at every size).
-//   size     256^3: 0.0210 against 0.0204 (0.97 x); 384^3: 1.105 x; 512^3: 1.088 x; 1024^3: 1.075 x.  Nothing was measured between 256^3 and
-//            384^3, so the gate is jac3_k's (below which the issue allows none): 300^3 inner points.
-inline int jac4_window(int) { return 26; }
-constexpr long long kJac4MinPoints = kJac3MinPoints;
-bool launch_jac4(const REAL* U, const REAL* B, REAL* W, const Coef& c, const Box& b, const int* skip, Fin2 fin, bool probe, PassPlan* plan_out = nullptr) {
-  // FP32 only: the FP64 instantiations need 12-16 bytes of scratch per lane at 128 registers, so FP64 keeps jac3_k (profiles/r26)
-  if constexpr (sizeof(REAL) == 4) {
-    constexpr int TB = 1024;
-    if (!ctx.tune.jac4 || !ctx.tune.jac3 || !ctx.tune.fuse_fin || !ctx.tune.use_t2 || !deep_pass_ok(U, B, W, c, b)) return false;
-    const long long npts = (long long)(b.ii1 - b.ii0 + 1) * (b.jj1 - b.jj0 + 1) * (b.kk1 - b.kk0 + 1);
-    if (ctx.tune.jac4 == 1 && (npts < kJac4MinPoints || pair_small_form_fits(b))) return false;  // (jac4 = 2: also there -- tests)
-    PassPlan p;
-    p.TB = TB, p.own = TB, p.halo_rows = 6, p.max_R = TB / 12;  // at least half of the workgroup's vectors must be its own
-    p.hv = 1;                                                   // four stages reach four elements beyond a window: one FP32 vector
-    p.wg_per_cu = 1, p.extra = 7.5;                             // (six redundant planes and a longer prologue per chunk)
-    p.tj = ctx.tune.jac4_tj, p.nres = 4, p.long_chunks = true;
-    const int Rfull = (b.nkp + VW - 1) / VW;
-    const int want = ctx.tune.jac4_kwin > 0 ? ctx.tune.jac4_kwin : jac4_window(Rfull);
-    if (Rfull > want + 2 * p.hv) p.kwin = want;
-    const auto lds_bytes = [](int R, int) { return ((size_t)2 * R + (size_t)2 * (TB + 2 * R) + (size_t)6 * TB) * sizeof(Vec<VW>) + 18 * sizeof(double); };
-    if (!plan_pass(p, b, b, lds_bytes)) return false;
-    if (plan_out) *plan_out = p;
-    if (probe) return true;
-    fin.single = 0;
-    const bool unit = ctx.tune.unit_coef && coef_is_unit(c);
-    const bool med = jac3_medium(c.dd), gate = jac3_gated(c.dd, med);
-    auto kernel = !unit ? &jac4_k<VW, TB, 0, 0> : &jac4_k<VW, TB, 1, 0>;
-    if (med) kernel = !unit ? &jac4_k<VW, TB, 0, 1> : &jac4_k<VW, TB, 1, 1>;
-    if (gate) {
-      kernel = !unit ? &jac4_k<VW, TB, 0, 0, 1> : &jac4_k<VW, TB, 1, 0, 1>;
-      if (med) kernel = !unit ? &jac4_k<VW, TB, 0, 1, 1> : &jac4_k<VW, TB, 1, 1, 1>;
-    }
-    launch_pass(kernel, LBL_JACOBI4, p, U, B, W, c, skip, fin);
-    return true;
-  } else {
-    return false;
-  }
-}
+#undef CZ_JAC_FORMS
 
 // the shell boxes of a decomposed brick, all in one launch (pair_shell_k); boxes: n x (ist,ied,jst,jed,kst,ked), 1-based
 template <int RB, int MAF = 0>

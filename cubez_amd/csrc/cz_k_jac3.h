@@ -88,12 +88,42 @@ __device__ __forceinline__ Vec<V> lds_whole(typename NatVec<V>::type x) {
 // read of the next stage.
 __device__ __forceinline__ void reads_stay_in_order() { __builtin_amdgcn_sched_barrier(0); }
 
+// A stage of jac3_k and jac4_k in two parts.  jac_fetch requests its six LDS operands -- centre, j-1, j+1, the plane before, and the k
+// neighbours beyond the wave's first and last vector (x_first, x_last: one element each, the same address in all lanes) -- and uses none of
+// them; jac_relax takes them whole (lds_whole) and does the arithmetic.  What a step puts between the two is what the round trip hides behind.
+template <int V>
+__device__ __forceinline__ LdsOperands<V> jac_fetch(const Vec<V>* cur, const Vec<V>* prv, int x, int R, int x_first, int x_last) {
+  LdsOperands<V> o;
+  o.pc = lds_request<V>(cur + x);
+  o.im = lds_request<V>(cur + x - R);
+  o.ip = lds_request<V>(cur + x + R);
+  o.pm = lds_request<V>(prv + x);
+  o.elo = reinterpret_cast<const REAL*>(cur)[(long long)x_first * V - 1];
+  o.ehi = reinterpret_cast<const REAL*>(cur)[(long long)(x_last + 1) * V];
+  return o;
+}
+template <int V, int UNIT, class DIV>
+__device__ __forceinline__ Vec<V> jac_relax(const LdsOperands<V>& o, const Vec<V>& nxt, const Vec<V>& bb, const Coef& c, const DIV& dv,
+                                            unsigned msk, unsigned cnt, double& acc) {
+  const Vec<V> pc = lds_whole<V>(o.pc);
+  const Vec<V> im = lds_whole<V>(o.im);
+  const Vec<V> ip = lds_whole<V>(o.ip);
+  const Vec<V> pm = lds_whole<V>(o.pm);
+  const REAL kl = lane_shr1(o.elo, pc.v[V - 1]);
+  const REAL kr = lane_shl1(o.ehi, pc.v[0]);
+  return relax_vec<V, UNIT>(pc, im, ip, pm, nxt, kl, kr, bb, c, dv, msk, cnt, acc);
+}
+
+// The division policy of both kernels:
 // MED = 1 (FP32): the division with one correction step (mediumdiv, cz_k_fastdiv.h), taken only for a divisor that passed the exhaustive
 // comparison with `n / d` on this context (jac3_medium, cz_h_launch.h)
 // GATE = 1: that division (medium or hoisted, by MED) in its gated form (GatedDiv, cz_k_pass.h): whether a numerator is huge is tested once per
 // vector and wave instead of at every point.  Taken only for a divisor that passed its comparison on this context (jac3_gated, cz_h_launch.h).
 // What the compiler has to make of it -- the tail without den_s a block of its own in the inner step -- is part of the listing in
 // profiles/r23/jac3_gated_division.txt.
+template <int MED, int GATE>
+using JacDiv = typename std::conditional<GATE != 0, GatedDiv<MED>, typename std::conditional<MED != 0, MediumDiv, HoistedDiv>::type>::type;
+
 template <int V, int TB, int UNIT, int MED, int GATE = 0>
 __global__ void __launch_bounds__(TB, 1)
 jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict__ W, Coef c, Geom2 g, double* partials,
@@ -113,7 +143,7 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
   const int ja = it.ja, jb = it.jb;
 
   double acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-  const typename std::conditional<GATE != 0, GatedDiv<MED>, typename std::conditional<MED != 0, MediumDiv, HoistedDiv>::type>::type dv{fastdiv_init(c.dd)};
+  const JacDiv<MED, GATE> dv{fastdiv_init(c.dd)};
 
   if (it.work) {
     const long long e2_0 = it.fb - 2 * (long long)R;  // first vector of E2
@@ -157,28 +187,10 @@ jac3_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
 
     // the k neighbours beyond the wave's first and last vector come from LDS (one element each, the same address in all lanes)
     const int x_first = __builtin_amdgcn_readfirstlane(x), x_last = __builtin_amdgcn_readlane(x, 63);
-    // A stage in two parts.  `fetch` requests its six LDS operands and uses none of them; `relax` takes them whole (lds_whole) and does
-    // the arithmetic.  What stands between the two in the step is what the round trip hides behind.
-    auto fetch = [&](const Vec<V>* cur, const Vec<V>* prv) __attribute__((always_inline)) -> LdsOperands<V> {
-      LdsOperands<V> o;
-      o.pc = lds_request<V>(cur + x);
-      o.im = lds_request<V>(cur + x - R);
-      o.ip = lds_request<V>(cur + x + R);
-      o.pm = lds_request<V>(prv + x);
-      o.elo = reinterpret_cast<const REAL*>(cur)[(long long)x_first * V - 1];
-      o.ehi = reinterpret_cast<const REAL*>(cur)[(long long)(x_last + 1) * V];
-      return o;
-    };
-    auto relax = [&](const LdsOperands<V>& o, const Vec<V>& nxt, const Vec<V>& bb, unsigned msk, unsigned cnt,
-                     double& acc) __attribute__((always_inline)) -> Vec<V> {
-      const Vec<V> pc = lds_whole<V>(o.pc);
-      const Vec<V> im = lds_whole<V>(o.im);
-      const Vec<V> ip = lds_whole<V>(o.ip);
-      const Vec<V> pm = lds_whole<V>(o.pm);
-      const REAL kl = lane_shr1(o.elo, pc.v[V - 1]);
-      const REAL kr = lane_shl1(o.ehi, pc.v[0]);
-      return relax_vec<V, UNIT>(pc, im, ip, pm, nxt, kl, kr, bb, c, dv, msk, cnt, acc);
-    };
+    // a stage in two parts (jac_fetch, jac_relax) with this thread's vector, row length, coefficients and division
+    auto fetch = [&](const Vec<V>* cur, const Vec<V>* prv) __attribute__((always_inline)) { return jac_fetch<V>(cur, prv, x, R, x_first, x_last); };
+    auto relax = [&](const LdsOperands<V>& o, const Vec<V>& nxt, const Vec<V>& bb, unsigned msk, unsigned cnt, double& acc)
+                     __attribute__((always_inline)) { return jac_relax<V, UNIT>(o, nxt, bb, c, dv, msk, cnt, acc); };
 
     // One plane step q.  uc = u(q+1), its outer rows hx and b1 = b(q) were requested one step ago; un / bn / hx receive this step's requests
     // (u(q+2), b(q+1), the outer rows of u(q+2)).  b2 = b(q-1), b3 = b(q-2): the right-hand sides of stages 2 and 3.

@@ -38,7 +38,7 @@ jac4_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
   const int ja = it.ja, jb = it.jb;
 
   double acc1 = 0.0, acc2 = 0.0, acc3 = 0.0, acc4 = 0.0;
-  const typename std::conditional<GATE != 0, GatedDiv<MED>, typename std::conditional<MED != 0, MediumDiv, HoistedDiv>::type>::type dv{fastdiv_init(c.dd)};
+  const JacDiv<MED, GATE> dv{fastdiv_init(c.dd)};
 
   if (it.work) {
     const long long e3_0 = it.fb - 3 * (long long)R;  // first vector of E3
@@ -83,26 +83,9 @@ jac4_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restrict_
 
     // the k neighbours beyond the wave's first and last vector come from LDS (one element each, the same address in all lanes)
     const int x_first = __builtin_amdgcn_readfirstlane(x), x_last = __builtin_amdgcn_readlane(x, 63);
-    auto fetch = [&](const Vec<V>* cur, const Vec<V>* prv) __attribute__((always_inline)) -> LdsOperands<V> {
-      LdsOperands<V> o;
-      o.pc = lds_request<V>(cur + x);
-      o.im = lds_request<V>(cur + x - R);
-      o.ip = lds_request<V>(cur + x + R);
-      o.pm = lds_request<V>(prv + x);
-      o.elo = reinterpret_cast<const REAL*>(cur)[(long long)x_first * V - 1];
-      o.ehi = reinterpret_cast<const REAL*>(cur)[(long long)(x_last + 1) * V];
-      return o;
-    };
-    auto relax = [&](const LdsOperands<V>& o, const Vec<V>& nxt, const Vec<V>& bb, unsigned msk, unsigned cnt,
-                     double& acc) __attribute__((always_inline)) -> Vec<V> {
-      const Vec<V> pc = lds_whole<V>(o.pc);
-      const Vec<V> im = lds_whole<V>(o.im);
-      const Vec<V> ip = lds_whole<V>(o.ip);
-      const Vec<V> pm = lds_whole<V>(o.pm);
-      const REAL kl = lane_shr1(o.elo, pc.v[V - 1]);
-      const REAL kr = lane_shl1(o.ehi, pc.v[0]);
-      return relax_vec<V, UNIT>(pc, im, ip, pm, nxt, kl, kr, bb, c, dv, msk, cnt, acc);
-    };
+    auto fetch = [&](const Vec<V>* cur, const Vec<V>* prv) __attribute__((always_inline)) { return jac_fetch<V>(cur, prv, x, R, x_first, x_last); };
+    auto relax = [&](const LdsOperands<V>& o, const Vec<V>& nxt, const Vec<V>& bb, unsigned msk, unsigned cnt, double& acc)
+                     __attribute__((always_inline)) { return jac_relax<V, UNIT>(o, nxt, bb, c, dv, msk, cnt, acc); };
 
     // One plane step q.  uc = u(q+1), its outer rows hx and b1 = b(q) were requested one step ago; un / bn / hx receive this step's requests
     // (u(q+2), b(q+1), the outer rows of u(q+2)).  b2 = b(q-1), b3 = b(q-2), b4 = b(q-3): the right-hand sides of stages 2, 3 and 4.

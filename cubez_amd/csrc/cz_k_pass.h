@@ -1,13 +1,22 @@
 // cz_k_pass.h -- part of cz_kernels.hip (ONE translation unit per precision; included inside its anonymous namespace after cz_k_fastdiv.h):
-// the FRAME of the temporally blocked passes -- jacobi2p_k (cz_k_pair2.h), rb4_k (cz_k_rb4.h), jac3_k (cz_k_jac3.h) and the shell kernel of a
-// split pass (cz_k_pair.h).  What they share is stated here once: the geometry (Geom2) and the finalisation record (Fin2), the per-point update
-// (relax_vec*), the map from a workgroup id to its work item (pass_item), the addresses of the windowed row view (RowView), the masks of a
-// vector (vec_mask), the staging of the outer rows (outer_row), the masked store (store_owned) and the residual epilogue (pass_epilogue, pass_finalize).
-// For rb4_k and jac3_k also the LDS carve-up (deep_lds).  What a kernel writes itself: how its threads are dealt to the vectors, which
-// vectors it owns, its prologue and the plane step with its requests.  (The prologue, requests, operand fetch and A/B loop of rb4_k and
-// jac3_k differ only in the depth 4 against 3, and stay two copies for a measured reason: stated once as helpers they changed the register
-// allocation and the instruction sequence of the plane steps of both kernels -- jac3_k 95 -> 86, rb4_k 128 -> 123 VGPRs -- and the Jacobi and
-// RB-SOR bench lines at 512^3 ran 1.6-1.8 % slower; DESIGN 5.2, profiles/r14/pass_frame.txt.)
+// the FRAME of the temporally blocked passes -- jacobi2p_k (cz_k_pair2.h), rb4_k (cz_k_rb4.h), jac3_k (cz_k_jac3.h), jac4_k (cz_k_jac4.h) and
+// the shell kernel of a split pass (cz_k_pair.h).  What they share is stated here once: the geometry (Geom2) and the finalisation record
+// (Fin2), the per-point update (relax_vec*), the map from a workgroup id to its work item (pass_item), the addresses of the windowed row
+// view (RowView), the masks of a vector (vec_mask), the staging of the outer rows (outer_row), the masked store (store_owned) and the
+// residual epilogue (pass_epilogue, pass_finalize).  For rb4_k, jac3_k and jac4_k also the LDS carve-up (deep_lds) and its size, which their
+// launcher takes from here (deep_lds_bytes).  jac3_k and jac4_k further share a stage's two halves and the division policy (jac_fetch,
+// jac_relax, JacDiv; cz_k_jac3.h).  What a kernel writes itself: how its threads are dealt to the vectors, which vectors it owns, its
+// prologue, its per-lane set-up and the plane step with its requests.  Those differ between rb4_k, jac3_k and jac4_k in little but the depth,
+// and stay copies for a reason that was checked each time, by the code the compiler makes of them:
+//   r14  prologue, requests, operand fetch and A/B loop of rb4_k and jac3_k stated once as helpers: other register allocation and instruction
+//        sequence in the plane steps of both (jac3_k 95 -> 86, rb4_k 128 -> 123 VGPRs), the Jacobi and RB-SOR bench lines at 512^3 1.6-1.8 %
+//        slower (profiles/r14/pass_frame.txt)
+//   r27  jac3_k and jac4_k, every kernel's instruction text against the parent's (profiles/r27/deep_pass_one_launcher.txt).  jac_fetch,
+//        jac_relax as free functions and JacDiv: all 365 FP32 and 352 FP64 kernels identical, register names included -- taken.  The same
+//        and the prologue block as a free function (outputs by reference): jac3_k identical, all 8 jac4_k differ, 4 in register names only, 4
+//        in the opcode sequence (+4 instructions) -- not taken.  The same and the per-lane set-up (f, bo, masks, outer_row, waveh) returned
+//        in a struct: all 8 jac3_k and all 8 jac4_k differ in the opcode sequence -- not taken.
+// DESIGN 5.2.
 // ------------------------------------------------------------------------------------------------------------
 // SEVERAL relaxation stages per pass over memory (temporal blocking).
 //
@@ -392,7 +401,7 @@ __device__ __forceinline__ void store_owned(char* plane, unsigned bo, unsigned o
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// The passes of D stages with ONE vector per thread (rb4_k: D = 4, jac3_k: D = 3): u on the own segment +- D rows, the intermediate fields
+// The passes of D stages with ONE vector per thread (rb4_k, jac4_k: D = 4, jac3_k: D = 3): u on the own segment +- D rows, the intermediate fields
 // f1 .. f(D-1) on E = own segment +- (D-1) rows, LV = TB vectors of which S = LV - 2 (D-1) R are the workgroup's own.
 // LDS: u in 2 buffers of LU = LV + 2R vectors, then f1 .. f(D-1) in 2 buffers of LV each -- plane p in buffer p & 1 -- then the 18 doubles of
 // the epilogue.  R vectors of padding in front of the u buffers and behind the last field buffer: the stages are evaluated on whole waves
@@ -404,12 +413,26 @@ struct DeepLds {
   Vec<V>* F;  // [field][plane & 1][LV]
   double* wsum;
 };
+// The vectors of that carve-up, i.e. where the epilogue's doubles start, and the dynamic LDS of a launch: the ONE statement of the size, for
+// the device (deep_lds) and the host (launch_deep, cz_h_launch.h).
+__host__ __device__ constexpr size_t deep_lds_vectors(int LV, int D, int R) {
+  return (size_t)R + (size_t)2 * (LV + 2 * R) + (size_t)(2 * (D - 1)) * LV + (size_t)R;
+}
+template <int V>
+__host__ __device__ constexpr size_t deep_lds_bytes(int LV, int D, int R) {
+  return deep_lds_vectors(LV, D, R) * sizeof(Vec<V>) + 18 * sizeof(double);
+}
 template <int V, int LV, int D>
 __device__ __forceinline__ DeepLds<V> deep_lds(char* smem, int R) {
   DeepLds<V> l;
   l.LU = LV + 2 * R;
   l.U = reinterpret_cast<Vec<V>*>(smem) + R;
   l.F = l.U + (size_t)2 * l.LU;
+  // = smem + deep_lds_vectors(LV, D, R).  Written from F, not from that expression: derived from it the plane steps of rb4_k, jac3_k and
+  // jac4_k compiled to other code (FP64 rb4_k with 8 bytes of scratch; profiles/r27/deep_pass_one_launcher.txt).  The assertion ties the two.
+  static_assert(deep_lds_vectors(LV, D, 1) == 1 + 2 * (LV + 2) + (2 * (D - 1)) * LV + 1 &&
+                    deep_lds_vectors(LV, D, 2) - deep_lds_vectors(LV, D, 1) == 6,
+                "deep_lds and deep_lds_vectors carve the same allocation: R + 2 LU + 2 (D - 1) LV + R vectors, linear in R");
   l.wsum = reinterpret_cast<double*>(l.F + (size_t)(2 * (D - 1)) * LV + R);
   return l;
 }

@@ -132,6 +132,33 @@ void launch_pivot(REAL* pvt, const Box& b, const MafArgs& ma) {
   }
   HIP_CHECK(hipGetLastError());
 }
+
+// The deep passes (launch_deep, cz_h_launch.h) behind their C entries.  "enable[,vectors per window[,planes per chunk]]" of CZHIP_RB4 and
+// CZHIP_JAC3: a variable that is set sets all three, what it leaves out to 1, 0, 0
+void parse_deep(const char* v, DeepSwitch& sw) {
+  if (!v) return;
+  sw = DeepSwitch{1, 0, 0};
+  sscanf(v, "%d,%d,%d", &sw.on, &sw.kwin, &sw.tj);
+}
+// ... and of the setters; negative: keep
+int set_deep(DeepSwitch& sw, int enable, int window, int planes) {
+  ensure_init();
+  if (enable >= 0) sw.on = enable;
+  if (window >= 0) sw.kwin = window;
+  if (planes >= 0) sw.tj = planes;
+  return 0;
+}
+// One pass of `kind` u -> w with the bookkeeping of its iterations (hist_dev given) or a skip flag; plan_out: only the plan (czhip_jac4_plan)
+int deep_async(DeepKind kind, const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, int g, const CZ_REAL* cf, int par,
+               CZ_REAL omg, double* res_dev, double res_normal, double eps, int itr, double* hist_dev, int* flag_dev, int* conv_itr_dev,
+               const int* skip_flag_dev, int probe, PassPlan* plan_out = nullptr) {
+  ensure_init();
+  const Box bx = make_box(sz, idx, g);
+  if (bx.empty || g < 2) return 0;
+  Fin2 fin = fin_check<Fin2>(hist_dev, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev);
+  fin.dst = res_dev;
+  return launch_deep(kind, u, b, w, make_coef(cf, omg), bx, hist_dev ? flag_dev : skip_flag_dev, fin, par, probe != 0, plan_out) ? 1 : 0;
+}
 }  // namespace
 
 namespace {
@@ -160,8 +187,8 @@ const char* czhip_tuning_describe(void) {
   const std::pair<const char*, long long> rows[] = {
       {"ready", ctx.ready ? 1 : 0}, {"threads", t.threads}, {"m", t.m}, {"tj", t.tj}, {"pf", t.pf}, {"fuse_fin", t.fuse_fin},
       {"use_t2", t.use_t2}, {"t2_threads", t.t2_threads}, {"t2_mv", t.t2_mv}, {"t2_tj", t.t2_tj}, {"t2_map", t.t2_map},
-      {"t2_any_rows", t.t2_any_rows}, {"t2_kwin", t.t2_kwin}, {"t2_pre", t.t2_pre}, {"rb4", t.rb4}, {"rb4_kwin", t.rb4_kwin},
-      {"rb4_tj", t.rb4_tj}, {"jac3", t.jac3}, {"jac3_kwin", t.jac3_kwin}, {"jac3_tj", t.jac3_tj}, {"jac3_medium", t.jac3_medium}, {"jac3_gate", t.jac3_gate}, {"jac4", t.jac4}, {"jac4_kwin", t.jac4_kwin}, {"jac4_tj", t.jac4_tj},
+      {"t2_any_rows", t.t2_any_rows}, {"t2_kwin", t.t2_kwin}, {"t2_pre", t.t2_pre}, {"rb4", t.rb4.on}, {"rb4_kwin", t.rb4.kwin},
+      {"rb4_tj", t.rb4.tj}, {"jac3", t.jac3.on}, {"jac3_kwin", t.jac3.kwin}, {"jac3_tj", t.jac3.tj}, {"jac3_medium", t.jac3_medium}, {"jac3_gate", t.jac3_gate}, {"jac4", t.jac4.on}, {"jac4_kwin", t.jac4.kwin}, {"jac4_tj", t.jac4.tj},
       {"unit_coef", t.unit_coef}, {"pcr_fast", t.pcr_fast}, {"pcr_variant", t.pcr_variant}, {"pcr_pipe", t.pcr_pipe},
       {"pipe_spin_ticks", t.pipe_spin_ticks}, {"pcr_rows", t.pcr_rows}, {"pcr_q", t.pcr_q}, {"pcr_wg_per_cu", t.pcr_wg_per_cu},
       {"pcr_max_wg", t.pcr_max_wg}, {"pcr_slots", t.pcr_slots}, {"psor_col", t.psor_col}, {"psor_wg_per_cu", t.psor_wg_per_cu},
@@ -211,16 +238,8 @@ int czhip_init(int device) {
   ctx.tune.t2_kwin = cfg.num(CZV_T2_KWIN, ctx.tune.t2_kwin);
   ctx.tune.t2_pre = cfg.num(CZV_T2_PRE, ctx.tune.t2_pre);
   ctx.tune.unit_coef = cfg.num(CZV_UNIT_COEF, ctx.tune.unit_coef);
-  if (const char* v = cfg.str(CZV_RB4)) {  // "enable[,vectors per window[,planes per chunk]]"
-    int en = 1, kw = 0, tj = 0;
-    sscanf(v, "%d,%d,%d", &en, &kw, &tj);
-    ctx.tune.rb4 = en, ctx.tune.rb4_kwin = kw, ctx.tune.rb4_tj = tj;
-  }
-  if (const char* v = cfg.str(CZV_JAC3)) {  // "enable[,vectors per window[,planes per chunk]]"
-    int en = 1, kw = 0, tj = 0;
-    sscanf(v, "%d,%d,%d", &en, &kw, &tj);
-    ctx.tune.jac3 = en, ctx.tune.jac3_kwin = kw, ctx.tune.jac3_tj = tj;
-  }
+  parse_deep(cfg.str(CZV_RB4), ctx.tune.rb4);
+  parse_deep(cfg.str(CZV_JAC3), ctx.tune.jac3);
   ctx.tune.jac3_medium = cfg.num(CZV_JAC3_MEDIUM, ctx.tune.jac3_medium);
   if (const char* pp = cfg.str(CZV_PCR_PIPE)) {  // "form[,seconds[,groups[,rows per thread]]]": form as Tuning::pcr_pipe; bound of the waits inside the kernel
     int w = 1, rows = 0, q = 1;
@@ -502,12 +521,8 @@ int czhip_rbsor2_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int
 int czhip_rbsor4_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, int g, const CZ_REAL* cf, int ofst, CZ_REAL omg,
                        double* res_dev, double res_normal, double eps, int itr, double* hist_dev, int* flag_dev, int* conv_itr_dev,
                        const int* skip_flag_dev, int probe) {
-  ensure_init();
-  const Box bx = make_box(sz, idx, g);
-  if (bx.empty || g < 2) return 0;
-  Fin2 fin = fin_check<Fin2>(hist_dev, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev);
-  fin.dst = res_dev;
-  return launch_rb4(u, b, w, make_coef(cf, omg), bx, hist_dev ? flag_dev : skip_flag_dev, fin, rb_parity(g, idx, ofst, 0), probe != 0) ? 1 : 0;
+  return deep_async(DEEP_RB4, u, w, b, sz, idx, g, cf, rb_parity(g, idx, ofst, 0), omg, res_dev, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev,
+                    skip_flag_dev, probe);
 }
 
 // THREE Jacobi sweeps in one pass over memory, u -> w (jac3_k; single-domain boxes).  res_dev[0..2] receive the sums dp^2 of sweeps itr, itr + 1,
@@ -517,22 +532,13 @@ int czhip_rbsor4_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int
 int czhip_jacobi3_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, int g, const CZ_REAL* cf, CZ_REAL omg,
                         double* res_dev, double res_normal, double eps, int itr, double* hist_dev, int* flag_dev, int* conv_itr_dev,
                         const int* skip_flag_dev, int probe) {
-  ensure_init();
-  const Box bx = make_box(sz, idx, g);
-  if (bx.empty || g < 2) return 0;
-  Fin2 fin = fin_check<Fin2>(hist_dev, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev);
-  fin.dst = res_dev;
-  return launch_jac3(u, b, w, make_coef(cf, omg), bx, hist_dev ? flag_dev : skip_flag_dev, fin, probe != 0) ? 1 : 0;
+  return deep_async(DEEP_JAC3, u, w, b, sz, idx, g, cf, 0, omg, res_dev, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev, skip_flag_dev, probe);
 }
 
 // jac3_k switches (measurements): enable 0 | 1 | 2 (2: also below the size gate -- tests), vectors per k window, planes per chunk (0: the
 // launcher's rule); negative: keep.
 int czhip_set_jac3(int enable, int window, int planes) {
-  ensure_init();
-  if (enable >= 0) ctx.tune.jac3 = enable;
-  if (window >= 0) ctx.tune.jac3_kwin = window;
-  if (planes >= 0) ctx.tune.jac3_tj = planes;
-  return 0;
+  return set_deep(ctx.tune.jac3, enable, window, planes);
 }
 
 // FOUR Jacobi sweeps in one pass over memory, u -> w (jac4_k; single-domain boxes).  As czhip_jacobi3_async with res_dev[0..3]: a converged
@@ -541,23 +547,15 @@ int czhip_set_jac3(int enable, int window, int planes) {
 int czhip_jacobi4_async(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, int g, const CZ_REAL* cf, CZ_REAL omg,
                         double* res_dev, double res_normal, double eps, int itr, double* hist_dev, int* flag_dev, int* conv_itr_dev,
                         const int* skip_flag_dev, int probe) {
-  ensure_init();
-  const Box bx = make_box(sz, idx, g);
-  if (bx.empty || g < 2) return 0;
-  Fin2 fin = fin_check<Fin2>(hist_dev, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev);
-  fin.dst = res_dev;
-  return launch_jac4(u, b, w, make_coef(cf, omg), bx, hist_dev ? flag_dev : skip_flag_dev, fin, probe != 0) ? 1 : 0;
+  return deep_async(DEEP_JAC4, u, w, b, sz, idx, g, cf, 0, omg, res_dev, res_normal, eps, itr, hist_dev, flag_dev, conv_itr_dev, skip_flag_dev, probe);
 }
 
-// the geometry launch_jac4 plans for the box under the switches in force: out[0..7] = vectors per row of a workgroup's view (R), own vectors per
+// the geometry launch_deep plans for jac4_k for the box under the switches in force: out[0..7] = vectors per row of a workgroup's view (R), own vectors per
 // segment (S), k windows per row, vectors a window owns (whole rows: the row length), row segments per window, planes per chunk, chunks, LDS
 // bytes.  Returns 1 where the pass takes the box (out is then filled), 0 otherwise.
 int czhip_jac4_plan(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* sz, const int* idx, int g, const CZ_REAL* cf, CZ_REAL omg, int* out) {
-  ensure_init();
-  const Box bx = make_box(sz, idx, g);
-  if (bx.empty || g < 2) return 0;
   PassPlan p;
-  if (!launch_jac4(u, b, w, make_coef(cf, omg), bx, nullptr, Fin2(), true, &p)) return 0;
+  if (!deep_async(DEEP_JAC4, u, w, b, sz, idx, g, cf, 0, omg, nullptr, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 1, &p)) return 0;
   const int vals[8] = {p.g.R, p.g.S, p.g.nwin, p.g.nwin > 1 ? p.g.KT : p.g.R, p.g.nsegw, p.g.TJ, p.nchunk, (int)p.lds};
   for (int i = 0; i < 8; i++) out[i] = vals[i];
   return 1;
@@ -567,17 +565,13 @@ int czhip_jac4_plan(const CZ_REAL* u, CZ_REAL* w, const CZ_REAL* b, const int* s
 // quads; a shorter solve gains one launch at most and keeps its composition of triples -- and 4 at jac4 = 2 (tests: no gate at all)
 int czhip_jac4_min_sweeps(void) {
   ensure_init();
-  return ctx.tune.jac4 == 2 ? 4 : 8;
+  return ctx.tune.jac4.on == 2 ? 4 : 8;
 }
 
 // jac4_k switches: enable 0 | 1 | 2 (2: also below the size gate -- tests), vectors per k window, planes per chunk (0: the launcher's rule);
 // negative: keep.
 int czhip_set_jac4(int enable, int window, int planes) {
-  ensure_init();
-  if (enable >= 0) ctx.tune.jac4 = enable;
-  if (window >= 0) ctx.tune.jac4_kwin = window;
-  if (planes >= 0) ctx.tune.jac4_tj = planes;
-  return 0;
+  return set_deep(ctx.tune.jac4, enable, window, planes);
 }
 
 // jac3_k FP32: the checked shorter division on (1) or off (0); negative: keep.  Returns the setting that was in force.
@@ -616,11 +610,7 @@ int czhip_jac3_gated(CZ_REAL d) {
 
 // rb4_k switches (measurements): enable 0 | 1, vectors per k window, planes per chunk (0: the launcher's rule); negative: keep.
 int czhip_set_rb4(int enable, int window, int planes) {
-  ensure_init();
-  if (enable >= 0) ctx.tune.rb4 = enable;  // (2: also on the small grids where the preloaded one-iteration pass is faster -- tests)
-  if (window >= 0) ctx.tune.rb4_kwin = window;
-  if (planes >= 0) ctx.tune.rb4_tj = planes;
-  return 0;
+  return set_deep(ctx.tune.rb4, enable, window, planes);  // (2: also on the small grids where the preloaded one-iteration pass is faster -- tests)
 }
 
 // The fused pass split the way a decomposed brick runs it: the slabs behind the faces with nID[f] >= 0 first

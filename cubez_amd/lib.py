@@ -204,44 +204,34 @@ class CzHip:
         self.lib.czhip_d2h(out, self._dres, 16)
         return bool(ok), out[0]
 
+    def _deep(self, kind, n, u, w, b, sz, idx, cf, omg, probe, ofst=None, ck=None):
+        """czhip_<kind>_async (rbsor4 | jacobi3 | jacobi4; ofst: the red-black entry's extra argument).  ck None: a bare launch, returns
+        (launched, its n sums); else with ck's bookkeeping or skip flag (pass_checked), returns launched"""
+        (_, szp), (_, idxp), (_, cfp) = self._i(sz), self._i(idx), self._r(cf)
+        if ck is None and not hasattr(self, "_dres"):
+            self._dres = self.lib.czhip_alloc_s3d((C.c_int * 3)(4, 4, 4))
+        f = getattr(self.lib, f"czhip_{kind}_async")
+        f.argtypes = ([C.c_void_p] * 5 + [C.c_int, C.c_void_p] + ([C.c_int] if ofst is not None else []) + [self.creal, C.c_void_p, C.c_double, C.c_double,
+                      C.c_int] + [C.c_void_p] * 4 + [C.c_int])
+        tail = (self._dres, 0.0, 0.0, 0, None, None, None, None) if ck is None else (*self._ck(ck), ck["skip"].ptr if ck.get("skip") is not None else None)
+        ok = bool(f(u.ptr, w.ptr, b.ptr, szp, idxp, GUIDE, cfp, *([int(ofst)] if ofst is not None else []), float(omg), *tail, int(probe)))
+        if ck is not None:
+            return ok
+        out = (C.c_double * n)()
+        self.lib.czhip_d2h(out, self._dres, 8 * n)
+        return (ok, *out)
+
     def rbsor4(self, u, w, b, sz, idx, cf, ofst, omg, probe=0):
         """u -> w = TWO red-black iterations (colour 0, 1, 0, 1) in one launch (rb4_k); returns (launched, res of iteration 1, of iteration 2)."""
-        (_, szp), (_, idxp), (_, cfp) = self._i(sz), self._i(idx), self._r(cf)
-        if not hasattr(self, "_dres"):
-            self._dres = self.lib.czhip_alloc_s3d((C.c_int * 3)(4, 4, 4))
-        self.lib.czhip_rbsor4_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, self.creal,
-                                                C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        ok = self.lib.czhip_rbsor4_async(u.ptr, w.ptr, b.ptr, szp, idxp, GUIDE, cfp, int(ofst), float(omg), self._dres, 0.0, 0.0, 0, None, None, None,
-                                         None, int(probe))
-        out = (C.c_double * 2)()
-        self.lib.czhip_d2h(out, self._dres, 16)
-        return bool(ok), out[0], out[1]
+        return self._deep("rbsor4", 2, u, w, b, sz, idx, cf, omg, probe, ofst=ofst)
 
     def jacobi3(self, u, w, b, sz, idx, cf, omg, probe=0):
         """u -> w = THREE Jacobi sweeps in one launch (jac3_k); returns (launched, res of sweep 1, 2, 3)."""
-        (_, szp), (_, idxp), (_, cfp) = self._i(sz), self._i(idx), self._r(cf)
-        if not hasattr(self, "_dres"):
-            self._dres = self.lib.czhip_alloc_s3d((C.c_int * 3)(4, 4, 4))
-        self.lib.czhip_jacobi3_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, self.creal,
-                                                 C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        ok = self.lib.czhip_jacobi3_async(u.ptr, w.ptr, b.ptr, szp, idxp, GUIDE, cfp, float(omg), self._dres, 0.0, 0.0, 0, None, None, None, None,
-                                          int(probe))
-        out = (C.c_double * 3)()
-        self.lib.czhip_d2h(out, self._dres, 24)
-        return bool(ok), out[0], out[1], out[2]
+        return self._deep("jacobi3", 3, u, w, b, sz, idx, cf, omg, probe)
 
     def jacobi4(self, u, w, b, sz, idx, cf, omg, probe=0):
         """u -> w = FOUR Jacobi sweeps in one launch (jac4_k); returns (launched, res of sweep 1, 2, 3, 4)."""
-        (_, szp), (_, idxp), (_, cfp) = self._i(sz), self._i(idx), self._r(cf)
-        if not hasattr(self, "_dres"):
-            self._dres = self.lib.czhip_alloc_s3d((C.c_int * 3)(4, 4, 4))
-        self.lib.czhip_jacobi4_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, self.creal,
-                                                 C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        ok = self.lib.czhip_jacobi4_async(u.ptr, w.ptr, b.ptr, szp, idxp, GUIDE, cfp, float(omg), self._dres, 0.0, 0.0, 0, None, None, None, None,
-                                          int(probe))
-        out = (C.c_double * 4)()
-        self.lib.czhip_d2h(out, self._dres, 32)
-        return bool(ok), out[0], out[1], out[2], out[3]
+        return self._deep("jacobi4", 4, u, w, b, sz, idx, cf, omg, probe)
 
     def jac4_plan(self, u, w, b, sz, idx, cf, omg):
         """the geometry jac4_k would run the box with (czhip_jac4_plan), or None where the pass does not take it"""
@@ -317,7 +307,7 @@ class CzHip:
 
     def pass_checked(self, kind, u, w, b, sz, idx, cf, omg, ck, ofst=0) -> bool:
         """one fused pass u -> w with the bookkeeping of its iterations (hist given) or only a skip flag (hist None, skip given):
-        kind jacobi2 | rbsor2 | rbsor4 | jacobi3; returns launched"""
+        kind jacobi2 | rbsor2 | rbsor4 | jacobi3 | jacobi4; returns launched"""
         (_, szp), (_, idxp), (_, cfp) = self._i(sz), self._i(idx), self._r(cf)
         res, rn, eps, itr, hist, flag, conv = self._ck(ck)
         skip = ck["skip"].ptr if ck.get("skip") is not None else None
@@ -327,10 +317,7 @@ class CzHip:
             f.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_void_p] + ([C.c_int] if kind == "rbsor2" else []) + [self.creal] + tail
             mid = [int(ofst)] if kind == "rbsor2" else []
             return bool(f(u.ptr, w.ptr, b.ptr, szp, idxp, None, GUIDE, cfp, *mid, float(omg), res, rn, eps, itr, hist, flag, conv, skip))
-        f = self.lib.czhip_rbsor4_async if kind == "rbsor4" else self.lib.czhip_jacobi3_async
-        f.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_void_p] + ([C.c_int] if kind == "rbsor4" else []) + [self.creal] + tail + [C.c_int]
-        mid = [int(ofst)] if kind == "rbsor4" else []
-        return bool(f(u.ptr, w.ptr, b.ptr, szp, idxp, GUIDE, cfp, *mid, float(omg), res, rn, eps, itr, hist, flag, conv, skip, 0))
+        return self._deep(kind, 0, u, w, b, sz, idx, cf, omg, 0, ofst=ofst if kind == "rbsor4" else None, ck=ck)
 
     def check(self, ck, pair=False):
         """czhip_check_async (pair: czhip_check2_async) on the sums in res"""

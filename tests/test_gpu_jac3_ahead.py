@@ -75,7 +75,7 @@ def _check_forms(h, p, b, sz, idx, cf, want, res, forms, nans=False):
 
 
 def _geometry(prec, sz, idx, kwin):
-    """(R, k windows, row segments per window) of the pass the launcher plans for this box (restated from launch_jac3 and plan_pass,
+    """(R, k windows, row segments per window) of the pass the launcher plans for this box (restated from launch_deep and plan_pass,
     cz_h_launch.h, as tests/test_gpu_jac3_flight.py does): 1024 vectors per workgroup, four halo rows.  Window 0 in czhip_set_jac3 is the
     launcher's own rule (26 / 36 vectors), NOT whole rows: whole rows of Rfull vectors are asked for with a window of Rfull"""
     v, hv = (4, 1) if prec == "f32" else (2, 2)

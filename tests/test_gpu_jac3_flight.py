@@ -11,7 +11,7 @@ test_gpu_jac3_steps.py), at the smallest shapes at which that staging can go wro
     outer row against the wave   R = 7 / 9 (inside one wave, TB - R inside the last wave), R = 64 (exactly one wave), R = 100 (two waves must
                                  request; TB - R = 924 inside wave 14)
 in FP32 and FP64, with unit and with general coefficients.  The row length R, the number of k windows and the number of row segments per
-window that a case is meant to run at are stated with it and checked against the launcher's rule (`_geometry`, restated from launch_jac3 and
+window that a case is meant to run at are stated with it and checked against the launcher's rule (`_geometry`, restated from launch_deep and
 plan_pass, cz_h_launch.h): window 0 in czhip_set_jac3 is that rule's own choice (26 / 36 vectors), not whole rows -- whole rows of Rfull
 vectors are asked for with a window of Rfull."""
 import numpy as np
@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _geometry(prec, sz, idx, kwin):
-    """(R, k windows, row segments per window) of the pass launch_jac3 plans for this box: TB = 1024 vectors per workgroup, four halo rows"""
+    """(R, k windows, row segments per window) of the pass launch_deep plans for jac3_k on this box: TB = 1024 vectors per workgroup, four halo rows"""
     v, hv = (4, 1) if prec == "f32" else (2, 2)
     rfull = -(-(sz[2] + 4) // v)
     want = kwin if kwin > 0 else (26 if v == 4 else 36)

@@ -16,13 +16,14 @@ BOXES = [((24, 20, 28), (1, 24, 1, 20, 1, 28)), ((40, 36, 61), None), ((9, 7, 11
 BOX_IDS = ["24x20x28_idx", "40x36x61", "9x7x1100"]
 
 # entry point -> sweeps (iterations) per launch
-SWEEPS = {"jacobi": 1, "rbsor": 1, "jacobi2": 2, "rbsor2": 1, "rbsor4": 2, "jacobi3": 3}
-# the launch forms each entry can be forced into: pair (threads, vectors, planes per chunk, k window), rb4 / jac3 (k window, planes)
+SWEEPS = {"jacobi": 1, "rbsor": 1, "jacobi2": 2, "rbsor2": 1, "rbsor4": 2, "jacobi3": 3, "jacobi4": 4}
+# the launch forms each entry can be forced into: pair (threads, vectors, planes per chunk, k window), rb4 / jac3 / jac4 (k window, planes)
 PAIR_FORMS = [(-2, 2, 0, -1), (512, 2, 5, 6), (1024, 2, 11, 17)]
 DEEP_FORMS = [(0, 0), (5, 0), (9, 3)]
-FORMS = {"jacobi": [None], "rbsor": [None], "jacobi2": PAIR_FORMS, "rbsor2": PAIR_FORMS, "rbsor4": DEEP_FORMS, "jacobi3": DEEP_FORMS}
+FORMS = {"jacobi": [None], "rbsor": [None], "jacobi2": PAIR_FORMS, "rbsor2": PAIR_FORMS, "rbsor4": DEEP_FORMS, "jacobi3": DEEP_FORMS,
+         "jacobi4": DEEP_FORMS}
 
-OMG = {"jacobi": 0.9, "jacobi2": 0.9, "jacobi3": 0.9, "rbsor": 1.3, "rbsor2": 1.3, "rbsor4": 1.3}
+OMG = {"jacobi": 0.9, "jacobi2": 0.9, "jacobi3": 0.9, "jacobi4": 0.9, "rbsor": 1.3, "rbsor2": 1.3, "rbsor4": 1.3}
 ITR = 7                # iteration number of the launch's first sweep
 NH = 16                # history entries on the device
 HSENT = -3.25          # sentinel of the history
@@ -44,8 +45,10 @@ def _set_form(h, kind, form):
         h.lib.czhip_set_pair_window(win)
     elif kind == "rbsor4":
         assert h.lib.czhip_set_rb4(2, *form) == 0
-    else:
+    elif kind == "jacobi3":
         assert h.lib.czhip_set_jac3(2, *form) == 0
+    else:
+        assert h.lib.czhip_set_jac4(2, *form) == 0
 
 
 def _reset_forms(h):
@@ -53,6 +56,7 @@ def _reset_forms(h):
     h.lib.czhip_set_pair_window(-1)
     h.lib.czhip_set_rb4(1, 0, 0)
     h.lib.czhip_set_jac3(1, 0, 0)
+    h.lib.czhip_set_jac4(1, 0, 0)
 
 
 def _problem(prec, box, kind):
@@ -129,7 +133,7 @@ def _free(*bufs):
 @pytest.mark.parametrize("box", BOXES, ids=BOX_IDS)
 @pytest.mark.parametrize("kind", list(SWEEPS))
 def test_checked_launch_bookkeeping_against_wide_oracle(kind, box, prec):
-    """For every landing -- no sweep, or sweep 1, 2, 3 of the launch first below eps -- and every forced form: the sums of all sweeps, hist
+    """For every landing -- no sweep, or sweep 1, 2, 3, 4 of the launch first below eps -- and every forced form: the sums of all sweeps, hist
     of every sweep up to the converged one (later entries keep their sentinel: the bookkeeping stops there), flag and conv_itr = the first
     converged sweep, the field after ALL sweeps of the launch bit for bit, the input untouched."""
     h = _hip(prec)
@@ -176,7 +180,9 @@ def test_checked_launch_bookkeeping_against_wide_oracle(kind, box, prec):
         _reset_forms(h)
         db.free()
     fused = kind not in ("jacobi", "rbsor")
-    if not (fused and box[1] is not None):  # (the fused passes leave an index range that includes the faces to the single sweeps)
+    if kind == "jacobi4" and prec == "f64":  # (jac4_k is built for FP32 only: the launcher declines every form)
+        assert launched == 0
+    elif not (fused and box[1] is not None):  # (the fused passes leave an index range that includes the faces to the single sweeps)
         assert launched == len(FORMS[kind]) * (n + 1)
 
 
@@ -214,6 +220,8 @@ def test_launch_after_convergence_changes_nothing(kind, box, prec):
                 try:
                     ck = dict(st, hist=None, skip=skip, res_normal=rn, eps=1e30, itr=ITR)
                     ok = _launch(h, kind, dp, dw, db, sz, idx, cf, ck)
+                    if kind == "jacobi4" and prec == "f64":  # (FP32 only: declined, so nothing may be written -- the branch below)
+                        assert not ok, form
                     assert (st["hist"].get() == HSENT).all() and int(st["flag"].get()[0]) == 0, (form, skip_set)
                     assert int(st["conv"].get()[0]) == CSENT and int(skip.get()[0]) == skip_set, (form, skip_set)
                     if skip_set or not ok:
