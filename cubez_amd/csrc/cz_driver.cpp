@@ -70,6 +70,7 @@ CZ::~CZ() {
   if (comm_cus > 0) reserve_comm_cus(0);  // the library context outlives this object
   REAL_TYPE* arrs[] = {WRK, WRK2, P, RHS, pcg_p, pcg_p_, pcg_r, pcg_r0, pcg_q, pcg_s, pcg_s_, pcg_t_, cg_r, cg_z, cg_p[0], cg_p[1], cg_q, pvt, MSK};
   if (mg) czhip_mg_destroy(mg);
+  mg = nullptr;  // (coef_clear below detaches the coefficients from a hierarchy that is still there)
   if (mgd) mgd_destroy(mgd);
   if (d_xc) (void)hipFree(d_xc);
   if (d_yc) (void)hipFree(d_yc);
@@ -217,6 +218,7 @@ int CZ::Setup(int argc, char** argv) {
   bc = CzBc();
   closed_box = 0;
   coef_clear();  // (and with unit coefficients: cz_set_face_coef comes after cz_setup)
+  coef_mg = 0;   // (and without the coefficient hierarchy: cz_set_coef_mg comes after cz_setup)
   closed_m[0] = closed_m[1] = closed_m[2] = 0.0;
   closed_m0_on_device = false;
   solve_plan = PassPlan();
@@ -1410,6 +1412,8 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
   // face coefficients: A_beta where the operator is applied (the start and the SpMV, which stays unfused), and the
   // preconditioner z = s M^-1 (s r) with M^-1 the constant-coefficient one below (cg_q is free for s r at that point)
   const bool coef = coef_on();
+  // the coefficients inside the hierarchy (cz_set_coef_mg): z = M_beta^-1 r, no scaling either side
+  const bool scale = coef && !coef_mg_on();
   const bool fuse_dir = fuse && numProc == 1 && !bc.any() && !coef;
   REAL_TYPE* const sc = reinterpret_cast<REAL_TYPE*>(d_res + 12);  // alpha, -alpha, beta, rho (cg_scal_k)
   double* const d_rr = d_res + 5;
@@ -1459,8 +1463,8 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
     }
     if (pc) {
       if (!Comm_S(cg_r)) return 0;  // (a decomposed pass reads the right-hand side in its ghost layer)
-      REAL_TYPE* const rin = coef ? cg_q : cg_r;  // what M^-1 is applied to
-      if (coef) {
+      REAL_TYPE* const rin = scale ? cg_q : cg_r;  // what M^-1 is applied to
+      if (scale) {
         coef_scale_async(cg_q, cg_r, coef_s, size, gc);
         flop += n;
       }
@@ -1486,7 +1490,7 @@ int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
         Preconditioner(cg_z, rin, fc, LS_JACOBI);
         flop += fc;
       }
-      if (coef) {
+      if (scale) {
         coef_scale_async(cg_z, cg_z, coef_s, size, gc);
         flop += n;
       }
@@ -1603,11 +1607,13 @@ static int bc_refuse(const char* who, const char* why) {
 // right-hand side here, inside the one synchronisation
 int CZ::set_bc(CzBc next, int closed, bool project, const char* who) {
   if (const char* why = unsolvable(next, closed)) return bc_refuse(who, why);
-  if (mg) mg_set_bc(mg, next);
-  if (mgd) mgd_set_bc(mgd, next);
   // face coefficients: the alias faces and the scaling follow the periodic directions; a face that was ignored and is read now may be bad
+  // (before the hierarchy takes the state: where it holds the coefficients, cz_set_coef_mg, it rebuilds from the new alias faces)
   if (coef_on() && next.per != coef_per && !coef_prepare(next.per))
     fprintf(stderr, "%s: a face coefficient that the new state reads is not finite and positive: the handle is left without coefficients\n", who);
+  if (mg) mg_set_bc(mg, next);
+  if (mgd) mgd_set_bc(mgd, next);
+  const bool coef_mg_ok = coef_mg_settle(who, true);
   bc = next;
   closed_box = closed;
   // the work vectors whose face layers carried the wraps and mirrors of the state before: zeros again, as the unmasked passes read them
@@ -1617,7 +1623,40 @@ int CZ::set_bc(CzBc next, int closed, bool project, const char* who) {
   mirror(P);
   wrk_shell_tag = 0;
   czhip_sync();
-  return 1;
+  return coef_mg_ok ? 1 : 0;  // (0: the state is taken, the coefficient hierarchy is not -- its line is printed)
+}
+
+// The coefficient hierarchy (cz_set_coef_mg) after a call of `who` made or changed the state it is built under: attached to
+// the hierarchy while the flag is on, coefficients are in force and the preconditioner is mg or mgrb on one domain, detached otherwise.
+// rebuilt: the hierarchy has just rebuilt what it held (mg_set_bc).  false: a coarse weight or diagonal is not finite and positive -- one
+// line, the flag off, the scaled preconditioner from now on
+bool CZ::coef_mg_settle(const char* who, bool rebuilt) {
+  if (!mg) return true;
+  const bool want = coef_mg && coef_on();
+  bool ok = true;
+  if (mg->coef_bad) ok = false, mg->coef_bad = 0;  // (mg_set_bc's rebuild: the hierarchy is the constant one already)
+  else if (want && !(mg->coef && rebuilt)) ok = czhip_mg_set_coef(mg, coef_b[0], coef_b[1], coef_b[2]) == 1;
+  else if (!want && mg->coef) czhip_mg_set_coef(mg, nullptr, nullptr, nullptr);
+  if (!ok) {
+    fprintf(stderr, "%s: a coarse weight of the coefficient hierarchy is not finite and positive: cz_set_coef_mg is off, the scaled preconditioner runs\n", who);
+    coef_mg = 0;
+  }
+  return ok;
+}
+
+int CZ::SetCoefMg(int on) {
+  const char* const who = "cz_set_coef_mg";
+  auto refuse = [&](const char* why) {
+    fprintf(stderr, "%s: %s\n", who, why);
+    return 0;
+  };
+  if (!set_up) return refuse("no problem is set up (cz_setup first)");
+  if (SW_maf) return refuse("the handle's operator is a MAF one, not the unit-coefficient operator");
+  if (numProc > 1) return refuse("a decomposed run: the face coefficients themselves are refused there (single domain only)");
+  coef_mg = on ? 1 : 0;
+  const bool ok = coef_mg_settle(who, false);
+  czhip_sync();
+  return ok ? 1 : 0;
 }
 
 int CZ::SetPeriodic(const int* dirs) {
@@ -1922,6 +1961,7 @@ int CZ::ProjectIO(int op, REAL_TYPE* const* vel, const long long* stride, int on
 // bad value leaves the handle without coefficients.
 void CZ::coef_clear() {
   if (!coef_on() && !coef_b[0]) return;
+  if (mg) czhip_mg_set_coef(mg, nullptr, nullptr, nullptr);  // (a hierarchy that reads the arrays, cz_set_coef_mg: the constant one again)
   HIP_CHECK(hipStreamSynchronize(stream()));
   for (REAL_TYPE*& a : coef_b) {
     if (a) czhip_free(a);
@@ -2004,8 +2044,9 @@ int CZ::SetFaceCoef(REAL_TYPE* const* b, const long long* stride, int on_device,
   // the work vectors whose shells the fused passes read as zeros (the unfused direction leaves mirrors and wraps there): as set_bc
   for (REAL_TYPE* a : {cg_z, cg_p[0], cg_p[1]})
     if (a) HIP_CHECK(hipMemsetAsync(a, 0, padded_cells() * sizeof(REAL_TYPE), st));
+  const bool coef_mg_ok = coef_mg_settle(who, false);  // (cz_set_coef_mg: the hierarchy is built from the new values)
   czhip_sync();
-  return 1;
+  return coef_mg_ok ? 1 : 0;
 }
 
 // profiling.txt (cz_Evaluate.cpp:506-545).  The reference prints PMlib's "Basic Report" (PMlib 6.4.x is a third-party
@@ -2254,6 +2295,7 @@ int cz_set_face_coef(cz_handle* h, const CZ_REAL* bx, const CZ_REAL* by, const C
   CZ_REAL* const b[3] = {const_cast<CZ_REAL*>(bx), const_cast<CZ_REAL*>(by), const_cast<CZ_REAL*>(bz)};
   return h ? h->cz.SetFaceCoef(b, stride, on_device, ready_stream) : 0;
 }
+int cz_set_coef_mg(cz_handle* h, int on) { return h ? h->cz.SetCoefMg(on) : 0; }
 int cz_set_neumann(cz_handle* h, const int* faces) { return h ? h->cz.SetNeumann(faces) : 0; }
 int cz_set_closed_box(cz_handle* h, int on) { return h ? h->cz.SetClosedBox(on) : 0; }
 int cz_set_periodic(cz_handle* h, const int* dirs) {
@@ -2316,6 +2358,7 @@ int cz_info(const cz_handle* h, int what) {
     case 24: return c.pcg_void_start;
     case 25: return c.coef_on() ? 1 : 0;
     case 26: return c.jac4_passes;
+    case 27: return c.coef_mg_on() ? 1 : 0;
     default: return -1;
   }
 }

@@ -96,6 +96,12 @@ class CZ {
   bool coef_prepare(int per);    // the alias faces for `per`, s, and the check (one host wait); false: a bad value, the arrays are freed
   void coef_clear();             // frees the four arrays (after the compute stream has drained)
   int SetFaceCoef(REAL_TYPE* const* b, const long long* stride, int on_device, void* user_stream);  // cz_set_face_coef: 1 / 0
+  // the coefficients inside the multigrid hierarchy (cz_set_coef_mg, cz_info 27): the flag as asked for; in force while the
+  // hierarchy holds the coefficients (coef_mg_settle keeps that in step with the flag, the coefficients and the preconditioner)
+  int coef_mg = 0;
+  bool coef_mg_on() const { return mg && mg->coef; }
+  bool coef_mg_settle(const char* who, bool rebuilt);
+  int SetCoefMg(int on);         // cz_set_coef_mg: 1 / 0
   int closed_box = 0;            // the closed box (cz_set_closed_box, cz_info 22): mask 63 and the three projections of pcg
   double closed_m[3] = {0, 0, 0};  // the means last removed: right-hand side, initial residual, answer (cz_closed_mean)
   bool closed_m0_on_device = false;  // closed_m[0] is still sc[7] of d_res (cz_set_rhs does not wait for it; ClosedMean fetches)

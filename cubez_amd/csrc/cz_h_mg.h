@@ -284,6 +284,100 @@ cz_mg* czhip_mg_create_rb(const int* sz, const int* idx, int g, const CZ_REAL* c
 int czhip_mg_levels(const cz_mg* h) { return h ? h->nlev : 0; }
 }  // extern "C"
 
+// ---- face coefficients inside the hierarchy (cz_k_mgc.h): the launches and the build.  The kernels run under the labels of
+// their twins in the constant cycle (level 0: jacobi, rbsor)
+namespace {
+MgcW mgc_w(const cz_mg* h, int l) { return MgcW{h->cw[0][l], h->cw[1][l], h->cw[2][l], h->cd[l]}; }
+MgLev mgc_lev(const cz_mg* h, int l) {
+  MgDLev D;
+  if (!mg_lev(D, h->lev[l])) cz_fatal(1, "czhip: coefficient V-cycle: level %d has no description\n", l);
+  return D.L;
+}
+// level 0's row kernels: a streaming grid of about 2048 workgroups (8 per CU), strided over the planes and the vectors of a plane's rows
+dim3 mgc0_grid(const MgLev& L, int slots) {
+  const unsigned gy = (unsigned)std::min(L.nj, 2048);
+  const long long per_plane = ((long long)L.ni * slots + 255) / 256;
+  return dim3((unsigned)std::max<long long>(1, std::min<long long>(per_plane, 2048 / gy)), gy);
+}
+void mgc_smooth_launch(cz_mg* h, int l, const REAL* u, REAL* w, const REAL* b, REAL omg) {
+  ScopedTimer tm(l ? LBL_MG_SMOOTH : LBL_JACOBI);
+  const MgLev L = mgc_lev(h, l);
+  const int slots = (L.nk + 2 * VW - 2) / VW;
+  if (l == 0 && (long long)L.ni * slots < 0x7ff00000LL) {
+    if (u) hipLaunchKernelGGL((mgc0_smooth_k<VW, false>), mgc0_grid(L, slots), dim3(256), 0, ctx.stream, u, w, b, L, mgc_w(h, l), omg, slots);
+    else hipLaunchKernelGGL((mgc0_smooth_k<VW, true>), mgc0_grid(L, slots), dim3(256), 0, ctx.stream, w, w, b, L, mgc_w(h, l), omg, slots);
+  } else if (u) hipLaunchKernelGGL(mgc_smooth_k<false>, mg_grid(L), dim3(64, 4), 0, ctx.stream, u, w, b, L, mgc_w(h, l), omg);
+  else hipLaunchKernelGGL(mgc_smooth_k<true>, mg_grid(L), dim3(64, 4), 0, ctx.stream, w, w, b, L, mgc_w(h, l), omg);
+  HIP_CHECK(hipGetLastError());
+}
+void mgc_rb_launch(cz_mg* h, int l, REAL* x, const REAL* b, REAL omg, int colour, int zero) {
+  ScopedTimer tm(l ? LBL_MG_RB : LBL_RBSOR);
+  const MgLev L = mgc_lev(h, l);
+  const dim3 grid((unsigned)(((L.nk + 1) / 2 + 63) / 64), (unsigned)((L.ni + 3) / 4), (unsigned)L.nj);
+  const int slots = (L.nk + 2 * VW - 2) / VW;
+  if (l == 0 && (long long)L.ni * slots < 0x7ff00000LL) {
+    const dim3 g0 = mgc0_grid(L, slots);
+    if (zero == 0) hipLaunchKernelGGL((mgc0_rb_k<VW, 0>), g0, dim3(256), 0, ctx.stream, x, b, L, mgc_w(h, l), omg, colour, slots);
+    else if (zero == 1) hipLaunchKernelGGL((mgc0_rb_k<VW, 1>), g0, dim3(256), 0, ctx.stream, x, b, L, mgc_w(h, l), omg, colour, slots);
+    else hipLaunchKernelGGL((mgc0_rb_k<VW, 2>), g0, dim3(256), 0, ctx.stream, x, b, L, mgc_w(h, l), omg, colour, slots);
+  } else if (zero == 0) hipLaunchKernelGGL(mgc_rb_k<0>, grid, dim3(64, 4), 0, ctx.stream, x, b, L, mgc_w(h, l), omg, colour);
+  else if (zero == 1) hipLaunchKernelGGL(mgc_rb_k<1>, grid, dim3(64, 4), 0, ctx.stream, x, b, L, mgc_w(h, l), omg, colour);
+  else hipLaunchKernelGGL(mgc_rb_k<2>, grid, dim3(64, 4), 0, ctx.stream, x, b, L, mgc_w(h, l), omg, colour);
+  HIP_CHECK(hipGetLastError());
+}
+void mgc_restrict_launch(cz_mg* h, int l, REAL* bc, const REAL* x, const REAL* b) {
+  ScopedTimer tm(LBL_MG_RESTRICT);
+  const MgLev F = mgc_lev(h, l), C = mgc_lev(h, l + 1);
+  hipLaunchKernelGGL(mgc_restrict_k, mg_grid(C), dim3(64, 4), 0, ctx.stream, bc, x, b, F, C, mgc_w(h, l));
+  HIP_CHECK(hipGetLastError());
+}
+template <bool RB, bool PER>
+void mgc_tail_launch(REAL* x, const REAL* b, const MgTail& T, const MgcTail& W) {
+  ScopedTimer tm(LBL_MG_TAIL);
+  const int bytes = T.total * (int)sizeof(REAL);
+  if (bytes > 64 * 1024) allow_dynamic_lds(&mgc_tail_k<RB, PER>, 160 * 1024);
+  hipLaunchKernelGGL((mgc_tail_k<RB, PER>), dim3(1), dim3(MG_TAIL_THREADS), bytes, ctx.stream, x, b, T, W);
+  HIP_CHECK(hipGetLastError());
+}
+
+void mgc_free(cz_mg* h) {
+  for (int l = 0; l < MG_MAXLEV; l++) {
+    for (int d = 0; d < 3; d++) {
+      if (l && h->cw[d][l]) czhip_free(const_cast<REAL*>(h->cw[d][l]));
+      h->cw[d][l] = nullptr;
+    }
+    if (h->cd[l]) czhip_free(h->cd[l]);
+    h->cd[l] = nullptr;
+  }
+  if (h->cbad) (void)hipFree(h->cbad);
+  h->cbad = nullptr;
+  h->coef = h->coef_bad = 0;
+}
+
+// every level's weights and diagonal under the hierarchy's boundary state, from level 0's weights; one host wait for the count.  false: some
+// coarse weight or diagonal is not finite and positive (h->coef_bad)
+bool mgc_build(cz_mg* h) {
+  HIP_CHECK(hipMemsetAsync(h->cbad, 0, sizeof(unsigned), ctx.stream));
+  for (int l = 0; l < h->nlev; l++) {
+    const MgLev L = mgc_lev(h, l);
+    if (l) {
+      const MgLev F = mgc_lev(h, l - 1);
+      const dim3 grid((unsigned)((L.nk + 1 + 63) / 64), (unsigned)((L.ni + 1 + 3) / 4), (unsigned)(L.nj + 1));
+      hipLaunchKernelGGL(mgc_coarsen_k, grid, dim3(64, 4), 0, ctx.stream, const_cast<REAL*>(h->cw[0][l]), const_cast<REAL*>(h->cw[1][l]),
+                         const_cast<REAL*>(h->cw[2][l]), h->cw[0][l - 1], h->cw[1][l - 1], h->cw[2][l - 1], F, L, h->cbad);
+      HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(mgc_diag_k, mg_grid(L), dim3(64, 4), 0, ctx.stream, h->cd[l], h->cw[0][l], h->cw[1][l], h->cw[2][l], L, l ? h->cbad : nullptr);
+    HIP_CHECK(hipGetLastError());
+  }
+  unsigned bad = 0u;
+  HIP_CHECK(hipMemcpyAsync(&bad, h->cbad, sizeof(unsigned), hipMemcpyDeviceToHost, ctx.stream));
+  HIP_CHECK(hipStreamSynchronize(ctx.stream));
+  h->coef_bad = bad != 0u;
+  return bad == 0u;
+}
+}  // namespace
+
 namespace czhip_internal {
 // every level's word from the state (mg_level_bc; without a periodic direction: the Neumann flags at every level, as before there were
 // any).  The arrays whose ghost layers carried the mirrors or wraps of an earlier state are zeros again, as the unmasked passes read them
@@ -299,6 +393,10 @@ void mg_set_bc(cz_mg* h, CzBc bc) {
   for (int l = std::max(h->first, 1); wraps && l < h->nlev; l++)  // (levels >= 1 have ghost layers other than zero only under a wrap)
     for (REAL* a : {h->x[l], h->t[l]})
       if (a) HIP_CHECK(hipMemsetAsync(a, 0, (size_t)(h->lev[l].sz[0] + 4) * (h->lev[l].sz[1] + 4) * (h->lev[l].sz[2] + 4) * sizeof(REAL), ctx.stream));
+  if (h->coef && !mgc_build(h)) {  // (the zeroed faces follow the state.  A bad coarse value: the constant hierarchy again, and the
+    mgc_free(h);                   // verdict waits in h->coef_bad for whoever set the coefficients)
+    h->coef_bad = 1;
+  }
 }
 }  // namespace czhip_internal
 
@@ -322,9 +420,37 @@ int czhip_mg_set_periodic(cz_mg* h, const int* dirs) {
 }
 int czhip_mg_kind(const cz_mg* h) { return h ? 1 + h->rb : 0; }
 
+// face coefficients inside the hierarchy: bx, by, bz are level 0's face weights, device arrays in the layout of the
+// level-0 arrays that stay the caller's; all three NULL: the constant hierarchy again.  1, or 0: refused (a NULL handle, some but not all
+// three, a hierarchy without level 0), or a coarse weight or diagonal that is not finite and positive -- the constant hierarchy again
+int czhip_mg_set_coef(cz_mg* h, const CZ_REAL* bx, const CZ_REAL* by, const CZ_REAL* bz) {
+  ensure_init();
+  const int given = (bx != nullptr) + (by != nullptr) + (bz != nullptr);
+  if (!h || (given != 0 && given != 3) || h->first != 0) return 0;
+  if (given == 0) {
+    if (h->coef || h->cd[0]) {
+      czhip_sync();
+      mgc_free(h);
+    }
+    return 1;
+  }
+  h->cw[0][0] = bx, h->cw[1][0] = by, h->cw[2][0] = bz;
+  if (!h->cbad) HIP_CHECK(hipMalloc(&h->cbad, sizeof(unsigned)));
+  for (int l = 0; l < h->nlev; l++) {
+    if (!h->cd[l]) h->cd[l] = czhip_alloc_s3d(h->lev[l].sz);
+    for (int d = 0; l && d < 3; d++)
+      if (!h->cw[d][l]) h->cw[d][l] = czhip_alloc_s3d(h->lev[l].sz);
+  }
+  h->coef = 1;
+  if (mgc_build(h)) return 1;
+  mgc_free(h);
+  return 0;
+}
+
 void czhip_mg_destroy(cz_mg* h) {
   if (!h) return;
   czhip_sync();
+  mgc_free(h);
   for (int l = 0; l < MG_MAXLEV; l++)
     for (REAL* a : {h->b[l], h->x[l], h->t[l]})
       if (a) czhip_free(a);
@@ -474,6 +600,69 @@ struct MgOps {
     if (l == 0) std::swap(x0, o0);
   }
 };
+
+// the operations of mg_walk with the face coefficients inside the hierarchy: the same order, fills and from-zero forms at
+// every level, the kernels of cz_k_mgc.h.  Level 0 is a level like the others -- its right-hand side is r, its iterate x0 = z, its temporary
+// o0 -- so the iterate never changes array: mg's sweeps go through the temporary and come back, mgrb's colour sweeps and the prolongation
+// run in place (no fused pass exists under coefficients)
+struct MgcOps {
+  cz_mg* h;
+  REAL omg;
+  const REAL* r;
+  REAL *x0, *o0;
+
+  REAL* x(int l) { return l ? h->x[l] : x0; }
+  REAL* t(int l) { return l ? h->t[l] : o0; }
+  const REAL* b(int l) { return l ? h->b[l] : r; }
+  // what the constant cycle does to an array of the level before a kernel reads its neighbours: level 0 the mirrors and wraps, levels >= 1 the wraps
+  bool fills(int l) const { return l ? mg_wraps(h, l) : h->lev[0].nm != 0; }
+  void fill(int l, REAL* a) {
+    if (l) mg_wrap(h, l, a);
+    else if (h->lev[0].nm) mg_mirror(h, a);
+  }
+  bool whole(int l) {
+    if (l < h->tail_from) return false;
+    MgTail T;
+    MgcTail W;
+    mg_tail_plan(T, mgc_lev(h, l), omg, h->rb, h->lev[l].nm);
+    int any = 0;
+    for (int m = 0; m < T.nlev; m++) any |= T.s[m].nm, W.g[m] = mgc_lev(h, l + m), W.w[m] = mgc_w(h, l + m);
+    for (int m = T.nlev; m < MG_TAIL_MAXLEV; m++) W.g[m] = MgLev(), W.w[m] = MgcW{nullptr, nullptr, nullptr, nullptr};
+    if (any >> 6) h->rb ? mgc_tail_launch<true, true>(h->x[l], h->b[l], T, W) : mgc_tail_launch<false, true>(h->x[l], h->b[l], T, W);
+    else h->rb ? mgc_tail_launch<true, false>(h->x[l], h->b[l], T, W) : mgc_tail_launch<false, false>(h->x[l], h->b[l], T, W);
+    return true;
+  }
+  void pair(int l, bool zero, bool post) {
+    if (h->rb) {
+      // (a level that is filled: from zero the array is cleared and swept as an iterate, as MgOps does -- a ghost may hold a value of the
+      // colour being written)
+      const int c0 = post ? 1 : 0;
+      const bool f = fills(l);
+      if (f && zero) {
+        const int* sz = h->lev[l].sz;
+        HIP_CHECK(hipMemsetAsync(x(l), 0, (size_t)(sz[0] + 4) * (sz[1] + 4) * (sz[2] + 4) * sizeof(REAL), ctx.stream));
+      } else if (f) {
+        fill(l, x(l));
+      }
+      for (int s = 0; s < 4; s++) {
+        mgc_rb_launch(h, l, x(l), b(l), omg, (c0 + s) & 1, zero && s < 2 && !f ? s + 1 : 0);
+        fill(l, x(l));
+      }
+      return;
+    }
+    if (!zero) fill(l, x(l));
+    mgc_smooth_launch(h, l, zero ? nullptr : x(l), t(l), b(l), omg);
+    fill(l, t(l));
+    mgc_smooth_launch(h, l, t(l), x(l), b(l), omg);
+  }
+  void restrict_down(int l) {
+    if (!h->rb) fill(l, x(l));  // (mgrb: filled after its last colour sweep)
+    mgc_restrict_launch(h, l, h->b[l + 1], x(l), b(l));
+  }
+  void prolong_up(int l) {
+    if (!czhip_internal::mg_prolong_async(x(l), x(l), h->x[l + 1], h->lev[l + 1], h->lev[l])) cz_fatal(1, "czhip: V-cycle: a level kernel refused its level\n");
+  }
+};
 }  // namespace
 
 namespace czhip_internal {
@@ -489,6 +678,11 @@ extern "C" {
 int czhip_mg_apply_async(cz_mg* h, CZ_REAL* z, const CZ_REAL* r, CZ_REAL omg) {
   ensure_init();
   if (!h || h->first != 0 || !z || !r || z == r || z == h->fine_tmp) return 0;
+  if (h->coef) {  // the coefficient cycle: the iterate stays in z
+    MgcOps ops{h, omg, r, z, h->fine_tmp};
+    mg_walk(ops, 0, h->nlev - 1);
+    return 1;
+  }
   // level 0's iterate changes array with every step: pair, prolongation, pair, or the coarsest level's four pairs (mgrb: a pair moves it
   // once, twice or not at all).  The last step writes z
   MgOps ops{h, omg, r, z, h->fine_tmp};

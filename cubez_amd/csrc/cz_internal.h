@@ -215,6 +215,13 @@ struct cz_mg {
   CzBc bc;                      // the state as set (mg_set_bc): lev[l].nm is level l's word of it.  Level 0 mirrors its Neumann faces, levels >= 1
                                 // take the masked diagonal; a periodic direction wraps at every level
   int zero4 = 0;                // mgrb, level 0: the two iterations from zero as one two-iteration pass over a cleared array (CZ_MGRB_ZERO4)
+  // face coefficients inside the hierarchy (czhip_mg_set_coef): every level's face weights and diagonal.  Level 0's weights
+  // are the caller's arrays, every other array is the hierarchy's own.  coef: the cycles take them; coef_bad: the last build counted a
+  // coarse weight or diagonal that is not finite and positive (mg_set_bc rebuilds and leaves its verdict here)
+  const CZ_REAL *cw[3][MG_MAXLEV] = {};
+  CZ_REAL* cd[MG_MAXLEV] = {};
+  unsigned* cbad = nullptr;
+  int coef = 0, coef_bad = 0;
 };
 
 #endif

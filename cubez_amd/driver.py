@@ -45,6 +45,7 @@ class CZ:
         lib.cz_set_rhs_div.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_double, C.POINTER(C.c_double)]
         lib.cz_sub_grad.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_double]
         lib.cz_set_face_coef.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_longlong), C.c_int, C.c_void_p]
+        lib.cz_set_coef_mg.argtypes = [C.c_void_p, C.c_int]
         lib.cz_set_eps.argtypes = [C.c_void_p, C.c_double]
         lib.cz_set_neumann.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         lib.cz_set_closed_box.argtypes = [C.c_void_p, C.c_int]
@@ -258,6 +259,16 @@ class CZ:
         if self.lib.cz_set_face_coef(self.h, *ptrs, strides, on_dev, stream) != 1:
             raise RuntimeError("set_face_coef: refused (see stderr)")
 
+    def set_coef_mg(self, on=True):
+        """the face coefficients inside the multigrid hierarchy: pcg ... mg | mgrb then preconditions with the V-cycle of the variable operator
+        itself, whose coarse levels carry the summed face coefficients, in place of the constant cycle inside the diagonal scaling -- the
+        preconditioner for large jumps (a density ratio of 1000).  The flag is remembered across set_face_coef and the boundary setters,
+        which rebuild the hierarchy; info()["coef_mg"] is 1 while it is in force (flag on, coefficients set, mg or mgrb); setup clears it.
+        Raises where the library refuses; a coarse weight that overflows is such a refusal, and it turns the flag off while the
+        coefficients stay (cz_set_coef_mg of include/cz_hip.h)"""
+        if self.lib.cz_set_coef_mg(self.h, 1 if on else 0) != 1:
+            raise RuntimeError(f"set_coef_mg({bool(on)}): refused (see stderr)")
+
     @staticmethod
     def _itemsize(a):
         return a.itemsize if isinstance(a, np.ndarray) else a.element_size()
@@ -319,7 +330,7 @@ class CZ:
         """what a (multi-GPU) run decided (cz_info of include/cz_hip.h)"""
         keys = ("ranks", "fused_pass", "shell_slabs", "overlap", "lagged_reduce", "rccl_ranks", "comm_cus", "pass_kind", "exchange_depth", "buffers", "bicg_fused", "rb4_passes",
                 "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother", "field_form", "neumann", "closed", "periodic", "void_start",
-                "face_coef", "jac4_passes")
+                "face_coef", "jac4_passes", "coef_mg")
         return {k: self.lib.cz_info(self.h, i) for i, k in enumerate(keys)}
 
     def config_in_force(self) -> dict:

@@ -84,6 +84,18 @@ class Refined:
             self.lo.set_face_coef(None)
             raise
 
+    def set_coef_mg(self, on=True):
+        """CZ.set_coef_mg on both libraries.  The FP32 inner solver is the one that preconditions: with pcg mg | mgrb the flag is in force
+        there (lo.info()["coef_mg"]); the FP64 handle only forms residuals, so the flag is accepted and idle on it.  Raises where either
+        library refuses: both flags are then off"""
+        try:
+            self.hi.set_coef_mg(on)
+            self.lo.set_coef_mg(on)
+        except Exception:
+            for cz in (self.hi, self.lo):
+                cz.lib.cz_set_coef_mg(cz.h, 0)
+            raise
+
     def solve(self, tol=1e-10, max_outer=20, inner_eps=INNER_EPS) -> int:
         """refine until |b - A p| <= tol |b - A p0|; returns the outer steps taken, 0 where max_outer steps did not reach it.
         history: [(outer step, |r| / |r0| after it, inner iterations of it)].  Collective in a decomposed run.

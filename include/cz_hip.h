@@ -438,6 +438,17 @@ int czhip_mg_set_neumann(cz_mg* h, const int* faces);
  *   that is not physical). */
 int czhip_fill_faces_async(CZ_REAL* p, const int* sz, const int* idx, int g, const int* kinds);
 int czhip_mg_set_periodic(cz_mg* h, const int* dirs);
+/* Face coefficients inside the hierarchy.  bx, by, bz: device arrays in the layout of the hierarchy's level-0 arrays
+ * (padded, guide 2), bx at a cell = the coefficient on the face towards the next cell in X, finite and positive on every face a cell of the
+ * box touches, face 0 of a periodic direction holding the copy of face n - 2 (what cz_set_face_coef keeps).  The arrays stay the caller's
+ * and are read by every cycle from now on: level 0 takes them as its face weights, level l + 1 the sums of the fine weights across each
+ * aggregate face (the exact Galerkin product; a Neumann face and the seam of a one-point periodic level carry a zero), every level a stored
+ * diagonal.  The call allocates about 1 + 4/7 of a fine array, builds under the hierarchy's boundary state (czhip_mg_set_neumann /
+ * czhip_mg_set_periodic rebuild), waits for the count of coarse weights and diagonals that are not finite and positive, and returns 1
+ * where there is none; else 0, and the hierarchy is the constant one again.  All three NULL: the constant hierarchy again, the arrays
+ * freed, 1.  0 with nothing changed: a NULL handle, some but not all pointers NULL.  With unit coefficients the cycle gives the bits of
+ * the constant cycle in every boundary state. */
+int czhip_mg_set_coef(cz_mg* h, const CZ_REAL* bx, const CZ_REAL* by, const CZ_REAL* bz);
 /* The closed box (all six faces zero-flux): the projections onto the zero-mean fields and PCG's update with one folded in.
  * czhip_shift_sums_async: a <- a - *m_dev over the inner box (one REAL subtraction per cell), then sums_dev[0] = sum a', sums_dev[1] = sum a'^2
  *   of the values a holds afterwards (REAL products accumulated in double, as czhip_cg_update_async forms r.r).  m_dev NULL: a is only read,
@@ -564,7 +575,8 @@ int cz_sub_grad(cz_handle*, CZ_REAL* u, CZ_REAL* v, CZ_REAL* w, const long long*
  *     jumps (DESIGN.md 5.19 has the counts); none stays z = r;
  *   cz_get_residual returns r = b - A p of that operator (kernel forms 2 and 3 of cz_info 20: the residual goes through a work array);
  *   cz_sub_grad subtracts (beta_x(i, j, k) (p(i+1) - p(i))) scale from u, likewise v and w, so that div(u - beta grad p) = div u - A p exactly;
- *   cz_set_rhs_div, cz_add_field and cz_precondition are unchanged (the last applies the constant-coefficient M^-1 without the scaling);
+ *   cz_set_rhs_div, cz_add_field and cz_precondition are unchanged (the last applies the constant-coefficient M^-1 without the scaling;
+ *     while cz_set_coef_mg is in force, the coefficient cycle M_beta^-1 that cz_solve applies);
  *   cz_solve, cz_sweeps and cz_evaluate of a solver other than pcg return 0 with one line and leave P alone.
  * All three pointers NULL clears the state (the arrays are freed; the handle then runs the code and gives the bytes of a handle that never
  * had coefficients); cz_setup clears it too.  cz_set_periodic / cz_set_closed_box / cz_set_neumann after this call keep the coefficients:
@@ -577,6 +589,17 @@ int cz_sub_grad(cz_handle*, CZ_REAL* u, CZ_REAL* v, CZ_REAL* w, const long long*
  * some before.  The same holds where a later change of the periodic directions makes the operator read a bad face 1: that setter prints
  * the line, takes the new state and leaves the handle without coefficients (cz_info 25 tells). */
 int cz_set_face_coef(cz_handle*, const CZ_REAL* bx, const CZ_REAL* by, const CZ_REAL* bz, const long long* stride, int on_device, void* ready_stream);
+/* The face coefficients inside the multigrid hierarchy: on = 1 asks that pcg ... mg | mgrb precondition with the V-cycle of
+ * the variable operator itself, z = M_beta^-1 r (czhip_mg_set_coef), in place of the constant cycle inside the diagonal scaling.  The flag
+ * is remembered; it is IN FORCE (cz_info 27) while it is on, face coefficients are in force (cz_info 25) and the set-up preconditioner is mg
+ * or mgrb; with none or jacobi it is accepted and idle.  The hierarchy is built inside whichever call makes or changes that state: this
+ * one, cz_set_face_coef, cz_set_neumann, cz_set_periodic, cz_set_closed_box.  While in force cz_solve applies the cycle without the scaling
+ * and cz_precondition applies the same cycle; everything else of cz_set_face_coef is untouched.  A handle on which the flag was never set,
+ * or is off again, gives the bytes of before in every state.  cz_setup clears the flag.  Returns 1, or 0 with one line on stderr and
+ * nothing changed: before cz_setup, a _maf handle, a decomposed run.  One refusal is NOT "nothing changed": a coarse weight or diagonal
+ * -- a sum of up to 4^l fine ones -- is not finite and positive.  The call that built the hierarchy (any of the five) then prints one
+ * line, returns 0 and turns the flag off; the face coefficients (and that call's own new state) stay, and the scaled preconditioner runs. */
+int cz_set_coef_mg(cz_handle*, int on);
 /* Zero-flux (Neumann) faces for pcg: faces[6], order X-, X+, Y-, Y+, Z-, Z+ of the GLOBAL box (the order of nID), non-zero =
  * the face is a zero-flux face, zero = a Dirichlet face as before; at least one face must stay Dirichlet.  Called after cz_setup; collective,
  * with the same mask on every rank.  On a Neumann face the face layer of the field is not data but the mirror of the first inner layer
@@ -656,7 +679,7 @@ double cz_last_solve_seconds(const cz_handle*);
  * returned 0, P holds the caller's bytes (in the closed box: less its mean), cz_result_iter, cz_result_res and the history are 0 / empty --
  * the start was the answer already, or the problem is scaled below the threshold (1); anything else, a refusal or an error included (0);
  * 25 face coefficients are in force (cz_set_face_coef; 0 | 1); 26 four-sweep Jacobi passes of the last Jacobi solve (czhip_jacobi4_async;
- * 14 counts the three-sweep passes beside them). */
+ * 14 counts the three-sweep passes beside them); 27 the coefficient hierarchy of cz_set_coef_mg is in force (0 | 1). */
 int cz_info(const cz_handle*, int what);
 /* The driver's and its communicator's own copies of their switches, as name=value, one per line: overlap, lag_reduce, comm_cus (as asked for;
  * 0 on a single domain), comm_cus_reserved (in force after set-up), bicg_fuse, bicg_devsc, bicg_alias, cg_fuse, mg_tail, mg_gather, mgrb_zero4,
