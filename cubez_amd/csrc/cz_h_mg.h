@@ -78,53 +78,108 @@ bool mg_tail_plan(MgTail& T, const MgLev& fine, REAL omg, bool rb = false, int b
 // (NM: the level kernels' instantiation for a level with Neumann faces, chosen here from the level's mask -- cz_k_mg.h, mg_weights)
 // (PER: some level of the tail wraps a periodic direction, DESIGN.md §5.15.  A level of one point in such a direction carries mask bits that
 // the finer levels do not, so both flags are taken over every level of the tail; without a periodic direction that is T.gl.nm)
-template <bool RB, bool NM, bool PER>
-void mg_tail_launch(REAL* x, const REAL* b, const MgTail& T) {
+// (the weight arrays keep their zero faces: no mask, so no NM)
+template <bool RB, bool PER, class WT>
+void mg_tail_launch(REAL* x, const REAL* b, const MgTail& T, const WT& W) {
   ScopedTimer tm(LBL_MG_TAIL);
   const int bytes = T.total * (int)sizeof(REAL);
-  if (bytes > 64 * 1024) allow_dynamic_lds(&mg_tail_k<RB, NM, PER>, 160 * 1024);
-  hipLaunchKernelGGL((mg_tail_k<RB, NM, PER>), dim3(1), dim3(MG_TAIL_THREADS), bytes, ctx.stream, x, b, T);
+  if (bytes > 64 * 1024) allow_dynamic_lds(&mg_tail_k<RB, PER, WT>, 160 * 1024);
+  hipLaunchKernelGGL((mg_tail_k<RB, PER, WT>), dim3(1), dim3(MG_TAIL_THREADS), bytes, ctx.stream, x, b, T, W);
   HIP_CHECK(hipGetLastError());
 }
-void mg_tail_launch(REAL* x, const REAL* b, const MgTail& T, bool rb) {
+// W: the weight arrays of the tail's levels; nullptr: the integers
+void mg_tail_launch(REAL* x, const REAL* b, const MgTail& T, bool rb, const MgcTail* W = nullptr) {
   int any = 0;
   for (int m = 0; m < T.nlev; m++) any |= T.s[m].nm;
-  if (any >> 6) {  // (one instantiation per smoother: a mask of zero gives the unmasked bits)
-    rb ? mg_tail_launch<true, true, true>(x, b, T) : mg_tail_launch<false, true, true>(x, b, T);
-  } else if (any & 63) rb ? mg_tail_launch<true, true, false>(x, b, T) : mg_tail_launch<false, true, false>(x, b, T);
-  else rb ? mg_tail_launch<true, false, false>(x, b, T) : mg_tail_launch<false, false, false>(x, b, T);
+  with_flags([&](auto RB, auto PER, auto NM) {  // (PER: one instantiation per smoother, a mask of zero gives the unmasked bits)
+    if (W) mg_tail_launch<RB(), PER()>(x, b, T, *W);
+    else mg_tail_launch<RB(), PER()>(x, b, T, MgConstTail<NM() || PER()>());
+  }, rb, (any >> 6) != 0, (any & 63) != 0);
 }
 
 dim3 mg_grid(const MgLev& L) { return dim3((unsigned)((L.nk + 63) / 64), (unsigned)((L.ni + 3) / 4), (unsigned)L.nj); }
-}  // namespace
+// level 0's row kernels under coefficients: a streaming grid of about 2048 workgroups (8 per CU), strided over the planes and the vectors of
+// a plane's rows; slots: the vectors a row can touch, whatever its phase
+int mgc0_slots(const MgLev& L) { return (L.nk + 2 * VW - 2) / VW; }
+bool mgc0_rows(const MgLev& L) { return L.l == 0 && (long long)L.ni * mgc0_slots(L) < 0x7ff00000LL; }
+dim3 mgc0_grid(const MgLev& L) {
+  const unsigned gy = (unsigned)std::min(L.nj, 2048);
+  const long long per_plane = ((long long)L.ni * mgc0_slots(L) + 255) / 256;
+  return dim3((unsigned)std::max<long long>(1, std::min<long long>(per_plane, 2048 / gy)), gy);
+}
+// f(the weights of a level as the level kernels take them): the arrays cw where given (cw.d), else the integers, masked where the level
+// has Neumann faces (NM: cz_k_mg.h, mg_weights)
+template <class F>
+void with_weights(const MgcW& cw, const MgLev& L, F&& f) {
+  if (cw.d) f(MgArr{cw});
+  else with_flags([&](auto NM) { f(MgConst<NM()>()); }, L.nm != 0);
+}
+// f(std::integral_constant<int, z>) for the from-zero form z = 0, 1, 2 of a colour sweep
+template <class F>
+void with_zero_form(int z, F&& f) {
+  if (z == 0) f(std::integral_constant<int, 0>());
+  else if (z == 1) f(std::integral_constant<int, 1>());
+  else f(std::integral_constant<int, 2>());
+}
 
-// ---- the launches of the level kernels: 0 = refused (nothing launched)
-namespace czhip_internal {
-int mg_smooth_async(const REAL* u, REAL* w, const REAL* b, const MgdLevel& M, REAL omg) {
+// ---- the launches of the level kernels: 0 = refused (nothing launched).  cw: the level's weight arrays; cw.d == nullptr:
+// the integers.  Under the arrays level 0 is a level like the others, swept by its row kernels (cz_k_mgc.h) under the labels of the constant
+// cycle's level 0 (jacobi, rbsor)
+int mg_smooth_launch(const REAL* u, REAL* w, const REAL* b, const MgdLevel& M, REAL omg, const MgcW& cw) {
   MgDLev D;
   if (!w || !b || u == w || !mg_lev(D, M) || M.dense) return 0;
   if (mg_none(D)) return 1;
-  ScopedTimer tm(LBL_MG_SMOOTH);
-  with_flags([&](auto ZERO, auto NM) { hipLaunchKernelGGL((mg_smooth_k<ZERO(), NM()>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, u ? u : w, w, b, D, omg); },
-             !u, D.L.nm != 0);
+  ScopedTimer tm(cw.d && M.level == 0 ? LBL_JACOBI : LBL_MG_SMOOTH);
+  with_flags([&](auto ZERO) {
+    if (cw.d && mgc0_rows(D.L))
+      hipLaunchKernelGGL((mgc0_smooth_k<VW, ZERO()>), mgc0_grid(D.L), dim3(256), 0, ctx.stream, u ? u : w, w, b, D.L, cw, omg, mgc0_slots(D.L));
+    else
+      with_weights(cw, D.L, [&](auto W) {
+        hipLaunchKernelGGL((mg_smooth_k<ZERO(), decltype(W)>), mg_grid(D.L), dim3(64, 4), 0, ctx.stream, u ? u : w, w, b, D, omg, W);
+      });
+  }, !u);
   HIP_CHECK(hipGetLastError());
   return 1;
 }
 
-// (a whole level only: the colour is that of the global index, and a cut would need an exchange per colour)
-int mg_rb_async(REAL* x, const REAL* b, const MgdLevel& M, REAL omg, int colour, int zero) {
+// (a whole level only: the colour is that of the global index, and a cut would need an exchange per colour.  Level 0: under the arrays only)
+int mg_rb_launch(REAL* x, const REAL* b, const MgdLevel& M, REAL omg, int colour, int zero, const MgcW& cw) {
   MgDLev D;
-  if (!x || !b || x == b || !mg_lev(D, M) || M.dense || !mg_whole(D) || M.level < 1 || (colour | 1) != 1 || zero < 0 || zero > 2) return 0;
+  if (!x || !b || x == b || !mg_lev(D, M) || M.dense || !mg_whole(D) || (M.level < 1 && !cw.d) || (colour | 1) != 1 || zero < 0 || zero > 2) return 0;
   if (mg_none(D)) return 1;
-  ScopedTimer tm(LBL_MG_RB);
+  ScopedTimer tm(cw.d && M.level == 0 ? LBL_RBSOR : LBL_MG_RB);
   const dim3 grid((unsigned)(((D.L.nk + 1) / 2 + 63) / 64), (unsigned)((D.L.ni + 3) / 4), (unsigned)D.L.nj);
-  with_flags([&](auto NM) {
-    if (zero == 0) hipLaunchKernelGGL((mg_rb_k<0, NM()>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
-    else if (zero == 1) hipLaunchKernelGGL((mg_rb_k<1, NM()>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
-    else hipLaunchKernelGGL((mg_rb_k<2, NM()>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour);
-  }, D.L.nm != 0);
+  with_zero_form(zero, [&](auto Z) {
+    if (cw.d && mgc0_rows(D.L))
+      hipLaunchKernelGGL((mgc0_rb_k<VW, Z()>), mgc0_grid(D.L), dim3(256), 0, ctx.stream, x, b, D.L, cw, omg, colour, mgc0_slots(D.L));
+    else
+      with_weights(cw, D.L, [&](auto W) { hipLaunchKernelGGL((mg_rb_k<Z(), decltype(W)>), grid, dim3(64, 4), 0, ctx.stream, x, b, D.L, omg, colour, W); });
+  });
   HIP_CHECK(hipGetLastError());
   return 1;
+}
+
+// rt = nullptr: every child is a point of F's own array, which then is the whole level (the weight arrays: that case only)
+int mg_restrict_launch(REAL* bc, const MgdLevel& MC, const REAL* x, const REAL* b, const REAL* rt, const MgdLevel& MF, const MgcW& cw) {
+  MgDLev F, C;
+  if (!bc || !x || !b || bc == x || bc == b || !mg_lev(F, MF) || !mg_lev(C, MC) || MF.dense || !mg_coarse_of(MF, MC) || (!rt && !(mg_whole(F) && mg_whole(C))) || (rt && cw.d)) return 0;
+  if (mg_none(C)) return 1;
+  ScopedTimer tm(LBL_MG_RESTRICT);
+  // (the children's residual takes the FINE level's weights: its mask)
+  if (cw.d) hipLaunchKernelGGL(mgc_restrict_k, mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, F.L, C.L, cw);  // (its own frame: cz_k_mgc.h)
+  else
+    with_flags([&](auto RT, auto NM) { hipLaunchKernelGGL((mg_restrict_k<RT(), MgConst<NM()>>), mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C, MgConst<NM()>()); },
+               rt != nullptr, F.L.nm != 0);
+  HIP_CHECK(hipGetLastError());
+  return 1;
+}
+}  // namespace
+
+namespace czhip_internal {
+int mg_smooth_async(const REAL* u, REAL* w, const REAL* b, const MgdLevel& M, REAL omg) { return mg_smooth_launch(u, w, b, M, omg, MgcW()); }
+int mg_rb_async(REAL* x, const REAL* b, const MgdLevel& M, REAL omg, int colour, int zero) { return mg_rb_launch(x, b, M, omg, colour, zero, MgcW()); }
+int mg_restrict_async(REAL* bc, const MgdLevel& MC, const REAL* x, const REAL* b, const REAL* rt, const MgdLevel& MF) {
+  return mg_restrict_launch(bc, MC, x, b, rt, MF, MgcW());
 }
 
 int mgd_resface_async(REAL* rt, const REAL* x, const REAL* b, const MgdLevel& M, const int* minus) {
@@ -139,19 +194,6 @@ int mgd_resface_async(REAL* rt, const REAL* x, const REAL* b, const MgdLevel& M,
     with_flags([&](auto NM) { hipLaunchKernelGGL(mgd_resface_k<NM()>, grid, dim3(64), 0, ctx.stream, rt, x, b, D, d, minus[0], minus[1]); }, D.L.nm != 0);
     HIP_CHECK(hipGetLastError());
   }
-  return 1;
-}
-
-// rt = nullptr: every child is a point of F's own array, which then is the whole level
-int mg_restrict_async(REAL* bc, const MgdLevel& MC, const REAL* x, const REAL* b, const REAL* rt, const MgdLevel& MF) {
-  MgDLev F, C;
-  if (!bc || !x || !b || bc == x || bc == b || !mg_lev(F, MF) || !mg_lev(C, MC) || MF.dense || !mg_coarse_of(MF, MC) || (!rt && !(mg_whole(F) && mg_whole(C)))) return 0;
-  if (mg_none(C)) return 1;
-  ScopedTimer tm(LBL_MG_RESTRICT);
-  // (the children's residual takes the FINE level's weights: its mask)
-  with_flags([&](auto RT, auto NM) { hipLaunchKernelGGL((mg_restrict_k<RT(), NM()>), mg_grid(C.L), dim3(64, 4), 0, ctx.stream, bc, x, b, rt, F, C); },
-             rt != nullptr, F.L.nm != 0);
-  HIP_CHECK(hipGetLastError());
   return 1;
 }
 
@@ -261,8 +303,6 @@ cz_mg* mg_create(const int* n0, int l0, bool tail, const int* sz0, const int* id
 }
 }  // namespace czhip_internal
 
-extern "C" {
-}  // extern "C"
 namespace {
 cz_mg* mg_create_public(const int* sz, const int* idx, int g, const CZ_REAL* cf, bool rb) {
   ensure_init();
@@ -284,62 +324,15 @@ cz_mg* czhip_mg_create_rb(const int* sz, const int* idx, int g, const CZ_REAL* c
 int czhip_mg_levels(const cz_mg* h) { return h ? h->nlev : 0; }
 }  // extern "C"
 
-// ---- face coefficients inside the hierarchy (cz_k_mgc.h): the launches and the build.  The kernels run under the labels of
-// their twins in the constant cycle (level 0: jacobi, rbsor)
+// ---- face coefficients inside the hierarchy (cz_k_mgc.h): the weights of a level for the launches above, and the build
 namespace {
-MgcW mgc_w(const cz_mg* h, int l) { return MgcW{h->cw[0][l], h->cw[1][l], h->cw[2][l], h->cd[l]}; }
+// (the constant hierarchy: no arrays -- the launches take the integers)
+MgcW mgc_w(const cz_mg* h, int l) { return h->coef ? MgcW{h->cw[0][l], h->cw[1][l], h->cw[2][l], h->cd[l]} : MgcW(); }
 MgLev mgc_lev(const cz_mg* h, int l) {
   MgDLev D;
-  if (!mg_lev(D, h->lev[l])) cz_fatal(1, "czhip: coefficient V-cycle: level %d has no description\n", l);
+  if (!mg_lev(D, h->lev[l])) cz_fatal(1, "czhip: V-cycle: level %d has no description\n", l);
   return D.L;
 }
-// level 0's row kernels: a streaming grid of about 2048 workgroups (8 per CU), strided over the planes and the vectors of a plane's rows
-dim3 mgc0_grid(const MgLev& L, int slots) {
-  const unsigned gy = (unsigned)std::min(L.nj, 2048);
-  const long long per_plane = ((long long)L.ni * slots + 255) / 256;
-  return dim3((unsigned)std::max<long long>(1, std::min<long long>(per_plane, 2048 / gy)), gy);
-}
-void mgc_smooth_launch(cz_mg* h, int l, const REAL* u, REAL* w, const REAL* b, REAL omg) {
-  ScopedTimer tm(l ? LBL_MG_SMOOTH : LBL_JACOBI);
-  const MgLev L = mgc_lev(h, l);
-  const int slots = (L.nk + 2 * VW - 2) / VW;
-  if (l == 0 && (long long)L.ni * slots < 0x7ff00000LL) {
-    if (u) hipLaunchKernelGGL((mgc0_smooth_k<VW, false>), mgc0_grid(L, slots), dim3(256), 0, ctx.stream, u, w, b, L, mgc_w(h, l), omg, slots);
-    else hipLaunchKernelGGL((mgc0_smooth_k<VW, true>), mgc0_grid(L, slots), dim3(256), 0, ctx.stream, w, w, b, L, mgc_w(h, l), omg, slots);
-  } else if (u) hipLaunchKernelGGL(mgc_smooth_k<false>, mg_grid(L), dim3(64, 4), 0, ctx.stream, u, w, b, L, mgc_w(h, l), omg);
-  else hipLaunchKernelGGL(mgc_smooth_k<true>, mg_grid(L), dim3(64, 4), 0, ctx.stream, w, w, b, L, mgc_w(h, l), omg);
-  HIP_CHECK(hipGetLastError());
-}
-void mgc_rb_launch(cz_mg* h, int l, REAL* x, const REAL* b, REAL omg, int colour, int zero) {
-  ScopedTimer tm(l ? LBL_MG_RB : LBL_RBSOR);
-  const MgLev L = mgc_lev(h, l);
-  const dim3 grid((unsigned)(((L.nk + 1) / 2 + 63) / 64), (unsigned)((L.ni + 3) / 4), (unsigned)L.nj);
-  const int slots = (L.nk + 2 * VW - 2) / VW;
-  if (l == 0 && (long long)L.ni * slots < 0x7ff00000LL) {
-    const dim3 g0 = mgc0_grid(L, slots);
-    if (zero == 0) hipLaunchKernelGGL((mgc0_rb_k<VW, 0>), g0, dim3(256), 0, ctx.stream, x, b, L, mgc_w(h, l), omg, colour, slots);
-    else if (zero == 1) hipLaunchKernelGGL((mgc0_rb_k<VW, 1>), g0, dim3(256), 0, ctx.stream, x, b, L, mgc_w(h, l), omg, colour, slots);
-    else hipLaunchKernelGGL((mgc0_rb_k<VW, 2>), g0, dim3(256), 0, ctx.stream, x, b, L, mgc_w(h, l), omg, colour, slots);
-  } else if (zero == 0) hipLaunchKernelGGL(mgc_rb_k<0>, grid, dim3(64, 4), 0, ctx.stream, x, b, L, mgc_w(h, l), omg, colour);
-  else if (zero == 1) hipLaunchKernelGGL(mgc_rb_k<1>, grid, dim3(64, 4), 0, ctx.stream, x, b, L, mgc_w(h, l), omg, colour);
-  else hipLaunchKernelGGL(mgc_rb_k<2>, grid, dim3(64, 4), 0, ctx.stream, x, b, L, mgc_w(h, l), omg, colour);
-  HIP_CHECK(hipGetLastError());
-}
-void mgc_restrict_launch(cz_mg* h, int l, REAL* bc, const REAL* x, const REAL* b) {
-  ScopedTimer tm(LBL_MG_RESTRICT);
-  const MgLev F = mgc_lev(h, l), C = mgc_lev(h, l + 1);
-  hipLaunchKernelGGL(mgc_restrict_k, mg_grid(C), dim3(64, 4), 0, ctx.stream, bc, x, b, F, C, mgc_w(h, l));
-  HIP_CHECK(hipGetLastError());
-}
-template <bool RB, bool PER>
-void mgc_tail_launch(REAL* x, const REAL* b, const MgTail& T, const MgcTail& W) {
-  ScopedTimer tm(LBL_MG_TAIL);
-  const int bytes = T.total * (int)sizeof(REAL);
-  if (bytes > 64 * 1024) allow_dynamic_lds(&mgc_tail_k<RB, PER>, 160 * 1024);
-  hipLaunchKernelGGL((mgc_tail_k<RB, PER>), dim3(1), dim3(MG_TAIL_THREADS), bytes, ctx.stream, x, b, T, W);
-  HIP_CHECK(hipGetLastError());
-}
-
 void mgc_free(cz_mg* h) {
   for (int l = 0; l < MG_MAXLEV; l++) {
     for (int d = 0; d < 3; d++) {
@@ -496,27 +489,40 @@ void mg_fine_pair(cz_mg* h, REAL* u, REAL* w, REAL* o, const REAL* b, REAL omg) 
   HIP_CHECK(hipMemcpyAsync(w, o, nbytes, hipMemcpyDeviceToDevice, ctx.stream));
 }
 
-// the operations of mg_walk on one domain.  Levels >= 1 keep b, x and a temporary t of their own; level 0's b is r, and its pair and
-// prolongation are out of place (the fused pass cannot run in place): its iterate is in x0, or not yet anywhere, and the next one goes to o0
+// the operations of mg_walk on one domain, for the constant hierarchy and for the one with face coefficients inside (the
+// same order, fills and from-zero forms; mgc_w gives a level's weight arrays, or none).  A level keeps b, x and a temporary t of its own
+// (mgrb: no t); level 0's are r, x0 and o0.  Every level >= 1, and level 0 under coefficients, is swept by the level kernels, and its
+// iterate never changes array: mg's sweeps go through the temporary and come back, mgrb's colour sweeps and the prolongation run in place.
+// The constant cycle's level 0 (fine) takes the solvers' fused passes instead, which cannot run in place: its iterate is in x0, or not yet
+// anywhere, and the next one goes to o0 -- its pair and its prolongation hand the iterate over
 struct MgOps {
   cz_mg* h;
   REAL omg;
   const REAL* r;
   REAL *x0, *o0;
 
-  void mirror(REAL* X) { mg_mirror(h, X); }
-  bool whole(int l) {
-    if (l < h->tail_from) return false;
-    MgDLev D;
-    MgTail T;
-    mg_lev(D, h->lev[l]);
-    mg_tail_plan(T, D.L, omg, h->rb, h->lev[l].nm);
-    mg_tail_launch(h->x[l], h->b[l], T, h->rb);
-    return true;
-  }
+  bool fine(int l) const { return l == 0 && !h->coef; }
   REAL* x(int l) { return l ? h->x[l] : x0; }
+  REAL* t(int l) { return l ? h->t[l] : o0; }
+  const REAL* b(int l) { return l ? h->b[l] : r; }
+  // what an array of the level needs before a kernel reads its neighbours: level 0 the mirrors and wraps of its face layers, levels >= 1 the wraps
+  bool fills(int l) const { return l ? mg_wraps(h, l) : h->lev[0].nm != 0; }
+  void fill(int l, REAL* a) {
+    if (l) mg_wrap(h, l, a);
+    else if (h->lev[0].nm) mg_mirror(h, a);
+  }
+  void mirror(REAL* X) { mg_mirror(h, X); }
   static void must(int launched) {
     if (!launched) cz_fatal(1, "czhip: V-cycle: a level kernel refused its level\n");
+  }
+  bool whole(int l) {
+    if (l < h->tail_from) return false;
+    MgTail T;
+    MgcTail W = MgcTail();
+    mg_tail_plan(T, mgc_lev(h, l), omg, h->rb, h->lev[l].nm);
+    for (int m = 0; h->coef && m < T.nlev; m++) W.g[m] = mgc_lev(h, l + m), W.w[m] = mgc_w(h, l + m);
+    mg_tail_launch(h->x[l], h->b[l], T, h->rb, h->coef ? &W : nullptr);
+    return true;
   }
   // ---- mgrb.  Level 0 takes the red-black passes that exist (two iterations per pass where the planner takes the box, else one per pass, else
   // the colour sweeps in place); ofst 0 runs colour 0 first, ofst 1 colour 1.  moves: how often such a pair hands the iterate to the other array
@@ -554,88 +560,25 @@ struct MgOps {
       }
     }
   }
-  void rb_pair(int l, bool zero, bool post) {
-    if (l == 0) return fine_rb_pair(zero, post);
-    const int c0 = post ? 1 : 0;
-    // (a periodic level: a wrap after every colour sweep serves the next one, and the first one after the prolongation.  On an odd periodic
-    // extent the seam points share a colour and the ghost holds the value from before the sweep; from zero that value is a zero, so the
-    // array is cleared and swept as an iterate -- the bits of the literal zeros)
-    const bool w = mg_wraps(h, l);
-    if (w && zero) {
-      const int* sz = h->lev[l].sz;
-      HIP_CHECK(hipMemsetAsync(h->x[l], 0, (size_t)(sz[0] + 4) * (sz[1] + 4) * (sz[2] + 4) * sizeof(REAL), ctx.stream));
-    } else if (w) {
-      mg_wrap(h, l, h->x[l]);
-    }
-    for (int s = 0; s < 4; s++) {
-      must(czhip_internal::mg_rb_async(h->x[l], h->b[l], h->lev[l], omg, (c0 + s) & 1, zero && s < 2 && !w ? s + 1 : 0));
-      mg_wrap(h, l, h->x[l]);
-    }
-  }
   // level 0's iterate must end in z: how many times the walk moves it
   int fine_moves() const {
     if (!h->rb) return h->nlev == 1 ? 4 : 3;
     return h->nlev == 1 ? fine_rb_moves(true) + 3 * fine_rb_moves(false) : fine_rb_moves(true) + 1 + fine_rb_moves(false);
   }
 
-  void pair(int l, bool zero, bool post) {
-    if (h->rb) return rb_pair(l, zero, post);
-    if (l == 0) {
-      mg_fine_pair(h, zero ? nullptr : x0, o0, x0, r, omg);
-      std::swap(x0, o0);
-      return;
-    }
-    if (!zero) mg_wrap(h, l, h->x[l]);
-    must(czhip_internal::mg_smooth_async(zero ? nullptr : h->x[l], h->t[l], h->b[l], h->lev[l], omg));
-    mg_wrap(h, l, h->t[l]);
-    must(czhip_internal::mg_smooth_async(h->t[l], h->x[l], h->b[l], h->lev[l], omg));
+  void fine_pair(bool zero, bool post) {
+    if (h->rb) return fine_rb_pair(zero, post);
+    mg_fine_pair(h, zero ? nullptr : x0, o0, x0, r, omg);
+    std::swap(x0, o0);
   }
-  void restrict_down(int l) {
-    if (l == 0 && h->lev[0].nm && !h->rb) mirror(x0);  // (mgrb: mirrored after its last colour sweep)
-    if (l && !h->rb) mg_wrap(h, l, h->x[l]);
-    must(czhip_internal::mg_restrict_async(h->b[l + 1], h->lev[l + 1], x(l), l ? h->b[l] : r, nullptr, h->lev[l]));
-  }
-  void prolong_up(int l) {
-    must(czhip_internal::mg_prolong_async(l ? h->x[l] : o0, x(l), h->x[l + 1], h->lev[l + 1], h->lev[l]));
-    if (l == 0) std::swap(x0, o0);
-  }
-};
 
-// the operations of mg_walk with the face coefficients inside the hierarchy: the same order, fills and from-zero forms at
-// every level, the kernels of cz_k_mgc.h.  Level 0 is a level like the others -- its right-hand side is r, its iterate x0 = z, its temporary
-// o0 -- so the iterate never changes array: mg's sweeps go through the temporary and come back, mgrb's colour sweeps and the prolongation
-// run in place (no fused pass exists under coefficients)
-struct MgcOps {
-  cz_mg* h;
-  REAL omg;
-  const REAL* r;
-  REAL *x0, *o0;
-
-  REAL* x(int l) { return l ? h->x[l] : x0; }
-  REAL* t(int l) { return l ? h->t[l] : o0; }
-  const REAL* b(int l) { return l ? h->b[l] : r; }
-  // what the constant cycle does to an array of the level before a kernel reads its neighbours: level 0 the mirrors and wraps, levels >= 1 the wraps
-  bool fills(int l) const { return l ? mg_wraps(h, l) : h->lev[0].nm != 0; }
-  void fill(int l, REAL* a) {
-    if (l) mg_wrap(h, l, a);
-    else if (h->lev[0].nm) mg_mirror(h, a);
-  }
-  bool whole(int l) {
-    if (l < h->tail_from) return false;
-    MgTail T;
-    MgcTail W;
-    mg_tail_plan(T, mgc_lev(h, l), omg, h->rb, h->lev[l].nm);
-    int any = 0;
-    for (int m = 0; m < T.nlev; m++) any |= T.s[m].nm, W.g[m] = mgc_lev(h, l + m), W.w[m] = mgc_w(h, l + m);
-    for (int m = T.nlev; m < MG_TAIL_MAXLEV; m++) W.g[m] = MgLev(), W.w[m] = MgcW{nullptr, nullptr, nullptr, nullptr};
-    if (any >> 6) h->rb ? mgc_tail_launch<true, true>(h->x[l], h->b[l], T, W) : mgc_tail_launch<false, true>(h->x[l], h->b[l], T, W);
-    else h->rb ? mgc_tail_launch<true, false>(h->x[l], h->b[l], T, W) : mgc_tail_launch<false, false>(h->x[l], h->b[l], T, W);
-    return true;
-  }
   void pair(int l, bool zero, bool post) {
+    if (fine(l)) return fine_pair(zero, post);
+    const MgcW cw = mgc_w(h, l);
     if (h->rb) {
-      // (a level that is filled: from zero the array is cleared and swept as an iterate, as MgOps does -- a ghost may hold a value of the
-      // colour being written)
+      // (a level that is filled: a fill after every colour sweep serves the next one, and the first one after the prolongation.  On an odd
+      // periodic extent the seam points share a colour and the ghost holds the value from before the sweep; from zero that value is a zero,
+      // so the array is cleared and swept as an iterate -- the bits of the literal zeros)
       const int c0 = post ? 1 : 0;
       const bool f = fills(l);
       if (f && zero) {
@@ -645,22 +588,23 @@ struct MgcOps {
         fill(l, x(l));
       }
       for (int s = 0; s < 4; s++) {
-        mgc_rb_launch(h, l, x(l), b(l), omg, (c0 + s) & 1, zero && s < 2 && !f ? s + 1 : 0);
+        must(mg_rb_launch(x(l), b(l), h->lev[l], omg, (c0 + s) & 1, zero && s < 2 && !f ? s + 1 : 0, cw));
         fill(l, x(l));
       }
       return;
     }
     if (!zero) fill(l, x(l));
-    mgc_smooth_launch(h, l, zero ? nullptr : x(l), t(l), b(l), omg);
+    must(mg_smooth_launch(zero ? nullptr : x(l), t(l), b(l), h->lev[l], omg, cw));
     fill(l, t(l));
-    mgc_smooth_launch(h, l, t(l), x(l), b(l), omg);
+    must(mg_smooth_launch(t(l), x(l), b(l), h->lev[l], omg, cw));
   }
   void restrict_down(int l) {
     if (!h->rb) fill(l, x(l));  // (mgrb: filled after its last colour sweep)
-    mgc_restrict_launch(h, l, h->b[l + 1], x(l), b(l));
+    must(mg_restrict_launch(h->b[l + 1], h->lev[l + 1], x(l), b(l), nullptr, h->lev[l], mgc_w(h, l)));
   }
   void prolong_up(int l) {
-    if (!czhip_internal::mg_prolong_async(x(l), x(l), h->x[l + 1], h->lev[l + 1], h->lev[l])) cz_fatal(1, "czhip: V-cycle: a level kernel refused its level\n");
+    must(czhip_internal::mg_prolong_async(fine(l) ? o0 : x(l), x(l), h->x[l + 1], h->lev[l + 1], h->lev[l]));
+    if (fine(l)) std::swap(x0, o0);
   }
 };
 }  // namespace
@@ -678,15 +622,10 @@ extern "C" {
 int czhip_mg_apply_async(cz_mg* h, CZ_REAL* z, const CZ_REAL* r, CZ_REAL omg) {
   ensure_init();
   if (!h || h->first != 0 || !z || !r || z == r || z == h->fine_tmp) return 0;
-  if (h->coef) {  // the coefficient cycle: the iterate stays in z
-    MgcOps ops{h, omg, r, z, h->fine_tmp};
-    mg_walk(ops, 0, h->nlev - 1);
-    return 1;
-  }
-  // level 0's iterate changes array with every step: pair, prolongation, pair, or the coarsest level's four pairs (mgrb: a pair moves it
-  // once, twice or not at all).  The last step writes z
+  // the constant cycle's level 0 changes array with every step: pair, prolongation, pair, or the coarsest level's four pairs (mgrb: a pair
+  // moves it once, twice or not at all).  The last step writes z.  Under coefficients the iterate stays in z
   MgOps ops{h, omg, r, z, h->fine_tmp};
-  if (ops.fine_moves() & 1) std::swap(ops.x0, ops.o0);
+  if (!h->coef && (ops.fine_moves() & 1)) std::swap(ops.x0, ops.o0);
   mg_walk(ops, 0, h->nlev - 1);
   return 1;
 }

@@ -8,6 +8,8 @@
 // summed in that order (c1 .. c6 of the reference).  The weights are small integers computed from (I, J, K, l, n0): exact in either
 // precision, no coefficient arrays.  At level 0 they are 1 and 6: the fine operator itself, whose sweep w * 1 = w gives the bits of jacobi_.
 // Every kernel is pointwise-independent and contains no reduction: the cycle is deterministic, bit for bit.
+// With face coefficients inside the hierarchy (cz_k_mgc.h) the weights are arrays instead; the cycle below is stated once
+// for both, over a weights policy.
 //
 // Geometry of one level's array (MgLev): padded extents and the padded 0-based index of the first inner point.  The global arrays use the
 // S3D layout with guide g; the tail kernel's LDS arrays the same description with one zero shell (nip = ni + 2, first point at 1).
@@ -59,35 +61,86 @@ __device__ __forceinline__ MgW mg_weights(const MgLev& L, int I, int J, int K) {
   return MgW{(REAL)wx, (REAL)wy, (REAL)wz, (REAL)d};
 }
 
-// the six weighted neighbours, in the reference's c1 .. c6 order; ZERO: u is identically zero (literal zeros, the same arithmetic)
-template <bool ZERO>
-__device__ __forceinline__ REAL mg_ss(const REAL* u, const MgLev& L, const MgW& w, long long p) {
-  const long long si = L.nkp, sj = (long long)L.nkp * L.nip;
-  const REAL z = (REAL)0;
-  const REAL ip = ZERO ? z : u[p + si], im = ZERO ? z : u[p - si], jp = ZERO ? z : u[p + sj], jm = ZERO ? z : u[p - sj];
-  const REAL kp = ZERO ? z : u[p + 1], km = ZERO ? z : u[p - 1];
-  return w.wx * ip + w.wx * im + w.wy * jp + w.wy * jm + w.wz * kp + w.wz * km;
-}
+// ---- the weights of a level: a policy W.  W.at(L, I, J, K) is the point's weights (L: the geometry of the array u that is read, (I, J, K)
+// the local index); what it returns gives ss<ZERO>(u, L, p), the six weighted neighbours of element p = mg_at(L, I, J, K) summed left to
+// right in the reference's c1 .. c6 order, and d(), the diagonal.  W.from(o) is the policy for an array whose local point (0, 0, 0) is the
+// global point o (a kernel argument carries none; the arrays have the array's own index).  Everything below that touches the operator takes
+// a policy and is stated once; a new level operator supplies a policy.
+
+// the integers of mg_weights at the global index
+template <bool NM>
+struct MgConst {
+  MgG o;
+  struct At {
+    MgW w;
+    // ZERO: u is identically zero (literal zeros, the same arithmetic)
+    template <bool ZERO>
+    __device__ __forceinline__ REAL ss(const REAL* u, const MgLev& L, long long p) const {
+      const long long si = L.nkp, sj = (long long)L.nkp * L.nip;
+      const REAL z = (REAL)0;
+      const REAL ip = ZERO ? z : u[p + si], im = ZERO ? z : u[p - si], jp = ZERO ? z : u[p + sj], jm = ZERO ? z : u[p - sj];
+      const REAL kp = ZERO ? z : u[p + 1], km = ZERO ? z : u[p - 1];
+      return w.wx * ip + w.wx * im + w.wy * jp + w.wy * jm + w.wz * kp + w.wz * km;
+    }
+    __device__ __forceinline__ REAL d() const { return w.d; }
+  };
+  __device__ __forceinline__ At at(const MgLev& L, int I, int J, int K) const { return At{mg_weights<NM>(L, I + o.i, J + o.j, K + o.k)}; }
+  __device__ __forceinline__ MgConst from(MgG g) const { return MgConst{g}; }
+};
+
+// face-weight arrays X, Y, Z and a diagonal D (cz_k_mgc.h): X(I, J, K) is the link between points I and I + 1
+struct MgcW {
+  const REAL *x, *y, *z, *d;
+};
+// the weights at element q of arrays with row stride ti and plane stride tj.  ZERO: u is identically zero -- every product is a weight
+// (finite, not negative) times a literal zero, and the sum is +0: nothing is read
+struct MgArrAt {
+  const MgcW& w;
+  long long q, ti, tj;
+  template <bool ZERO>
+  __device__ __forceinline__ REAL ss(const REAL* u, const MgLev& L, long long p) const {
+    if (ZERO) return (REAL)0;
+    const long long si = L.nkp, sj = (long long)L.nkp * L.nip;
+    return w.x[q] * u[p + si] + w.x[q - ti] * u[p - si] + w.y[q] * u[p + sj] + w.y[q - tj] * u[p - sj] + w.z[q] * u[p + 1] + w.z[q - 1] * u[p - 1];
+  }
+  __device__ __forceinline__ REAL d() const { return w.d[q]; }
+};
+// weight arrays with the geometry of the array read (the level kernels)
+struct MgArr {
+  MgcW w;
+  __device__ __forceinline__ MgArrAt at(const MgLev& L, int I, int J, int K) const {
+    return MgArrAt{w, mg_at(L, I, J, K), L.nkp, (long long)L.nkp * L.nip};
+  }
+  __device__ __forceinline__ const MgArr& from(MgG) const { return *this; }
+};
+// weight arrays of geometry G while u lives elsewhere (the tail: u in LDS, the weights in their global arrays)
+struct MgArrG {
+  const MgcW& w;
+  const MgLev& G;
+  __device__ __forceinline__ MgArrAt at(const MgLev&, int I, int J, int K) const {
+    return MgArrAt{w, mg_at(G, I, J, K), G.nkp, (long long)G.nkp * G.nip};
+  }
+};
 
 // one relaxed Jacobi sweep at a point (cz_solver.f90:334-351 with the level's weights): pn = pp + ((ss - bb)/D - pp) omg, IEEE division
 // (ZPP: the point's own value is a literal zero although its neighbours are read -- the second colour of a red-black iteration from zero)
-template <bool NM, bool ZERO, bool ZPP = ZERO>
-__device__ __forceinline__ REAL mg_sweep_pt(const REAL* u, const REAL* b, const MgLev& L, int I, int J, int K, REAL omg, MgG o = MgG{0, 0, 0}) {
-  const MgW w = mg_weights<NM>(L, I + o.i, J + o.j, K + o.k);
+template <bool ZERO, bool ZPP = ZERO, class W>
+__device__ __forceinline__ REAL mg_sweep_pt(const REAL* u, const REAL* b, const MgLev& L, const W& wt, int I, int J, int K, REAL omg) {
+  const auto w = wt.at(L, I, J, K);
   const long long p = mg_at(L, I, J, K);
   const REAL pp = ZPP ? (REAL)0 : u[p];
-  const REAL ss = mg_ss<ZERO>(u, L, w, p);
-  const REAL dp = ((ss - b[p]) / w.d - pp) * omg;
+  const REAL ss = w.template ss<ZERO>(u, L, p);
+  const REAL dp = ((ss - b[p]) / w.d() - pp) * omg;
   return pp + dp;
 }
 
 // residual at a point, written like blas_calc_rk_ (cz_blas.f90:705-711): b - (ss - D x)
-template <bool NM>
-__device__ __forceinline__ REAL mg_res_pt(const REAL* x, const REAL* b, const MgLev& L, int I, int J, int K, MgG o = MgG{0, 0, 0}) {
-  const MgW w = mg_weights<NM>(L, I + o.i, J + o.j, K + o.k);
+template <class W>
+__device__ __forceinline__ REAL mg_res_pt(const REAL* x, const REAL* b, const MgLev& L, const W& wt, int I, int J, int K) {
+  const auto w = wt.at(L, I, J, K);
   const long long p = mg_at(L, I, J, K);
-  const REAL ss = mg_ss<false>(x, L, w, p);
-  return b[p] - (ss - w.d * x[p]);
+  const REAL ss = w.template ss<false>(x, L, p);
+  return b[p] - (ss - w.d() * x[p]);
 }
 
 // b_{l+1}(I, J, K) = the residual summed over the <= 8 children (j, i, k; k innermost) as the tree
@@ -111,11 +164,11 @@ __device__ __forceinline__ REAL mg_tree(bool hi, bool hj, bool hk, R res) {
   return hj ? t[0] + t[1] : t[0];
 }
 
-template <bool NM>
-__device__ __forceinline__ REAL mg_restrict_pt(const REAL* x, const REAL* b, const MgLev& F, int I, int J, int K) {
+template <class W>
+__device__ __forceinline__ REAL mg_restrict_pt(const REAL* x, const REAL* b, const MgLev& F, const W& wt, int I, int J, int K) {
   const int i0 = 2 * I, j0 = 2 * J, k0 = 2 * K;
   const bool hi = i0 + 1 < F.ni, hj = j0 + 1 < F.nj, hk = k0 + 1 < F.nk;
-  return mg_tree(hi, hj, hk, [&](int ib, int jb, int kb) { return mg_res_pt<NM>(x, b, F, i0 + ib, j0 + jb, k0 + kb); });
+  return mg_tree(hi, hj, hk, [&](int ib, int jb, int kb) { return mg_res_pt(x, b, F, wt, i0 + ib, j0 + jb, k0 + kb); });
 }
 
 // u = x + R(alpha xc(parent)), alpha = R(1.8): one rounding per operation (no contraction: the build has -ffp-contract=off)
@@ -137,11 +190,12 @@ struct MgDLev {
   int gni, gnj, gnk;
 };
 
-template <bool ZERO, bool NM>
-__global__ void __launch_bounds__(256) mg_smooth_k(const REAL* __restrict__ u, REAL* __restrict__ w, const REAL* __restrict__ b, MgDLev D, REAL omg) {
+// (W: the weights as a kernel argument, MgConst<NM> or MgArr; wt.from(o) the policy of the array at hand)
+template <bool ZERO, class W>
+__global__ void __launch_bounds__(256) mg_smooth_k(const REAL* __restrict__ u, REAL* __restrict__ w, const REAL* __restrict__ b, MgDLev D, REAL omg, W wt) {
   const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
   if (K >= D.L.nk || I >= D.L.ni) return;
-  w[mg_at(D.L, I, J, K)] = mg_sweep_pt<NM, ZERO>(u, b, D.L, I, J, K, omg, D.o);
+  w[mg_at(D.L, I, J, K)] = mg_sweep_pt<ZERO>(u, b, D.L, wt.from(D.o), I, J, K, omg);
 }
 
 // ---- pcg ... mgrb: one colour sweep of a level >= 1, IN PLACE.  The colour of a point is (I + J + K) & 1; the points of
@@ -149,26 +203,27 @@ __global__ void __launch_bounds__(256) mg_smooth_k(const REAL* __restrict__ u, R
 // thread kk of row (I, J) owns K = 2 kk + ((I + J + c) & 1).  A workgroup is (64, 4) with one row per wave, so that offset is wave-uniform and
 // the colour c a launch argument: no lane selects operands.  Z: 0 = from the iterate; 1 = the first colour of an iteration from zero (x is not
 // read); 2 = its second colour (reads the freshly written colour, its own value is a literal zero).  The same bits as a sweep from a cleared x.
-template <int Z, bool NM>
-__device__ __forceinline__ REAL mg_rb_pt(const REAL* x, const REAL* b, const MgLev& L, int I, int J, int K, REAL omg) {
-  return mg_sweep_pt<NM, Z == 1, Z != 0>(x, b, L, I, J, K, omg);
+template <int Z, class W>
+__device__ __forceinline__ REAL mg_rb_pt(const REAL* x, const REAL* b, const MgLev& L, const W& wt, int I, int J, int K, REAL omg) {
+  return mg_sweep_pt<Z == 1, Z != 0>(x, b, L, wt, I, J, K, omg);
 }
 
-template <int Z, bool NM>
-__global__ void __launch_bounds__(256) mg_rb_k(REAL* x, const REAL* __restrict__ b, MgLev L, REAL omg, int c) {
+// (the array is the whole level: global index = local index)
+template <int Z, class W>
+__global__ void __launch_bounds__(256) mg_rb_k(REAL* x, const REAL* __restrict__ b, MgLev L, REAL omg, int c, W wt) {
   const int I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
   const int K = 2 * (blockIdx.x * 64 + threadIdx.x) + ((I + J + c) & 1);
   if (K >= L.nk || I >= L.ni) return;
-  x[mg_at(L, I, J, K)] = mg_rb_pt<Z, NM>(x, b, L, I, J, K, omg);
+  x[mg_at(L, I, J, K)] = mg_rb_pt<Z>(x, b, L, wt.from(MgG{0, 0, 0}), I, J, K, omg);
 }
 
 // bc (owned coarse points) = the children's residual tree; owned children computed here, children on the + neighbours (the brick's
 // ghost layer) read from rt after its exchange.  C.L may be a dense block (no shell): the gathered level's send buffer.  DIST = false: the
 // domain owns the whole level (offsets 0, global extents = the local ones, rt not read) -- the same text with those constants folded in,
 // kept as an instantiation of its own because the FP32 launch measured 1-2 % slower without it (profiles/r11/mg_one_cycle.txt)
-template <bool DIST, bool NM>
+template <bool DIST, class W>
 __global__ void __launch_bounds__(256) mg_restrict_k(REAL* __restrict__ bc, const REAL* __restrict__ x, const REAL* __restrict__ b, const REAL* __restrict__ rt,
-                                                     MgDLev F, MgDLev C) {
+                                                     MgDLev F, MgDLev C, W wt) {
   const int K = blockIdx.x * 64 + threadIdx.x, I = blockIdx.y * 4 + threadIdx.y, J = blockIdx.z;
   if (K >= C.L.nk || I >= C.L.ni) return;
   const MgG fo = DIST ? F.o : MgG{0, 0, 0}, co = DIST ? C.o : MgG{0, 0, 0};
@@ -177,9 +232,10 @@ __global__ void __launch_bounds__(256) mg_restrict_k(REAL* __restrict__ bc, cons
   const int gi = 2 * (I + co.i), gj = 2 * (J + co.j), gk = 2 * (K + co.k);
   const bool hi = gi + 1 < gni, hj = gj + 1 < gnj, hk = gk + 1 < gnk;
   const int li = gi - fo.i, lj = gj - fo.j, lk = gk - fo.k;
+  const auto wf = wt.from(fo);  // (the children's residual takes the FINE level's weights)
   bc[mg_at(C.L, I, J, K)] = mg_tree(hi, hj, hk, [&](int ib, int jb, int kb) {
     const int ci = li + ib, cj = lj + jb, ck = lk + kb;
-    if (!DIST || (ci < F.L.ni && cj < F.L.nj && ck < F.L.nk)) return mg_res_pt<NM>(x, b, F.L, ci, cj, ck, fo);
+    if (!DIST || (ci < F.L.ni && cj < F.L.nj && ck < F.L.nk)) return mg_res_pt(x, b, F.L, wf, ci, cj, ck);
     return rt[mg_at(F.L, ci, cj, ck)];
   });
 }
@@ -204,7 +260,7 @@ __global__ void __launch_bounds__(64) mgd_resface_k(REAL* __restrict__ rt, const
   else K = 0, I = a, J = c;
   if (I >= D.L.ni || J >= D.L.nj || K >= D.L.nk) return;
   if ((d >= 1 && mi && I == 0) || (d == 2 && mj && J == 0)) return;  // written by the I (J) face launch
-  rt[mg_at(D.L, I, J, K)] = mg_res_pt<NM>(x, b, D.L, I, J, K, D.o);
+  rt[mg_at(D.L, I, J, K)] = mg_res_pt(x, b, D.L, MgConst<NM>{D.o}, I, J, K);
 }
 
 // one rank's dense block (ni, nj, nk; K fastest) into the gathered global array at global offset o: an exact copy
@@ -227,6 +283,17 @@ struct MgTail {
   int len[MG_TAIL_MAXLEV];      // REALs per LDS array of level m
   int total;               // REALs of LDS in all
   REAL omg;
+};
+// the weights of the tail's levels (WT of mg_tail_k): lev(m) is level m's policy.  The integers need nothing from the host; the arrays of
+// tail level m are read from their global arrays (geometry g[m]): read-only, a few KiB, resident in L2
+template <bool NM>
+struct MgConstTail {
+  __device__ __forceinline__ MgConst<NM> lev(int) const { return MgConst<NM>{MgG{0, 0, 0}}; }
+};
+struct MgcTail {
+  MgLev g[MG_TAIL_MAXLEV];
+  MgcW w[MG_TAIL_MAXLEV];
+  __device__ __forceinline__ MgArrG lev(int m) const { return MgArrG{w[m], g[m]}; }
 };
 
 // every point of level L, by the workgroup
@@ -280,38 +347,38 @@ __device__ __forceinline__ void mg_tail_wrap(const MgLev& L, REAL* a) {
 // x <- two smoothing iterations of the level (zero: from zero); RB: red-black in place, backward (colours 1, 0) where post; else relaxed
 // Jacobi through t.  Ends with the workgroup in step.  PER: a wrap follows every sweep and colour sweep (x is wrapped on return; on an odd
 // periodic extent the seam points share a colour and the shell holds the value from before the sweep -- from zero that is the cleared LDS)
-template <bool RB, bool NM, bool PER>
-__device__ __forceinline__ void mg_tail_pair(const MgLev& L, const REAL* b, REAL* x, REAL* t, bool zero, bool post, REAL omg) {
+template <bool RB, bool PER, class W>
+__device__ __forceinline__ void mg_tail_pair(const MgLev& L, const W& wt, const REAL* b, REAL* x, REAL* t, bool zero, bool post, REAL omg) {
   if (RB) {
     const int c0 = post ? 1 : 0;
     if (zero) {
-      mg_each_colour(L, c0, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<1, NM>(x, b, L, I, J, K, omg); });
+      mg_each_colour(L, c0, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<1>(x, b, L, wt, I, J, K, omg); });
       __syncthreads();
       if (PER) mg_tail_wrap(L, x);
-      mg_each_colour(L, 1 - c0, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<2, NM>(x, b, L, I, J, K, omg); });
+      mg_each_colour(L, 1 - c0, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<2>(x, b, L, wt, I, J, K, omg); });
       __syncthreads();
       if (PER) mg_tail_wrap(L, x);
     }
     for (int s = zero ? 2 : 0; s < 4; s++) {
-      mg_each_colour(L, (c0 + s) & 1, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<0, NM>(x, b, L, I, J, K, omg); });
+      mg_each_colour(L, (c0 + s) & 1, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_rb_pt<0>(x, b, L, wt, I, J, K, omg); });
       __syncthreads();
       if (PER) mg_tail_wrap(L, x);
     }
     return;
   }
-  if (zero) mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<NM, true>(t, b, L, I, J, K, omg); });
-  else mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<NM, false>(x, b, L, I, J, K, omg); });
+  if (zero) mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<true>(t, b, L, wt, I, J, K, omg); });
+  else mg_each(L, [&](int I, int J, int K) { t[mg_at(L, I, J, K)] = mg_sweep_pt<false>(x, b, L, wt, I, J, K, omg); });
   __syncthreads();
   if (PER) mg_tail_wrap(L, t);
-  mg_each(L, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_sweep_pt<NM, false>(t, b, L, I, J, K, omg); });
+  mg_each(L, [&](int I, int J, int K) { x[mg_at(L, I, J, K)] = mg_sweep_pt<false>(t, b, L, wt, I, J, K, omg); });
   __syncthreads();
   if (PER) mg_tail_wrap(L, x);
 }
 
 // RB: the cycle of pcg ... mgrb (its levels keep b and x only: T.len[m] apart, no t).  PER: some level of the tail wraps (T.s[m].nm bits 6 .. 8;
-// without it, the code from before there were periodic directions)
-template <bool RB, bool NM, bool PER>
-__global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ xg, const REAL* __restrict__ bg, MgTail T) {
+// without it, the code from before there were periodic directions).  WT: the levels' weights, MgConstTail<NM> or MgcTail
+template <bool RB, bool PER, class WT>
+__global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ xg, const REAL* __restrict__ bg, MgTail T, WT W) {
   extern __shared__ __align__(16) unsigned char mg_lds_raw[];
   REAL* const lds = reinterpret_cast<REAL*>(mg_lds_raw);
   for (int q = threadIdx.x; q < T.total; q += blockDim.x) lds[q] = (REAL)0;  // the zero shells (and a defined start)
@@ -326,16 +393,16 @@ __global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ 
   for (int m = 0; m + 1 < T.nlev; m++) {
     const MgLev& L = T.s[m];
     REAL *b = lds + T.off[m], *x = b + T.len[m], *t = x + T.len[m];
-    mg_tail_pair<RB, NM, PER>(L, b, x, t, true, false, omg);
+    mg_tail_pair<RB, PER>(L, W.lev(m), b, x, t, true, false, omg);
     const MgLev& Cl = T.s[m + 1];
     REAL* bc = lds + T.off[m + 1];
-    mg_each(Cl, [&](int I, int J, int K) { bc[mg_at(Cl, I, J, K)] = mg_restrict_pt<NM>(x, b, L, I, J, K); });
+    mg_each(Cl, [&](int I, int J, int K) { bc[mg_at(Cl, I, J, K)] = mg_restrict_pt(x, b, L, W.lev(m), I, J, K); });
     __syncthreads();
   }
   {  // the coarsest level: four pairs from zero, the last two post (mg_walk's order)
     const int m = T.nlev - 1;
     REAL *b = lds + T.off[m], *x = b + T.len[m], *t = x + T.len[m];
-    for (int s = 0; s < 4; s++) mg_tail_pair<RB, NM, PER>(T.s[m], b, x, t, s == 0, s >= 2, omg);
+    for (int s = 0; s < 4; s++) mg_tail_pair<RB, PER>(T.s[m], W.lev(m), b, x, t, s == 0, s >= 2, omg);
   }
   // up: x += R(alpha x_c(parent)) in place, post-smoothing pair
   for (int m = T.nlev - 2; m >= 0; m--) {
@@ -349,7 +416,7 @@ __global__ void __launch_bounds__(MG_TAIL_THREADS) mg_tail_k(REAL* __restrict__ 
     });
     __syncthreads();
     if (PER) mg_tail_wrap(L, x);
-    mg_tail_pair<RB, NM, PER>(L, b, x, t, false, true, omg);
+    mg_tail_pair<RB, PER>(L, W.lev(m), b, x, t, false, true, omg);
   }
   {
     const REAL* x0 = lds + T.off[0] + T.len[0];
