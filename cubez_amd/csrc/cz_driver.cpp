@@ -52,11 +52,11 @@ constexpr int POLL_SLOTS = 4;
 
 CZ::CZ() {
   czhip_init(-1);
-  HIP_CHECK(hipMalloc(&d_res, 24 * sizeof(double)));
-  HIP_CHECK(hipMemset(d_res, 0, 24 * sizeof(double)));
-  HIP_CHECK(hipMalloc(&d_flag, (2 + 2 * POLL_SLOTS) * sizeof(int)));
-  HIP_CHECK(hipMemset(d_flag, 0, (2 + 2 * POLL_SLOTS) * sizeof(int)));
-  HIP_CHECK(hipHostMalloc(&h_scal, 24 * sizeof(double), hipHostMallocDefault));
+  HIP_CHECK(hipMalloc(&d_res, sizeof(CzScalars)));
+  HIP_CHECK(hipMemset(d_res, 0, sizeof(CzScalars)));
+  HIP_CHECK(hipMalloc(&d_flag, sizeof(CzFlags)));
+  HIP_CHECK(hipMemset(d_flag, 0, sizeof(CzFlags)));
+  HIP_CHECK(hipHostMalloc(&h_scal, sizeof(CzScalars), hipHostMallocDefault));
   HIP_CHECK(hipHostMalloc(&h_flag, 2 * POLL_SLOTS * sizeof(int), hipHostMallocDefault));
   cfg = CzConfig::from_env();  // the environment as this driver was created in (cz_config.h); nothing below asks it again
   overlap = cfg.num(CZV_OVERLAP, overlap);
@@ -529,12 +529,25 @@ bool CZ::Comm_SUM_dev(double* d_val, int count, const int* skip_flag) {
 }
 bool CZ::Comm_SUM_1(double* host_val) {
   if (numProc == 1) return true;
-  HIP_CHECK(hipMemcpyAsync(d_res + 8, host_val, sizeof(double), hipMemcpyHostToDevice, stream()));
-  if (!comm_allreduce_sum(comm, d_res + 8, 1, stream())) return false;
-  HIP_CHECK(hipMemcpyAsync(h_scal + 8, d_res + 8, sizeof(double), hipMemcpyDeviceToHost, stream()));
-  HIP_CHECK(hipStreamSynchronize(stream()));
-  *host_val = h_scal[8];
+  HIP_CHECK(hipMemcpyAsync(&d_res->comm_sum, host_val, sizeof(double), hipMemcpyHostToDevice, stream()));
+  if (!comm_allreduce_sum(comm, &d_res->comm_sum, 1, stream())) return false;
+  *host_val = *fetch(&d_res->comm_sum);
   return true;
+}
+
+// The read-back of d_res (cz_driver.h): the mirror of a member is the same member of h_scal
+template <class T> const T* CZ::fetch_queued(const T* dev, int n) {
+  const void *const block = d_res, *const member = dev;
+  const size_t at = (size_t)(static_cast<const char*>(member) - static_cast<const char*>(block));
+  if (at + (size_t)n * sizeof(T) > sizeof(CzScalars)) cz_fatal(1, "error : a read-back beyond the device scalars\n");
+  T* const host = static_cast<T*>(static_cast<void*>(static_cast<char*>(static_cast<void*>(h_scal)) + at));
+  HIP_CHECK(hipMemcpyAsync(host, dev, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, stream()));
+  return host;
+}
+template <class T> const T* CZ::fetch(const T* dev, int n) {
+  const T* const host = fetch_queued(dev, n);
+  HIP_CHECK(hipStreamSynchronize(stream()));
+  return host;
 }
 
 // WRK must carry the guide cells / faces of the array it ping-pongs with.  Single-domain runs know two kinds of shells that never change
@@ -589,7 +602,7 @@ void CZ::plan_overlap() {
 // Returns false (nothing launched) when the split does not apply; the caller then takes the unsplit path.
 bool CZ::pair_overlapped(REAL_TYPE* src, REAL_TYPE* dst, REAL_TYPE* B, int rb, const int* skip, double* res_slot, const MafPtrs* maf) {
   if (n_shell == 0) return false;
-  double* rs = res_slot ? res_slot : d_res;
+  double* rs = res_slot ? res_slot : d_res->pass;
   const int gc = GUIDE;
   hipStream_t st = stream();
   if (!pair_probe(src, dst, B, size, interior, interior1, gc, cf[6], maf ? 1 : 0)) return false;
@@ -617,7 +630,7 @@ int CZ::finish_stationary(int itr_max, bool converge_check, double& res) {
     if (!in_precond) czhip_sync();
     return itr_max + 1;
   }
-  HIP_CHECK(hipMemcpyAsync(h_flag, d_flag, 2 * sizeof(int), hipMemcpyDeviceToHost, stream()));
+  HIP_CHECK(hipMemcpyAsync(h_flag, &d_flag->converged, 2 * sizeof(int), hipMemcpyDeviceToHost, stream()));  // (flag, iteration)
   HIP_CHECK(hipStreamSynchronize(stream()));
   const bool conv = h_flag[0] != 0;
   const int n_exec = conv ? h_flag[1] : itr_max;
@@ -637,17 +650,15 @@ void CZ::read_history(int n_exec, double& res) {
 
 // :67-77 after a sweep (nres = 1) or a pair of sweeps (nres = 2): all-reduce of the residual(s), then the test on the device
 bool CZ::reduce_test(int nres, int itr, const int* skip) {
-  if (!Comm_SUM_dev(d_res, nres, skip)) return false;
-  if (nres == 2) czhip_check2_async(d_res, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);
-  else czhip_check_async(d_res, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);
+  if (!Comm_SUM_dev(d_res->pass, nres, skip)) return false;
+  if (nres == 2) czhip_check2_async(d_res->pass, res_normal, eps, itr, d_hist, &d_flag->converged, &d_flag->iteration);
+  else czhip_check_async(d_res->pass, res_normal, eps, itr, d_hist, &d_flag->converged, &d_flag->iteration);
   return true;
 }
 
-// d_res[0] of the sweep(s) just issued, read back behind them: NaN = the sweep gave up a wait between its workgroups (pcr_lex_wg_k)
+// the residual sum of the sweep(s) just issued, read back behind them: NaN = the sweep gave up a wait between its workgroups (pcr_lex_wg_k)
 bool CZ::sweep_failed(const char* solver) {
-  HIP_CHECK(hipMemcpyAsync(h_scal + 9, d_res, sizeof(double), hipMemcpyDeviceToHost, stream()));
-  HIP_CHECK(hipStreamSynchronize(stream()));
-  if (!std::isnan(h_scal[9])) return false;
+  if (!std::isnan(*fetch(d_res->pass))) return false;
   fprintf(stderr, "cz rank %d: %s: the residual of a sweep is NaN -- a hand-off between the workgroups of the one-launch lexicographic sweep did "
                   "not arrive within its bound (czhip_set_pcr_lex_timeout), or the data hold NaN.  The iterate is void.  CZHIP_PCR_PIPE=0 selects "
                   "the launch-per-diagonal form.\n", myRank, solver);
@@ -701,7 +712,7 @@ CZ::PassPlan CZ::plan_pass(REAL_TYPE* X, REAL_TYPE* B, int s_type, int itr_max, 
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// The host's lagging, non-blocking view of the device convergence flag.  Each poll issues a stream-ordered copy of d_flag[0] and looks at
+// The host's lagging, non-blocking view of the device convergence flag.  Each poll issues a stream-ordered copy of d_flag->converged and looks at
 // the copy issued two polls earlier; the caller decides when to poll (its cadence).  The events are released with the poller, early returns
 // included.
 // INVARIANT (rank lock step): the answer decides whether this rank issues further passes, i.e. further collectives.  It is a function of
@@ -721,7 +732,7 @@ class CZ::FlagPoll {
     const int slot = npoll_ % POLL_SLOTS;
     if (npoll_ >= POLL_SLOTS) HIP_CHECK(hipEventDestroy(ev_[slot]));
     if (lag_) cz_.wait_lagged_tests();  // every rank must read the same flag: the copy follows the tests of all passes issued so far
-    HIP_CHECK(hipMemcpyAsync(cz_.h_flag + 2 * slot, cz_.d_flag, sizeof(int), hipMemcpyDeviceToHost, stream()));
+    HIP_CHECK(hipMemcpyAsync(cz_.h_flag + 2 * slot, &cz_.d_flag->converged, sizeof(int), hipMemcpyDeviceToHost, stream()));
     HIP_CHECK(hipEventCreateWithFlags(&ev_[slot], hipEventDisableTiming));
     HIP_CHECK(hipEventRecord(ev_[slot], stream()));
     if (++npoll_ < 3) return false;
@@ -753,7 +764,7 @@ class CZ::FusedLoop {
   const PassPlan& plan;
   REAL_TYPE* const B;
   const bool converge_check;
-  const int* skip = nullptr;  // checked solves: d_flag (launches queued after convergence are no-ops)
+  const int* skip = nullptr;  // checked solves: d_flag->converged (launches queued after convergence are no-ops)
   REAL_TYPE* buf[3] = {nullptr, nullptr, nullptr};
   const int nbuf;
   int cur = 0;
@@ -782,8 +793,8 @@ bool CZ::fused_begin(FusedLoop& L, REAL_TYPE* X, int itr_max, bool x_is_zero, co
   reset_ticket();
   if (L.converge_check) {
     ensure_hist(itr_max + 3);
-    HIP_CHECK(hipMemsetAsync(d_flag, 0, 4 * sizeof(int), stream()));  // flag, iteration, the two snapshots of the lagged mode
-    L.skip = d_flag;
+    HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(CzFlags), stream()));  // flag, iteration, the two snapshots of the lagged mode
+    L.skip = &d_flag->converged;
   }
   // the fused pass reads two ghost layers (and the edge cells) of X and one of B
   if (plan.depth == 2 && numProc > 1 && (!Comm_S2(X) || !Comm_S2(L.B))) return false;
@@ -810,17 +821,17 @@ bool CZ::split_pass(FusedLoop& L, int rb, int nres, int itr, const MafPtrs* mpp)
   hipStream_t st = stream();
   const int p = (int)L.launches.size();
   if (p >= 2) HIP_CHECK(hipStreamWaitEvent(st, ev_chk[p & 1], 0));  // the test of pass p-2
-  double* rs = d_res + ((p & 1) ? 10 : 0);
-  // Pass p looks at the flag as the test of pass p-2 left it (d_flag[2 + (p & 1)], written by that test and by nothing else until
-  // pass p is over): every workgroup of the pass, its pack and its unpack take the same decision.  The live flag d_flag[0] may be
+  double* rs = d_res->lagged[p & 1];
+  // Pass p looks at the flag as the test of pass p-2 left it (d_flag->snap[p & 1], written by that test and by nothing else until
+  // pass p is over): every workgroup of the pass, its pack and its unpack take the same decision.  The live flag d_flag->converged may be
   // set by the test of pass p-1 while pass p is running.
-  int* snap = d_flag + 2 + (p & 1);
+  int* snap = &d_flag->snap[p & 1];
   if (!pair_overlapped(L.src(), L.dst(), L.B, rb, snap, rs, mpp)) return false;
   HIP_CHECK(hipEventRecord(ev_int, st));
   HIP_CHECK(hipStreamWaitEvent(comm_stream, ev_int, 0));
   if (!comm_allreduce_sum(comm, rs, nres, comm_stream)) return false;  // :67, all the pass's residuals
-  if (nres == 2) check2_on_stream(comm_stream, rs, res_normal, eps, itr, d_hist, d_flag, d_flag + 1, snap);  // :69-77
-  else check_on_stream(comm_stream, rs, res_normal, eps, itr, d_hist, d_flag, d_flag + 1, snap);
+  if (nres == 2) check2_on_stream(comm_stream, rs, res_normal, eps, itr, d_hist, &d_flag->converged, &d_flag->iteration, snap);  // :69-77
+  else check_on_stream(comm_stream, rs, res_normal, eps, itr, d_hist, &d_flag->converged, &d_flag->iteration, snap);
   HIP_CHECK(hipEventRecord(ev_chk[p & 1], comm_stream));
   return true;
 }
@@ -838,7 +849,7 @@ bool CZ::whole_exchange_test(FusedLoop& L, int nres, int itr) {
 int CZ::zero_start_pass(REAL_TYPE* src, REAL_TYPE* dst, REAL_TYPE* B, const BMade* made, int rb) {
   static const BMade read_b{0, nullptr, nullptr, nullptr, (REAL_TYPE)0, (REAL_TYPE)0, nullptr};
   const BMade& m = made ? *made : read_b;
-  return pass_from_zero_made(src, dst, B, m.op, m.x, m.y, m.z, m.a, m.a_dev, m.b, size, innerFidx, idx1, GUIDE, cf, ac1, rb, d_res, 0);
+  return pass_from_zero_made(src, dst, B, m.op, m.x, m.y, m.z, m.a, m.a_dev, m.b, size, innerFidx, idx1, GUIDE, cf, ac1, rb, d_res->pass, 0);
 }
 
 // The end of a JACOBI / RBSOR solve: drain, read the bookkeeping back, and hand the iterate of the converged (or last) iteration to the
@@ -895,8 +906,8 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
   auto jacobi_pass = [&](int n, REAL_TYPE* s, REAL_TYPE* d, double* rs, bool check, int it, int probe) -> int {
     const double rn = check ? res_normal : 0.0, ep = check ? eps : 0.0;
     double* hist = (check && converge_check) ? d_hist : nullptr;
-    int* flag = check ? d_flag : nullptr;
-    int* conv = check ? d_flag + 1 : nullptr;
+    int* flag = check ? &d_flag->converged : nullptr;
+    int* conv = check ? &d_flag->iteration : nullptr;
     const int* sk = check ? skip : nullptr;
     if (n == 4) return czhip_jacobi4_async(s, d, B, size, innerFidx, gc, cf, ac1, rs, rn, ep, it, hist, flag, conv, sk, probe);
     if (n == 3) return czhip_jacobi3_async(s, d, B, size, innerFidx, gc, cf, ac1, rs, rn, ep, it, hist, flag, conv, sk, probe);
@@ -904,11 +915,11 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
   };
   // THREE sweeps per pass (jac3_k) where the whole inner box is one launch of one rank with constant coefficients, outside a preconditioner
   // solve; triples while three sweeps remain, then the pair or the single sweep
-  const bool jac3 = plan.kind == PassPlan::WHOLE && numProc == 1 && !maf && !in_precond && itr_max >= 3 && jacobi_pass(3, X, WRK, d_res, false, 0, 1) != 0;
+  const bool jac3 = plan.kind == PassPlan::WHOLE && numProc == 1 && !maf && !in_precond && itr_max >= 3 && jacobi_pass(3, X, WRK, d_res->pass, false, 0, 1) != 0;
   // FOUR sweeps per pass (jac4_k) where that pass takes the box as well and the solve is long enough (czhip_jac4_min_sweeps: a solve of
   // fewer than eight sweeps keeps the triples it had, the passes cz_info 14 reports): quads while four sweeps remain, then the triple,
   // the pair or the single sweep
-  const bool jac4 = jac3 && itr_max >= czhip_jac4_min_sweeps() && jacobi_pass(4, X, WRK, d_res, false, 0, 1) != 0;
+  const bool jac4 = jac3 && itr_max >= czhip_jac4_min_sweeps() && jacobi_pass(4, X, WRK, d_res->pass, false, 0, 1) != 0;
   jac3_passes = 0, jac4_passes = 0;
   bool stop = false;
   int itr = 1;
@@ -920,8 +931,8 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
     if (pass && plan.kind == PassPlan::SPLIT) {
       if (!split_pass(L, -1, 2, itr, mpp)) return 0;  // :58 twice, :63 hidden behind the interior, :67-77 for both sweeps
     } else if (pass && jac3 && itr + 2 <= itr_max && !(plan.zero_start && itr == 1)) {
-      done = (jac4 && itr + 3 <= itr_max) ? 4 : 3;  // :58 + :67-77, `done` times (d_res[0 .. done-1]; the re-runs below write d_res[4..6])
-      if (!jacobi_pass(done, src, dst, d_res, true, itr, 0)) {
+      done = (jac4 && itr + 3 <= itr_max) ? 4 : 3;  // :58 + :67-77, `done` times (pass[0 .. done-1]; the re-runs below write `rerun`)
+      if (!jacobi_pass(done, src, dst, d_res->pass, true, itr, 0)) {
         cz_fatal(1, "error : the %s-sweep pass refused after a successful probe\n", done == 4 ? "four" : "three");
       }
       (done == 4 ? jac4_passes : jac3_passes)++;
@@ -931,11 +942,11 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
       if (plan.zero_start && itr == 1)
         launched = zero_start_pass(src, dst, B, made, -1);
       else if (maf)
-        launched = pair_maf_async(src, dst, B, size, innerFidx, idx1, gc, d_xc, d_yc, d_zc, ac1, -1, d_res, res_normal, eps, itr,
-                                  in_kernel_check ? d_hist : nullptr, d_flag, d_flag + 1, skip);  // :45-53 twice
+        launched = pair_maf_async(src, dst, B, size, innerFidx, idx1, gc, d_xc, d_yc, d_zc, ac1, -1, d_res->pass, res_normal, eps, itr,
+                                  in_kernel_check ? d_hist : nullptr, &d_flag->converged, &d_flag->iteration, skip);  // :45-53 twice
       else
-        launched = czhip_jacobi2_async(src, dst, B, size, innerFidx, idx1, gc, cf, ac1, d_res, res_normal, eps, itr,
-                                       in_kernel_check ? d_hist : nullptr, d_flag, d_flag + 1, skip);  // :58 + :67-77, twice
+        launched = czhip_jacobi2_async(src, dst, B, size, innerFidx, idx1, gc, cf, ac1, d_res->pass, res_normal, eps, itr,
+                                       in_kernel_check ? d_hist : nullptr, &d_flag->converged, &d_flag->iteration, skip);  // :58 + :67-77, twice
       if (!launched) {
         cz_fatal(1, "error : fused pass refused after a successful probe\n");
       }
@@ -944,13 +955,13 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
       if (plan.lag) wait_lagged_tests();  // the tests still in flight on the exchange stream come first
       const bool fused_check = converge_check && numProc == 1;  // no all-reduce between sweep and test: one launch
       if (maf)
-        jacobi_maf_async(src, dst, B, size, innerFidx, gc, d_xc, d_yc, d_zc, ac1, d_res, skip, fused_check ? 1 : 0, res_normal, eps,
-                         itr, d_hist, d_flag, d_flag + 1);
+        jacobi_maf_async(src, dst, B, size, innerFidx, gc, d_xc, d_yc, d_zc, ac1, d_res->pass, skip, fused_check ? 1 : 0, res_normal, eps,
+                         itr, d_hist, &d_flag->converged, &d_flag->iteration);
       else if (fused_check)
-        czhip_jacobi_checked_async(src, dst, B, size, innerFidx, gc, cf, ac1, d_res, res_normal, eps, itr, d_hist, d_flag,
-                                   d_flag + 1);  // :58 + :67-77
+        czhip_jacobi_checked_async(src, dst, B, size, innerFidx, gc, cf, ac1, d_res->pass, res_normal, eps, itr, d_hist,
+                                   &d_flag->converged, &d_flag->iteration);  // :58 + :67-77
       else
-        czhip_jacobi_async(src, dst, B, size, innerFidx, gc, cf, ac1, d_res, 0, skip);  // :58
+        czhip_jacobi_async(src, dst, B, size, innerFidx, gc, cf, ac1, d_res->pass, 0, skip);  // :58
       if (!Comm_S(dst, skip)) return 0;                                             // :63
       if (converge_check && !fused_check && !reduce_test(1, itr, skip)) return 0;  // :67-77
       done = 1;
@@ -963,13 +974,13 @@ int CZ::JACOBI(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, doubl
   return fused_end(L, X, itr_max, res, [&](const Launch& l, int k, REAL_TYPE* s, REAL_TYPE* d) {
     // k + 1 sweeps from the launch's source: a triple, a pair, or one plain sweep
     if (k >= 1) {
-      if (!jacobi_pass(k + 1, s, d, d_res + 4, false, 0, 0)) {
+      if (!jacobi_pass(k + 1, s, d, d_res->rerun, false, 0, 0)) {
         cz_fatal(1, "error : %s refused after a successful probe\n", k == 2 ? "the three-sweep pass" : "fused pass");
       }
     } else if (maf) {  // the first sweep of a fused pass: one plain sweep
-      jacobi_maf_async(s, d, B, size, innerFidx, gc, d_xc, d_yc, d_zc, ac1, d_res + 4, nullptr, 0, 0.0, 0.0, 0, nullptr, nullptr, nullptr);
+      jacobi_maf_async(s, d, B, size, innerFidx, gc, d_xc, d_yc, d_zc, ac1, d_res->rerun, nullptr, 0, 0.0, 0.0, 0, nullptr, nullptr, nullptr);
     } else {
-      czhip_jacobi_async(s, d, B, size, innerFidx, gc, cf, ac1, d_res + 4, 0, nullptr);
+      czhip_jacobi_async(s, d, B, size, innerFidx, gc, cf, ac1, d_res->rerun, 0, nullptr);
     }
   });
 }
@@ -994,7 +1005,7 @@ int CZ::RBSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double
   // exchange two ghost layers once per iteration.  SINGLE: the reference's two in-place colour launches with an exchange after each colour.
   // Round 4: TWO iterations per pass over memory (rb4_k) where the whole inner box is one launch of one rank with constant coefficients.
   const bool rb4 = plan.kind == PassPlan::WHOLE && numProc == 1 && !maf &&
-                   czhip_rbsor4_async(X, WRK, B, size, innerFidx, gc, cf, ip, ac1, d_res, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 1) != 0;
+                   czhip_rbsor4_async(X, WRK, B, size, innerFidx, gc, cf, ip, ac1, d_res->pass, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 1) != 0;
   rb4_passes = 0;
   bool stop = false;
   int itr = 1;
@@ -1006,18 +1017,18 @@ int CZ::RBSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double
     if (plan.kind == PassPlan::SPLIT) {
       if (!split_pass(L, rb_par(gc, innerFidx, ip), 1, itr, mpp)) return 0;
     } else if (plan.kind == PassPlan::WHOLE && rb4 && itr + 1 <= itr_max && !(plan.zero_start && itr == 1)) {
-      if (!czhip_rbsor4_async(src, dst, B, size, innerFidx, gc, cf, ip, ac1, d_res, res_normal, eps, itr, in_kernel_check ? d_hist : nullptr, d_flag,
-                              d_flag + 1, skip, 0)) {  // :205-209 twice (+ :218-230 for both iterations)
+      if (!czhip_rbsor4_async(src, dst, B, size, innerFidx, gc, cf, ip, ac1, d_res->pass, res_normal, eps, itr, in_kernel_check ? d_hist : nullptr,
+                              &d_flag->converged, &d_flag->iteration, skip, 0)) {  // :205-209 twice (+ :218-230 for both iterations)
         cz_fatal(1, "error : the two-iteration red-black pass refused after a successful probe\n");
       }
       done = 2;
       rb4_passes++;
     } else if (plan.kind == PassPlan::WHOLE) {
       const int launched = (plan.zero_start && itr == 1) ? zero_start_pass(src, dst, B, made, ip)
-                           : maf ? pair_maf_async(src, dst, B, size, innerFidx, idx1, gc, d_xc, d_yc, d_zc, ac1, ip, d_res, res_normal, eps, itr,
-                                                in_kernel_check ? d_hist : nullptr, d_flag, d_flag + 1, skip)  // :190-200
-                               : czhip_rbsor2_async(src, dst, B, size, innerFidx, idx1, gc, cf, ip, ac1, d_res, res_normal, eps, itr,
-                                                    in_kernel_check ? d_hist : nullptr, d_flag, d_flag + 1, skip);  // :205-209 (+ :218-230)
+                           : maf ? pair_maf_async(src, dst, B, size, innerFidx, idx1, gc, d_xc, d_yc, d_zc, ac1, ip, d_res->pass, res_normal, eps, itr,
+                                                in_kernel_check ? d_hist : nullptr, &d_flag->converged, &d_flag->iteration, skip)  // :190-200
+                               : czhip_rbsor2_async(src, dst, B, size, innerFidx, idx1, gc, cf, ip, ac1, d_res->pass, res_normal, eps, itr,
+                                                    in_kernel_check ? d_hist : nullptr, &d_flag->converged, &d_flag->iteration, skip);  // :205-209 (+ :218-230)
       if (!launched) {
         cz_fatal(1, "error : fused red-black iteration refused after a successful probe\n");
       }
@@ -1025,13 +1036,13 @@ int CZ::RBSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double
     } else {
       for (int color = 0; color < 2; color++) {  // :205-209
         if (maf)
-          rbsor_maf_async(X, B, size, innerFidx, gc, d_xc, d_yc, d_zc, ip, color, ac1, d_res, color, skip,
-                          (in_kernel_check && color == 1) ? 1 : 0, res_normal, eps, itr, d_hist, d_flag, d_flag + 1);
+          rbsor_maf_async(X, B, size, innerFidx, gc, d_xc, d_yc, d_zc, ip, color, ac1, d_res->pass, color, skip,
+                          (in_kernel_check && color == 1) ? 1 : 0, res_normal, eps, itr, d_hist, &d_flag->converged, &d_flag->iteration);
         else if (in_kernel_check && color == 1)
-          czhip_rbsor_checked_async(X, B, size, innerFidx, gc, cf, ip, color, ac1, d_res, 1, res_normal, eps, itr, d_hist,
-                                    d_flag, d_flag + 1);
+          czhip_rbsor_checked_async(X, B, size, innerFidx, gc, cf, ip, color, ac1, d_res->pass, 1, res_normal, eps, itr, d_hist,
+                                    &d_flag->converged, &d_flag->iteration);
         else
-          czhip_rbsor_async(X, B, size, innerFidx, gc, cf, ip, color, ac1, d_res, color, skip);
+          czhip_rbsor_async(X, B, size, innerFidx, gc, cf, ip, color, ac1, d_res->pass, color, skip);
         // the reference exchanges once per iteration (:215); exchanging after each colour makes the decomposed run
         // identical to the single-domain one
         if (!Comm_S(X, skip)) return 0;
@@ -1047,7 +1058,7 @@ int CZ::RBSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double
   }
   // the first iteration of a two-iteration pass converged: one fused iteration
   return fused_end(L, X, itr_max, res, [&](const Launch&, int, REAL_TYPE* s, REAL_TYPE* d) {
-    if (!czhip_rbsor2_async(s, d, B, size, innerFidx, idx1, gc, cf, ip, ac1, d_res + 4, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr)) {
+    if (!czhip_rbsor2_async(s, d, B, size, innerFidx, idx1, gc, cf, ip, ac1, d_res->rerun, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr)) {
       cz_fatal(1, "error : fused red-black iteration refused after a successful probe\n");
     }
   });
@@ -1061,13 +1072,13 @@ int CZ::PSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double&
   const int* skip = nullptr;
   if (converge_check) {
     ensure_hist(itr_max + 2);
-    HIP_CHECK(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), stream()));
-    skip = d_flag;
+    HIP_CHECK(hipMemsetAsync(d_flag, 0, offsetof(CzFlags, snap), stream()));  // flag, iteration
+    skip = &d_flag->converged;
   }
   FlagPoll poll(*this, false);
   bool stop = false;
   for (int itr = 1; itr <= itr_max && !stop; itr++) {
-    psor_async(X, B, size, innerFidx, gc, cf, maf ? d_xc : nullptr, d_yc, d_zc, ac1, d_res, 0, skip);  // :108-122
+    psor_async(X, B, size, innerFidx, gc, cf, maf ? d_xc : nullptr, d_yc, d_zc, ac1, d_res->pass, 0, skip);  // :108-122
     flop += (maf ? 66.0 : 18.0) * npts();
     if (!Comm_S(X, skip)) return 0;  // :124 (decomposed: block-local sweeps, ghosts of the last exchange)
     if (converge_check) {
@@ -1100,7 +1111,7 @@ int CZ::line_stages() {
 // reference's sequential test is kept as is.  1: converged, 0: go on, -1: failed (message printed).
 int CZ::line_test(int itr, int s_type) {
   if (!reduce_test(1, itr)) return -1;
-  HIP_CHECK(hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, stream()));
+  HIP_CHECK(hipMemcpyAsync(h_flag, &d_flag->converged, sizeof(int), hipMemcpyDeviceToHost, stream()));
   if (sweep_failed(printMethod(s_type))) return -1;  // (synchronises)
   return h_flag[0] ? 1 : 0;
 }
@@ -1123,9 +1134,9 @@ bool CZ::line_iteration(const cz_solvers::Line& d, REAL_TYPE* X, REAL_TYPE* B, i
   const int gc = GUIDE;
   auto launch = [&](int par, int slot) {
     switch (d.kernel) {
-      case cz_solvers::PCR_RB: pcr_rb_async(X, MSK, B, size, innerFidx, gc, pn, par, ac1, d_res, slot); break;
-      case cz_solvers::PCR_VARIANT: pcr_variant_async(X, d.order == 2 ? WRK : nullptr, MSK, B, size, innerFidx, gc, pn, d.order, par, d.final4, ac1, d_res, slot); break;
-      case cz_solvers::PCR_MAF: pcr_maf_async(X, MSK, B, size, innerFidx, gc, pn, d.order, par, d_xc, d_yc, d_zc, ac1, d_res, slot); break;
+      case cz_solvers::PCR_RB: pcr_rb_async(X, MSK, B, size, innerFidx, gc, pn, par, ac1, d_res->pass, slot); break;
+      case cz_solvers::PCR_VARIANT: pcr_variant_async(X, d.order == 2 ? WRK : nullptr, MSK, B, size, innerFidx, gc, pn, d.order, par, d.final4, ac1, d_res->pass, slot); break;
+      case cz_solvers::PCR_MAF: pcr_maf_async(X, MSK, B, size, innerFidx, gc, pn, d.order, par, d_xc, d_yc, d_zc, ac1, d_res->pass, slot); break;
       case cz_solvers::NO_LINE: break;
     }
   };
@@ -1160,7 +1171,7 @@ int CZ::LSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double&
   const int pn = line_stages();
   if (converge_check) {
     ensure_hist(itr_max + 2);
-    HIP_CHECK(hipMemsetAsync(d_flag, 0, 2 * sizeof(int), stream()));
+    HIP_CHECK(hipMemsetAsync(d_flag, 0, offsetof(CzFlags, snap), stream()));  // flag, iteration
   }
   int itr;
   for (itr = 1; itr <= itr_max; itr++) {
@@ -1178,22 +1189,20 @@ int CZ::LSOR(double& res, REAL_TYPE* X, REAL_TYPE* B, const int itr_max, double&
 // cz_Poisson.cpp:239-270.  The reference reduces in REAL on every rank and all-reduces the REAL; here the double
 // partial sums are all-reduced and rounded to REAL once.
 REAL_TYPE CZ::Fdot1(REAL_TYPE* x, double& flop) {
-  dot1_async(x, size, innerFidx, GUIDE, d_res + 1);
+  dot1_async(x, size, innerFidx, GUIDE, &d_res->fdot);
   return dot_read(flop);
 }
 
 REAL_TYPE CZ::Fdot2(REAL_TYPE* x, REAL_TYPE* y, double& flop) {
-  dot2_async(x, y, size, innerFidx, GUIDE, d_res + 1);
+  dot2_async(x, y, size, innerFidx, GUIDE, &d_res->fdot);
   return dot_read(flop);
 }
 
 // the partial sums of the dot product just launched: all-reduced, read back, rounded
 REAL_TYPE CZ::dot_read(double& flop) {
   flop += 2.0 * npts();
-  if (!Comm_SUM_dev(d_res + 1, 1)) exit(0);
-  HIP_CHECK(hipMemcpyAsync(h_scal + 1, d_res + 1, sizeof(double), hipMemcpyDeviceToHost, stream()));
-  HIP_CHECK(hipStreamSynchronize(stream()));
-  return (REAL_TYPE)h_scal[1];
+  if (!Comm_SUM_dev(&d_res->fdot, 1)) exit(0);
+  return (REAL_TYPE)*fetch(&d_res->fdot);
 }
 
 // The work vectors the preconditioner solves into are allocated zero-filled and afterwards only written on the inner box,
@@ -1211,7 +1220,7 @@ bool CZ::bicg_fusable(int pc_type) {
   const PassPlan plan = plan_pass(pcg_p_, pcg_p, pc_type, 8, false, true, rb, true);
   if (!(plan.kind == PassPlan::WHOLE && plan.zero_start)) return false;
   return czhip_jacobi2_from_zero_made_async(pcg_p_, WRK, pcg_s, 2, pcg_r, pcg_q, pcg_p, (REAL_TYPE)0, (REAL_TYPE)0, size, innerFidx, idx1, GUIDE, cf, ac1,
-                                            rb ? 0 : -1, d_res, 1) != 0;
+                                            rb ? 0 : -1, d_res->pass, 1) != 0;
 }
 
 void CZ::Preconditioner(REAL_TYPE* xx, REAL_TYPE* bb, double& flop, int s_type, const BMade* made) {
@@ -1259,9 +1268,8 @@ int CZ::PBiCGSTAB(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop, int s_t
   MafPtrs mp{d_xc, d_yc, d_zc, pvt};
   auto fetch2 = [&](double* d_two, REAL_TYPE& a, REAL_TYPE& b2) -> bool {  // all-reduce + D2H of two device doubles
     if (!Comm_SUM_dev(d_two, 2)) return false;
-    HIP_CHECK(hipMemcpyAsync(h_scal + 2, d_two, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    a = (REAL_TYPE)h_scal[2], b2 = (REAL_TYPE)h_scal[3];
+    const double* const two = fetch(d_two, 2);
+    a = (REAL_TYPE)two[0], b2 = (REAL_TYPE)two[1];
     return true;
   };
   REAL_TYPE rho_next = 0.0;
@@ -1269,9 +1277,10 @@ int CZ::PBiCGSTAB(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop, int s_t
   // where it is the whole-box fused pass from a literal zero: one launch and one read of an array less per solve.
   const bool fuse = !maf && bicg_fusable(pc_type);
   bicg_fused = 0;
-  // alpha / omega on the device between their dot products and their users (bicg_scalar_async): d_res[12..15] holds alpha, omega, -alpha, -omega
-  // as REALs.  CZ_BICG_DEVSC=0: the host computes them from read-back dot products as in rounds 1-2 (and as the reference does).
-  REAL_TYPE* const d_bs = reinterpret_cast<REAL_TYPE*>(d_res + 12);
+  // alpha / omega on the device between their dot products and their users (bicg_scalar_async): d_res->sc holds alpha, omega, -alpha, -omega
+  // as REALs (ScBicg).  CZ_BICG_DEVSC=0: the host computes them from read-back dot products as in rounds 1-2 (and as the reference does).
+  REAL_TYPE* const d_bs = d_res->sc;
+  CzScalars::Bicg* const dots = &d_res->bicg;  // q.r0, t.s / t.t, r.r / r.r0
   const bool devsc = cfg.on(CZV_BICG_DEVSC, true);
   bool pc_copy = !cz_solvers::row(pc_type).precond_runs;  // Preconditioner() would copy (cz_Poisson.cpp:318-320)
   if (!cfg.on(CZV_BICG_ALIAS, true)) pc_copy = false;  // (the copy is made: A/B and the bit-equality test)
@@ -1316,23 +1325,23 @@ int CZ::PBiCGSTAB(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop, int s_t
     if (line_error) return 0;
 
     // :417/:421 q = A p_  and  :427 q.r0
-    calc_ax_dots_async(pcg_q, p_, pcg_r0, size, innerFidx, gc, cf, maf ? &mp : nullptr, d_res + 2);
+    calc_ax_dots_async(pcg_q, p_, pcg_r0, size, innerFidx, gc, cf, maf ? &mp : nullptr, dots->q_r0);
     flop += (maf ? 63.0 : 13.0) * npts() + 2.0 * npts();
     REAL_TYPE r_alpha = (REAL_TYPE)0;
     if (devsc) {
       // alpha = rho / (q . r0) (:427) is made on the device and read there by the launches that need it; the host reads it back with omega and
       // the residual at the end of the iteration (one wait instead of three: 2 x 25-35 us of idle GPU per iteration, a fifth of an iteration at 128^3)
-      if (!Comm_SUM_dev(d_res + 2, 2)) return 0;
-      bicg_scalar_async(1, d_res + 2, rho, d_bs);
+      if (!Comm_SUM_dev(dots->q_r0, 2)) return 0;
+      bicg_scalar_async(1, dots->q_r0, rho, d_bs);
     } else {
       REAL_TYPE q_r0, q_q;
-      if (!fetch2(d_res + 2, q_r0, q_q)) return 0;
+      if (!fetch2(dots->q_r0, q_r0, q_q)) return 0;
       alpha = rho / q_r0;  // :427
       r_alpha = -alpha;
     }
-    BMade made_s{1, pcg_q, pcg_r, nullptr, r_alpha, (REAL_TYPE)0, devsc ? d_bs + 2 : nullptr};
+    BMade made_s{1, pcg_q, pcg_r, nullptr, r_alpha, (REAL_TYPE)0, devsc ? d_bs + SC_B_NALPHA : nullptr};
     if (fuse) bicg_fused++;  // :434 withheld likewise: s = r - alpha q
-    else triad_async(pcg_s, pcg_q, pcg_r, r_alpha, size, innerFidx, gc, devsc ? d_bs + 2 : nullptr);  // :434
+    else triad_async(pcg_s, pcg_q, pcg_r, r_alpha, size, innerFidx, gc, devsc ? d_bs + SC_B_NALPHA : nullptr);  // :434
     flop += 2.0 * npts();
     if (!Comm_S(pcg_s)) return 0;  // :438
 
@@ -1343,34 +1352,32 @@ int CZ::PBiCGSTAB(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop, int s_t
     if (line_error) return 0;
 
     // :453/:457 t_ = A s_  and  :464 t_.s, t_.t_
-    calc_ax_dots_async(pcg_t_, s_, pcg_s, size, innerFidx, gc, cf, maf ? &mp : nullptr, d_res + 4);
+    calc_ax_dots_async(pcg_t_, s_, pcg_s, size, innerFidx, gc, cf, maf ? &mp : nullptr, dots->t_s);
     flop += (maf ? 63.0 : 13.0) * npts() + 4.0 * npts();
     if (devsc) {
-      if (!Comm_SUM_dev(d_res + 4, 2)) return 0;
-      bicg_scalar_async(2, d_res + 4, (REAL_TYPE)0, d_bs);  // omega = (t . s) / (t . t)  :464
+      if (!Comm_SUM_dev(dots->t_s, 2)) return 0;
+      bicg_scalar_async(2, dots->t_s, (REAL_TYPE)0, d_bs);  // omega = (t . s) / (t . t)  :464
     } else {
       REAL_TYPE ts, tt;
-      if (!fetch2(d_res + 4, ts, tt)) return 0;
+      if (!fetch2(dots->t_s, ts, tt)) return 0;
       omega = ts / tt;  // :464
       r_omega = -omega;
     }
 
-    bicg2_async(X, p_, s_, alpha, omega, size, innerFidx, gc, devsc ? d_bs : nullptr, devsc ? d_bs + 1 : nullptr);  // :470
+    bicg2_async(X, p_, s_, alpha, omega, size, innerFidx, gc, devsc ? d_bs + SC_B_ALPHA : nullptr, devsc ? d_bs + SC_B_OMEGA : nullptr);  // :470
     flop += 4.0 * npts();
     // :476 r = s - omega t_  with  :481 res = r.r  and the next :376 rho = r.r0
-    triad_dots_async(pcg_r, pcg_t_, pcg_s, pcg_r0, r_omega, size, innerFidx, gc, d_res + 6, devsc ? d_bs + 3 : nullptr);
+    triad_dots_async(pcg_r, pcg_t_, pcg_s, pcg_r0, r_omega, size, innerFidx, gc, dots->r_r, devsc ? d_bs + SC_B_NOMEGA : nullptr);
     flop += 2.0 * npts() + 2.0 * npts();
     REAL_TYPE rr;
     if (devsc) {  // the one wait of the iteration: r.r, r.r0 and the two scalars the next beta needs
-      if (!Comm_SUM_dev(d_res + 6, 2)) return 0;
-      HIP_CHECK(hipMemcpyAsync(h_scal + 2, d_res + 6, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-      HIP_CHECK(hipMemcpyAsync(h_scal + 12, d_res + 12, 2 * sizeof(REAL_TYPE), hipMemcpyDeviceToHost, st));
-      HIP_CHECK(hipStreamSynchronize(st));
-      rr = (REAL_TYPE)h_scal[2], rho_next = (REAL_TYPE)h_scal[3];
-      const REAL_TYPE* hs = reinterpret_cast<const REAL_TYPE*>(h_scal + 12);
-      alpha = hs[0], omega = hs[1];
+      if (!Comm_SUM_dev(dots->r_r, 2)) return 0;
+      const double* const two = fetch_queued(dots->r_r, 2);
+      const REAL_TYPE* const hs = fetch(d_bs, 2);  // (alpha and omega are neighbours: SC_B_ALPHA, SC_B_OMEGA)
+      rr = (REAL_TYPE)two[0], rho_next = (REAL_TYPE)two[1];
+      alpha = hs[SC_B_ALPHA], omega = hs[SC_B_OMEGA];
       r_omega = -omega;
-    } else if (!fetch2(d_res + 6, rr, rho_next)) {
+    } else if (!fetch2(dots->r_r, rr, rho_next)) {
       return 0;
     }
     res = rr;
@@ -1393,183 +1400,196 @@ int CZ::PBiCGSTAB(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop, int s_t
 //   r = b - A x;  for itr = 1 .. ItrMax:  z = M^-1 r;  rho = r.z;  p = z (itr 1) | z + beta p, beta = rho / rho_old;  q = A p;
 //   alpha = rho / p.q;  x = alpha p + x;  r = (-alpha) q + r;  res = sqrt(r.r * res_normal)
 // Every scalar is made on the device (cg_scal_k) from REAL-rounded double sums, so the host waits once per iteration, for r.r and rho.
-// Breakdown: |rho| < FLT_MIN (absolute, in both precisions) ends the solve with itr = 0 BEFORE the iteration's update of x and r.  none:
-// the host holds rho before the first launch.  jacobi | mg | mgrb: the host reads rho at the iteration's one wait, after the update pass was
-// launched, so that pass carries the test itself (cg_update_guarded_async: it stores nothing under the threshold); the unfused update
-// (CZ_CG_FUSE=0) waits for rho before its triads instead.  pcg_void_start (cz_info 24): the breakdown came at iteration 1 -- x is the caller's.
-// CZ_CG_FUSE (default on): x, r and r.r in one pass (czhip_cg_update_async); in a single-domain run also the direction update inside the
-// SpMV pass (czhip_cg_dir_ax_async, ping-pong between cg_p[0] and cg_p[1]).  Off, and for the direction in decomposed runs: the update,
-// Comm_S(p), then the SpMV with its dot folded in.
-int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
-  const int gc = GUIDE;
-  hipStream_t st = stream();
-  const size_t nbytes = padded_cells() * sizeof(REAL_TYPE);
-  const double n = npts();
-  const bool pc = pc_type == LS_JACOBI || pc_type == LS_MG || pc_type == LS_MGRB;
-  const bool fuse = cfg.on(CZV_CG_FUSE, true);
-  // the direction pass reads z's and p's shells as zeros: single domain only, and no Neumann face (whose layer of p is the mirror)
-  // (nor a periodic direction, whose layer is the wrap)
-  // face coefficients: A_beta where the operator is applied (the start and the SpMV, which stays unfused), and the
-  // preconditioner z = s M^-1 (s r) with M^-1 the constant-coefficient one below (cg_q is free for s r at that point)
-  const bool coef = coef_on();
-  // the coefficients inside the hierarchy (cz_set_coef_mg): z = M_beta^-1 r, no scaling either side
-  const bool scale = coef && !coef_mg_on();
-  const bool fuse_dir = fuse && numProc == 1 && !bc.any() && !coef;
-  REAL_TYPE* const sc = reinterpret_cast<REAL_TYPE*>(d_res + 12);  // alpha, -alpha, beta, rho (cg_scal_k)
-  double* const d_rr = d_res + 5;
-  double* const d_pq = d_res + 3;                 // (the unfused SpMV writes q.q to d_res[4])
-  double* const d_rho = pc ? d_res + 2 : d_rr;    // none: rho is the r.r of the previous update
-  REAL_TYPE* const z = pc ? cg_z : cg_r;
-  // the closed box: sc[4] the lagged mean of the residual, sc[5] / sc[6] the means of steps 1 and 3 as cz_closed_mean reports them
-  const bool closed = closed_box != 0;
-  double* const d_cl = d_res + 20;                // (project's two sums)
-  res = 0.0;
-  cg_fused = 0;
-  mg_cycles = 0;
-  pcg_void_start = 0;
+// Breakdown (cg_breakdown): |rho| < FLT_MIN (absolute, in both precisions) ends the solve with itr = 0 BEFORE the iteration's update of x and
+// r.  none: the host holds rho before the first launch.  jacobi | mg | mgrb: the host reads rho at the iteration's one wait, after the update
+// pass was launched, so that pass carries the test itself (cg_update_guarded_async: it stores nothing under the threshold); the unfused
+// update (CZ_CG_FUSE=0) waits for rho before its triads instead.
+// The steps below are the lines of that algorithm, each with its operation count beside its launches; CgMode (cz_driver.h): the modes, decided once
+// The operator in constant or face-coefficient form: out = A p with p.out, out.out in dots[0], dots[1] (b null), or out = b - A p (the
+// coefficient form leaves two sums in dots that nobody reads; the constant form none).  false: the launch was refused
+bool CZ::cg_apply_A(REAL_TYPE* out, REAL_TYPE* p, const REAL_TYPE* b, double* dots) {
+  if (coef_on()) return coef_ax_async(b ? 1 : 0, out, p, b, coef_b[0], coef_b[1], coef_b[2], size, innerFidx, GUIDE, dots) != 0;
+  if (b) calc_rk_async(out, p, b, size, innerFidx, GUIDE, cf);
+  else calc_ax_dots_async(out, p, p, size, innerFidx, GUIDE, cf, nullptr, dots);
+  return true;
+}
 
+// true: the solve ends with itr = 0; pcg_void_start (cz_info 24): the breakdown came at iteration 1 -- x is the caller's
+bool CZ::cg_breakdown(REAL_TYPE rho, int itr) {
+  if (!(fabs(rho) < FLT_MIN)) return false;
+  pcg_void_start = itr == 1;
+  return true;
+}
+
+// Start: r = b - A x (14 per cell, 23 with coefficients); the closed box's step 1 (4 per cell): the initial residual into the range of the
+// operator -- the pass that writes r' returns sum r' (the first lagged mean) and sum r'^2; none: the one r.r that no update made -> rho
+bool CZ::cg_start(const CgMode& m, REAL_TYPE* X, const REAL_TYPE* B, REAL_TYPE& rho, double& flop) {
+  const double n = npts();
+  REAL_TYPE* const sc = d_res->sc;
   mirror(X);
-  if (!coef) calc_rk_async(cg_r, X, B, size, innerFidx, gc, cf);
-  else if (!coef_ax_async(1, cg_r, X, B, coef_b[0], coef_b[1], coef_b[2], size, innerFidx, gc, d_res + 10)) return 0;
-  flop += (coef ? 23.0 : 14.0) * n;
-  if (closed) {
-    // step 1: the initial residual into the range of the operator; the pass that writes r' returns sum r' (the first lagged mean, sc[4])
-    // and sum r'^2 (none: the one r.r that no update made)
-    if (!project(cg_r, sc + 4, sc + 5) || !Comm_SUM_dev(d_cl, 2)) return 0;
-    mean_scalar_async(d_cl, g_npts, sc + 4, nullptr);
+  if (!cg_apply_A(cg_r, X, B, d_res->cg_r0)) return false;
+  flop += (m.coef ? 23.0 : 14.0) * n;
+  if (m.closed) {
+    if (!project(cg_r, sc + SC_LAG_MEAN, &d_res->closed_mean[0]) || !Comm_SUM_dev(d_res->project, 2)) return false;
+    mean_scalar_async(d_res->project, g_npts, sc + SC_LAG_MEAN, nullptr);
     flop += 4.0 * n;
   }
-  if (!Comm_S(cg_r)) return 0;
-  REAL_TYPE rho = (REAL_TYPE)0;
-  if (!pc) {  // the one r.r that no update made
-    if (closed) {
-      HIP_CHECK(hipMemcpyAsync(d_rr, d_cl + 1, sizeof(double), hipMemcpyDeviceToDevice, st));
-    } else {
-      dot1_async(cg_r, size, innerFidx, gc, d_rr);
-      flop += 2.0 * n;
-      if (!Comm_SUM_dev(d_rr, 1)) return 0;
-    }
-    HIP_CHECK(hipMemcpyAsync(h_scal + 5, d_rr, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    rho = (REAL_TYPE)h_scal[5];
+  if (!Comm_S(cg_r)) return false;
+  if (m.pc) return true;
+  if (m.closed) {
+    HIP_CHECK(hipMemcpyAsync(&d_res->cg.rr, &d_res->project[1], sizeof(double), hipMemcpyDeviceToDevice, stream()));
+  } else {
+    dot1_async(cg_r, size, innerFidx, GUIDE, &d_res->cg.rr);
+    flop += 2.0 * n;
+    if (!Comm_SUM_dev(&d_res->cg.rr, 1)) return false;
   }
+  rho = (REAL_TYPE)*fetch(&d_res->cg.rr);
+  return true;
+}
+
+// z = M^-1 rin, or with the scaling either side z = s M^-1 (s r) (1 per cell each): the single-domain cycle, the distributed cycle, under
+// a mask the 8 relaxed sweeps from zero as single sweeps (8 x 18 per cell), or Preconditioner's 8 sweeps (its own count)
+bool CZ::cg_apply_M(const CgMode& m, double& flop) {
+  const double n = npts();
+  REAL_TYPE* const rin = m.scale ? cg_q : cg_r;  // what M^-1 is applied to
+  if (m.scale) {
+    coef_scale_async(cg_q, cg_r, coef_s, size, GUIDE);
+    flop += n;
+  }
+  if (mg || mgd) {
+    if (mg ? !czhip_mg_apply_async(mg, cg_z, rin, ac1) : !mgd_apply(mgd, cg_z, rin, ac1)) return false;  // z = V_0(r)
+    mg_cycles++;
+  } else if (bc.any()) {
+    // between cg_z and cg_p[1] (free: the direction is not fused), the exchange and the mirror before every sweep that reads its input
+    HIP_CHECK(hipMemsetAsync(cg_z, 0, padded_cells() * sizeof(REAL_TYPE), stream()));
+    REAL_TYPE *src = cg_z, *dst = cg_p[1];
+    for (int s = 0; s < 8; s++) {
+      if (s) {
+        if (!Comm_S(src)) return false;
+        mirror(src);
+      }
+      czhip_jacobi_async(src, dst, rin, size, innerFidx, GUIDE, cf, ac1, d_res->pass, 0, nullptr);
+      std::swap(src, dst);
+    }
+    flop += 8 * 18.0 * n;
+  } else {
+    double fc = 0.0;
+    Preconditioner(cg_z, rin, fc, LS_JACOBI);
+    flop += fc;
+  }
+  if (m.scale) {
+    coef_scale_async(cg_z, cg_z, coef_s, size, GUIDE);
+    flop += n;
+  }
+  return true;
+}
+
+// Precondition: z = M^-1 r, then rho = r.z (2 per cell)
+bool CZ::cg_precondition(const CgMode& m, double& flop) {
+  if (!Comm_S(cg_r) || !cg_apply_M(m, flop)) return false;  // (the exchange: a decomposed pass reads the right-hand side in its ghost layer)
+  dot2_async(cg_r, cg_z, size, innerFidx, GUIDE, m.d_rho);
+  flop += 2.0 * npts();
+  return Comm_SUM_dev(m.d_rho, 1);
+}
+
+// Direction and SpMV: rho and beta = rho / rho_old on the device; p = z (iteration 1) | beta p + z (2 per cell) and q = A p with p.q (13 + 2
+// per cell, 22 + 2 with coefficients) in the fused pass, or as copy / triad, exchange, mirror, operator; then alpha = rho / p.q.  cg_p[cur] is p
+bool CZ::cg_direction(const CgMode& m, int itr, int& cur, double& flop) {
+  const double n = npts();
+  REAL_TYPE* const sc = d_res->sc;
+  cg_scalar_async(0, m.d_rho, itr == 1, sc);
+  if (m.fuse_dir) {
+    czhip_cg_dir_ax_async(cg_p[cur ^ 1], cg_q, m.z, cg_p[cur], itr == 1 ? nullptr : sc + SC_BETA, size, innerFidx, GUIDE, cf, &d_res->cg.pq);
+    cur ^= 1;
+    cg_fused++;
+  } else {
+    if (itr == 1) HIP_CHECK(hipMemcpyAsync(cg_p[cur], m.z, padded_cells() * sizeof(REAL_TYPE), hipMemcpyDeviceToDevice, stream()));
+    else triad_async(cg_p[cur], cg_p[cur], m.z, (REAL_TYPE)0, size, innerFidx, GUIDE, sc + SC_BETA);
+    if (!Comm_S(cg_p[cur])) return false;
+    mirror(cg_p[cur]);
+    if (!cg_apply_A(cg_q, cg_p[cur], nullptr, &d_res->cg.pq)) return false;  // (the unfused SpMV writes q.q to cg.qq)
+  }
+  if (itr > 1) flop += 2.0 * n;
+  flop += (m.coef ? 22.0 : 13.0) * n + 2.0 * n;
+  if (!Comm_SUM_dev(&d_res->cg.pq, 1)) return false;
+  cg_scalar_async(1, &d_res->cg.pq, 0, sc);
+  return true;
+}
+
+// Update: x = alpha p + x, r = (-alpha) q + r, r.r (6 per cell).  Closed: r = ((-alpha) q + r) - the lagged mean, sum r^2 and sum r side by
+// side: one all-reduce, then the mean the next update removes.  Fused: one guarded pass.  Unfused: the triads carry no test of their
+// own, so the host learns rho before them.  1: launched, 0: failed, -1: breakdown (nothing updated)
+int CZ::cg_update(const CgMode& m, REAL_TYPE* X, const REAL_TYPE* p, int itr, double& flop) {
+  REAL_TYPE* const sc = d_res->sc;
+  double* const d_rr = &d_res->cg.rr;
+  if (m.closed || m.fuse) {
+    cg_update_guarded_async(m.closed, X, cg_r, p, cg_q, sc, size, innerFidx, GUIDE, d_rr);
+  } else {
+    if (m.pc && cg_breakdown((REAL_TYPE)*fetch(m.d_rho), itr)) return -1;
+    triad_async(X, p, X, (REAL_TYPE)0, size, innerFidx, GUIDE, sc + SC_ALPHA);
+    triad_async(cg_r, cg_q, cg_r, (REAL_TYPE)0, size, innerFidx, GUIDE, sc + SC_NALPHA);
+    dot1_async(cg_r, size, innerFidx, GUIDE, d_rr);
+  }
+  flop += 6.0 * npts();
+  if (!Comm_SUM_dev(d_rr, m.closed ? 2 : 1)) return 0;
+  if (m.closed) mean_scalar_async(&d_res->cg.rsum, g_npts, sc + SC_LAG_MEAN, nullptr);
+  return 1;
+}
+
+// End: the closed box's step 3 (3 per cell), the answer of zero mean (the sums read owned cells only; the exchange carries the shifted
+// values into the ghost layers) and the two means for cz_closed_mean; the ghost layers of the result, as PBiCGSTAB leaves them
+bool CZ::cg_end(const CgMode& m, REAL_TYPE* X, double& flop) {
+  if (m.closed) {
+    if (!project(X, &d_res->closed_mean[1], nullptr)) return false;
+    flop += 3.0 * npts();
+    const REAL_TYPE* const hm = fetch(d_res->closed_mean, 2);
+    closed_m[1] = (double)hm[0], closed_m[2] = (double)hm[1];
+  }
+  if (!Comm_S(X)) return false;
+  mirror(X);
+  return true;
+}
+
+int CZ::PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop) {
+  CgMode m;
+  m.pc = pc_type == LS_JACOBI || pc_type == LS_MG || pc_type == LS_MGRB;
+  m.fuse = cfg.on(CZV_CG_FUSE, true);
+  m.coef = coef_on();
+  m.scale = m.coef && !coef_mg_on();
+  m.fuse_dir = m.fuse && numProc == 1 && !bc.any() && !m.coef;
+  m.closed = closed_box != 0;
+  m.z = m.pc ? cg_z : cg_r;
+  m.d_rho = m.pc ? &d_res->cg.rho : &d_res->cg.rr;
+  res = 0.0;
+  cg_fused = mg_cycles = pcg_void_start = 0;
+  REAL_TYPE rho = (REAL_TYPE)0;
+  if (!cg_start(m, X, B, rho, flop)) return 0;
   int cur = 0;  // cg_p[cur] is p
   int itr;
   for (itr = 1; itr <= ItrMax; itr++) {
-    if (!pc && fabs(rho) < FLT_MIN) {  // breakdown (as PBiCGSTAB)
-      pcg_void_start = itr == 1;
+    if (!m.pc && cg_breakdown(rho, itr)) {  // (none: the host holds rho before the first launch; as PBiCGSTAB)
       itr = 0;
       break;
     }
-    if (pc) {
-      if (!Comm_S(cg_r)) return 0;  // (a decomposed pass reads the right-hand side in its ghost layer)
-      REAL_TYPE* const rin = scale ? cg_q : cg_r;  // what M^-1 is applied to
-      if (scale) {
-        coef_scale_async(cg_q, cg_r, coef_s, size, gc);
-        flop += n;
-      }
-      if (mg || mgd) {
-        if (mg ? !czhip_mg_apply_async(mg, cg_z, rin, ac1) : !mgd_apply(mgd, cg_z, rin, ac1)) return 0;  // z = V_0(r)
-        mg_cycles++;
-      } else if (bc.any()) {
-        // the 8 relaxed sweeps from zero as single sweeps between cg_z and cg_p[1] (free: the direction is not fused), the exchange and the
-        // mirror before every sweep that reads its input
-        HIP_CHECK(hipMemsetAsync(cg_z, 0, nbytes, st));
-        REAL_TYPE *src = cg_z, *dst = cg_p[1];
-        for (int s = 0; s < 8; s++) {
-          if (s) {
-            if (!Comm_S(src)) return 0;
-            mirror(src);
-          }
-          czhip_jacobi_async(src, dst, rin, size, innerFidx, gc, cf, ac1, d_res, 0, nullptr);
-          std::swap(src, dst);
-        }
-        flop += 8 * 18.0 * n;
-      } else {
-        double fc = 0.0;
-        Preconditioner(cg_z, rin, fc, LS_JACOBI);
-        flop += fc;
-      }
-      if (scale) {
-        coef_scale_async(cg_z, cg_z, coef_s, size, gc);
-        flop += n;
-      }
-      dot2_async(cg_r, cg_z, size, innerFidx, gc, d_rho);
-      flop += 2.0 * n;
-      if (!Comm_SUM_dev(d_rho, 1)) return 0;
+    if (m.pc && !cg_precondition(m, flop)) return 0;
+    if (!cg_direction(m, itr, cur, flop)) return 0;
+    const int updated = cg_update(m, X, cg_p[cur], itr, flop);
+    if (updated == 0) return 0;
+    // the one wait of the iteration: r.r (and this iteration's rho), one copy of the four dots
+    if (updated > 0) fetch(&d_res->cg.rho, 4);
+    // (pc: found after the iteration's launches, whose update pass stored nothing: x is that of the iteration before)
+    if (updated < 0 || (m.pc && cg_breakdown((REAL_TYPE)h_scal->cg.rho, itr))) {
+      itr = 0;
+      break;
     }
-    cg_scalar_async(0, d_rho, itr == 1, sc);  // rho; beta = rho / rho_old
-    if (fuse_dir) {
-      czhip_cg_dir_ax_async(cg_p[cur ^ 1], cg_q, z, cg_p[cur], itr == 1 ? nullptr : sc + 2, size, innerFidx, gc, cf, d_pq);
-      cur ^= 1;
-      cg_fused++;
-    } else {
-      if (itr == 1) HIP_CHECK(hipMemcpyAsync(cg_p[cur], z, nbytes, hipMemcpyDeviceToDevice, st));
-      else triad_async(cg_p[cur], cg_p[cur], z, (REAL_TYPE)0, size, innerFidx, gc, sc + 2);  // p = beta p + z
-      if (!Comm_S(cg_p[cur])) return 0;
-      mirror(cg_p[cur]);
-      if (!coef) calc_ax_dots_async(cg_q, cg_p[cur], cg_p[cur], size, innerFidx, gc, cf, nullptr, d_pq);
-      else if (!coef_ax_async(0, cg_q, cg_p[cur], nullptr, coef_b[0], coef_b[1], coef_b[2], size, innerFidx, gc, d_pq)) return 0;
-    }
-    if (itr > 1) flop += 2.0 * n;
-    flop += (coef ? 22.0 : 13.0) * n + 2.0 * n;
-    if (!Comm_SUM_dev(d_pq, 1)) return 0;
-    cg_scalar_async(1, d_pq, 0, sc);  // alpha = rho / p.q
-    REAL_TYPE* const p = cg_p[cur];
-    if (closed) {
-      // r = ((-alpha) q + r) - sc[4], sum r^2 and sum r side by side: one all-reduce, then the mean the next update removes
-      cg_update_guarded_async(true, X, cg_r, p, cg_q, sc, size, innerFidx, gc, d_rr);
-    } else if (fuse) {
-      cg_update_guarded_async(false, X, cg_r, p, cg_q, sc, size, innerFidx, gc, d_rr);
-    } else {
-      if (pc) {  // the triads carry no test of their own: the host learns rho before them
-        HIP_CHECK(hipMemcpyAsync(h_scal + 2, d_rho, sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (fabs((REAL_TYPE)h_scal[2]) < FLT_MIN) {
-          pcg_void_start = itr == 1;
-          itr = 0;
-          break;
-        }
-      }
-      triad_async(X, p, X, (REAL_TYPE)0, size, innerFidx, gc, sc);
-      triad_async(cg_r, cg_q, cg_r, (REAL_TYPE)0, size, innerFidx, gc, sc + 1);
-      dot1_async(cg_r, size, innerFidx, gc, d_rr);
-    }
-    flop += 6.0 * n;
-    if (!Comm_SUM_dev(d_rr, closed ? 2 : 1)) return 0;
-    if (closed) mean_scalar_async(d_rr + 1, g_npts, sc + 4, nullptr);
-    // the one wait of the iteration: r.r (and this iteration's rho)
-    HIP_CHECK(hipMemcpyAsync(h_scal + 2, d_res + 2, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const REAL_TYPE rr = (REAL_TYPE)h_scal[5];
-    if (pc) {
-      rho = (REAL_TYPE)h_scal[2];
-      if (fabs(rho) < FLT_MIN) {  // (found after the iteration's launches, whose update pass stored nothing: x is that of the iteration before)
-        pcg_void_start = itr == 1;
-        itr = 0;
-        break;
-      }
-    }
-    res = rr;
-    res *= res_normal;
-    res = sqrt(res);
+    const REAL_TYPE rr = (REAL_TYPE)h_scal->cg.rr;
+    res = sqrt((double)rr * res_normal);
     history.push_back(res);
     if (res < eps) break;
-    if (!pc) rho = rr;
+    rho = m.pc ? (REAL_TYPE)h_scal->cg.rho : rr;
   }
   if (itr > ItrMax) itr = ItrMax;
-  if (closed) {
-    // step 3: the answer of zero mean (the sums read owned cells only; the exchange below carries the shifted values into the ghost layers)
-    if (!project(X, sc + 6, nullptr)) return 0;
-    flop += 3.0 * n;
-    HIP_CHECK(hipMemcpyAsync(h_scal + 16, sc + 5, 2 * sizeof(REAL_TYPE), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const REAL_TYPE* hm = reinterpret_cast<const REAL_TYPE*>(h_scal + 16);
-    closed_m[1] = (double)hm[0], closed_m[2] = (double)hm[1];
-  }
-  if (!Comm_S(X)) return 0;  // (the ghost layers of the result, as PBiCGSTAB leaves them)
-  mirror(X);
-  return itr;
+  return cg_end(m, X, flop) ? itr : 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1646,12 +1666,8 @@ bool CZ::coef_mg_settle(const char* who, bool rebuilt) {
 
 int CZ::SetCoefMg(int on) {
   const char* const who = "cz_set_coef_mg";
-  auto refuse = [&](const char* why) {
-    fprintf(stderr, "%s: %s\n", who, why);
-    return 0;
-  };
-  if (!set_up) return refuse("no problem is set up (cz_setup first)");
-  if (SW_maf) return refuse("the handle's operator is a MAF one, not the unit-coefficient operator");
+  auto refuse = [&](const char* why) { return bc_refuse(who, why); };
+  if (const char* why = bc_unready(this)) return refuse(why);  // (no set-up, a MAF operator)
   if (numProc > 1) return refuse("a decomposed run: the face coefficients themselves are refused there (single domain only)");
   coef_mg = on ? 1 : 0;
   const bool ok = coef_mg_settle(who, false);
@@ -1684,18 +1700,17 @@ int CZ::SetClosedBox(int on) {
 }
 
 // A <- A - m over the inner box, m = (REAL)(sum A / npts) over the GLOBAL inner box: a pass that sums, one all-reduce, the mean on the device
-// (*m_dev, *keep_dev), a pass that subtracts and leaves this rank's sum A' and sum A'^2 in d_res[20..21] (the caller all-reduces what it uses)
+// (*m_dev, *keep_dev), a pass that subtracts and leaves this rank's sum A' and sum A'^2 in d_res->project (the caller all-reduces what it uses)
 bool CZ::project(REAL_TYPE* A, REAL_TYPE* m_dev, REAL_TYPE* keep_dev) {
-  double* const d_cl = d_res + 20;
+  double* const d_cl = d_res->project;
   if (!czhip_shift_sums_async(A, nullptr, size, innerFidx, GUIDE, d_cl) || !Comm_SUM_dev(d_cl, 1)) return false;
   mean_scalar_async(d_cl, g_npts, m_dev, keep_dev);
   return czhip_shift_sums_async(A, m_dev, size, innerFidx, GUIDE, d_cl) != 0;
 }
 
-// (no host wait here: cz_set_rhs from a device array stays an event hand-over; the mean stays in sc[7] until cz_closed_mean asks for it)
+// (no host wait here: cz_set_rhs from a device array stays an event hand-over; the mean stays in d_res->rhs_mean until cz_closed_mean asks for it)
 bool CZ::project_rhs() {
-  REAL_TYPE* const sc = reinterpret_cast<REAL_TYPE*>(d_res + 12);
-  if (!project(RHS, sc + 7, nullptr) || !Comm_S2(RHS)) return false;
+  if (!project(RHS, &d_res->rhs_mean, nullptr) || !Comm_S2(RHS)) return false;
   closed_m0_on_device = true;
   return true;
 }
@@ -1703,10 +1718,7 @@ bool CZ::project_rhs() {
 double CZ::ClosedMean(int which) {
   if (which < 0 || which > 2) return std::nan("");
   if (which == 0 && closed_m0_on_device) {
-    const REAL_TYPE* const sc = reinterpret_cast<const REAL_TYPE*>(d_res + 12);
-    HIP_CHECK(hipMemcpyAsync(h_scal + 18, sc + 7, sizeof(REAL_TYPE), hipMemcpyDeviceToHost, stream()));
-    HIP_CHECK(hipStreamSynchronize(stream()));
-    closed_m[0] = (double)*reinterpret_cast<const REAL_TYPE*>(h_scal + 18);
+    closed_m[0] = (double)*fetch(&d_res->rhs_mean);
     closed_m0_on_device = false;
   }
   return closed_m[which];
@@ -1800,10 +1812,7 @@ void CZ::field_copy_cells(void* a, const void* tmp, int abytes, const long long*
 // Every refusal comes before the first launch.
 int CZ::FieldIO(int which, void* a, int abytes, const long long* stride, int on_device, void* user_stream, int op, double scale, double* sumsq,
                 const char* who) {
-  auto refuse = [&](const char* why) {
-    fprintf(stderr, "%s: %s\n", who, why);
-    return 0;
-  };
+  auto refuse = [&](const char* why) { return bc_refuse(who, why); };
   const bool to_user = op == FIO_EXPORT || op == FIO_RESIDUAL;
   const bool refine = op == FIO_RESIDUAL || op == FIO_ADD;
   const bool none = op == FIO_RESIDUAL && !a;  // the norm only
@@ -1840,9 +1849,9 @@ int CZ::FieldIO(int which, void* a, int abytes, const long long* stride, int on_
     if (!Comm_S(P)) return 0;
     mirror(P);
     if (coef_on()) {
-      last_field_form = field_residual_coef_async(P, RHS, WRK, dev, abytes, size, innerFidx, GUIDE, stride, coef_b[0], coef_b[1], coef_b[2], scale, form, d_res + 10);
+      last_field_form = field_residual_coef_async(P, RHS, WRK, dev, abytes, size, innerFidx, GUIDE, stride, coef_b[0], coef_b[1], coef_b[2], scale, form, d_res->field_sumsq);
     } else {
-      last_field_form = field_residual_async(P, RHS, WRK, dev, abytes, size, innerFidx, GUIDE, stride, cf, scale, form, d_res + 10);
+      last_field_form = field_residual_async(P, RHS, WRK, dev, abytes, size, innerFidx, GUIDE, stride, cf, scale, form, d_res->field_sumsq);
     }
   } else if (op == FIO_ADD) {
     last_field_form = field_add_async(P, dev, abytes, size, innerFidx, GUIDE, stride, scale, form);
@@ -1863,8 +1872,8 @@ int CZ::FieldIO(int which, void* a, int abytes, const long long* stride, int on_
     }
   }
   if (op == FIO_RESIDUAL) {
-    if (!Comm_SUM_dev(d_res + 10, 1)) return 0;
-    HIP_CHECK(hipMemcpyAsync(h_scal + 10, d_res + 10, sizeof(double), hipMemcpyDeviceToHost, st));
+    if (!Comm_SUM_dev(d_res->field_sumsq, 1)) return 0;
+    fetch_queued(d_res->field_sumsq);  // (the wait is the hand-back's below)
   }
   if (none) {
     HIP_CHECK(hipStreamSynchronize(st));
@@ -1879,7 +1888,7 @@ int CZ::FieldIO(int which, void* a, int abytes, const long long* stride, int on_
   } else {
     field_hand_back(user_stream, op == FIO_RESIDUAL);  // (the one wait with a stream: the sum is a host value on return)
   }
-  if (op == FIO_RESIDUAL) *sumsq = h_scal[10];
+  if (op == FIO_RESIDUAL) *sumsq = h_scal->field_sumsq[0];
   return 1;
 }
 
@@ -1888,13 +1897,9 @@ int CZ::FieldIO(int which, void* a, int abytes, const long long* stride, int on_
 // PRJ_GRAD: vel = vel - grad P scale in place, P's face layers re-made first.  Checks, hand-over and staging are FieldIO's; every refusal
 // comes before the first launch.
 int CZ::ProjectIO(int op, REAL_TYPE* const* vel, const long long* stride, int on_device, void* user_stream, double scale, double* sumsq, const char* who) {
-  auto refuse = [&](const char* why) {
-    fprintf(stderr, "%s: %s\n", who, why);
-    return 0;
-  };
+  auto refuse = [&](const char* why) { return bc_refuse(who, why); };
   const int abytes = (int)sizeof(REAL_TYPE);
-  if (!set_up) return refuse("no problem is set up (cz_setup first)");
-  if (SW_maf) return refuse("the handle's operator is a MAF one, not the unit-coefficient operator");
+  if (const char* why = bc_unready(this)) return refuse(why);  // (no set-up, a MAF operator)
   if (numProc > 1)
     return refuse("a decomposed run: faces between bricks need an exchange of one velocity layer, which is the follow-up (single domain only)");
   const REAL_TYPE rs = (REAL_TYPE)scale;
@@ -1923,7 +1928,7 @@ int CZ::ProjectIO(int op, REAL_TYPE* const* vel, const long long* stride, int on
   }
   const int form = field_form == 3 ? 3 : 0;
   if (op == PRJ_DIV) {
-    last_field_form = field_div_async(RHS, dev[0], dev[1], dev[2], size, GUIDE, stride, bc.per, scale, form, d_res + 10);
+    last_field_form = field_div_async(RHS, dev[0], dev[1], dev[2], size, GUIDE, stride, bc.per, scale, form, d_res->field_sumsq);
   } else {
     mirror(P);
     if (coef_on()) last_field_form = field_grad_coef_async(dev[0], dev[1], dev[2], P, coef_b[0], coef_b[1], coef_b[2], size, GUIDE, stride, bc.per, scale, form);
@@ -1936,7 +1941,7 @@ int CZ::ProjectIO(int op, REAL_TYPE* const* vel, const long long* stride, int on
     } else if (!Comm_S2(RHS)) {
       return 0;
     }
-    if (sumsq) HIP_CHECK(hipMemcpyAsync(h_scal + 10, d_res + 10, sizeof(double), hipMemcpyDeviceToHost, st));
+    if (sumsq) fetch_queued(d_res->field_sumsq);  // (the wait is the hand-back's below)
   }
   if (!on_device) {
     std::vector<unsigned char> tmp;
@@ -1950,7 +1955,7 @@ int CZ::ProjectIO(int op, REAL_TYPE* const* vel, const long long* stride, int on
   } else {
     field_hand_back(user_stream, op == PRJ_DIV && sumsq);  // (a sum asked for is a host value on return; without one no host wait)
   }
-  if (op == PRJ_DIV && sumsq) *sumsq = h_scal[10];
+  if (op == PRJ_DIV && sumsq) *sumsq = h_scal->field_sumsq[0];
   return 1;
 }
 
@@ -1973,27 +1978,19 @@ void CZ::coef_clear() {
 }
 
 bool CZ::coef_prepare(int per) {
-  hipStream_t st = stream();
-  unsigned* const d_bad = reinterpret_cast<unsigned*>(d_res + 11);
-  unsigned* const h_bad = reinterpret_cast<unsigned*>(h_scal + 11);
-  HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(unsigned), st));
-  coef_prep_async(coef_b[0], coef_b[1], coef_b[2], coef_s, size, innerFidx, GUIDE, per, coef_per, d_bad);
-  HIP_CHECK(hipMemcpyAsync(h_bad, d_bad, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
+  HIP_CHECK(hipMemsetAsync(&d_res->coef_bad, 0, sizeof(unsigned), stream()));  // (the counter's own zeroing: the kernel counts atomically)
+  coef_prep_async(coef_b[0], coef_b[1], coef_b[2], coef_s, size, innerFidx, GUIDE, per, coef_per, &d_res->coef_bad);
+  const unsigned bad = *fetch(&d_res->coef_bad);
   coef_per = per;
-  if (*h_bad) coef_clear();
-  return *h_bad == 0u;
+  if (bad) coef_clear();
+  return bad == 0u;
 }
 
 int CZ::SetFaceCoef(REAL_TYPE* const* b, const long long* stride, int on_device, void* user_stream) {
   const char* const who = "cz_set_face_coef";
-  auto refuse = [&](const char* why) {
-    fprintf(stderr, "%s: %s\n", who, why);
-    return 0;
-  };
+  auto refuse = [&](const char* why) { return bc_refuse(who, why); };
   const int abytes = (int)sizeof(REAL_TYPE);
-  if (!set_up) return refuse("no problem is set up (cz_setup first)");
-  if (SW_maf) return refuse("the handle's operator is a MAF one, not the unit-coefficient operator");
+  if (const char* why = bc_unready(this)) return refuse(why);  // (no set-up, a MAF operator)
   const int given = (b[0] != nullptr) + (b[1] != nullptr) + (b[2] != nullptr);
   if (given == 0) {  // back to the unit coefficients: the work vectors as the fused passes read them (set_bc does the same)
     coef_clear();

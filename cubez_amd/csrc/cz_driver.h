@@ -13,6 +13,7 @@
 #include "cz_solvers.h"  // enum LinearSolver (cz_Define.h:68-89) and the table of the names accepted: one row each
 
 typedef CZ_REAL REAL_TYPE;  // cz_Define.h:28-37
+#include "cz_scalars.h"     // CzScalars, CzFlags: the layout of d_res / h_scal and of d_flag
 #define GUIDE 2             // cz_Define.h:40
 
 // CB_Define_stub.h:64-70 / cz_fparam.fi:10-16
@@ -104,7 +105,7 @@ class CZ {
   int SetCoefMg(int on);         // cz_set_coef_mg: 1 / 0
   int closed_box = 0;            // the closed box (cz_set_closed_box, cz_info 22): mask 63 and the three projections of pcg
   double closed_m[3] = {0, 0, 0};  // the means last removed: right-hand side, initial residual, answer (cz_closed_mean)
-  bool closed_m0_on_device = false;  // closed_m[0] is still sc[7] of d_res (cz_set_rhs does not wait for it; ClosedMean fetches)
+  bool closed_m0_on_device = false;  // closed_m[0] is still d_res->rhs_mean (cz_set_rhs does not wait for it; ClosedMean fetches)
   double g_npts = 0.0;           // cells of the GLOBAL inner box (1 / res_normal)
   int field_form = 0;            // CZ_FIELD_FORM: 3 = the generic import / export kernel whatever the strides
   int last_field_form = 0;       // the kernel form of the last import / export (cz_info 20: 1 k rows, 2 tile transpose, 3 generic)
@@ -139,12 +140,12 @@ class CZ {
   int interior[6], interior1[6]; // the rest of the inner box / its first-sweep range
 
   // device-side convergence bookkeeping (cz_Poisson.cpp:67-77 moved to the GPU)
-  double* d_res = nullptr;       // [0] sum dp^2 of the current iteration, [1..7] dot products
+  CzScalars* d_res = nullptr;    // residual sums, dot products and device-made scalars, one named member per user (cz_scalars.h)
   double* d_hist = nullptr;      // residual history, index = iteration
   int hist_cap = 0;
-  int* d_flag = nullptr;         // [0] converged flag, [1] iteration at which it was set
-  double* h_scal = nullptr;      // pinned: mirrors of d_res
-  int* h_flag = nullptr;         // pinned
+  CzFlags* d_flag = nullptr;     // converged flag, iteration at which it was set, the lagged split's two snapshots
+  CzScalars* h_scal = nullptr;   // pinned: the mirror of d_res, member for member (fetch)
+  int* h_flag = nullptr;         // pinned: the host's copies of d_flag's first two words, one pair per poll in flight
 
   CZ();
   ~CZ();
@@ -180,7 +181,7 @@ class CZ {
   static const char* unsolvable(CzBc next, int closed);  // the setters' one rule on the combined state: nullptr, or the line of the refusal
   const char* bc_unready(const void* arg) const;         // what every setter refuses before it reads its argument: nullptr, or the line
   int set_bc(CzBc next, int closed, bool project, const char* who);  // the one way to a new state: the rule, the hierarchy, the store, the work vectors, P's face layers
-  bool project(REAL_TYPE* A, REAL_TYPE* m_dev, REAL_TYPE* keep_dev);  // A <- A - mean(A) over the global inner box; d_res[20..21] = this rank's sum A', sum A'^2
+  bool project(REAL_TYPE* A, REAL_TYPE* m_dev, REAL_TYPE* keep_dev);  // A <- A - mean(A) over the global inner box; d_res->project = this rank's sum A', sum A'^2
   double ClosedMean(int which);      // cz_closed_mean
   bool project_rhs();                // ... of RHS, ghost layers included; closed_m[0]
   void mirror(REAL_TYPE* X);         // X's face layers of the state: mirrors on the Neumann faces, wraps in the periodic directions (nothing without either)
@@ -217,12 +218,40 @@ class CZ {
   // the loop of s_type's family (cz_solvers.h): what Solve, Sweeps and Preconditioner call
   int run(int s_type, double& res, REAL_TYPE* X, REAL_TYPE* B, int itr_max, double& flop, bool converge_check = true, bool x_is_zero = false,
           const BMade* made = nullptr);
+  // the read-back of d_res: `n` values from the member at `dev` on (n > 1: a group cz_scalars.h states) copied to the same member of h_scal
+  // behind what the compute stream holds; the pointer to that mirror.  fetch waits for the copy, fetch_queued leaves the wait to the caller
+  template <class T> const T* fetch_queued(const T* dev, int n = 1);
+  template <class T> const T* fetch(const T* dev, int n = 1);
   REAL_TYPE dot_read(double& flop);
   REAL_TYPE Fdot1(REAL_TYPE* x, double& flop);
   REAL_TYPE Fdot2(REAL_TYPE* x, REAL_TYPE* y, double& flop);
   void Preconditioner(REAL_TYPE* xx, REAL_TYPE* bb, double& flop, int s_type, const BMade* made = nullptr);
   int PBiCGSTAB(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop, int s_type);
   int PCG(double& res, REAL_TYPE* X, REAL_TYPE* B, double& flop);  // beyond the reference (DESIGN.md "PCG")
+  // ... the modes of one solve, decided once at its start; then the operator, the breakdown test and the steps (cz_driver.cpp, above CZ::PCG)
+  struct CgMode {
+    bool pc;        // a preconditioner (jacobi | mg | mgrb): z = M^-1 r in cg_z; none: z IS r and rho is the r.r of the update before
+    bool fuse;      // CZ_CG_FUSE (default on): x, r and r.r in one guarded pass (czhip_cg_update_async); off: two triads and a dot
+    // ... and the direction inside the SpMV pass (czhip_cg_dir_ax_async, ping-pong between cg_p[0] and cg_p[1]); else the update, Comm_S(p),
+    // then the SpMV with its dot folded in.  The fused pass reads z's and p's shells as zeros: single domain only, no Neumann face (whose
+    // layer of p is the mirror) nor a periodic direction (whose layer is the wrap), and no face coefficients (their SpMV stays unfused)
+    bool fuse_dir;
+    // face coefficients: A_beta where the operator is applied (cg_apply_A), and the preconditioner z = s M^-1 (s r) with
+    // M^-1 the constant-coefficient one (cg_q is free for s r at that point) ...
+    bool coef;
+    bool scale;     // ... unless the hierarchy holds the coefficients (cz_set_coef_mg): z = M_beta^-1 r, no scaling either side
+    bool closed;    // the closed box: the three projections, the lagged mean in sc[SC_LAG_MEAN]
+    REAL_TYPE* z;   // cg_z, or cg_r
+    double* d_rho;  // where rho is summed: cg.rho, or (none) cg.rr
+  };
+  bool cg_apply_A(REAL_TYPE* out, REAL_TYPE* p, const REAL_TYPE* b, double* dots);
+  bool cg_breakdown(REAL_TYPE rho, int itr);
+  bool cg_start(const CgMode& m, REAL_TYPE* X, const REAL_TYPE* B, REAL_TYPE& rho, double& flop);
+  bool cg_apply_M(const CgMode& m, double& flop);
+  bool cg_precondition(const CgMode& m, double& flop);
+  bool cg_direction(const CgMode& m, int itr, int& cur, double& flop);
+  int cg_update(const CgMode& m, REAL_TYPE* X, const REAL_TYPE* p, int itr, double& flop);
+  bool cg_end(const CgMode& m, REAL_TYPE* X, double& flop);
   bool neumann_refused(const char* who, int s_type) const;          // a mask is set and the solver is not pcg: one line, true
 
   // cz_comm.cpp replacements (no-ops when numProc == 1, like cz_comm.cpp:25,76,104)

@@ -72,11 +72,15 @@ void calc_ax_dots_async(CZ_REAL* ap, const CZ_REAL* p, const CZ_REAL* y, const i
                         const MafPtrs* maf, double* dots_dev);
 void triad_dots_async(CZ_REAL* z, const CZ_REAL* x, const CZ_REAL* y, const CZ_REAL* w, CZ_REAL a, const int* sz, const int* idx, int g,
                       double* dots_dev, const CZ_REAL* a_dev = nullptr);
-// BiCGSTAB's alpha (step 1) / omega (step 2) made on the device from the dot products of the launch before: sc_dev[0..3] = alpha, omega, -alpha,
-// -omega; the *_dev arguments of the updates above read them there, so the host does not wait for the dot products in mid-iteration
+// The indices of the scalars made on the device (sc_dev below; CzScalars::sc), as bicg_scal_k and cg_scal_k / cg_update_k (cz_k_blas.h) write
+// and read them and as the driver hands them to the *_dev arguments of the vector updates
+enum ScBicg { SC_B_ALPHA = 0, SC_B_OMEGA = 1, SC_B_NALPHA = 2, SC_B_NOMEGA = 3 };
+enum ScCg { SC_ALPHA = 0, SC_NALPHA = 1, SC_BETA = 2, SC_RHO = 3, SC_LAG_MEAN = 4 };  // (SC_LAG_MEAN: the closed box, mean_scal_k)
+// BiCGSTAB's alpha (step 1) / omega (step 2) made on the device from the dot products of the launch before: sc_dev[ScBicg]; the *_dev
+// arguments of the updates above read them there, so the host does not wait for the dot products in mid-iteration
 void bicg_scalar_async(int step, const double* dots_dev, CZ_REAL rho, CZ_REAL* sc_dev);
 // PCG's rho / beta (step 0, from the dot in dot_dev[0]; first: no beta) and alpha (step 1, from p.Ap in dot_dev[0]) made on the device:
-// sc_dev[0..3] = alpha, -alpha, beta, rho (cg_scal_k)
+// sc_dev[ScCg] (cg_scal_k)
 void cg_scalar_async(int step, const double* dot_dev, int first, CZ_REAL* sc_dev);
 void mean_scalar_async(const double* sum_dev, double npts, CZ_REAL* m_dev, CZ_REAL* keep_dev);  // *m_dev = (REAL)(sum_dev[0] / npts) (closed box)
 // PCG's update pass (czhip_cg_update_async; closed: czhip_cg_update_closed_async) guarded by rho = sc_dev[3]: under the breakdown threshold

@@ -115,7 +115,7 @@ ewise_k(REAL* Z, const REAL* X, const REAL* Y, REAL a, REAL b, EGeom g) {
 
 // BiCGSTAB's scalars on the device (cz_Poisson.cpp:427, 464), from the dot products the launch before left in `dots` (all-reduced in a
 // decomposed run), with the host's own operations -- the double sums rounded to REAL, then one REAL division: the same bits as the host path.
-//   STEP 1: alpha = rho / (q . r0)              sc[0] = alpha, sc[2] = -alpha
+//   STEP 1: alpha = rho / (q . r0)              sc[0] = alpha, sc[2] = -alpha      (the indices: enum ScBicg, cz_internal.h)
 //   STEP 2: omega = (t . s) / (t . t)           sc[1] = omega, sc[3] = -omega
 template <int STEP>
 __global__ void bicg_scal_k(const double* __restrict__ dots, REAL rho, REAL* __restrict__ sc) {
@@ -459,7 +459,7 @@ __global__ void mean_scal_k(const double* __restrict__ sum, double npts, REAL* _
 }
 
 // PCG's scalars on the device, with the host's operations (REAL division of REAL-rounded double sums), like bicg_scal_k.
-// sc[0] = alpha, sc[1] = -alpha, sc[2] = beta, sc[3] = rho (the REAL of the current iteration; the previous one until STEP 0 replaces it).
+// (enum ScCg, cz_internal.h) sc[0] = alpha, sc[1] = -alpha, sc[2] = beta, sc[3] = rho (the REAL of the current iteration; the previous one until STEP 0 replaces it).
 //   STEP 0: rho = (REAL)dot[0];  beta = rho / rho_old unless `first`;  rho_old <- rho
 //   STEP 1: alpha = rho / (REAL)dot[0]   (dot = p . A p)
 template <int STEP>

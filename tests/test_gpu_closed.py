@@ -393,6 +393,60 @@ def test_refusals_and_state(capfd):
     assert capfd.readouterr().err.count("cz_set_closed_box:") == 2
 
 
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_rhs_mean_survives_every_call_that_uses_the_scalars(prec, monkeypatch):
+    """The mean that set_rhs removes on a closed box stays on the device until closed_mean(0) asks for it (the one member of the driver's
+    device scalars that lives across calls; it used to land in a different double in each precision).  Handle A asks at
+    once.  The B handles make the same two calls from the same device array, then every call a pcg handle accepts that touches the
+    scalars, and ask last: the same kernel on the same input, so the same bits, without a tolerance.  A handle's preconditioner and
+    CZ_CG_FUSE are fixed when it is made, so the second solve (none, CZ_CG_FUSE=0) has a handle of its own"""
+    from test_gpu_problem import _torch
+    torch = _torch()
+    gsz = (9, 7, 12)
+    b, p = PP.problem(gsz, prec, 5)
+    bd = torch.from_numpy(b).cuda()
+    ones = [np.ones(gsz, dtype=b.dtype) for _ in range(3)]
+
+    def start(pc):
+        cz = _handle(prec, list(gsz) + ["pcg", 3, 1.0, pc])
+        cz.set_rhs(bd)
+        return cz
+
+    a = start("mgrb")
+    try:
+        want = a.closed_mean(0)
+    finally:
+        a.close()
+    assert want != 0.0 and math.isfinite(want)
+
+    b1 = start("mgrb")
+    try:
+        b1.set_field(p)
+        b1.set_eps(1e-30)
+        assert b1.solve() == 3  # (cut at three iterations)
+        assert b1.get_residual()[1] > 0.0
+        b1.set_face_coef(*ones)
+        assert b1.info()["face_coef"] == 1 and b1.get_residual()[1] > 0.0
+        b1.set_face_coef(None)
+        sz, idx, ins, r = TN._cycle_rhs(prec, gsz)
+        assert np.isfinite(b1.precondition(r)[ins]).all()
+        got = [b1.closed_mean(w) for w in range(3)]
+    finally:
+        b1.close()
+    assert got[0] == want and math.isfinite(got[1]) and math.isfinite(got[2]), (got, want)
+
+    monkeypatch.setenv("CZ_CG_FUSE", "0")
+    b2 = start("none")
+    try:
+        b2.set_field(p)
+        b2.set_eps(1e-30)
+        assert b2.solve() == 3
+        got = [b2.closed_mean(w) for w in range(3)]
+    finally:
+        b2.close()
+    assert got[0] == want and math.isfinite(got[1]) and math.isfinite(got[2]), (got, want)
+
+
 def test_setup_clears_the_mode_and_off_gives_the_unmasked_bits():
     """cz_setup (through cz_evaluate) after the mode: the unmasked solve of a fresh handle; on = 0 after on = 1: a Dirichlet solve of the
     caller's problem with the bits of a handle that never saw the mode, given the projected right-hand side"""
