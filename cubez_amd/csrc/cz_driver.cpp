@@ -219,6 +219,7 @@ int CZ::Setup(int argc, char** argv) {
   closed_box = 0;
   coef_clear();  // (and with unit coefficients: cz_set_face_coef comes after cz_setup)
   coef_mg = 0;   // (and without the coefficient hierarchy: cz_set_coef_mg comes after cz_setup)
+  mg_lines = 0;  // (and without line iterations: cz_set_mg_lines comes after cz_setup)
   closed_m[0] = closed_m[1] = closed_m[2] = 0.0;
   closed_m0_on_device = false;
   solve_plan = PassPlan();
@@ -1661,7 +1662,24 @@ bool CZ::coef_mg_settle(const char* who, bool rebuilt) {
     fprintf(stderr, "%s: a coarse weight of the coefficient hierarchy is not finite and positive: cz_set_coef_mg is off, the scaled preconditioner runs\n", who);
     coef_mg = 0;
   }
+  // the line iterations of cz_set_mg_lines follow: the hierarchy holds the flag (and its scratch) while the flag is on
+  // and the smoother is mgrb; its cycles take it while they take the coefficients, so a dropped hierarchy leaves the lines idle
+  if (pc_type == LS_MGRB && czhip_mg_set_lines(mg, mg_lines) != 1) cz_fatal(1, "%s: the hierarchy refused the line iterations\n", who);
   return ok;
+}
+
+int CZ::SetMgLines(int on) {
+  const char* const who = "cz_set_mg_lines";
+  auto refuse = [&](const char* why) { return bc_refuse(who, why); };
+  if (const char* why = bc_unready(this)) return refuse(why);  // (no set-up, a MAF operator)
+  if (numProc > 1) return refuse("a decomposed run: the coefficient hierarchy that the lines run under is refused there (single domain only)");
+  if ((on | 1) != 1) return refuse("the flag is 0 or 1");
+  if (on && !(ac1 <= (REAL_TYPE)1))
+    return refuse("the handle's coefficient exceeds 1: line iterations take 0 < coef <= 1 (over-relaxed, the lagged wrap of a periodic Z makes the preconditioner indefinite)");
+  mg_lines = on;
+  coef_mg_settle(who, true);  // (the coefficient hierarchy stands as it is: only the flag travels)
+  czhip_sync();
+  return 1;
 }
 
 int CZ::SetCoefMg(int on) {
@@ -2293,6 +2311,7 @@ int cz_set_face_coef(cz_handle* h, const CZ_REAL* bx, const CZ_REAL* by, const C
   return h ? h->cz.SetFaceCoef(b, stride, on_device, ready_stream) : 0;
 }
 int cz_set_coef_mg(cz_handle* h, int on) { return h ? h->cz.SetCoefMg(on) : 0; }
+int cz_set_mg_lines(cz_handle* h, int on) { return h ? h->cz.SetMgLines(on) : 0; }
 int cz_set_neumann(cz_handle* h, const int* faces) { return h ? h->cz.SetNeumann(faces) : 0; }
 int cz_set_closed_box(cz_handle* h, int on) { return h ? h->cz.SetClosedBox(on) : 0; }
 int cz_set_periodic(cz_handle* h, const int* dirs) {
@@ -2356,6 +2375,7 @@ int cz_info(const cz_handle* h, int what) {
     case 25: return c.coef_on() ? 1 : 0;
     case 26: return c.jac4_passes;
     case 27: return c.coef_mg_on() ? 1 : 0;
+    case 28: return c.mg_lines_on() ? 1 : 0;
     default: return -1;
   }
 }

@@ -103,6 +103,11 @@ class CZ {
   bool coef_mg_on() const { return mg && mg->coef; }
   bool coef_mg_settle(const char* who, bool rebuilt);
   int SetCoefMg(int on);         // cz_set_coef_mg: 1 / 0
+  // zebra line iterations along Z in mgrb's cycle (cz_set_mg_lines, cz_info 28): the flag as asked for; in force while the
+  // coefficient hierarchy is and the preconditioner is mgrb (coef_mg_settle carries the flag to the hierarchy)
+  int mg_lines = 0;
+  bool mg_lines_on() const { return mg_lines && coef_mg_on() && mg->rb && mg->lines; }
+  int SetMgLines(int on);        // cz_set_mg_lines: 1 / 0
   int closed_box = 0;            // the closed box (cz_set_closed_box, cz_info 22): mask 63 and the three projections of pcg
   double closed_m[3] = {0, 0, 0};  // the means last removed: right-hand side, initial residual, answer (cz_closed_mean)
   bool closed_m0_on_device = false;  // closed_m[0] is still d_res->rhs_mean (cz_set_rhs does not wait for it; ClosedMean fetches)

@@ -369,7 +369,73 @@ bool mgc_build(cz_mg* h) {
   h->coef_bad = bad != 0u;
   return bad == 0u;
 }
+
+// ---- zebra line iterations along Z (cz_k_mgline.h)
+// a level takes them where it has X or Y links: a level of one row is its own line and keeps the point sweeps (in the closed box that line
+// is the whole singular operator)
+bool mg_line_level(const cz_mg* h, int l) { return (long long)h->lev[l].gn[0] * h->lev[l].gn[1] > 1; }
+// the rows of one colour as mg_line_k numbers them, and the REALs of one scratch table
+MgLine mg_line_plan(const MgLev& L) {
+  MgLine P = MgLine();
+  P.mh = (L.ni + 1) / 2, P.rows = L.nj * P.mh;
+  P.pitch = (long long)((L.nk + VW - 1) / VW) * VW;
+  return P;
+}
+unsigned mg_line_blocks(const MgLine& P) { return (unsigned)((P.rows + MGL_ROWS - 1) / MGL_ROWS); }
+size_t mg_line_table(const cz_mg* h) {
+  size_t n = 0;
+  for (int l = h->first; l < h->nlev; l++) {
+    if (!mg_line_level(h, l)) continue;
+    const MgLine P = mg_line_plan(mgc_lev(h, l));
+    n = std::max(n, (size_t)mg_line_blocks(P) * MGL_ROWS * (size_t)P.pitch);
+  }
+  return n;
+}
+// one sweep of colour `colour` of level l in place; zero as mg_rb_launch's.  An end is folded at level 0 on a zero-flux Z face (the level's
+// word has no such bit while Z is periodic)
+int mg_line_launch(cz_mg* h, REAL* x, const REAL* b, int l, REAL omg, int colour, int zero, const MgcW& cw) {
+  MgDLev D;
+  const MgdLevel& M = h->lev[l];
+  if (!x || !b || x == b || !cw.d || !h->line_s[0] || !mg_lev(D, M) || M.dense || !mg_whole(D) || (colour | 1) != 1 || zero < 0 || zero > 2) return 0;
+  if (mg_none(D)) return 1;
+  if ((long long)D.L.nj * ((D.L.ni + 1) / 2) > 0x7fffff00LL) return 0;
+  ScopedTimer tm(M.level == 0 ? LBL_RBSOR : LBL_MG_RB);
+  MgLine P = mg_line_plan(D.L);
+  P.c = colour;
+  P.fold = M.level == 0 ? (M.nm >> 4) & 3 : 0;
+  with_zero_form(zero, [&](auto Z) {
+    hipLaunchKernelGGL((mg_line_k<VW, Z()>), dim3(mg_line_blocks(P)), dim3(MGL_ROWS), 0, ctx.stream, x, b, D.L, cw, omg, P, h->line_s[0], h->line_s[1]);
+  });
+  HIP_CHECK(hipGetLastError());
+  return 1;
+}
+void mg_line_free(cz_mg* h) {
+  for (REAL*& a : h->line_s) {
+    if (a) (void)hipFree(a);
+    a = nullptr;
+  }
+  h->lines = 0;
+}
 }  // namespace
+
+extern "C" {
+int czhip_mg_line_chunk(void) { return MGL_CHUNK; }
+
+int czhip_mg_set_lines(cz_mg* h, int on) {
+  if (!h || !h->rb || (on | 1) != 1) return 0;
+  ensure_init();
+  if (!on) {
+    if (h->lines) czhip_sync();
+    mg_line_free(h);
+    return 1;
+  }
+  if (h->lines) return 1;
+  const size_t n = std::max<size_t>(mg_line_table(h), 1);
+  for (REAL*& a : h->line_s) HIP_CHECK(hipMalloc(&a, n * sizeof(REAL)));
+  h->lines = 1;
+  return 1;
+}
+}  // extern "C"
 
 namespace czhip_internal {
 // every level's word from the state (mg_level_bc; without a periodic direction: the Neumann flags at every level, as before there were
@@ -444,6 +510,7 @@ void czhip_mg_destroy(cz_mg* h) {
   if (!h) return;
   czhip_sync();
   mgc_free(h);
+  mg_line_free(h);
   for (int l = 0; l < MG_MAXLEV; l++)
     for (REAL* a : {h->b[l], h->x[l], h->t[l]})
       if (a) czhip_free(a);
@@ -515,8 +582,10 @@ struct MgOps {
   static void must(int launched) {
     if (!launched) cz_fatal(1, "czhip: V-cycle: a level kernel refused its level\n");
   }
+  // line iterations are in force under the coefficients only; the tail kernel has no line form
+  bool lines() const { return h->lines && h->coef && h->rb; }
   bool whole(int l) {
-    if (l < h->tail_from) return false;
+    if (l < h->tail_from || lines()) return false;
     MgTail T;
     MgcTail W = MgcTail();
     mg_tail_plan(T, mgc_lev(h, l), omg, h->rb, h->lev[l].nm);
@@ -587,8 +656,10 @@ struct MgOps {
       } else if (f) {
         fill(l, x(l));
       }
+      const bool line = lines() && cw.d && mg_line_level(h, l);  // (zebra lines along Z: the same order, fills and from-zero forms)
       for (int s = 0; s < 4; s++) {
-        must(mg_rb_launch(x(l), b(l), h->lev[l], omg, (c0 + s) & 1, zero && s < 2 && !f ? s + 1 : 0, cw));
+        const int colour = (c0 + s) & 1, form = zero && s < 2 && !f ? s + 1 : 0;
+        must(line ? mg_line_launch(h, x(l), b(l), l, omg, colour, form, cw) : mg_rb_launch(x(l), b(l), h->lev[l], omg, colour, form, cw));
         fill(l, x(l));
       }
       return;

@@ -226,6 +226,10 @@ struct cz_mg {
   CZ_REAL* cd[MG_MAXLEV] = {};
   unsigned* cbad = nullptr;
   int coef = 0, coef_bad = 0;
+  // zebra line iterations along Z (czhip_mg_set_lines): the flag, in force while coef is, and the scratch of the backward
+  // march -- cp and dp of the rows of one colour of the largest level, the hierarchy's own
+  int lines = 0;
+  CZ_REAL* line_s[2] = {};
 };
 
 #endif

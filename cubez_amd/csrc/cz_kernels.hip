@@ -59,6 +59,7 @@ namespace {
 #include "cz_k_project.h"
 #include "cz_k_coef.h"
 #include "cz_k_mgc.h"
+#include "cz_k_mgline.h"
 #include "cz_h_ctx.h"
 #include "cz_h_launch.h"
 

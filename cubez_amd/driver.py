@@ -46,6 +46,7 @@ class CZ:
         lib.cz_sub_grad.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_double]
         lib.cz_set_face_coef.argtypes = [C.c_void_p] * 4 + [C.POINTER(C.c_longlong), C.c_int, C.c_void_p]
         lib.cz_set_coef_mg.argtypes = [C.c_void_p, C.c_int]
+        lib.cz_set_mg_lines.argtypes = [C.c_void_p, C.c_int]
         lib.cz_set_eps.argtypes = [C.c_void_p, C.c_double]
         lib.cz_set_neumann.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         lib.cz_set_closed_box.argtypes = [C.c_void_p, C.c_int]
@@ -269,6 +270,14 @@ class CZ:
         if self.lib.cz_set_coef_mg(self.h, 1 if on else 0) != 1:
             raise RuntimeError(f"set_coef_mg({bool(on)}): refused (see stderr)")
 
+    def set_mg_lines(self, on=True):
+        """zebra line iterations along Z in the V-cycle of pcg ... mgrb, for a grid refined towards a wall (cell aspect ratios of 30 and
+        more, where point smoothers stall): lay the refined direction on Z.  The flag is remembered; info()["mg_lines"] is 1 while it is
+        in force (flag on, info()["coef_mg"] 1, mgrb); with mg, jacobi or none it is accepted and idle; setup clears it.  Raises where the
+        library refuses: before setup, a decomposed run, a coefficient above 1 (cz_set_mg_lines of include/cz_hip.h)"""
+        if self.lib.cz_set_mg_lines(self.h, 1 if on else 0) != 1:
+            raise RuntimeError(f"set_mg_lines({bool(on)}): refused (see stderr)")
+
     @staticmethod
     def _itemsize(a):
         return a.itemsize if isinstance(a, np.ndarray) else a.element_size()
@@ -330,7 +339,7 @@ class CZ:
         """what a (multi-GPU) run decided (cz_info of include/cz_hip.h)"""
         keys = ("ranks", "fused_pass", "shell_slabs", "overlap", "lagged_reduce", "rccl_ranks", "comm_cus", "pass_kind", "exchange_depth", "buffers", "bicg_fused", "rb4_passes",
                 "exact_reruns", "cg_fused", "jac3_passes", "mg_levels", "mg_cycles", "mg_gather_level", "mg_exchanges", "mg_smoother", "field_form", "neumann", "closed", "periodic", "void_start",
-                "face_coef", "jac4_passes", "coef_mg")
+                "face_coef", "jac4_passes", "coef_mg", "mg_lines")
         return {k: self.lib.cz_info(self.h, i) for i, k in enumerate(keys)}
 
     def config_in_force(self) -> dict:

@@ -18,9 +18,9 @@ ABI_SYMBOLS = [
     "czhip_real_bytes", "czhip_arch", "czhip_init", "czhip_finalize", "czhip_alloc_s3d", "czhip_free", "czhip_h2d",
     "czhip_d2h", "czhip_sync", "czhip_stream", "czhip_set_tuning", "czhip_get_tuning",
     "czhip_jacobi_async", "czhip_rbsor_async", "czhip_check_async", "czhip_jacobi_checked_async",
-    "czhip_rbsor_checked_async", "czhip_jacobi2_async", "czhip_set_tuning2", "czhip_set_pcr_mode", "czhip_set_pcr_lex", "czhip_set_pcr_lex_timeout", "czhip_set_pcr_lex_limits", "czhip_set_psor", "czhip_set_psor_ahead", "czhip_use_t2", "czhip_set_pair_window", "czhip_set_pair_map", "czhip_set_pair_preload", "czhip_set_unit_coef", "czhip_config_describe", "czhip_tuning_describe", "czhip_set_comm_cus", "czhip_selftest_fastdiv", "czhip_selftest_mediumdiv", "czhip_selftest_gateddiv", "czhip_pair_maf_async", "czhip_rbsor2_async", "czhip_rbsor4_async", "czhip_set_rb4", "czhip_jacobi3_async", "czhip_set_jac3", "czhip_jacobi4_async", "czhip_set_jac4", "czhip_jac4_plan", "czhip_jac4_min_sweeps", "czhip_set_jac3_medium", "czhip_set_jac3_gate", "czhip_jac3_gated", "czhip_jac3_division", "czhip_jacobi2_from_zero_async", "czhip_jacobi2_from_zero_made_async", "czhip_check2_async", "czhip_pair_split_async", "czhip_cg_update_async", "czhip_cg_dir_ax_async", "czhip_mg_smooth_async", "czhip_mg_restrict_async", "czhip_mg_prolong_async", "czhip_mg_tail_async", "czhip_mg_create", "czhip_mg_levels", "czhip_mg_apply_async", "czhip_mg_destroy", "czhip_mg_rb_async", "czhip_mg_tail_rb_async", "czhip_mg_create_rb", "czhip_mg_kind", "czhip_mirror_faces_async", "czhip_mg_set_neumann", "czhip_fill_faces_async", "czhip_mg_set_periodic", "czhip_mg_set_coef", "czhip_shift_sums_async", "czhip_cg_update_closed_async", "psor_", "psor_maf_", "pcr_", "pcr_eda_", "pcr_esa_", "pcr_rb_esa_", "pcr_j_esa_", "pcr_rb_maf_", "pcr_rb_esa_maf_", "pcr_maf_", "pcr_eda_maf_", "pcr_esa_maf_",
+    "czhip_rbsor_checked_async", "czhip_jacobi2_async", "czhip_set_tuning2", "czhip_set_pcr_mode", "czhip_set_pcr_lex", "czhip_set_pcr_lex_timeout", "czhip_set_pcr_lex_limits", "czhip_set_psor", "czhip_set_psor_ahead", "czhip_use_t2", "czhip_set_pair_window", "czhip_set_pair_map", "czhip_set_pair_preload", "czhip_set_unit_coef", "czhip_config_describe", "czhip_tuning_describe", "czhip_set_comm_cus", "czhip_selftest_fastdiv", "czhip_selftest_mediumdiv", "czhip_selftest_gateddiv", "czhip_pair_maf_async", "czhip_rbsor2_async", "czhip_rbsor4_async", "czhip_set_rb4", "czhip_jacobi3_async", "czhip_set_jac3", "czhip_jacobi4_async", "czhip_set_jac4", "czhip_jac4_plan", "czhip_jac4_min_sweeps", "czhip_set_jac3_medium", "czhip_set_jac3_gate", "czhip_jac3_gated", "czhip_jac3_division", "czhip_jacobi2_from_zero_async", "czhip_jacobi2_from_zero_made_async", "czhip_check2_async", "czhip_pair_split_async", "czhip_cg_update_async", "czhip_cg_dir_ax_async", "czhip_mg_smooth_async", "czhip_mg_restrict_async", "czhip_mg_prolong_async", "czhip_mg_tail_async", "czhip_mg_create", "czhip_mg_levels", "czhip_mg_apply_async", "czhip_mg_destroy", "czhip_mg_rb_async", "czhip_mg_tail_rb_async", "czhip_mg_create_rb", "czhip_mg_kind", "czhip_mirror_faces_async", "czhip_mg_set_neumann", "czhip_fill_faces_async", "czhip_mg_set_periodic", "czhip_mg_set_coef", "czhip_mg_set_lines", "czhip_mg_line_chunk", "czhip_shift_sums_async", "czhip_cg_update_closed_async", "psor_", "psor_maf_", "pcr_", "pcr_eda_", "pcr_esa_", "pcr_rb_esa_", "pcr_j_esa_", "pcr_rb_maf_", "pcr_rb_esa_maf_", "pcr_maf_", "pcr_eda_maf_", "pcr_esa_maf_",
     "cz_create", "cz_destroy", "cz_evaluate", "cz_setup", "cz_solve", "cz_sweeps", "cz_result_iter", "cz_result_res",
-    "cz_history", "cz_field", "cz_set_rhs", "cz_set_field", "cz_get_field", "cz_get_residual", "cz_add_field", "cz_set_rhs_div", "cz_sub_grad", "cz_set_face_coef", "cz_set_coef_mg", "cz_set_neumann", "cz_set_periodic", "cz_set_closed_box", "cz_closed_mean", "cz_set_eps", "cz_set_itr_max", "cz_local_size", "cz_error_max", "cz_set_quiet", "cz_last_solve_seconds", "cz_kernel_ms",
+    "cz_history", "cz_field", "cz_set_rhs", "cz_set_field", "cz_get_field", "cz_get_residual", "cz_add_field", "cz_set_rhs_div", "cz_sub_grad", "cz_set_face_coef", "cz_set_coef_mg", "cz_set_mg_lines", "cz_set_neumann", "cz_set_periodic", "cz_set_closed_box", "cz_closed_mean", "cz_set_eps", "cz_set_itr_max", "cz_local_size", "cz_error_max", "cz_set_quiet", "cz_last_solve_seconds", "cz_kernel_ms",
     "cz_set_debug", "cz_set_profile", "cz_info", "cz_config_in_force", "cz_precondition", "czhip_timing", "czhip_timing_read",
     "cz_comm_unique_id_bytes", "cz_comm_get_unique_id", "cz_comm_bootstrap", "cz_comm_shutdown", "cz_comm_selftest", "cz_comm_auto_division",
     "cz_comm_decompose", "cz_comm_local_world", "cz_comm_local_world_free", "cz_comm_bootstrap_local",

@@ -96,6 +96,17 @@ class Refined:
                 cz.lib.cz_set_coef_mg(cz.h, 0)
             raise
 
+    def set_mg_lines(self, on=True):
+        """CZ.set_mg_lines on both libraries: in force on the FP32 inner solver with pcg mgrb under set_coef_mg (lo.info()["mg_lines"]),
+        accepted and idle on the FP64 handle.  Raises where either library refuses: both flags are then off"""
+        try:
+            self.hi.set_mg_lines(on)
+            self.lo.set_mg_lines(on)
+        except Exception:
+            for cz in (self.hi, self.lo):
+                cz.lib.cz_set_mg_lines(cz.h, 0)
+            raise
+
     def solve(self, tol=1e-10, max_outer=20, inner_eps=INNER_EPS) -> int:
         """refine until |b - A p| <= tol |b - A p0|; returns the outer steps taken, 0 where max_outer steps did not reach it.
         history: [(outer step, |r| / |r0| after it, inner iterations of it)].  Collective in a decomposed run.

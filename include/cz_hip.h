@@ -449,6 +449,18 @@ int czhip_mg_set_periodic(cz_mg* h, const int* dirs);
  * freed, 1.  0 with nothing changed: a NULL handle, some but not all pointers NULL.  With unit coefficients the cycle gives the bits of
  * the constant cycle in every boundary state. */
 int czhip_mg_set_coef(cz_mg* h, const CZ_REAL* bx, const CZ_REAL* by, const CZ_REAL* bz);
+/* Zebra line iterations along Z inside the hierarchy.  on = 1: while the hierarchy holds face coefficients
+ * (czhip_mg_set_coef), every pair of smoothing iterations of a red-black hierarchy runs two zebra line iterations in place of two
+ * red-black point iterations: the colour of row (I, J) is (I + J) & 1, one sweep of a colour solves every row of that colour exactly along
+ * K (Thomas, IEEE division) and relaxes with the cycle's coefficient, forward iterations sweep colour 0 then 1, backward ones 1 then 0.
+ * An end of a row is folded into the diagonal on a zero-flux Z face of level 0; every other end reads the ghost cell, so a periodic Z is a
+ * lagged wrap.  A level with one row (ni = nj = 1) keeps the point sweeps, and the one-workgroup tail is not taken.  The flag is idle while
+ * the hierarchy has no coefficients.  on = 1 allocates the scratch of the backward march (two tables of the rows of one colour of the
+ * largest level: about one fine array), on = 0 frees it; czhip_mg_destroy frees it too.  The cycle's coefficient must lie in (0, 1]: the
+ * caller's to keep.  Returns 1, or 0 with nothing changed: a NULL handle, a Jacobi hierarchy (czhip_mg_kind 1), on other than 0 | 1.
+ * czhip_mg_line_chunk: the cells of a row that the line kernel marches at a time in this precision (rows longer than that take the scratch). */
+int czhip_mg_set_lines(cz_mg* h, int on);
+int czhip_mg_line_chunk(void);
 /* The closed box (all six faces zero-flux): the projections onto the zero-mean fields and PCG's update with one folded in.
  * czhip_shift_sums_async: a <- a - *m_dev over the inner box (one REAL subtraction per cell), then sums_dev[0] = sum a', sums_dev[1] = sum a'^2
  *   of the values a holds afterwards (REAL products accumulated in double, as czhip_cg_update_async forms r.r).  m_dev NULL: a is only read,
@@ -600,6 +612,16 @@ int cz_set_face_coef(cz_handle*, const CZ_REAL* bx, const CZ_REAL* by, const CZ_
  * -- a sum of up to 4^l fine ones -- is not finite and positive.  The call that built the hierarchy (any of the five) then prints one
  * line, returns 0 and turns the flag off; the face coefficients (and that call's own new state) stay, and the scaled preconditioner runs. */
 int cz_set_coef_mg(cz_handle*, int on);
+/* Zebra line iterations along Z in the V-cycle of pcg ... mgrb, for grids refined towards a wall: lay the refined direction
+ * on Z.  on = 1 asks that the cycle smooths with line iterations (czhip_mg_set_lines) while the coefficient hierarchy is in force.  The flag
+ * is remembered; it is IN FORCE (cz_info 28) while it is on, cz_info 27 is 1 and the set-up preconditioner is mgrb; with mg, jacobi or none
+ * it is accepted and idle.  Whichever call settles the coefficient hierarchy carries the flag to it; where that hierarchy is dropped for a
+ * coarse overflow the lines go idle with it.  While in force cz_solve and cz_precondition apply the line cycle.  A handle on which the
+ * flag was never set, or is off again, gives the bytes of before in every state.  cz_setup clears the flag.  Returns 1, or 0 with one line
+ * on stderr and nothing changed: before cz_setup, a _maf handle, a decomposed run, on other than 0 | 1, and on = 1 on a handle whose
+ * coefficient exceeds 1 -- line iterations take 0 < coef <= 1: over-relaxed, the lagged wrap of a periodic Z makes the preconditioner
+ * indefinite. */
+int cz_set_mg_lines(cz_handle*, int on);
 /* Zero-flux (Neumann) faces for pcg: faces[6], order X-, X+, Y-, Y+, Z-, Z+ of the GLOBAL box (the order of nID), non-zero =
  * the face is a zero-flux face, zero = a Dirichlet face as before; at least one face must stay Dirichlet.  Called after cz_setup; collective,
  * with the same mask on every rank.  On a Neumann face the face layer of the field is not data but the mirror of the first inner layer
@@ -679,7 +701,8 @@ double cz_last_solve_seconds(const cz_handle*);
  * returned 0, P holds the caller's bytes (in the closed box: less its mean), cz_result_iter, cz_result_res and the history are 0 / empty --
  * the start was the answer already, or the problem is scaled below the threshold (1); anything else, a refusal or an error included (0);
  * 25 face coefficients are in force (cz_set_face_coef; 0 | 1); 26 four-sweep Jacobi passes of the last Jacobi solve (czhip_jacobi4_async;
- * 14 counts the three-sweep passes beside them); 27 the coefficient hierarchy of cz_set_coef_mg is in force (0 | 1). */
+ * 14 counts the three-sweep passes beside them); 27 the coefficient hierarchy of cz_set_coef_mg is in force (0 | 1);
+ * 28 the line iterations of cz_set_mg_lines are in force (0 | 1). */
 int cz_info(const cz_handle*, int what);
 /* The driver's and its communicator's own copies of their switches, as name=value, one per line: overlap, lag_reduce, comm_cus (as asked for;
  * 0 on a single domain), comm_cus_reserved (in force after set-up), bicg_fuse, bicg_devsc, bicg_alias, cg_fuse, mg_tail, mg_gather, mgrb_zero4,
