@@ -78,14 +78,11 @@ __device__ __forceinline__ long long egeom_eo(const EGeom& g, long long f) {
   return r * g.nkp + (f - r * g.R) * V;
 }
 
-template <int V, int OP>
-__global__ void __launch_bounds__(256)
-ewise_k(REAL* Z, const REAL* X, const REAL* Y, REAL a, REAL b, EGeom g) {
-  const long long f = g.F0 + (long long)blockIdx.x * 256 + threadIdx.x;
-  if (f >= g.Fend) return;
-  if (g.pa) a = *g.pa;
-  if (g.pb) b = *g.pb;
-  const long long pe = (long long)(g.jj0 + blockIdx.y) * g.PSE + egeom_eo<V>(g, f);
+// The streaming row frame of the kernels below: a thread owns vector f = erow_f of the row view in every plane it visits; erow_mask = the
+// components of that vector with k inside the box; egeom_eo = its element offset inside a plane.
+__device__ __forceinline__ long long erow_f(const EGeom& g) { return g.F0 + (long long)blockIdx.x * 256 + threadIdx.x; }
+template <int V>
+__device__ __forceinline__ unsigned erow_mask(const EGeom& g, long long f) {
   const int kv = (int)(f % g.R);
   unsigned mk = 0;
 #pragma unroll
@@ -93,6 +90,29 @@ ewise_k(REAL* Z, const REAL* X, const REAL* Y, REAL a, REAL b, EGeom g) {
     const int kk = kv * V + cc;
     if (kk >= g.kk0 && kk <= g.kk1) mk |= 1u << cc;
   }
+  return mk;
+}
+// body(pe, mk) at the thread's vector of the planes blockIdx.y, blockIdx.y + gridDim.y, ... below nplanes; pe = its element offset in the
+// array.  Not entered by a thread beyond the update range, nor -- unless EMPTY_TOO -- by one without a component inside the box.
+template <int V, bool EMPTY_TOO = false, class BODY>
+__device__ __forceinline__ void erow_planes(const EGeom& g, int nplanes, BODY body) {
+  const long long f = erow_f(g);
+  if (f >= g.Fend) return;
+  const unsigned mk = erow_mask<V>(g, f);
+  if (!EMPTY_TOO && mk == 0) return;
+  const long long eo = egeom_eo<V>(g, f);
+  for (int pl = blockIdx.y; pl < nplanes; pl += gridDim.y) body((long long)(g.jj0 + pl) * g.PSE + eo, mk);
+}
+
+template <int V, int OP>
+__global__ void __launch_bounds__(256)
+ewise_k(REAL* Z, const REAL* X, const REAL* Y, REAL a, REAL b, EGeom g) {
+  const long long f = erow_f(g);
+  if (f >= g.Fend) return;
+  if (g.pa) a = *g.pa;
+  if (g.pb) b = *g.pb;
+  const long long pe = (long long)(g.jj0 + blockIdx.y) * g.PSE + egeom_eo<V>(g, f);
+  const unsigned mk = erow_mask<V>(g, f);
   if (mk == 0) return;
   Vec<V> x = ldve<V>(X, pe), y, z, o;
   if (OP != OP_COPY) y = ldve<V>(Y, pe);
@@ -104,13 +124,7 @@ ewise_k(REAL* Z, const REAL* X, const REAL* Y, REAL a, REAL b, EGeom g) {
     if (OP == OP_BICG2) o.v[cc] = a * x.v[cc] + b * y.v[cc] + z.v[cc];                // :554
     if (OP == OP_COPY) o.v[cc] = x.v[cc];
   }
-  if (mk == (1u << V) - 1) {
-    stve<V>(Z, pe, o);
-  } else {
-#pragma unroll
-    for (int cc = 0; cc < V; cc++)
-      if (mk & (1u << cc)) Z[pe + cc] = o.v[cc];
-  }
+  stve_masked<V>(Z, pe, o, mk);
 }
 
 // BiCGSTAB's scalars on the device (cz_Poisson.cpp:427, 464), from the dot products the launch before left in `dots` (all-reduced in a
@@ -165,53 +179,25 @@ pivot_k(REAL* PVT, EGeom g, MafArgs ma, int nkp, int nip) {
 
 // dot products (cz_blas.f90:361-362, :426): per-point product in REAL, accumulated in double.  A workgroup strides over
 // the planes (few thousand workgroups in all); the last one to finish sums the partials in fixed order into dst[0]
-// (same write-through hand-off as the sweeps: no second launch).
+// (sums_finish, cz_k_sums.h: no second launch).
 template <int V, int TWO>
 __global__ void __launch_bounds__(256)
 dot_k(const REAL* X, const REAL* Y, EGeom g, int nplanes, double* partials, double* dst, unsigned* counter) {
-  __shared__ double wsum[4];
-  __shared__ int last_flag;
-  const long long f = g.F0 + (long long)blockIdx.x * 256 + threadIdx.x;
-  double acc = 0.0;
-  if (f < g.Fend) {
-    const int kv = (int)(f % g.R);
-    unsigned mk = 0;
+  __shared__ double wsum[5];  // cz_k_sums.h
+  double acc[1] = {0.0};
+  // (a thread whose vector lies outside the box in k walks its planes all the same and adds nothing: one division for mask and offset.
+  // Skipping it as the kernels below do costs dot_k<4, 1> 155 instructions and nine scalar registers, profiles/r32/sums_kernel_text.txt)
+  erow_planes<V, true>(g, nplanes, [&](long long pe, unsigned mk) {
+    const Vec<V> x = ldve<V>(X, pe);
+    Vec<V> y = x;
+    if (TWO) y = ldve<V>(Y, pe);
 #pragma unroll
     for (int cc = 0; cc < V; cc++) {
-      const int kk = kv * V + cc;
-      if (kk >= g.kk0 && kk <= g.kk1) mk |= 1u << cc;
+      const REAL tt = x.v[cc] * y.v[cc];
+      if (mk & (1u << cc)) acc[0] += (double)tt;
     }
-    const long long eo = egeom_eo<V>(g, f);
-    for (int pl = blockIdx.y; pl < nplanes; pl += gridDim.y) {
-      const long long pe = (long long)(g.jj0 + pl) * g.PSE + eo;
-      const Vec<V> x = ldve<V>(X, pe);
-      Vec<V> y = x;
-      if (TWO) y = ldve<V>(Y, pe);
-#pragma unroll
-      for (int cc = 0; cc < V; cc++) {
-        const REAL tt = x.v[cc] * y.v[cc];
-        if (mk & (1u << cc)) acc += (double)tt;
-      }
-    }
-  }
-  const double s = block_sum<256>(acc, wsum);
-  const int nblk = gridDim.x * gridDim.y;
-  const int me = blockIdx.y * gridDim.x + blockIdx.x;
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(&partials[me], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last_flag = arrive_and_test_last(counter, nblk);
-  }
-  __syncthreads();
-  if (last_flag) {
-    double x = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 256) x += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const double tot = block_sum<256>(x, wsum);
-    if (threadIdx.x == 0) {
-      dst[0] = tot;
-      *counter = 0u;
-    }
-  }
+  });
+  sums_finish<256>(acc, partials, counter, wsum, [&](const double (&tot)[1]) { dst[0] = tot[0]; });
 }
 
 // z = a*x + y on the inner box (blas_triad, cz_blas.f90:297) with the two dot products that follow it in BiCGSTAB folded
@@ -220,72 +206,25 @@ template <int V>
 __global__ void __launch_bounds__(256)
 triad_dots_k(REAL* Z, const REAL* X, const REAL* Y, const REAL* W, REAL a, EGeom g, int nplanes, double* partials, double* dst,
              unsigned* counter) {
-  __shared__ double wsum[4];
-  __shared__ int last_flag;
-  const long long f = g.F0 + (long long)blockIdx.x * 256 + threadIdx.x;
+  __shared__ double wsum[5];  // cz_k_sums.h
   if (g.pa) a = *g.pa;
-  double acc1 = 0.0, acc2 = 0.0;
-  if (f < g.Fend) {
-    const int kv = (int)(f % g.R);
-    unsigned mk = 0;
+  double acc[2] = {0.0, 0.0};
+  erow_planes<V>(g, nplanes, [&](long long pe, unsigned mk) {
+    const Vec<V> x = ldve<V>(X, pe), y = ldve<V>(Y, pe), w = ldve<V>(W, pe);
+    Vec<V> o;
 #pragma unroll
     for (int cc = 0; cc < V; cc++) {
-      const int kk = kv * V + cc;
-      if (kk >= g.kk0 && kk <= g.kk1) mk |= 1u << cc;
-    }
-    if (mk != 0) {
-      const long long eo = egeom_eo<V>(g, f);
-      for (int pl = blockIdx.y; pl < nplanes; pl += gridDim.y) {
-        const long long pe = (long long)(g.jj0 + pl) * g.PSE + eo;
-        const Vec<V> x = ldve<V>(X, pe), y = ldve<V>(Y, pe), w = ldve<V>(W, pe);
-        Vec<V> o;
-#pragma unroll
-        for (int cc = 0; cc < V; cc++) {
-          o.v[cc] = a * x.v[cc] + y.v[cc];
-          const REAL zz = o.v[cc] * o.v[cc];
-          const REAL zw = o.v[cc] * w.v[cc];
-          if (mk & (1u << cc)) {
-            acc1 += (double)zz;
-            acc2 += (double)zw;
-          }
-        }
-        if (mk == (1u << V) - 1) {
-          stve<V>(Z, pe, o);
-        } else {
-#pragma unroll
-          for (int cc = 0; cc < V; cc++)
-            if (mk & (1u << cc)) Z[pe + cc] = o.v[cc];
-        }
+      o.v[cc] = a * x.v[cc] + y.v[cc];
+      const REAL zz = o.v[cc] * o.v[cc];
+      const REAL zw = o.v[cc] * w.v[cc];
+      if (mk & (1u << cc)) {
+        acc[0] += (double)zz;
+        acc[1] += (double)zw;
       }
     }
-  }
-  const double s1 = block_sum<256>(acc1, wsum);
-  __syncthreads();
-  const double s2 = block_sum<256>(acc2, wsum);
-  const int nblk = gridDim.x * gridDim.y;
-  const int me = blockIdx.y * gridDim.x + blockIdx.x;
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(&partials[me], s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&partials[nblk + me], s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last_flag = arrive_and_test_last(counter, nblk);
-  }
-  __syncthreads();
-  if (last_flag) {
-    double x1 = 0.0, x2 = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 256) {
-      x1 += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      x2 += __hip_atomic_load(&partials[nblk + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    const double t1 = block_sum<256>(x1, wsum);
-    __syncthreads();
-    const double t2 = block_sum<256>(x2, wsum);
-    if (threadIdx.x == 0) {
-      dst[0] = t1;
-      dst[1] = t2;
-      *counter = 0u;
-    }
-  }
+    stve_masked<V>(Z, pe, o, mk);
+  });
+  sums_finish<256>(acc, partials, counter, wsum, [&](const double (&tot)[2]) { dst[0] = tot[0], dst[1] = tot[1]; });
 }
 
 // PCG's update (beyond the reference): x = alpha*p + x, r = (-alpha)*q + r (blas_triad twice) and dst[0] = sum r*r, one pass over the four
@@ -297,157 +236,60 @@ triad_dots_k(REAL* Z, const REAL* X, const REAL* Y, const REAL* W, REAL a, EGeom
 template <int V, bool CLOSED>
 __global__ void __launch_bounds__(256)
 cg_update_k(REAL* X, REAL* Rr, const REAL* Pd, const REAL* Q, EGeom g, int nplanes, double* partials, double* dst, unsigned* counter) {
-  __shared__ double wsum[4];
-  __shared__ int last_flag;
-  const long long f = g.F0 + (long long)blockIdx.x * 256 + threadIdx.x;
+  __shared__ double wsum[5];  // cz_k_sums.h
+  constexpr int N = CLOSED ? 2 : 1;  // sum r*r; CLOSED: and sum r
   const REAL a = *g.pa, na = *g.pb;
   const REAL m = CLOSED ? g.pa[4] : (REAL)0;
   const bool live = !(g.pg && fabs(*g.pg) < (REAL)FLT_MIN);  // (the host's test, CZ::PCG)
-  double acc = 0.0, accs = 0.0;
-  if (live && f < g.Fend) {
-    const int kv = (int)(f % g.R);
-    unsigned mk = 0;
+  double acc[N] = {};
+  if (live) {
+    erow_planes<V>(g, nplanes, [&](long long pe, unsigned mk) {
+      const Vec<V> p = ldve<V>(Pd, pe), q = ldve<V>(Q, pe), x = ldve<V>(X, pe), r = ldve<V>(Rr, pe);
+      Vec<V> xo, ro;
 #pragma unroll
-    for (int cc = 0; cc < V; cc++) {
-      const int kk = kv * V + cc;
-      if (kk >= g.kk0 && kk <= g.kk1) mk |= 1u << cc;
-    }
-    if (mk != 0) {
-      const long long eo = egeom_eo<V>(g, f);
-      for (int pl = blockIdx.y; pl < nplanes; pl += gridDim.y) {
-        const long long pe = (long long)(g.jj0 + pl) * g.PSE + eo;
-        const Vec<V> p = ldve<V>(Pd, pe), q = ldve<V>(Q, pe), x = ldve<V>(X, pe), r = ldve<V>(Rr, pe);
-        Vec<V> xo, ro;
-#pragma unroll
-        for (int cc = 0; cc < V; cc++) {
-          xo.v[cc] = a * p.v[cc] + x.v[cc];
-          ro.v[cc] = na * q.v[cc] + r.v[cc];
-          if (CLOSED) ro.v[cc] = ro.v[cc] - m;
-          const REAL rr = ro.v[cc] * ro.v[cc];
-          if (mk & (1u << cc)) {
-            acc += (double)rr;
-            if (CLOSED) accs += (double)ro.v[cc];
-          }
-        }
-        if (mk == (1u << V) - 1) {
-          stve<V>(X, pe, xo);
-          stve<V>(Rr, pe, ro);
-        } else {
-#pragma unroll
-          for (int cc = 0; cc < V; cc++)
-            if (mk & (1u << cc)) X[pe + cc] = xo.v[cc], Rr[pe + cc] = ro.v[cc];
+      for (int cc = 0; cc < V; cc++) {
+        xo.v[cc] = a * p.v[cc] + x.v[cc];
+        ro.v[cc] = na * q.v[cc] + r.v[cc];
+        if (CLOSED) ro.v[cc] = ro.v[cc] - m;
+        const REAL rr = ro.v[cc] * ro.v[cc];
+        if (mk & (1u << cc)) {
+          acc[0] += (double)rr;
+          if (CLOSED) acc[N - 1] += (double)ro.v[cc];
         }
       }
-    }
+      stve_masked<V>(X, pe, xo, mk);
+      stve_masked<V>(Rr, pe, ro, mk);
+    });
   }
-  const double s = block_sum<256>(acc, wsum);
-  double s2 = 0.0;
-  if (CLOSED) {
-    __syncthreads();
-    s2 = block_sum<256>(accs, wsum);
-  }
-  const int nblk = gridDim.x * gridDim.y;
-  const int me = blockIdx.y * gridDim.x + blockIdx.x;
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(&partials[me], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (CLOSED) __hip_atomic_store(&partials[nblk + me], s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last_flag = arrive_and_test_last(counter, nblk);
-  }
-  __syncthreads();
-  if (last_flag) {
-    double x = 0.0, x2 = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 256) {
-      x += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (CLOSED) x2 += __hip_atomic_load(&partials[nblk + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    const double tot = block_sum<256>(x, wsum);
-    double tot2 = 0.0;
-    if (CLOSED) {
-      __syncthreads();
-      tot2 = block_sum<256>(x2, wsum);
-    }
-    if (threadIdx.x == 0) {
-      dst[0] = tot;
-      if (CLOSED) dst[1] = tot2;
-      *counter = 0u;
-    }
-  }
+  sums_finish<256>(acc, partials, counter, wsum, [&](const double (&tot)[N]) {
+    dst[0] = tot[0];
+    if (CLOSED) dst[1] = tot[N - 1];
+  });
 }
 
 // The closed box: a <- a - *m over the inner box (SHIFT; false: a is only read, m is not), with dst[0] = sum a' and
 // dst[1] = sum a'^2 of the values a holds afterwards -- the squares as REAL products widened, like every dot here.  It projects the
-// right-hand side, the initial residual and the answer of a closed-box solve.  Row split, vector width, edge masks, offsets and the
-// last-workgroup finalisation are those of cg_update_k / triad_dots_k.
+// right-hand side, the initial residual and the answer of a closed-box solve.  Row frame and hand-off are those of triad_dots_k.
 template <int V, bool SHIFT>
 __global__ void __launch_bounds__(256)
 shift_sums_k(REAL* A, const REAL* mp, EGeom g, int nplanes, double* partials, double* dst, unsigned* counter) {
-  __shared__ double wsum[4];
-  __shared__ int last_flag;
-  const long long f = g.F0 + (long long)blockIdx.x * 256 + threadIdx.x;
+  __shared__ double wsum[5];  // cz_k_sums.h
   const REAL m = SHIFT ? *mp : (REAL)0;
-  double acc1 = 0.0, acc2 = 0.0;
-  if (f < g.Fend) {
-    const int kv = (int)(f % g.R);
-    unsigned mk = 0;
+  double acc[2] = {0.0, 0.0};
+  erow_planes<V>(g, nplanes, [&](long long pe, unsigned mk) {
+    Vec<V> o = ldve<V>(A, pe);
 #pragma unroll
     for (int cc = 0; cc < V; cc++) {
-      const int kk = kv * V + cc;
-      if (kk >= g.kk0 && kk <= g.kk1) mk |= 1u << cc;
-    }
-    if (mk != 0) {
-      const long long eo = egeom_eo<V>(g, f);
-      for (int pl = blockIdx.y; pl < nplanes; pl += gridDim.y) {
-        const long long pe = (long long)(g.jj0 + pl) * g.PSE + eo;
-        Vec<V> o = ldve<V>(A, pe);
-#pragma unroll
-        for (int cc = 0; cc < V; cc++) {
-          if (SHIFT) o.v[cc] = o.v[cc] - m;
-          const REAL aa = o.v[cc] * o.v[cc];
-          if (mk & (1u << cc)) {
-            acc1 += (double)o.v[cc];
-            acc2 += (double)aa;
-          }
-        }
-        if (SHIFT) {
-          if (mk == (1u << V) - 1) {
-            stve<V>(A, pe, o);
-          } else {
-#pragma unroll
-            for (int cc = 0; cc < V; cc++)
-              if (mk & (1u << cc)) A[pe + cc] = o.v[cc];
-          }
-        }
+      if (SHIFT) o.v[cc] = o.v[cc] - m;
+      const REAL aa = o.v[cc] * o.v[cc];
+      if (mk & (1u << cc)) {
+        acc[0] += (double)o.v[cc];
+        acc[1] += (double)aa;
       }
     }
-  }
-  const double s1 = block_sum<256>(acc1, wsum);
-  __syncthreads();
-  const double s2 = block_sum<256>(acc2, wsum);
-  const int nblk = gridDim.x * gridDim.y;
-  const int me = blockIdx.y * gridDim.x + blockIdx.x;
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(&partials[me], s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&partials[nblk + me], s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last_flag = arrive_and_test_last(counter, nblk);
-  }
-  __syncthreads();
-  if (last_flag) {
-    double x1 = 0.0, x2 = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 256) {
-      x1 += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      x2 += __hip_atomic_load(&partials[nblk + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    const double t1 = block_sum<256>(x1, wsum);
-    __syncthreads();
-    const double t2 = block_sum<256>(x2, wsum);
-    if (threadIdx.x == 0) {
-      dst[0] = t1;
-      dst[1] = t2;
-      *counter = 0u;
-    }
-  }
+    if (SHIFT) stve_masked<V>(A, pe, o, mk);
+  });
+  sums_finish<256>(acc, partials, counter, wsum, [&](const double (&tot)[2]) { dst[0] = tot[0], dst[1] = tot[1]; });
 }
 
 // the mean of a closed-box projection on the device: double division, then the one rounding to REAL; keep (optional) receives a copy that

@@ -14,7 +14,7 @@
 //                 row cut into the 16-byte vectors of Q, stored aligned; every operand loaded with REAL-aligned 16-byte loads (the rows i - 1,
 //                 i + 1, j - 1, j + 1 of P and i - 1, j - 1 of BX, BY are the rows neighbouring threads ask for at the same time: L2 / MALL);
 //                 a vector that the box cuts goes cell by cell.  The sums go through the workgroups' partials and are added in index order by
-//                 the workgroup that arrives last (proj_sum_finish's scheme, two sums side by side).
+//                 the workgroup that arrives last (sums_finish, cz_k_sums.h; MODE 1 has one sum).
 //   coef_scale_k  out = S in where S is not zero, 0 elsewhere, over whole padded arrays (S is zero outside the box): the diagonal scaling
 //                 either side of the preconditioner.  out may be in.
 //   grad_coef_*   cz_sub_grad's coefficient form: U(i) = U(i) - (BX(i) (P(i+1) - P(i))) scale, V and W likewise -- grad_row_k / grad_any_k with
@@ -63,40 +63,6 @@ __global__ __launch_bounds__(256) void coef_prep_k(REAL* __restrict__ BX, REAL* 
   if (nbad) atomicAdd(bad, nbad);
 }
 
-// two sums of the grid: the workgroups' sums -> partials[me], partials[nblk + me]; the workgroup that arrives last adds each row in index
-// order into out[0], out[1] (every thread of the grid calls it)
-__device__ __forceinline__ void coef_sums_finish(double acc0, double acc1, double* partials, double* out, unsigned* counter) {
-  __shared__ double wsum[4];
-  __shared__ int last_flag;
-  const double s0 = block_sum<256>(acc0, wsum);
-  __syncthreads();
-  const double s1 = block_sum<256>(acc1, wsum);
-  const int nblk = gridDim.x * gridDim.y;
-  const int me = blockIdx.y * gridDim.x + blockIdx.x;
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(&partials[me], s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&partials[nblk + me], s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last_flag = arrive_and_test_last(counter, nblk);
-  }
-  __syncthreads();
-  if (last_flag) {
-    double x0 = 0.0, x1 = 0.0;
-    for (int n = threadIdx.x; n < nblk; n += 256) {
-      x0 += __hip_atomic_load(&partials[n], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      x1 += __hip_atomic_load(&partials[nblk + n], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    const double t0 = block_sum<256>(x0, wsum);
-    __syncthreads();
-    const double t1 = block_sum<256>(x1, wsum);
-    if (threadIdx.x == 0) {
-      out[0] = t0;
-      out[1] = t1;
-      *counter = 0u;
-    }
-  }
-}
-
 // A p at the cell at element e of the padded arrays
 __device__ __forceinline__ REAL coef_ax_cell(const REAL* __restrict__ P, const REAL* __restrict__ BX, const REAL* __restrict__ BY, const REAL* __restrict__ BZ,
                                              long long e, long long nkp, long long PSE) {
@@ -111,6 +77,7 @@ template <int V, int MODE>
 __global__ __launch_bounds__(256) void ax_coef_k(REAL* __restrict__ Q, const REAL* __restrict__ P, const REAL* __restrict__ B, const REAL* __restrict__ BX,
                                                  const REAL* __restrict__ BY, const REAL* __restrict__ BZ, const FieldGeom g, const FieldBox bx,
                                                  const int slots, double* partials, double* out, unsigned* counter) {
+  __shared__ double wsum[5];  // cz_k_sums.h
   const int per_plane = (bx.hi0 - bx.lo0 + 1) * slots;
   const long long nkp = g.nkp;
   double acc0 = 0.0, acc1 = 0.0;
@@ -169,7 +136,8 @@ __global__ __launch_bounds__(256) void ax_coef_k(REAL* __restrict__ Q, const REA
       }
     }
   }
-  coef_sums_finish(acc0, acc1, partials, out, counter);
+  const double acc[2] = {acc0, acc1};
+  sums_finish<256>(acc, partials, counter, wsum, [&](const double (&tot)[2]) { out[0] = tot[0], out[1] = tot[1]; });
 }
 
 // (no __restrict__: the scaling after the preconditioner runs in place)

@@ -15,6 +15,14 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// End of a line-solver launch, all threads: the workgroups' residual sums by the hand-off of cz_k_sums.h, one partial per workgroup of
+// the one-dimensional grid, into dst[0] (= or +=).
+template <int TB>
+__device__ __forceinline__ void line_residual(double acc, double* partials, double* dst, int accumulate, unsigned* counter, double* wsum) {
+  const double a1[1] = {acc};
+  sums_finish<TB>(a1, partials, SumsGrid1{}, counter, wsum, SumsNoMore{}, [&](const double (&tot)[1]) { dst[0] = accumulate ? dst[0] + tot[0] : tot[0]; });
+}
+
 struct PcrGeom {
   int nkp, nip;                 // padded extents
   int kk0, n;                   // padded index of kst, number of unknowns per column
@@ -204,26 +212,9 @@ pcr_rb_k(REAL* X, REAL* WOUT, const REAL* __restrict__ MSK, const REAL* __restri
   }
   wave_lds_sync();  // (the next column's set-up overwrites the buffers)
   }  // columns of this wave
-  // ---- residual: partial per workgroup, fixed-order sum by the last one (write-through hand-off as in stencil_k)
+  // ---- residual: partial per workgroup, fixed-order sum by the last one (line_residual)
   __syncthreads();
-  const double sblk = block_sum<64 * NW>(acc, wsum);
-  int* last_flag = reinterpret_cast<int*>(wsum + 8);
-  const int nblk = gridDim.x;
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(&partials[blockIdx.x], sblk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *last_flag = arrive_and_test_last(counter, nblk);
-  }
-  __syncthreads();
-  if (*last_flag) {
-    double x = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 64 * NW) x += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const double tot = block_sum<64 * NW>(x, wsum);
-    if (threadIdx.x == 0) {
-      dst[0] = accumulate ? dst[0] + tot : tot;
-      *counter = 0u;
-    }
-  }
+  line_residual<64 * NW>(acc, partials, dst, accumulate, counter, wsum);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -564,26 +555,9 @@ pcr_rb2_k(REAL* X, REAL* WOUT, const REAL* __restrict__ MSK, const REAL* __restr
     }
     wave_lds_sync();  // the next group's source term overwrites buffer 0
   }
-  // ---- residual: partial per workgroup, fixed-order sum by the last one (write-through hand-off as in stencil_k)
+  // ---- residual: partial per workgroup, fixed-order sum by the last one (line_residual)
   __syncthreads();
-  const double sblk = block_sum<64 * NW>(acc, wsum);
-  int* last_flag = reinterpret_cast<int*>(wsum + 16);
-  const int nblk = gridDim.x;
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(&partials[blockIdx.x], sblk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *last_flag = arrive_and_test_last(counter, nblk);
-  }
-  __syncthreads();
-  if (*last_flag) {
-    double x = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 64 * NW) x += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const double tot = block_sum<64 * NW>(x, wsum);
-    if (threadIdx.x == 0) {
-      dst[0] = accumulate ? dst[0] + tot : tot;
-      *counter = 0u;
-    }
-  }
+  line_residual<64 * NW>(acc, partials, dst, accumulate, counter, wsum);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -842,26 +816,9 @@ pcr_line_reg_k(REAL* X, REAL* WOUT, const REAL* __restrict__ MSK, const REAL* __
       }
     }
   }
-  // ---- residual: partial per workgroup, fixed-order sum by the last one (write-through hand-off as in stencil_k)
+  // ---- residual: partial per workgroup, fixed-order sum by the last one (line_residual)
   __syncthreads();
-  const double sblk = block_sum<64 * NW>(acc, wsum);
-  int* last_flag = reinterpret_cast<int*>(wsum + 16);
-  const int nblk = gridDim.x;
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(&partials[blockIdx.x], sblk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *last_flag = arrive_and_test_last(counter, nblk);
-  }
-  __syncthreads();
-  if (*last_flag) {
-    double x = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 64 * NW) x += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const double tot = block_sum<64 * NW>(x, wsum);
-    if (threadIdx.x == 0) {
-      dst[0] = accumulate ? dst[0] + tot : tot;
-      *counter = 0u;
-    }
-  }
+  line_residual<64 * NW>(acc, partials, dst, accumulate, counter, wsum);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1026,24 +983,7 @@ pcr_line_reg_maf_k(REAL* X, const REAL* __restrict__ MSK, const REAL* __restrict
     }
   }
   // ---- residual (as in pcr_line_reg_k)
-  const double sblk = block_sum<64 * NW>(acc, wsum);
-  int* last_flag = reinterpret_cast<int*>(wsum + NW + 2);
-  const int nblk = gridDim.x;
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(&partials[blockIdx.x], sblk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *last_flag = arrive_and_test_last(counter, nblk);
-  }
-  __syncthreads();
-  if (*last_flag) {
-    double x = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 64 * NW) x += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const double tot = block_sum<64 * NW>(x, wsum);
-    if (threadIdx.x == 0) {
-      dst[0] = accumulate ? dst[0] + tot : tot;
-      *counter = 0u;
-    }
-  }
+  line_residual<64 * NW>(acc, partials, dst, accumulate, counter, wsum);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1099,18 +1039,6 @@ __device__ __forceinline__ bool pipe_give_up(unsigned& polls, long long& t0, lon
   if (now - t0 <= limit) return false;
   __hip_atomic_store(&ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return true;
-}
-
-__device__ __forceinline__ double block_sum_rt(double x, double* wsum, int nwaves) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) wsum[wave] = x;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < nwaves; w++) s += wsum[w];
-  return s;  // valid on thread 0
 }
 
 // workgroup barrier that orders LDS accesses only: __syncthreads() would also wait for every global load and store in flight
@@ -1517,27 +1445,18 @@ pcr_lex_wg_k(REAL* X, const REAL* __restrict__ MSK, const REAL* __restrict__ RHS
     }
     __syncthreads();
     const double sblk = block_sum_rt(acc, wsum, nwaves);
-    if (t == 0) __hip_atomic_store(&partials[strip], sblk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == 0) sums_put(&partials[strip], sblk);
     if (kLexProf && prof && t == 0) {
       long long* q = prof + (size_t)8 * strip;
       q[0] = pf_start, q[1] = pf_first, q[2] = (long long)wall_clock64(), q[3] = pf_wait, q[4] = pf_nwait, q[5] = blockIdx.x, q[6] = (pf_ph[0] << 32) | pf_ph[1], q[7] = (pf_ph[2] << 32) | pf_ph[3];
     }
   }
-  // ---- residual: the strips' partials in strip order, by the workgroup that arrives last (hand-off as in stencil_k)
-  int* last_flag = sh + 4;
-  const int nblk = gridDim.x;
-  if (t == 0) *last_flag = arrive_and_test_last(counter, nblk);
-  __syncthreads();
-  if (*last_flag) {
-    double xs = 0.0;
-    for (int q = t; q < nstrips; q += NT * R) xs += __hip_atomic_load(&partials[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const double tot = block_sum_rt(xs, wsum, nwaves);
-    if (t == 0) {
+  // ---- residual: the strips' partials in strip order, by the workgroup that arrives last (cz_k_sums.h; the thread count is a run-time one)
+  if (sums_arrive<0>(counter, gridDim.x, wsum, NT * R)) {
+    sums_last<0, 1>(partials, 0, nstrips, counter, wsum, SumsNoMore{}, [&](const double (&tot)[1]) {
       const bool bad = __hip_atomic_load(&ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-      dst[0] = bad ? __builtin_nan("") : (accumulate ? dst[0] + tot : tot);
-      *counter = 0u;
-    }
+      dst[0] = bad ? __builtin_nan("") : (accumulate ? dst[0] + tot[0] : tot[0]);
+    }, NT * R);
   }
 }
 

@@ -3,7 +3,7 @@
 // the shell kernel of a split pass (cz_k_pair.h).  What they share is stated here once: the geometry (Geom2) and the finalisation record
 // (Fin2), the per-point update (relax_vec*), the map from a workgroup id to its work item (pass_item), the addresses of the windowed row
 // view (RowView), the masks of a vector (vec_mask), the staging of the outer rows (outer_row), the masked store (store_owned) and the
-// residual epilogue (pass_epilogue, pass_finalize).  For rb4_k, jac3_k and jac4_k also the LDS carve-up (deep_lds) and its size, which their
+// residual epilogue (pass_epilogue, on cz_k_sums.h).  For rb4_k, jac3_k and jac4_k also the LDS carve-up (deep_lds) and its size, which their
 // launcher takes from here (deep_lds_bytes).  jac3_k and jac4_k further share a stage's two halves and the division policy (jac_fetch,
 // jac_relax, JacDiv; cz_k_jac3.h).  What a kernel writes itself: how its threads are dealt to the vectors, which vectors it owns, its
 // prologue, its per-lane set-up and the plane step with its requests.  Those differ between rb4_k, jac3_k and jac4_k in little but the depth,
@@ -438,68 +438,38 @@ __device__ __forceinline__ DeepLds<V> deep_lds(char* smem, int R) {
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// The workgroup whose ticket came last sums all per-workgroup partials in a fixed order (sc1 loads, see stencil_k) and does the
-// bookkeeping of cz_Poisson.cpp:67-77 for the iterations of the pass in order: record the residual of iteration itr + s, stop at the first
-// that converged.  N sums are N iterations, or with fin.single (N = 2: the two colours of a red-black iteration, cz_Poisson.cpp:205-209
-// accumulate into one res) ONE.  Called by every thread of that workgroup.  The order of the additions is part of the contract: a thread's
-// strided partials, then its strided `extra` terms (written by an earlier launch on this stream), block_sum per residual, t1 + t2 last.
-template <int TB, int N>
-__device__ __forceinline__ void pass_finalize(const double* partials, int nblk, const Fin2& fin, double* wsum) {
-  const int t = threadIdx.x;
-  double x[N];
-#pragma unroll
-  for (int s = 0; s < N; s++) x[s] = 0.0;
-  for (int i = t; i < nblk; i += TB) {
-#pragma unroll
-    for (int s = 0; s < N; s++) x[s] += __hip_atomic_load(&partials[s * nblk + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  for (int i = t; i < fin.n_extra; i += TB) {
-#pragma unroll
-    for (int s = 0; s < N; s++) x[s] += fin.extra[s * fin.n_extra + i];
-  }
-  double tot[N];
-#pragma unroll
-  for (int s = 0; s < N; s++) {
-    __syncthreads();
-    tot[s] = block_sum<TB>(x[s], wsum);
-  }
-  if (t == 0) {
-    const bool single = N == 2 && fin.single;
-    if (single) tot[0] = tot[0] + tot[1];
-    const int nit = single ? 1 : N;
-    for (int s = 0; s < nit; s++) fin.dst[s] = tot[s];
-    if (fin.do_check) {
-      for (int s = 0; s < nit; s++) {
-        const double r = sqrt(tot[s] * fin.res_normal);
-        fin.hist[fin.itr + s] = r;
-        if (r < fin.eps) {
-          *fin.flag = 1;
-          *fin.conv_itr = fin.itr + s;
-          break;
-        }
-      }
-    }
-    *fin.counter = 0u;
-  }
-}
-
-// End of a pass kernel, all threads: the workgroup's N residual sums as write-through partials (partials[s * nblk + id]), the ticket, and
-// the finalisation by the workgroup that arrives last (hand-off: arrive_and_test_last).  wsum: 18 doubles of LDS.
+// End of a pass kernel, all threads: the workgroup's N residual sums through the hand-off of cz_k_sums.h (partials[s * nblk + id]).  What
+// the pass adds to it: a thread of the last workgroup also takes its strided share of the `extra` terms (written by an earlier launch on
+// this stream) after its partials, and thread 0 does the bookkeeping of cz_Poisson.cpp:67-77 for the iterations of the pass in order --
+// record the residual of iteration itr + s, stop at the first that converged.  N sums are N iterations, or with fin.single (N = 2: the two
+// colours of a red-black iteration, cz_Poisson.cpp:205-209 accumulate into one res) ONE: t1 + t2 comes last.  wsum: TB / 64 + 1 doubles of LDS.
 template <int TB, int N>
 __device__ __forceinline__ void pass_epilogue(const double (&acc)[N], double* partials, const Fin2& fin, double* wsum) {
-  const int lb = blockIdx.x, nblk = gridDim.x;
-  double s[N];
-#pragma unroll
-  for (int n = 0; n < N; n++) {
-    __syncthreads();
-    s[n] = block_sum<TB>(acc[n], wsum);
-  }
-  int* last_flag = reinterpret_cast<int*>(wsum + 16);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int n = 0; n < N; n++) __hip_atomic_store(&partials[n * nblk + lb], s[n], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *last_flag = arrive_and_test_last(fin.counter, nblk);
-  }
+  const SumsAt at{(int)blockIdx.x, (int)gridDim.x};
   __syncthreads();
-  if (*last_flag) pass_finalize<TB, N>(partials, nblk, fin, wsum);
+  sums_finish<TB>(
+      acc, partials, at, fin.counter, wsum,
+      [&](double (&x)[N]) {
+        for (int i = threadIdx.x; i < fin.n_extra; i += TB) {
+#pragma unroll
+          for (int q = 0; q < N; q++) x[q] += fin.extra[q * fin.n_extra + i];
+        }
+      },
+      [&](double (&tot)[N]) {
+        const bool single = N == 2 && fin.single;
+        if (single) tot[0] = tot[0] + tot[1];
+        const int nit = single ? 1 : N;
+        for (int q = 0; q < nit; q++) fin.dst[q] = tot[q];
+        if (fin.do_check) {
+          for (int q = 0; q < nit; q++) {
+            const double r = sqrt(tot[q] * fin.res_normal);
+            fin.hist[fin.itr + q] = r;
+            if (r < fin.eps) {
+              *fin.flag = 1;
+              *fin.conv_itr = fin.itr + q;
+              break;
+            }
+          }
+        }
+      });
 }

@@ -8,7 +8,7 @@
 // (RHS, P) are cz_k_field.h's A side.
 //   div   at every inner cell  d = ((U(i) - U(i-1)) + (V(j) - V(j-1))) + (W(k) - W(k-1)),  RHS = d scale, each operation rounded once; 0 at the
 //         brick's other cells; sum d^2 (double squares, double sums) through the workgroups' partials, summed in a fixed order by the
-//         workgroup that arrives last (as resid_row_k).  3 reads + 1 write per cell: the rows i - 1 and j - 1 and the element k - 1 are
+//         workgroup that arrives last (cz_k_sums.h).  3 reads + 1 write per cell: the rows i - 1 and j - 1 and the element k - 1 are
 //         the rows and elements that neighbouring threads of the grid ask for at the same time, served by L2 / MALL.
 //   grad  U(i, j, k) = U(i, j, k) - (P(i+1, j, k) - P(i, j, k)) scale for faces 0 .. ni - 2 at inner j, k; V and W likewise.  P's face layers
 //         are the handle's (mirror, wrap or Dirichlet value).  A thread reads only elements of the velocity that it writes itself, and no
@@ -26,34 +26,11 @@ __device__ __forceinline__ REAL div_cell(const REAL* __restrict__ U, const REAL*
   return (dx + dy) + dz;
 }
 
-// the workgroup's sum -> partials; the workgroup that arrives last sums them in index order into out[0] (every thread of the grid calls it)
-__device__ __forceinline__ void proj_sum_finish(double acc, double* partials, double* out, unsigned* counter) {
-  __shared__ double wsum[4];
-  __shared__ int last_flag;
-  const double sblk = block_sum<256>(acc, wsum);
-  const int nblk = gridDim.x * gridDim.y;
-  const int me = blockIdx.y * gridDim.x + blockIdx.x;
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(&partials[me], sblk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last_flag = arrive_and_test_last(counter, nblk);
-  }
-  __syncthreads();
-  if (last_flag) {
-    double x = 0.0;
-    for (int n = threadIdx.x; n < nblk; n += 256) x += __hip_atomic_load(&partials[n], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const double tot = block_sum<256>(x, wsum);
-    if (threadIdx.x == 0) {
-      out[0] = tot;
-      *counter = 0u;
-    }
-  }
-}
-
 template <int V>
 __global__ __launch_bounds__(256) void div_row_k(REAL* __restrict__ B, const REAL* __restrict__ U, const REAL* __restrict__ Vv, const REAL* __restrict__ W,
                                                  const FieldGeom g, const int per, const REAL scale, const int slots, double* partials, double* out,
                                                  unsigned* counter) {
+  __shared__ double wsum[5];  // cz_k_sums.h
   const int per_plane = g.ni * slots;
   double acc = 0.0;
   for (int j = blockIdx.y; j < g.nj; j += gridDim.y) {
@@ -104,11 +81,13 @@ __global__ __launch_bounds__(256) void div_row_k(REAL* __restrict__ B, const REA
       }
     }
   }
-  proj_sum_finish(acc, partials, out, counter);
+  const double a1[1] = {acc};
+  sums_finish<256>(a1, partials, counter, wsum, [&](const double (&tot)[1]) { out[0] = tot[0]; });
 }
 
 __global__ __launch_bounds__(256) void div_any_k(REAL* __restrict__ B, const REAL* __restrict__ U, const REAL* __restrict__ Vv, const REAL* __restrict__ W,
                                                  const FieldGeom g, const int per, const REAL scale, double* partials, double* out, unsigned* counter) {
+  __shared__ double wsum[5];  // cz_k_sums.h
   const long long per_plane = (long long)g.ni * g.nk;
   double acc = 0.0;
   for (int j = blockIdx.y; j < g.nj; j += gridDim.y) {
@@ -128,7 +107,8 @@ __global__ __launch_bounds__(256) void div_any_k(REAL* __restrict__ B, const REA
       B[a] = r;
     }
   }
-  proj_sum_finish(acc, partials, out, counter);
+  const double a1[1] = {acc};
+  sums_finish<256>(a1, partials, counter, wsum, [&](const double (&tot)[1]) { out[0] = tot[0]; });
 }
 
 // run s of the k row whose cell 0 is element u of X and element a of P: X = X - (P(+pstep) - P) scale at the cells klo .. khi.  alias != 0:

@@ -417,25 +417,17 @@ psor_col_k(REAL* __restrict__ P, const REAL* __restrict__ B, Coef c, PsorColGeom
 #pragma unroll
     for (int n = 0; n < NC; n++) {
       const double sblk = block_sum<NT>((wv < NCW && cs == n) ? acc : 0.0, wsum);
-      if (t == 0 && order[NC * ticket + n] >= 0) __hip_atomic_store(&partials[order[NC * ticket + n]], sblk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (t == 0 && order[NC * ticket + n] >= 0) sums_put(&partials[order[NC * ticket + n]], sblk);
       __syncthreads();
     }
   }
-  // ---- residual: the columns' partials in column order, by the workgroup that arrives last (hand-off as in stencil_k)
-  const int nblk = gridDim.x;
+  // ---- residual: the columns' partials in column order, by the workgroup that arrives last (cz_k_sums.h)
   __syncthreads();
-  if (t == 0) sh[3] = arrive_and_test_last(counter, nblk);
-  __syncthreads();
-  if (sh[3]) {
-    double xs = 0.0;
-    for (int q = t; q < ncols; q += NT) xs += __hip_atomic_load(&partials[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const double tot = block_sum<NT>(xs, wsum);
-    if (t == 0) {
+  if (sums_arrive<NT>(counter, gridDim.x, wsum)) {
+    sums_last<NT, 1>(partials, 0, ncols, counter, wsum, SumsNoMore{}, [&](const double (&tot)[1]) {
       const bool bad = __hip_atomic_load(&ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-      dst[0] = bad ? __builtin_nan("") : (accumulate ? dst[0] + tot : tot);
+      dst[0] = bad ? __builtin_nan("") : (accumulate ? dst[0] + tot[0] : tot[0]);
       if (bad) ctl[2] = 1u;  // (sticky: the launcher clears ctl[0..1] only; the host asks with psor_failed)
-      *counter = 0u;
-    }
+    });
   }
 }

@@ -7,7 +7,7 @@
 //               cells of a row:
 //                 sum    cells 4 s .. 4 s + 3 -- a partition that depends on the brick alone, so that the sum has the same bits whatever the
 //                        destination is (its type, its strides, none at all); squares and sums in double, block_sum, then the fixed-order sum
-//                        of the workgroups' partials by the workgroup that arrives last (as dot_k);
+//                        of the workgroups' partials by the workgroup that arrives last (cz_k_sums.h);
 //                 store  cells 4 s - ph .. 4 s - ph + 3, ph = the phase of the destination row against a 16-byte boundary: whole 16-byte
 //                        vectors of the DESTINATION stored aligned (one of four floats, two of two doubles), the cells before the first and
 //                        after the last whole vector of a row one by one.  ph = 0 (aligned rows of a multiple of the vector width -- any
@@ -57,8 +57,7 @@ __global__ __launch_bounds__(256) void resid_row_k(T* __restrict__ dst, const RE
                                                    double* out, unsigned* counter) {
   constexpr int VT = 16 / sizeof(T);
   typedef T nvt __attribute__((ext_vector_type(VT)));
-  __shared__ double wsum[4];
-  __shared__ int last_flag;
+  __shared__ double wsum[5];  // cz_k_sums.h
   const int per_plane = g.ni * slots;
   double acc = 0.0;
   for (int j = blockIdx.y; j < g.nj; j += gridDim.y) {
@@ -106,24 +105,8 @@ __global__ __launch_bounds__(256) void resid_row_k(T* __restrict__ dst, const RE
       }
     }
   }
-  const double sblk = block_sum<256>(acc, wsum);
-  const int nblk = gridDim.x * gridDim.y;
-  const int me = blockIdx.y * gridDim.x + blockIdx.x;
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(&partials[me], sblk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last_flag = arrive_and_test_last(counter, nblk);
-  }
-  __syncthreads();
-  if (last_flag) {
-    double x = 0.0;
-    for (int n = threadIdx.x; n < nblk; n += 256) x += __hip_atomic_load(&partials[n], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const double tot = block_sum<256>(x, wsum);
-    if (threadIdx.x == 0) {
-      out[0] = tot;
-      *counter = 0u;
-    }
-  }
+  const double a1[1] = {acc};
+  sums_finish<256>(a1, partials, counter, wsum, [&](const double (&tot)[1]) { out[0] = tot[0]; });
 }
 
 template <class T>

@@ -266,13 +266,7 @@ stencil_k(const REAL* P, const REAL* B, REAL* OUT, Coef c, Geom g, int par, doub
             const REAL uq = pc[m].v[cc] * o.v[cc];
             if (wmask & (1u << cc)) acc += (double)uq;
           }
-          if (wmask == (1u << V) - 1) {
-            stve<V>(Uc, eo[m], pc[m]);
-          } else {
-#pragma unroll
-            for (int cc = 0; cc < V; cc++)
-              if (wmask & (1u << cc)) Uc[eo[m] + cc] = pc[m].v[cc];
-          }
+          stve_masked<V>(Uc, eo[m], pc[m], wmask);
         }
         if (MODE == MODE_RB) {
           // in place: components of the other colour / outside the box keep their value; a full-vector store
@@ -288,13 +282,7 @@ stencil_k(const REAL* P, const REAL* B, REAL* OUT, Coef c, Geom g, int par, doub
               if (wmask & (1u << cc)) Oc[eo[m] + cc] = o.v[cc];
           }
         } else {
-          if (wmask == (1u << V) - 1) {
-            stve<V>(Oc, eo[m], o);
-          } else {
-#pragma unroll
-            for (int cc = 0; cc < V; cc++)
-              if (wmask & (1u << cc)) Oc[eo[m] + cc] = o.v[cc];
-          }
+          stve_masked<V>(Oc, eo[m], o, wmask);
         }
       }
 
@@ -331,55 +319,30 @@ stencil_k(const REAL* P, const REAL* B, REAL* OUT, Coef c, Geom g, int par, doub
   }
 
   if (MODE == MODE_JACOBI || MODE == MODE_RB || MODE == MODE_DIRAX || ax_dots) {
+    constexpr int N = (MODE == MODE_AX) ? 2 : 1;  // MODE_AX comes here with ax_dots only: sum out*y and sum out*out
+    double accs[N];
+    accs[0] = acc;
+    if (N == 2) accs[N - 1] = acc2;
+    double s[N];
     __syncthreads();
-    const double s = block_sum<TB>(acc, wsum);
-    double s2 = 0.0;
-    if (ax_dots) {
-      __syncthreads();
-      s2 = block_sum<TB>(acc2, wsum);
-    }
+    sums_block<TB, N>(accs, wsum, s);
     if (fin.dst == nullptr) {
-      if (t == 0) partials[lb] = s;
-    } else {
-      int* last_flag = reinterpret_cast<int*>(wsum + 16);
-      if (t == 0) {
-        // write-through (sc1) store of the partial, drained, then the ticket: no L2 write-back fence per workgroup
-        // (a release fence here flushes the XCD's dirty p' lines and cost +27 % on the whole sweep, profiles/README.md)
-        __hip_atomic_store(&partials[lb], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (ax_dots) __hip_atomic_store(&partials[nblk + lb], s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *last_flag = arrive_and_test_last(fin.counter, nblk);
-      }
-      __syncthreads();
-      if (*last_flag) {
-        double x = 0.0, x2 = 0.0;
-        // every load of the handed-off partials is an sc1 (agent-scope) load
-        for (int i = t; i < nblk; i += TB) {
-          x += __hip_atomic_load(&partials[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (ax_dots) x2 += __hip_atomic_load(&partials[nblk + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        const double tot = block_sum<TB>(x, wsum);
-        double tot2 = 0.0;
-        if (ax_dots) {
-          __syncthreads();
-          tot2 = block_sum<TB>(x2, wsum);
-        }
-        if (t == 0) {
-          double r = fin.accumulate ? fin.dst[0] + tot : tot;
-          fin.dst[0] = r;
-          if (ax_dots) fin.dst2[0] = tot2;
-          if (fin.do_check) {  // cz_Poisson.cpp:69-77
-            r *= fin.res_normal;
-            r = sqrt(r);
-            fin.hist[fin.itr] = r;
-            if (r < fin.eps) {
-              *fin.flag = 1;
-              *fin.conv_itr = fin.itr;
-            }
+      if (t == 0) partials[lb] = s[0];  // a later launch folds the partials
+    } else if (sums_arrive<TB>(s, partials, nblk, lb, fin.counter, nblk, wsum)) {  // cz_k_sums.h
+      sums_last<TB, N>(partials, nblk, nblk, fin.counter, wsum, SumsNoMore{}, [&](const double (&tot)[N]) {
+        double r = fin.accumulate ? fin.dst[0] + tot[0] : tot[0];
+        fin.dst[0] = r;
+        if (ax_dots) fin.dst2[0] = tot[N - 1];
+        if (fin.do_check) {  // cz_Poisson.cpp:69-77
+          r *= fin.res_normal;
+          r = sqrt(r);
+          fin.hist[fin.itr] = r;
+          if (r < fin.eps) {
+            *fin.flag = 1;
+            *fin.conv_itr = fin.itr;
           }
-          *fin.counter = 0u;
         }
-      }
+      });
     }
   }
 }

@@ -42,6 +42,7 @@ constexpr int VW = 4;
 
 namespace {
 #include "cz_k_common.h"
+#include "cz_k_sums.h"
 #include "cz_k_fastdiv.h"
 #include "cz_k_pass.h"
 #include "cz_k_stencil.h"

@@ -4,8 +4,9 @@ For every kernel (.amdhsa_kernel) of either file, by its demangled name without 
     identical             the same instructions, operands included
     register names only   the same opcodes in the same order, some operand differs
     opcode sequence differs
-with the instruction count, VGPRs, SGPRs and scratch bytes of both sides (.amdhsa_next_free_vgpr, .amdhsa_next_free_sgpr,
-.amdhsa_private_segment_fixed_size), then the kernels new and gone, then whether the kernels both files have come in the same order.
+with the instruction count, VGPRs, SGPRs, scratch bytes and static LDS bytes of both sides (.amdhsa_next_free_vgpr, .amdhsa_next_free_sgpr,
+.amdhsa_private_segment_fixed_size, .amdhsa_group_segment_fixed_size), then the kernels new and gone, then whether the kernels both files
+have come in the same order, then the kernels in which the branch needs more of a resource than the parent.
 A --rename rule rewrites the PARENT's names before the match (a renamed kernel beside its twin).  --only: list only the names that match
 (the summary counts all).  --diff: also the unified diff of the instructions of the kernels that match and differ.  Only the numbers of
 the block labels (.LBB<n>_<m>) are normalised: they count the functions of the file.  The tool compares text; it looks for no particular
@@ -18,7 +19,8 @@ import subprocess
 import sys
 
 LABEL = re.compile(r"\.LBB\d+_")
-RES = {"vgpr": ".amdhsa_next_free_vgpr", "sgpr": ".amdhsa_next_free_sgpr", "scratch": ".amdhsa_private_segment_fixed_size"}
+RES = {"vgpr": ".amdhsa_next_free_vgpr", "sgpr": ".amdhsa_next_free_sgpr", "scratch": ".amdhsa_private_segment_fixed_size",
+       "lds": ".amdhsa_group_segment_fixed_size"}
 
 
 def demangle(names):
@@ -82,7 +84,7 @@ def parse(path):
 
 
 def fmt(n, r):
-    return f"{n:5d} instr {r.get('vgpr', -1):3d} v {r.get('sgpr', -1):3d} s {r.get('scratch', -1):4d} scratch"
+    return f"{n:5d} instr {r.get('vgpr', -1):3d} v {r.get('sgpr', -1):3d} s {r.get('scratch', -1):4d} scratch {r.get('lds', -1):6d} lds"
 
 
 def main():
@@ -111,7 +113,7 @@ def main():
     pn, P = load(a.parent, True)
     bn, B = load(a.branch, False)
     count = {"identical": 0, "register names only": 0, "opcode sequence differs": 0}
-    scratch = []
+    scratch, more = [], []
     for x in bn:
         if B[x][1].get("scratch", 0):
             scratch.append(x)
@@ -120,6 +122,9 @@ def main():
         (pb, pr, was), (bb, br, _) = P[x], B[x]
         verdict = "identical" if pb == bb else "register names only" if [i.split()[0] for i in pb] == [i.split()[0] for i in bb] else "opcode sequence differs"
         count[verdict] += 1
+        up = [f"{k} {pr.get(k, 0)} -> {br.get(k, 0)}" for k in RES if br.get(k, 0) > pr.get(k, 0)]
+        if up:
+            more.append(f"{x}: " + ", ".join(up))
         if only is None or only.search(x) or only.search(was):
             twin = f"  (parent: {was})" if was != x else ""
             print(f"{verdict:24s} {x}{twin}\n{'':24s}   parent {fmt(len(pb), pr)} | branch {fmt(len(bb), br)}")
@@ -141,6 +146,7 @@ def main():
         print(f"order of the kernels in both: DIFFERS, first at parent `{moved[0]}`")
         rest = [x for x in po if only is None or not only.search(x)]
         print("  without the --only kernels: " + ("the same" if rest == [x for x in bo if x in set(rest)] else "DIFFERS"))
+    print(f"kernels in which the branch needs more than the parent ({len(more)}):" + "".join("\n  " + m for m in more))
     if only:
         listed = [x for x in scratch if only.search(x)]
         print(f"kernels of the branch with scratch: {len(scratch)}; among the --only kernels: " + (", ".join(listed) if listed else "none"))

@@ -193,20 +193,7 @@ jacobi2_k(const REAL* __restrict__ U, const REAL* __restrict__ B, REAL* __restri
     }
   }
 
-  // ---- residuals: per-workgroup partials, finalised by the last workgroup (write-through hand-off, see stencil_k)
-  __syncthreads();
-  const double s1 = block_sum<TB>(acc1, wsum);
-  __syncthreads();
-  const double s2 = block_sum<TB>(acc2, wsum);
-  int* last_flag = reinterpret_cast<int*>(wsum + 16);
-  if (t == 0) {
-    __hip_atomic_store(&partials[lb], s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&partials[nblk + lb], s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned ticket = __hip_atomic_fetch_add(fin.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *last_flag = (ticket == (unsigned)nblk - 1u);
-  }
-  __syncthreads();
-  if (*last_flag) pass_finalize<TB, 2>(partials, nblk, fin, wsum);
+  // ---- residuals: per-workgroup partials, finalised by the last workgroup (pass_epilogue, cz_k_pass.h; lb is blockIdx.x here)
+  const double acc[2] = {acc1, acc2};
+  pass_epilogue<TB, 2>(acc, partials, fin, wsum);
 }
-
